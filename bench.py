@@ -14,13 +14,18 @@ Pairs are independent units: by default two of them are in flight per GPU (two c
 two measure 135.7 ms per pair, three 136.8, four 137.7; four for the small configurations C1 / C2), so the CUs the raster sweep of one pair leaves idle evaluate the other pair's
 planes; all K pairs complete inside the timed region.  --in-flight 1 gives the one-pair-at-a-time number.
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step,
+the workload and the fallback counters of the timed region).  --full adds what takes work beyond that: hipEvent brackets of the
+launches and a solo pair for the roofline and per-kernel figures, the sanity check of the last pair against its ground truth, the
+reference-order CPU baseline (minutes of host time) and the accuracy on the real Middlebury pair.  --dump-outputs DIR writes what
+the last timed step computed to DIR/<name>.npy (float32 / float64): the same arguments give the same inputs on every run.
 """
 import argparse
 import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -38,6 +43,7 @@ F64_LANE_OPS_PEAK = 78.6e12 / 2.0
 VALU_CYCLES_PER_WINSTR = 4.0
 N_SIMD = 1024
 PMC_FILE = os.path.join(ROOT, "profiles", "refine_pmc.json")  # SQ_INSTS_VALU etc. of k_refine, stamped with the kernel sources' hash
+DUMP_LIMIT_BYTES = 60 * 1000 * 1000  # --dump-outputs stays under 64 MB: larger outputs are written as a fixed, seeded sample
 
 
 def kernel_source_hash():
@@ -136,8 +142,8 @@ def cpu_baseline(device_index=0, crop=0, extra_legs=True):
 
 
 def real_pair_accuracy(device_index=0):
-    """bad-2.0 against REAL ground truth (the synthetic pairs have none worth the name): the Middlebury-2014 Motorcycle pair shipped with
-    scikit-image in this image, left view, pixels with known ground truth -- the whole 741x500 pair (max_dis 64) and its half-size
+    """bad-2.0 against REAL ground truth (the synthetic pairs have none worth the name): the Middlebury-2014 Motorcycle pair committed
+    under tests/golden/motorcycle/, left view, pixels with known ground truth -- the whole 741x500 pair (max_dis 64) and its half-size
     version (370x250, max_dis 32: the size SURVEY.md 8(c) quotes the unmodified reference on) where that directory exists, and always
     the 200x128 half-size crop committed under tests/data/.  GRD, 5 levels, lambda 0.3, 3 iterations, seed 12345, raw planes and
     after post-processing.  Outside the timed region."""
@@ -162,6 +168,20 @@ def real_pair_accuracy(device_index=0):
     finally:
         g.close()
     return out
+
+
+def dump_outputs(directory, arrays):
+    """DIR/<name>.npy for every array (float64 stays float64, everything else becomes float32).  Above DUMP_LIMIT_BYTES in all, every
+    array is written as the 1-D sample of its values at a fixed, seeded set of flat indices (the same set on every run)."""
+    arrays = {k: np.ascontiguousarray(v, np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = int(a.size * DUMP_LIMIT_BYTES / total)
+            idx = np.sort(np.random.default_rng(12345).choice(a.size, keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def main():
@@ -193,12 +213,16 @@ def main():
     ap.add_argument("--raster-launches", action="store_true", help="raster sweep as one launch per anti-diagonal instead of the persistent kernel")
     ap.add_argument("--cc", default="GRD", choices=["GRD", "CEN", "IMG"],
                     help="cost function (BASELINE.json's metric is GRD; CEN = census; IMG = the volume-free GrdPC / CSPC plane costs, for comparison)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: per-kernel hipEvent brackets, roofline (one more pair "
+                                                        "alone on the GPU), bad-2.0 of the last pair, the CPU baseline and the real-pair accuracy")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the 8-bit maps of the last timed step (and, except for the C4 batch, "
+                                                                         "its unquantised disparities) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-crop", type=int, default=0, help="CPU baseline on a centred crop of this many columns of C3 (with the whole pair extrapolated and "
                                                             "labelled so) instead of the whole pair, which takes three to four minutes of host time")
     ap.add_argument("--cpu-c3-only", action="store_true", help="CPU baseline: skip the C2 and C1 legs")
     ap.add_argument("--no-real-pair", action="store_true", help="skip the accuracy figure on the real Middlebury pair (real_pair_bad2)")
-    ap.add_argument("--no-kernel-timing", action="store_true", help="do not bracket launches with hipEvents")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full: do not bracket launches with hipEvents")
     args = ap.parse_args()
 
     import torch
@@ -260,8 +284,17 @@ def main():
     first = rank * npairs
     if batch_mode and rank == 0 and not args.same_pair:
         first, npairs = 0, args.steps * world
-    host_pairs = [synth.make_config(args.config, index=first + k) for k in range(npairs)]
-    cfg, _, _, gl, gr = host_pairs[(args.steps - 1) % npairs]  # ground truth of the LAST timed pair (checked below)
+    need_gt = {(args.steps - 1) % npairs, min(args.steps, npairs) - 1}  # the last timed pair's ground truth (--full checks it)
+
+    def make_pair(k):
+        c, l, r, g, _ = synth.make_config(args.config, index=first + k)
+        return c, l, r, (g if k in need_gt else None)
+
+    # one pair per timed step: numpy releases the GIL in the array work, so the pairs are made side by side (the same arrays)
+    workers = max(1, min(16, len(os.sched_getaffinity(0)), npairs))
+    with ThreadPoolExecutor(workers) as pool:
+        host_pairs = list(pool.map(make_pair, range(npairs)))
+    cfg, _, _, gl = host_pairs[(args.steps - 1) % npairs]  # ground truth of the LAST timed pair (checked below)
     w, h = cfg["w"], cfg["h"]
     use_pp = bool(cfg.get("use_pp"))
     d_pairs = [(torch.from_numpy(p[1]).to(dev), torch.from_numpy(p[2]).to(dev)) for p in host_pairs]
@@ -336,7 +369,7 @@ def main():
             step(k, pair=npairs - 1 - k % npairs)  # warm-up on pairs from the END of the list: the timed region starts on inputs not seen yet
     for ctx in ctxs:
         ctx.synchronize()
-        ctx.enable_timing(not args.no_kernel_timing)
+        ctx.enable_timing(args.full and not args.no_kernel_timing)
         ctx.reset_timing()
     fallbacks_before = (sum(ctx.get_option(capi.OPT_SWEEP_FALLBACKS) for ctx in ctxs), sum(ctx.get_option(capi.OPT_VOLUME_FALLBACKS) for ctx in ctxs))
     sync_all()
@@ -361,8 +394,17 @@ def main():
         fb = torch.tensor([sweep_fallbacks, volume_fallbacks], dtype=torch.float64, device=red_dev)
         dist.all_reduce(fb, op=dist.ReduceOp.SUM)
         sweep_fallbacks, volume_fallbacks = int(fb[0].item()), int(fb[1].item())
+    if rank == 0 and args.dump_outputs:  # what the last timed step handed its caller, before anything else runs on the contexts
+        if batch_mode:
+            maps = batch_maps[-1].cpu().numpy()
+            dump = {"disparity_map_left": maps[0], "disparity_map_right": maps[1]}
+        else:
+            last = (args.steps - 1) % nfl
+            dump = {"disparity_map_left": d_out[last][0].cpu().numpy(), "disparity_map_right": d_out[last][1].cpu().numpy(),
+                    "disparity_left": ctxs[last].disparity_f64(0), "disparity_right": ctxs[last].disparity_f64(1)}
+        dump_outputs(args.dump_outputs, dump)
     timing = {}
-    for ctx in ctxs:
+    for ctx in (ctxs if args.full else ()):
         for k, v in ctx.timing().items():
             acc = timing.setdefault(k, {"launches": 0, "ms": 0.0, "evals": 0})
             for f in acc:
@@ -372,7 +414,7 @@ def main():
     # launch's hipEvent bracket measures the mixture, so the dominant kernel is timed once more with ONE pair on the GPU
     # (same inputs, same code path; outside the timed region, which `value` comes from).
     solo = timing
-    if nfl > 1:
+    if nfl > 1 and args.full:
         fold_keep = ctxs[0].get_option(capi.OPT_SWEEP_FOLD)
         ctxs[0].set_option(capi.OPT_SWEEP_FOLD, 0)  # a pair that is alone on the GPU runs the sweep with the library's default (one wave per level)
         ctxs[0].enable_timing(not args.no_kernel_timing)
@@ -406,8 +448,8 @@ def main():
                                     "gather of the 8-bit maps -- all inside the timed region" % (args.steps * world)) if batch_mode else
                                    "every rank generates its own pairs (no collective in the timed region)"},
         }
-        ref = solo["refine"]
-        if ref["launches"]:
+        ref = solo.get("refine")
+        if ref and ref["launches"]:
             # the dominant kernel: k_refine = all halving steps of one PlaneRefinement iteration (cs_patchmatch.cc:292-345)
             avg_s = ref["ms"] / ref["launches"] / 1e3
             steps_per_launch = ref["evals"] / ref["launches"] / (2 * w * h)
@@ -496,30 +538,31 @@ def main():
         # hipEvent brackets of the launches, summed per kernel class and divided by the pairs.  With several pairs in flight the brackets
         # of different pairs OVERLAP in time (a launch's bracket also contains whatever the other streams ran meanwhile), so these do not
         # add up to ms_per_step and are not kernel durations: the key says so.  Durations: roofline.kernels / kernel_ms_one_pair_alone.
-        out["kernel_bracket_ms_per_pair_overlapping" if nfl > 1 else "kernel_ms_per_step"] = {k: v["ms"] / args.steps for k, v in timing.items()}
-        out["kernel_launches_per_step"] = {k: v["launches"] / args.steps for k, v in timing.items()}
+        if args.full:
+            out["kernel_bracket_ms_per_pair_overlapping" if nfl > 1 else "kernel_ms_per_step"] = {k: v["ms"] / args.steps for k, v in timing.items()}
+            out["kernel_launches_per_step"] = {k: v["launches"] / args.steps for k, v in timing.items()}
         out["sweep_fallbacks"] = int(sweep_fallbacks)
         out["volume_fallbacks"] = int(volume_fallbacks)
         out["table_volumes_active"] = bool(all(table_volumes_active)) if args.cc == "GRD" and not args.volumes else None
         out["timed_region_note"] = ("sweep_fallbacks / volume_fallbacks: raster sweeps repeated with per-diagonal launches after a hand-over timeout, and "
                                     "optional volumes given up, INSIDE the timed region (all contexts of all ranks); both must be 0 or the run exits non-zero")
-        if nfl > 1:
+        if nfl > 1 and args.full:
             out["kernel_ms_one_pair_alone"] = {k: v["ms"] for k, v in solo.items()}
-        if world == 1 and not args.no_cpu_baseline and args.cc == "GRD":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.cc == "GRD":
             try:
                 out["cpu_baseline"] = cpu_baseline(dev_index, crop=args.cpu_crop, extra_legs=not args.cpu_c3_only)
             except Exception as e:  # the timed result must not be lost to a problem of the reporting leg: say so in its place
                 out["cpu_baseline"] = {"error": repr(e)}
                 print("bench.py: the cpu_baseline leg failed: %r" % (e,), file=sys.stderr)
         # sanity of the LAST pair that was timed (not part of the timed region)
-        if batch_mode:  # rank 0's last own pair: index steps-1 of the batch; its 8-bit map came back through the gather
+        if args.full and batch_mode:  # rank 0's last own pair: index steps-1 of the batch; its 8-bit map came back through the gather
             gl = host_pairs[min(args.steps, npairs) - 1][3]
             out["bad2_vs_gt_left"] = synth.bad_fraction(batch_maps[min(args.steps, npairs) - 1, 0].cpu().numpy().astype(np.float64) / cfg["dis_scale"], gl, 2.0)
-        else:
+        elif args.full:
             last = ctxs[(args.steps - 1) % nfl]
             out["bad2_vs_gt_left"] = synth.bad_fraction(last.disparity_f64(0), gl, 2.0)
         out["distinct_pairs"] = npairs
-        if world == 1 and not args.no_real_pair:
+        if args.full and world == 1 and not args.no_real_pair:
             try:
                 out["real_pair_bad2"] = real_pair_accuracy(dev_index)
             except Exception as e:

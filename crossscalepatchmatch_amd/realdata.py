@@ -1,15 +1,18 @@
 """Real photographs for the tests and for bench.py's accuracy key: the Middlebury-2014 "Motorcycle" pair (Scharstein et al.,
-GCPR 2014) that scikit-image ships in this image, and the half-size crop of it committed under tests/data/ (made by
-tests/data/make_real_pair.py).  The reference ships no images; BASELINE.json's configs name Middlebury and KITTI pairs and the
+GCPR 2014) in scikit-image's copy, committed under tests/golden/motorcycle/, and the half-size crop of it committed under
+tests/data/ (made by tests/data/make_real_pair.py).  The reference ships no images; BASELINE.json's configs name Middlebury and KITTI pairs and the
 reference's only entry point reads PNGs (main.cc:68-69).  Inputs only -- PIL decodes here, the product decodes with
 host/image_io.cc (which tests/test_gpu_realpair.py holds against PIL pixel for pixel).
 """
+import io
+import lzma
 import os
 
 import numpy as np
 
-SKIMAGE_DATA = os.environ.get("CSPM_SKIMAGE_DATA", "/opt/conda/lib/python3.9/site-packages/skimage/data")
-CROP_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "data")
+_TESTS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests")
+FULL_DIR = os.path.join(_TESTS, "golden", "motorcycle")
+CROP_DIR = os.path.join(_TESTS, "data")
 
 # the flags the full-size pair is run with (ground truth 7.2 .. 59.9 px): main.cc's flags, D = 64, 8-bit maps in 1/4 px
 FULL = dict(w=741, h=500, max_dis=64, dis_scale=4, scale_num=5, reg_lambda=0.3)
@@ -18,9 +21,15 @@ CROP = dict(w=200, h=128, max_dis=32, dis_scale=8, scale_num=5, reg_lambda=0.3)
 
 
 def full_files():
-    """(left.png, right.png, disp.npz) of the 741x500 pair, or None when scikit-image's data directory is not on this machine"""
-    f = [os.path.join(SKIMAGE_DATA, n) for n in ("motorcycle_left.png", "motorcycle_right.png", "motorcycle_disp.npz")]
+    """(left.png, right.png, disp.npy.xz) of the 741x500 pair, or None when the checkout lacks them"""
+    f = [os.path.join(FULL_DIR, n) for n in ("motorcycle_left.png", "motorcycle_right.png", "motorcycle_disp.npy.xz")]
     return f if all(os.path.exists(p) for p in f) else None
+
+
+def read_full_gt(path):
+    """the ground truth of the left view as distributed (float32 [500, 741], inf = unknown) from its LZMA-compressed .npy"""
+    with open(path, "rb") as f:
+        return np.load(io.BytesIO(lzma.decompress(f.read())))
 
 
 def crop_files():
@@ -47,7 +56,7 @@ def load_full():
     f = full_files()
     if f is None:
         return None
-    gt = np.load(f[2])["arr_0"].astype(np.float64)
+    gt = read_full_gt(f[2]).astype(np.float64)
     gt[~np.isfinite(gt)] = np.nan
     return dict(FULL), _bgr(f[0]), _bgr(f[1]), gt
 
@@ -64,7 +73,7 @@ def load_half():
     for p in f[:2]:
         im = Image.open(p).convert("RGB")
         out.append(_bgr(im.resize((im.width // 2, im.height // 2), Image.BOX)))
-    g = np.load(f[2])["arr_0"].astype(np.float64)
+    g = read_full_gt(f[2]).astype(np.float64)
     g[~np.isfinite(g)] = np.nan
     h, w = g.shape[0] // 2 * 2, g.shape[1] // 2 * 2
     b = g[:h, :w].reshape(h // 2, 2, w // 2, 2).transpose(0, 2, 1, 3).reshape(h // 2, w // 2, 4)

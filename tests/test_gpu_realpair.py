@@ -1,5 +1,5 @@
 """A real photograph through everything (round-5 review, Missing 3: every other test, the goldens, smoke and bench.py draw their
-images from synth.py).  The Middlebury-2014 "Motorcycle" pair that scikit-image ships in this image (741x500 RGB + ground truth,
+images from synth.py).  The Middlebury-2014 "Motorcycle" pair committed under tests/golden/motorcycle/ (741x500 RGB + ground truth,
 SURVEY.md 8(c)) and the half-size 200x128 crop of it committed under tests/data/ (tests/data/make_real_pair.py) -- large
 saturated highlights next to fine texture, photographic gradients, occlusions, a true range of ~60 px: what neither generator
 of synth.py produces at once.  The reference's only entry point reads PNGs (main.cc:68-69) and writes 8-bit maps
@@ -7,7 +7,7 @@ of synth.py produces at once.  The reference's only entry point reads PNGs (main
 bit) and in the reference order (the north-star bar), with the accuracy against the real ground truth printed and written to
 gpurun_out/real_pair.json.
 
-The committed crop can never silently vanish; the full pair is skipped LOUDLY when scikit-image's data directory is absent."""
+Neither the committed crop nor the committed full pair can silently vanish: a missing file skips the full pair LOUDLY."""
 import json
 import os
 import subprocess
@@ -72,7 +72,7 @@ def _files_under_test():
 
 
 def test_committed_crop_is_there_and_is_the_documented_window():
-    """the fixture cannot vanish: three files, 200x128, and -- where scikit-image's pair is on the machine -- exactly columns
+    """the fixture cannot vanish: three files, 200x128, and -- with the committed full-size pair -- exactly columns
     [80, 280) x rows [70, 198) of the half-size pair"""
     cfg, l, r, gt = rd.load_crop()
     assert l.shape == r.shape == (128, 200, 3) and gt.shape == (128, 200) and l.dtype == np.uint8
@@ -98,7 +98,7 @@ def test_host_image_io_decodes_foreign_pngs_like_pil(io_check, tmp_path):
         np.testing.assert_array_equal(read_pnm(oc), want, err_msg=f)
         np.testing.assert_array_equal(read_pnm(og), want[..., 1], err_msg=f)
     if rd.full_files() is None:
-        print("NOTE: scikit-image's motorcycle pair is not on this machine; only the committed crop was decoded")
+        print("NOTE: the full-size motorcycle pair is missing from tests/golden/motorcycle/; only the committed crop was decoded")
 
 
 def _gpu_run(ctx, cc, cfg, l, r, iters, seed):
@@ -172,7 +172,7 @@ def test_real_full_pair_cli_and_c_abi_against_the_oracle(gpu_ctx, tmp_path):
     ~1.3e11 window taps on the host, twice: about two minutes on 16 threads."""
     full = rd.load_full()
     if full is None:
-        pytest.skip(f"REAL-PAIR TEST NOT RUN: {rd.SKIMAGE_DATA}/motorcycle_*.png is not on this machine "
+        pytest.skip(f"REAL-PAIR TEST NOT RUN: {rd.FULL_DIR}/motorcycle_* is missing "
                     "(the committed half-size crop was still tested)")
     cfg, l, r, gt = full
     lf, rf, _ = rd.full_files()
@@ -223,7 +223,7 @@ def test_real_half_size_pair_accuracy_next_to_the_reference_probe(gpu_ctx):
     planes equal the oracle's at this size too (levels 370, 185, 93, 47, 24)."""
     half = rd.load_half()
     if half is None:
-        pytest.skip(f"REAL-PAIR TEST NOT RUN: {rd.SKIMAGE_DATA}/motorcycle_*.png is not on this machine")
+        pytest.skip(f"REAL-PAIR TEST NOT RUN: {rd.FULL_DIR}/motorcycle_* is missing")
     cfg, l, r, gt = half
     _gpu_run(gpu_ctx, "GRD", cfg, l, r, 3, 12345)
     pc = po.PlaneCost(l, r, cfg["max_dis"], 35, cfg["scale_num"], cfg["reg_lambda"])

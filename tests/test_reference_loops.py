@@ -1,13 +1,17 @@
-"""The reference's OWN loops next to the oracle (round-4 review, item 7; runs only where /root/reference exists).
+"""The reference's OWN loops next to the oracle (round-4 review, item 7).
 
-cs_patchmatch.cc, plane_cost/pre_ss_pc.cc, pre_cs_pc.cc, grd_pc.cc, cspc.cc, cc/grd_cc.cpp and cc/cen_cc.cc are compiled UNMODIFIED, in place, against
-test-only stand-ins for <opencv2/opencv.hpp> and <gflags/gflags.h> (tests/helpers/refcheck/): every OpenCV call is delegated to
+cs_patchmatch.cc, plane_cost/pre_ss_pc.cc, pre_cs_pc.cc, grd_pc.cc, cspc.cc, cc/grd_cc.cpp and cc/cen_cc.cc are compiled UNMODIFIED
+against test-only stand-ins for <opencv2/opencv.hpp> and <gflags/gflags.h> (tests/helpers/refcheck/): every OpenCV call is delegated to
 the oracle's restated contracts and cv::RNG is the specified counter-based generator in its ROW_SHARED mode (the reference builds
 with USE_OMP and re-seeds every row, cs_patchmatch.cc:129-131).  THIS PINS NOTHING -- a build against stand-ins is not a reference
 build -- but it is the one available check that the oracle's TRANSCRIPTION of the reference-owned code
 (loop structure, traversal orders, strict-`<` accept rules, indexing, the order of the random draws, post-processing) has no slip:
 planes, stored costs, 8-bit maps and sampled GetPlaneCost values must be identical to the oracle's reference order, bit for bit.
-Nothing of the reference enters the repository; the binary is built in a temporary directory."""
+
+What that binary computed on every case below is recorded under tests/golden/refloops_<case>.npz (inputs and outputs,
+tests/golden/make_refloops.py), so the oracle is held against it on any checkout.  Where build() could compile the binary
+(oracle/build_ref.py -> oracle/_ref/refcheck: the reference checkout was readable), it is also run here and must reproduce the
+record.  Nothing of the reference enters the repository."""
 import os
 import struct
 import subprocess
@@ -16,34 +20,16 @@ import numpy as np
 import pytest
 
 from crossscalepatchmatch_amd import synth
+from oracle import build_ref
 from oracle import pyoracle as po
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/CSPM"
-HELP = os.path.join(ROOT, "tests", "helpers")
-SOURCES = ["cs_patchmatch.cc", "plane_cost/pre_ss_pc.cc", "plane_cost/pre_cs_pc.cc", "cc/grd_cc.cpp", "cc/cen_cc.cc", "plane_cost/grd_pc.cc", "plane_cost/cspc.cc"]
-
-pytestmark = pytest.mark.skipif(not all(os.path.exists(os.path.join(REF, s)) for s in SOURCES),
-                                reason="the reference checkout is not on this machine (GPU box)")
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+DIS_SCALE, SEED = 16, 4321
 
 
-@pytest.fixture(scope="module")
-def refcheck_exe(tmp_path_factory):
-    d = tmp_path_factory.mktemp("refcheck")
-    fwd = d / "fwd"
-    fwd.mkdir()
-    for hname in ("plane_cost/i_plane_cost.h", "plane_cost/pre_ss_pc.h", "plane_cost/pre_cs_pc.h", "cc/grd_cc.h", "cc/cen_cc.h",
-                  "plane_cost/grd_pc.h", "plane_cost/cspc.h"):  # the reference spells its includes with backslashes (cs_patchmatch.h:12)
-        (fwd / hname.replace("/", "\\")).write_text(f'#pragma once\n#include "{hname}"\n')
-    for hname in ("commfunc.h", "cc_method.h"):  # cc/grd_cc.h:2-3: #include "..\commfunc.h"
-        (fwd / ("..\\" + hname)).write_text(f'#pragma once\n#include "{hname}"\n')
-    po.build()
-    exe = str(d / "refcheck")
-    cmd = ["g++", "-O1", "-std=c++14", "-ffp-contract=off", "-w", "-I", str(fwd), "-I", os.path.join(HELP, "refcheck"), "-I", REF,
-           "-o", exe, os.path.join(HELP, "refcheck_main.cc")] + [os.path.join(REF, s) for s in SOURCES] + \
-          ["-L", os.path.join(ROOT, "oracle"), "-lcspm_oracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle")]
-    subprocess.check_call(cmd)  # no -fopenmp: the rows run in order, so the n-th cv::RNG is the n-th row (stand-in header)
-    return exe
+def golden_path(name):
+    return os.path.join(GOLDEN, f"refloops_{name}.npz")
 
 
 def _run_reference(exe, tmp_path, l, r, max_dis, dis_scale, scale_num, lam, iters, use_pp, wnd, seed, queries, kind=0):
@@ -102,18 +88,46 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("name,kind,dims,scale_num,lam,iters,use_pp,wnd,cc", CASES, ids=[c[0] for c in CASES])
-def test_reference_loops_equal_the_oracle(refcheck_exe, tmp_path, name, kind, dims, scale_num, lam, iters, use_pp, wnd, cc):
+def case_inputs(name, kind, dims):
+    """the pair and the GetPlaneCost queries of one case (what the record was made from)"""
     w, h, max_dis = dims
-    dis_scale, seed = 16, 4321
     if kind == "noise":
         l, r = synth.make_pair(w, h, max_dis, regions=2, seed=len(name))[:2]
     else:
         l, r = synth.make_adversarial(kind, w, h, max_dis, seed=3)
     rng = np.random.default_rng(7)
-    queries = _queries(rng, 60, w, h, max_dis)
-    qcost, views = _run_reference(refcheck_exe, tmp_path, l, r, max_dis, dis_scale, scale_num, lam, iters, use_pp, wnd, seed, queries,
-                                  kind={"GRD": 0, "CEN": 1, "IMG": 2}[cc])
+    return l, r, _queries(rng, 60, w, h, max_dis)
+
+
+def run_case(exe, tmp_path, name, kind, dims, scale_num, lam, iters, use_pp, wnd, cc):
+    """the reference binary on one case: (GetPlaneCost of the queries, [(plane records [h, w, 10], 8-bit map)] per view)"""
+    l, r, queries = case_inputs(name, kind, dims)
+    return _run_reference(exe, tmp_path, l, r, dims[2], DIS_SCALE, scale_num, lam, iters, use_pp, wnd, SEED, queries,
+                          kind={"GRD": 0, "CEN": 1, "IMG": 2}[cc])
+
+
+@pytest.mark.parametrize("name,kind,dims,scale_num,lam,iters,use_pp,wnd,cc", CASES, ids=[c[0] for c in CASES])
+def test_reference_loops_equal_the_oracle(tmp_path, name, kind, dims, scale_num, lam, iters, use_pp, wnd, cc):
+    w, h, max_dis = dims
+    dis_scale, seed = DIS_SCALE, SEED
+    l, r, queries = case_inputs(name, kind, dims)
+    with np.load(golden_path(name)) as g:
+        rec_in = {k: g[k] for k in ("l", "r", "xyv", "npnt")}
+        qcost = g["qcost"]
+        views = [(g["planes0"], g["dis0"]), (g["planes1"], g["dis1"])]
+    # the record is of exactly these inputs
+    for key, want in (("l", l), ("r", r), ("xyv", queries[0]), ("npnt", queries[1])):
+        np.testing.assert_array_equal(rec_in[key], want, err_msg=f"{name}: recorded input {key} (tests/golden/make_refloops.py)")
+    # the reference's loops themselves, where build() could compile them: they reproduce the record
+    failed = build_ref.failure(build_ref.REFCHECK)
+    if failed is not None:
+        pytest.fail("oracle/_ref/refcheck did not build:\n" + failed)
+    if os.path.exists(build_ref.REFCHECK):
+        live_q, live_views = run_case(build_ref.REFCHECK, tmp_path, name, kind, dims, scale_num, lam, iters, use_pp, wnd, cc)
+        np.testing.assert_array_equal(live_q, qcost, err_msg=f"{name}: the reference binary's GetPlaneCost against its record")
+        for v in (0, 1):
+            np.testing.assert_array_equal(live_views[v][0], views[v][0], err_msg=f"{name}: the reference binary's planes against its record, view {v}")
+            np.testing.assert_array_equal(live_views[v][1], views[v][1], err_msg=f"{name}: the reference binary's 8-bit map against its record, view {v}")
     # the oracle: reference order (serial sweep, serial window sum), one thread, the row-shared random streams of the reference's USE_OMP build
     pc = po.PlaneCost(l, r, max_dis, wnd, scale_num, lam, cc=cc)
     xyv, npnt = queries

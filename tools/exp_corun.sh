@@ -7,4 +7,4 @@ CSPM_SWEEP_WG=3 python tools/corun_probe.py C3 5 > $O/sweep_wg3.txt 2>&1
 (cd /tmp && export TMPDIR=/tmp && rocprofv3 --pmc SQ_WAVES --output-format csv -d /tmp/pmcx -o p -- python $GRAFT_REPO_ROOT/tools/corun_probe.py C3 3 > $GRAFT_REPO_ROOT/$O/under_pmc.txt 2>&1)
 cat $O/*.txt
 python -m pytest tests/test_gpu_bench_ranks.py -m gpu -x -q 2>&1 | tail -5
-python bench.py --no-cpu-baseline > gpurun_out/r06_bench_a.json 2> gpurun_out/r06_bench_a.err; python tools/bench_brief.py a < gpurun_out/r06_bench_a.json
+python bench.py --full --no-cpu-baseline > $O/bench_a.json 2> $O/bench_a.err; python tools/bench_brief.py a < $O/bench_a.json

@@ -8,6 +8,6 @@ for vs in 0 1; do
 done
 grep "level 0" $O/row_stats_c3_sort0.txt; grep "level 0" $O/row_stats_c3_sort1.txt; grep "level 0" $O/row_stats_real_sort0.txt; grep "level 0" $O/row_stats_real_sort1.txt
 tail -3 $O/time_phases_sort0.txt; tail -3 $O/time_phases_sort1.txt
-python bench.py --no-cpu-baseline > gpurun_out/r06_bench_b.json 2> gpurun_out/r06_bench_b.err; python - <<'PY'
-import json; d=json.load(open("gpurun_out/r06_bench_b.json")); print(d["value"], d["ms_per_step"], d["sweep_fallbacks"], d["volume_fallbacks"], d["table_volumes_active"], {k:round(v["avg_launch_ms"],2) for k,v in d["roofline"]["kernels"].items()}, d.get("real_pair_bad2"))
+python bench.py --full --no-cpu-baseline > $O/bench_b.json 2> $O/bench_b.err; python - $O/bench_b.json <<'PY'
+import json, sys; d=json.load(open(sys.argv[1])); print(d["value"], d["ms_per_step"], d["sweep_fallbacks"], d["volume_fallbacks"], d["table_volumes_active"], {k:round(v["avg_launch_ms"],2) for k,v in d["roofline"]["kernels"].items()}, d.get("real_pair_bad2"))
 PY
