@@ -32,6 +32,7 @@ OPT_VOLUME_RETRY_PAIRS = 15  # a cost object that runs without the optional volu
 OPT_VIEW_SORT = 17           # view propagation evaluates a row's proposals in target-column order (default 1; identical planes either way)
 OPT_SWEEP_FOLD = 18          # cross-scale sweep workgroups of levels - 1 waves, the coarsest level folded onto them (default 1; identical planes)
 OPT_FAULT_VOLUME_ALLOC = 16  # write only, TEST HOOK: the n-th optional-volume allocation from now on fails
+CA_BOX, CA_GF, CA_BF = 0, 1, 2  # cost aggregation: BoxCA, GFCA, BFCA (ca_filter/)
 
 # every symbol include/cspm.h declares
 SYMBOLS = [
@@ -43,6 +44,7 @@ SYMBOLS = [
     "cspm_get_planes", "cspm_set_planes", "cspm_get_disparity_u8", "cspm_get_disparity_f64",
     "cspm_disparity_u8_device", "cspm_postprocess", "cspm_postprocess_device", "cspm_enable_timing", "cspm_reset_timing", "cspm_get_timing",
     "cspm_taps_per_view_pass", "cspm_row_engine_taps_per_view_pass", "cspm_fpm_begin", "cspm_fpm_candidates", "cspm_fpm_commit",
+    "cspm_aggregate_cv_host", "cspm_local_stereo",
 ]
 
 
@@ -131,6 +133,8 @@ def load_library():
         "cspm_fpm_commit": (C.c_int, [vp, dp]),
         "cspm_taps_per_view_pass": (C.c_longlong, [vp]),
         "cspm_row_engine_taps_per_view_pass": (C.c_longlong, [vp]),
+        "cspm_aggregate_cv_host": (C.c_int, [C.c_int, C.c_int, dp, C.c_int, C.c_int, C.c_int, dp]),
+        "cspm_local_stereo": (C.c_int, [vp, C.c_int]),
     }
     assert sorted(sig) == sorted(SYMBOLS)
     for name, (res, args) in sig.items():
@@ -284,6 +288,11 @@ class StereoContext:
         self._chk(self.L.cspm_plane_cost_batch(self.p, view, len(xy), xy.ctypes.data_as(C.POINTER(C.c_int)), _dp(npar), _dp(out)))
         return out
 
+    # ---- local stereo ----
+    def local_stereo(self, method):
+        """cost aggregation (CA_BOX / CA_GF / CA_BF) + cross-scale winner-take-all into both views' plane fields (asynchronous)"""
+        self._chk(self.L.cspm_local_stereo(self.p, int(method)))
+
     # ---- PatchMatch ----
     def params(self, seed=12345, schedule=SCHED_RASTER, rb_rounds=1, rb_neighbours=4, rng_mode=RNG_PER_PIXEL, early_exit=1):
         return PmParams(seed, schedule, rb_rounds, rb_neighbours, rng_mode, early_exit)
@@ -363,3 +372,16 @@ class StereoContext:
 
     def row_engine_taps_per_view_pass(self):
         return self.L.cspm_row_engine_taps_per_view_pass(self.p)
+
+
+def aggregate_cv_host(device, method, guide, vol):
+    """CAMethod::aggreCV on host arrays: guide (h, w, 3) f64 used as given, vol (n, h, w) f64; returns the volume with slices 1..
+    filtered (slice 0 as it was)"""
+    L = load_library()
+    g = np.ascontiguousarray(guide, dtype=np.float64)
+    v = np.array(vol, dtype=np.float64, order="C", copy=True)
+    assert g.ndim == 3 and g.shape[2] == 3 and v.ndim == 3 and v.shape[1:] == g.shape[:2]
+    rc = L.cspm_aggregate_cv_host(device, int(method), _dp(g), g.shape[1], g.shape[0], v.shape[0], _dp(v))
+    if rc != 0:
+        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    return v

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "cspm_kernels.h"
+#include "cspm_ca.h"
 
 using namespace cspm;
 
@@ -146,6 +147,15 @@ struct cspm_ctx {
   int fpm_phase = -1, fpm_iter = 0, fpm_step = 0, fpm_inc = 1;
   long long fpm_count = 0;
   cspm_pm_params fpm_params{};
+  // local stereo (cspm_local_stereo): scratch kept between pairs of the same geometry
+  std::vector<void *> ca_allocs;
+  long long ca_key[4] = {0, 0, 0, 0};  // W, H, max_dis, levels
+  double *ca_gn = nullptr, *ca_t = nullptr, *ca_s = nullptr, *ca_raw = nullptr, *ca_out = nullptr, *ca_best = nullptr;
+  int *ca_bestd = nullptr;
+  double *ca_vol[CSPM_MAX_LEVELS] = {nullptr};
+  unsigned long long *ca_keys = nullptr;
+  CaGuideT ca_gt{nullptr, nullptr, nullptr, nullptr};
+  int ca_nb = 0;
   // timing
   bool timing = false;
   std::vector<TimingRec> recs;
@@ -1039,6 +1049,159 @@ int enqueue_postprocess_device(cspm_ctx *c, int dis_scale, void *d_l_out, void *
   return CSPM_OK;
 }
 
+// ---- cost aggregation (cspm_ca.h) ----------------------------------------------------------------------------------------------
+constexpr int kCaRadiusBox = 3, kCaRadiusGf = 9;  // BoxCA.cpp:11, GuidedFilter.h:24
+inline int ca_min_size(int method) { return method == CSPM_CA_BOX ? 2 * kCaRadiusBox + 1 : (method == CSPM_CA_GF ? 2 * kCaRadiusGf + 1 : 17); }
+inline const char *ca_name(int method) { return method == CSPM_CA_BOX ? "BOX" : (method == CSPM_CA_GF ? "GF" : "BF"); }
+
+// device buffers of one aggregation: the guide (3 natural slabs), its GF terms (16 transposed slabs), the walks' scratch
+// (t: max(9, 4 nb) slabs, s: 4 nb slabs) for batches of up to nb slices
+struct CaWork {
+  double *gn, *t, *s;
+  CaGuideT gt;
+  int nb;
+};
+inline size_t ca_t_slabs(int nb) { return (size_t)std::max(9, 4 * nb); }
+
+// the guide-only terms of GF for the guide in w.gn (GuidedFilter.cpp:138-208, 248-263: N, mean_I, Sigma + eps, cofactors, 1/DET)
+void ca_prepare_guide(cspm_ctx *c, int method, const CaWork &w, int W, int H) {
+  if (method != CSPM_CA_GF) return;
+  const size_t px = (size_t)W * H;
+  Timed t(c, CSPM_K_MISC, 0);
+  hipLaunchKernelGGL((k_ca_ywalk<9, CaInGuide>), dim3((W + kCaBlock - 1) / kCaBlock, 1), dim3(kCaBlock), 0, c->stream, CaInGuide{w.gn, px}, W, H,
+                     kCaRadiusGf, w.t);
+  hipLaunchKernelGGL((k_ca_xwalk<9, CaEpGuide>), dim3((H + kCaBlock - 1) / kCaBlock, 1), dim3(kCaBlock), 0, c->stream, (const double *)w.t, W, H,
+                     kCaRadiusGf, CaEpGuide{w.gt, w.gn, W, H, kCaRadiusGf, (double)0.0001f});
+}
+
+// aggreCV's filter of n (<= w.nb) slices: src -> dst, n slabs of W x H each (src == dst allowed except for BF)
+void ca_filter(cspm_ctx *c, int method, const CaWork &w, int W, int H, const double *src, int n, double *dst) {
+  const size_t px = (size_t)W * H;
+  const dim3 gy((W + kCaBlock - 1) / kCaBlock, n), gx((H + kCaBlock - 1) / kCaBlock, n);
+  Timed t(c, CSPM_K_MISC, 0);
+  if (method == CSPM_CA_BOX) {  // BoxCA.cpp:8-12
+    hipLaunchKernelGGL((k_ca_ywalk<1, CaInPlain>), gy, dim3(kCaBlock), 0, c->stream, CaInPlain{src, 1, px}, W, H, kCaRadiusBox, w.t);
+    hipLaunchKernelGGL((k_ca_xwalk<1, CaEpStore>), gx, dim3(kCaBlock), 0, c->stream, (const double *)w.t, W, H, kCaRadiusBox, CaEpStore{dst, W, px});
+  } else if (method == CSPM_CA_GF) {  // GFCA.cpp:8-11, GuidedFilter.cpp:180-298
+    hipLaunchKernelGGL((k_ca_ywalk<4, CaInGfP>), gy, dim3(kCaBlock), 0, c->stream, CaInGfP{src, w.gn, px}, W, H, kCaRadiusGf, w.t);
+    hipLaunchKernelGGL((k_ca_xwalk<4, CaEpGfA>), gx, dim3(kCaBlock), 0, c->stream, (const double *)w.t, W, H, kCaRadiusGf, CaEpGfA{w.gt, w.s, W, H, kCaRadiusGf});
+    hipLaunchKernelGGL((k_ca_ywalk<4, CaInPlain>), gy, dim3(kCaBlock), 0, c->stream, CaInPlain{w.s, 4, px}, W, H, kCaRadiusGf, w.t);
+    hipLaunchKernelGGL((k_ca_xwalk<4, CaEpGfQ>), gx, dim3(kCaBlock), 0, c->stream, (const double *)w.t, W, H, kCaRadiusGf, CaEpGfQ{w.gt, dst, W, H, kCaRadiusGf});
+  } else {  // BFCA.cpp:8-12
+    hipLaunchKernelGGL(k_ca_bf, dim3(ew_grid((long long)px)), dim3(256), 0, c->stream, (const double *)w.gn, src, W, H, n, dst);
+  }
+}
+
+// allocate a CaWork for images of up to px pixels and batches of nb slices
+int ca_alloc_work(cspm_ctx *c, size_t px, int nb, CaWork *w, std::vector<void *> *track) {
+  int rc;
+  double *gt;
+  w->nb = nb;
+  if ((rc = dalloc(c, &w->gn, 3 * px, track)) || (rc = dalloc(c, &gt, 16 * px, track)) || (rc = dalloc(c, &w->t, ca_t_slabs(nb) * px, track)) ||
+      (rc = dalloc(c, &w->s, (size_t)4 * nb * px, track)))
+    return rc;
+  w->gt = CaGuideT{gt, gt + 3 * px, gt + 6 * px, gt + 15 * px};
+  return CSPM_OK;
+}
+
+// slices per batch: the walks' scratch and the raw / aggregated batch (10 slabs per slice) within 6 GiB, 2 .. 128.  Large batches
+// matter: a walk has one lane per column (or row) and slice, and a 1242 x 375 level walked in 32-slice batches keeps only ~190 waves
+// busy in its X walks -- 85 ms per C3 pair for GF; the whole level 0 of a C3 pair in one batch takes 4.8 GB
+inline int ca_batch(size_t px) { return (int)std::max<long long>(2, std::min<long long>(128, (6LL << 30) / (80LL * (long long)px))); }
+
+// cells d0 .. d0+n-1 of level s, view v, as the cost object holds them: its volume, or the slab kernels cspm_get_cost_slab uses
+const double *ca_raw_cells(cspm_ctx *c, int v, int s, int d0, int n, double *scratch) {
+  const Level &L = c->cost.lv[s];
+  const size_t px = (size_t)L.W * L.H;
+  if (L.vol[v]) return L.vol[v] + (size_t)d0 * px;
+  Timed t(c, CSPM_K_MISC, 0);
+  if (c->is_cen)
+    hipLaunchKernelGGL(k_cen_volume, dim3(stride_grid((long long)px * n)), dim3(256), 0, c->stream, c->cen_code[0][s], c->cen_code[1][s], L.W, L.H, d0,
+                       n, v, scratch, (unsigned long long *)nullptr);
+  else
+    hipLaunchKernelGGL((k_grd_volume<SrcU32, true>), dim3(stride_grid((long long)px * n)), dim3(256), 0, c->stream, SrcU32{L.pix[0], L.Wp, L.pad},
+                       SrcU32{L.pix[1], L.Wp, L.pad}, L.grd[0], L.grd[1], L.Wp, L.pad, L.W, L.H, d0, n, v, scratch, (unsigned long long *)nullptr);
+  return scratch;
+}
+
+// the context's local-stereo scratch for its current geometry (kept between pairs: no allocator call, no synchronisation)
+int ca_ensure(cspm_ctx *c) {
+  const Cost &cd = c->cost;
+  const long long key[4] = {c->W, c->H, c->max_dis, cd.levels};
+  if (c->ca_nb && std::equal(key, key + 4, c->ca_key)) return CSPM_OK;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (void *p : c->ca_allocs) (void)hipFree(p);
+  c->ca_allocs.clear();
+  c->ca_nb = 0;
+  const size_t px = (size_t)c->W * c->H;
+  const int nb = ca_batch(px);
+  CaWork w;
+  int rc;
+  if ((rc = ca_alloc_work(c, px, nb, &w, &c->ca_allocs))) return rc;
+  if ((rc = dalloc(c, &c->ca_raw, (size_t)nb * px, &c->ca_allocs)) || (rc = dalloc(c, &c->ca_out, (size_t)nb * px, &c->ca_allocs)) ||
+      (rc = dalloc(c, &c->ca_best, px, &c->ca_allocs)) || (rc = dalloc(c, &c->ca_bestd, px, &c->ca_allocs)) ||
+      (rc = dalloc(c, &c->ca_keys, CSPM_MAX_LEVELS, &c->ca_allocs)))
+    return rc;
+  for (int s = 1; s < cd.levels; ++s)
+    if ((rc = dalloc(c, &c->ca_vol[s], (size_t)(cd.lv[s].D + 1) * cd.lv[s].W * cd.lv[s].H, &c->ca_allocs))) return rc;
+  c->ca_gn = w.gn;
+  c->ca_t = w.t;
+  c->ca_s = w.s;
+  c->ca_gt = w.gt;
+  c->ca_nb = nb;
+  std::copy(key, key + 4, c->ca_key);
+  return CSPM_OK;
+}
+
+// Local stereo of one view (cspm.h): aggregate levels 1.. whole and keep them, then level 0 in batches of slices folded into the WTA
+int ca_local_view(cspm_ctx *c, int method, int v) {
+  const Cost &cd = c->cost;
+  const CaWork w{c->ca_gn, c->ca_t, c->ca_s, c->ca_gt, c->ca_nb};
+  const int nb = c->ca_nb;
+  HIPCHK(c, hipMemsetAsync(c->ca_keys, 0, sizeof(unsigned long long) * CSPM_MAX_LEVELS, c->stream));
+  CaLevels lv{};
+  lv.levels = cd.levels;
+  lv.cs = cd.cs;
+  lv.max_key = c->ca_keys;
+  for (int s = cd.levels - 1; s >= 0; --s) {
+    const Level &L = cd.lv[s];
+    lv.W[s] = L.W; lv.H[s] = L.H; lv.D[s] = L.D; lv.wgt[s] = c->scale_wgt[s];
+    const size_t px = (size_t)L.W * L.H;
+    {
+      Timed t(c, CSPM_K_MISC, 0);
+      hipLaunchKernelGGL(k_ca_guide_u32, dim3(ew_grid((long long)px)), dim3(256), 0, c->stream, L.pix[v], L.W, L.H, L.Wp, L.pad, w.gn);
+    }
+    if (L.D >= 1) ca_prepare_guide(c, method, w, L.W, L.H);
+    if (s > 0) {
+      double *A = c->ca_vol[s];
+      lv.vol[s] = A;
+      const double *raw0 = ca_raw_cells(c, v, s, 0, 1, A);  // slice 0 is left as it is (BoxCA.cpp:8, GFCA.cpp:8, BFCA.cpp:8)
+      if (raw0 != A) HIPCHK(c, hipMemcpyAsync(A, raw0, sizeof(double) * px, hipMemcpyDeviceToDevice, c->stream));
+      for (int d0 = 1; d0 <= L.D; d0 += nb) {
+        const int n = std::min(nb, L.D + 1 - d0);
+        ca_filter(c, method, w, L.W, L.H, ca_raw_cells(c, v, s, d0, n, c->ca_raw), n, A + (size_t)d0 * px);
+      }
+      Timed t(c, CSPM_K_MISC, 0);
+      hipLaunchKernelGGL(k_ca_max, dim3(1024), dim3(256), 0, c->stream, (const double *)A, (long long)(L.D + 1) * (long long)px, c->ca_keys + s);
+    } else {
+      HIPCHK(c, hipMemsetAsync(c->ca_bestd, 0, sizeof(int) * px, c->stream));
+      // slices d0 .. d0+n-1 give the costs of d = d0 .. d0+n-2 (each cost interpolates towards the next slice): batches overlap by one
+      for (int d0 = 1; d0 <= L.D - 1;) {
+        const int n = std::min(nb, L.D + 1 - d0);
+        ca_filter(c, method, w, L.W, L.H, ca_raw_cells(c, v, 0, d0, n, c->ca_raw), n, c->ca_out);
+        Timed t(c, CSPM_K_MISC, 0);
+        hipLaunchKernelGGL(k_ca_wta, dim3(ew_grid((long long)px)), dim3(256), 0, c->stream, lv, (const double *)c->ca_out, d0, n, c->ca_best, c->ca_bestd);
+        d0 += n - 1;
+      }
+      Timed t(c, CSPM_K_MISC, 0);
+      hipLaunchKernelGGL(k_ca_planes, dim3(ew_grid((long long)px)), dim3(256), 0, c->stream, c->f[v], (long long)px, (const double *)c->ca_best,
+                         (const int *)c->ca_bestd);
+    }
+  }
+  HIPCHK(c, hipGetLastError());
+  return CSPM_OK;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -1099,6 +1262,7 @@ void cspm_destroy(cspm_ctx *c) {
   free_cost(c);
   free_field(c);
   free_images(c);
+  for (void *p : c->ca_allocs) (void)hipFree(p);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
 }
@@ -1500,6 +1664,74 @@ int cspm_get_max_cost(cspm_ctx *c, int view, int level, double *out) {
 int cspm_get_scale_weights(const cspm_ctx *c, double *out) {
   if (!c || !out || !c->cost_alloc) return CSPM_ERR_ARG;
   for (int s = 0; s < c->cost.levels; ++s) out[s] = c->scale_wgt[s];
+  return CSPM_OK;
+}
+
+// CAMethod::aggreCV on host buffers (ca_method.h:23; BoxCA.cpp, GFCA.cpp, BFCA.cpp): slices 1 .. n_slices-1 filtered in place
+int cspm_aggregate_cv_host(int device, int method, const double *guide, int w, int h, int n_slices, double *vol) {
+  if (method < CSPM_CA_BOX || method > CSPM_CA_BF) return fail(nullptr, CSPM_ERR_ARG, "unknown aggregation method (CSPM_CA_BOX / GF / BF)");
+  if (!guide || !vol || w < 1 || h < 1 || n_slices < 1) return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
+  if (n_slices > 1 && std::min(w, h) < ca_min_size(method))
+    return fail(nullptr, CSPM_ERR_ARG, std::string(ca_name(method)) + " needs min(w, h) >= " + std::to_string(ca_min_size(method)) + ", the slabs are " +
+                                           std::to_string(w) + "x" + std::to_string(h));
+  if (n_slices == 1) return CSPM_OK;
+  cspm_ctx *c = nullptr;
+  int rc = cspm_create(&c, device);
+  if (rc) return rc;
+  std::vector<void *> tmp;
+  auto done = [&](int code) {
+    if (code) g_create_error = c->err;
+    for (void *p : tmp) (void)hipFree(p);
+    cspm_destroy(c);
+    return code;
+  };
+  const size_t px = (size_t)w * h;
+  const int nb = ca_batch(px);
+  CaWork wk;
+  double *dv = nullptr, *dout = nullptr;
+  if ((rc = ca_alloc_work(c, px, nb, &wk, &tmp)) || (rc = dalloc(c, &dv, (size_t)(n_slices - 1) * px, &tmp)) ||
+      (rc = dalloc(c, &dout, (size_t)nb * px, &tmp)))
+    return done(rc);
+  std::vector<double> gn(3 * px);  // channel-major, the values as given
+  for (size_t i = 0; i < px; ++i)
+    for (int k = 0; k < 3; ++k) gn[k * px + i] = guide[3 * i + k];
+  if (hipMemcpyAsync(wk.gn, gn.data(), sizeof(double) * 3 * px, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(dv, vol + px, sizeof(double) * (n_slices - 1) * px, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+    return done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  ca_prepare_guide(c, method, wk, w, h);
+  for (int d0 = 0; d0 < n_slices - 1; d0 += nb) {
+    const int n = std::min(nb, n_slices - 1 - d0);
+    ca_filter(c, method, wk, w, h, dv + (size_t)d0 * px, n, dout);
+    if (hipMemcpyAsync(dv + (size_t)d0 * px, dout, sizeof(double) * n * px, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+      return done(fail(c, CSPM_ERR_HIP, "copy failed"));
+  }
+  if (hipGetLastError() != hipSuccess ||
+      hipMemcpyAsync(vol + px, dv, sizeof(double) * (n_slices - 1) * px, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return done(fail(c, CSPM_ERR_HIP, "aggregation kernels failed"));
+  return done(CSPM_OK);
+}
+
+// local stereo over the ctx's cost object (cspm.h): asynchronous on the ctx stream like cspm_patchmatch
+int cspm_local_stereo(cspm_ctx *c, int method) {
+  if (!c) return CSPM_ERR_ARG;
+  if (method < CSPM_CA_BOX || method > CSPM_CA_BF) return fail(c, CSPM_ERR_ARG, "unknown aggregation method (CSPM_CA_BOX / GF / BF)");
+  if (!c->cost_alloc || !c->cost_ready) return fail(c, CSPM_ERR_STATE, "local stereo needs a cost object (cspm_build_cost_grd / _cen / cspm_finish_cost)");
+  if (c->is_img) return fail(c, CSPM_ERR_STATE, "GrdPC / CSPC costs have no cost cells to aggregate");
+  const Cost &cd = c->cost;
+  if (cd.lv[0].D < 2) return fail(c, CSPM_ERR_ARG, "local stereo needs max_dis >= 2");
+  for (int s = 0; s < cd.levels; ++s)
+    if (cd.lv[s].D >= 1 && std::min(cd.lv[s].W, cd.lv[s].H) < ca_min_size(method))
+      return fail(c, CSPM_ERR_ARG, std::string(ca_name(method)) + " needs min(w, h) >= " + std::to_string(ca_min_size(method)) + "; level " +
+                                       std::to_string(s) + " is " + std::to_string(cd.lv[s].W) + "x" + std::to_string(cd.lv[s].H));
+  DevGuard guard_(c->device);
+  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  int rc;
+  if ((rc = ensure_field(c)) || (rc = ca_ensure(c))) return rc;
+  c->field_consistent = false;  // min_cost is the local-stereo cost, not the plane cost of this cost object
+  if (c->pm_runs_unchecked) c->phases_unchecked = true;  // an unchecked PatchMatch run can no longer be repeated over these planes
+  for (int v = 0; v < 2; ++v)
+    if ((rc = ca_local_view(c, method, v))) return rc;
   return CSPM_OK;
 }
 

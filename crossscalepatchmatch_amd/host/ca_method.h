@@ -1,5 +1,6 @@
-// ca_method.h -- cost-aggregation plugin interface, as CSPM/ca_method.h:8-25.  PatchMatch never calls it (the
-// reference's ca_filter/* is not compiled into CSPM.vcxproj); kept as a header-level surface only.
+// ca_method.h -- cost-aggregation plugin interface, as CSPM/ca_method.h:8-25.  Implemented by BoxCA, GFCA and BFCA
+// (ca_filter/device_ca.h, on the GPU); CSPatchMatch::LocalStereo runs the same filters inside the device cost object.
+// PatchMatch itself never calls it, as in the reference.
 #pragma once
 #include "commfunc.h"
 

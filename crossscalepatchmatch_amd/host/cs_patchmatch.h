@@ -21,6 +21,11 @@ class CSPatchMatch {
   // End waits for it and fills dis() -- PlaneToDisp, or PostProcessing when use_pp.  PatchMatch == Begin + End.
   void PatchMatchBegin(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp);
   void PatchMatchEnd();
+  // local stereo instead of PatchMatch (an addition): cost aggregation with ca_method (CSPM_CA_BOX / GF / BF) over one of this
+  // library's PreSSPC / PreCSPC costs, then cross-scale winner-take-all of fronto-parallel planes (include/cspm.h
+  // cspm_local_stereo); dis(), planes(), disparity() and use_pp as after PatchMatch.  Begin / End as above (End = PatchMatchEnd).
+  void LocalStereo(const int &ca_method, const IPlaneCost *plane_cost, const bool &use_pp);
+  void LocalStereoBegin(const int &ca_method, const IPlaneCost *plane_cost, const bool &use_pp);
 
   // additions (the reference seeds from time(NULL) and has one schedule)
   void set_seed(uint64_t seed) { seed_ = seed; }

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "../../include/cspm.h"
+#include "ca_filter/device_ca.h"
 #include "cc/cen_cc.h"
 #include "cc/grd_cc.h"
 #include "cs_patchmatch.h"
@@ -52,6 +53,21 @@ void CenCC::build(const Mat &lImg, const Mat &rImg, int maxDis, Mat *vol, int ri
 }
 void CenCC::buildCV(const Mat &lImg, const Mat &rImg, const int maxDis, Mat *costVol) { build(lImg, rImg, maxDis, costVol, 0); }
 void CenCC::buildRightCV(const Mat &lImg, const Mat &rImg, const int maxDis, Mat *rCostVol) { build(lImg, rImg, maxDis, rCostVol, 1); }
+
+// ---------------------------------------------------------------- BoxCA / GFCA / BFCA (ca_filter/*.cpp)
+void DeviceCA::aggreCV(const Mat &lImg, const Mat &rImg, const int maxDis, Mat *costVol) {
+  (void)rImg;  // unused, as in the reference
+  CV_Assert(lImg.type() == CV_64FC3);  // the colour branch (GuidedFilter.cpp:171, BilateralFilter.cpp:56)
+  CV_Assert(maxDis >= 1 && costVol);
+  const int h = lImg.rows, w = lImg.cols;
+  for (int d = 0; d < maxDis; ++d) CV_Assert(costVol[d].type() == CV_64FC1 && costVol[d].rows == h && costVol[d].cols == w);
+  std::vector<double> g = packed64(lImg), vol((size_t)maxDis * h * w);
+  for (int d = 0; d < maxDis; ++d)
+    for (int y = 0; y < h; ++y) std::memcpy(&vol[((size_t)d * h + y) * w], costVol[d].ptr<double>(y), sizeof(double) * w);
+  check(cspm_aggregate_cv_host(DeviceSlot::current().device(), method_, g.data(), w, h, maxDis, vol.data()), NULL, "CAMethod::aggreCV");
+  for (int d = 1; d < maxDis; ++d)
+    for (int y = 0; y < h; ++y) std::memcpy(costVol[d].ptr<double>(y), &vol[((size_t)d * h + y) * w], sizeof(double) * w);
+}
 
 // ---------------------------------------------------------------- DeviceSlot, PreSSPC / PreCSPC / GrdPC / CSPC
 int DevicePlaneCost::device = 0;
@@ -338,6 +354,21 @@ void CSPatchMatch::PatchMatchEnd() {
       check(cspm_get_disparity_u8(ctx, v, dis_scale_, dis_[v].data, dis_[v].step), ctx, "cspm_get_disparity_u8");
   }
   last_ctx_ = ctx;
+}
+
+void CSPatchMatch::LocalStereoBegin(const int &ca_method, const IPlaneCost *plane_cost, const bool &use_pp) {
+  if (pending_ctx_) throw std::runtime_error("CSPatchMatch::LocalStereoBegin: the previous run has not been ended");
+  const IDevicePlaneCost *dev = dynamic_cast<const IDevicePlaneCost *>(plane_cost);
+  if (!dev) throw std::runtime_error("CSPatchMatch::LocalStereo needs one of this library's PreSSPC / PreCSPC costs");
+  cspm_ctx *ctx = dev->device_ctx();
+  check(cspm_local_stereo(ctx, ca_method), ctx, "cspm_local_stereo");  // asynchronous: enqueued on the context's stream
+  pending_ctx_ = ctx;
+  pending_pp_ = use_pp;
+}
+
+void CSPatchMatch::LocalStereo(const int &ca_method, const IPlaneCost *plane_cost, const bool &use_pp) {
+  LocalStereoBegin(ca_method, plane_cost, use_pp);
+  PatchMatchEnd();
 }
 
 void CSPatchMatch::PatchMatch(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp) {

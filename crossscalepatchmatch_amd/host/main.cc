@@ -1,6 +1,7 @@
 // main.cc -- command line with the reference's ten flags and defaults (CSPM/main.cc:23-34) and its flow
 // (main.cc:57-139): read the pair, construct the plane cost (timed), run PatchMatch, print "Total Time", write the
-// two 8-bit maps.  Runs on the GPU through the host layer.  Extra flags: --seed --schedule --device --iters.
+// two 8-bit maps.  Runs on the GPU through the host layer.  Extra flags: --seed --schedule --device --iters --ca_name (local stereo).
+#include "../../include/cspm.h"
 #include "commfunc.h"
 #include "cs_patchmatch.h"
 #include "get_method.h"
@@ -28,6 +29,8 @@ DEFINE_int32(dis_scale, 0, "factor applied to disparities before 8-bit quantisat
 DEFINE_string(cc_name, "CCName", "matching cost: GRD | CEN");
 DEFINE_string(pc_name, "PRE", "plane cost family: PRE = PreSSPC / PreCSPC over --cc_name's cost volumes (the reference's main.cc); "
                               "IMG = GrdPC / CSPC, the volume-free colour + gradient costs (main.cc:106-107, commented out there)");
+DEFINE_string(ca_name, "", "local stereo instead of PatchMatch: cost aggregation BOX | GF | BF over --cc_name's cost volumes, then "
+              "cross-scale winner-take-all (empty: PatchMatch); not with --pc_name=IMG");
 DEFINE_bool(use_cs, false, "cross-scale aggregation over a 5-level pyramid (PreCSPC) instead of PreSSPC");
 DEFINE_bool(use_pp, false, "left-right check, hole filling and weighted median afterwards");
 DEFINE_double(reg_lambda, 0.0, "cross-scale regularisation weight");
@@ -85,6 +88,14 @@ void load(PairRun &p) {
   }
 }
 
+// --ca_name -> CSPM_CA_*, -1 for a name the library does not implement
+int ca_method() {
+  if (FLAGS_ca_name == "BOX") return CSPM_CA_BOX;
+  if (FLAGS_ca_name == "GF") return CSPM_CA_GF;
+  if (FLAGS_ca_name == "BF") return CSPM_CA_BF;
+  return -1;
+}
+
 void begin(PairRun &p, CCMethod *cost_fn) {
   if (p.rc != EXIT_SUCCESS) return;
   try {
@@ -100,7 +111,8 @@ void begin(PairRun &p, CCMethod *cost_fn) {
     p.matcher.reset(new CSPatchMatch(p.left, p.right, FLAGS_max_dis, FLAGS_dis_scale));
     p.matcher->set_seed(static_cast<uint64_t>(FLAGS_seed));
     p.matcher->set_schedule(FLAGS_schedule == "redblack" ? 1 : 0);
-    p.matcher->PatchMatchBegin(FLAGS_iters, p.cost.get(), FLAGS_use_pp);
+    if (FLAGS_ca_name.empty()) p.matcher->PatchMatchBegin(FLAGS_iters, p.cost.get(), FLAGS_use_pp);
+    else p.matcher->LocalStereoBegin(ca_method(), p.cost.get(), FLAGS_use_pp);
   } catch (const std::exception &e) {  // a bad pair must not take the batch down
     p.log << "Error: " << e.what() << "\n";
     p.rc = EXIT_FAILURE;
@@ -252,6 +264,14 @@ int run_batch(const std::vector<BatchJob> &jobs, int skipped, int bad_lines) {
 }
 
 int run() {
+  if (!FLAGS_ca_name.empty() && ca_method() < 0) {  // checked before anything opens a device
+    cout << "Error: --ca_name must be BOX, GF or BF (got " << FLAGS_ca_name << ")\n";
+    return EXIT_FAILURE;
+  }
+  if (!FLAGS_ca_name.empty() && FLAGS_pc_name == "IMG") {
+    cout << "Error: --ca_name aggregates cost volumes; --pc_name=IMG (GrdPC / CSPC) has none\n";
+    return EXIT_FAILURE;
+  }
   DevicePlaneCost::device = FLAGS_device;
   if (FLAGS_use_pp && !(FLAGS_l_disp_pfm.empty() && FLAGS_r_disp_pfm.empty()) && !FLAGS_quiet)
     cout << "Note: the PFM maps hold the plane disparities before post-processing\n";

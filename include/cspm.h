@@ -264,6 +264,33 @@ int cspm_fpm_candidates(cspm_ctx *ctx, int phase, int iter, int step, const cspm
                         double *plane_out);
 int cspm_fpm_commit(cspm_ctx *ctx, const double *cost);
 
+/* ---- cost aggregation and local stereo (CAMethod, ca_method.h:8-25; ca_filter/) ------------------------------------------------
+ * The three CAMethod implementations of the reference, applied to f64 slabs of h*w with a 3-channel f64 guide:
+ *   CSPM_CA_BOX  BoxCA: BoxFilter(p, 3), the unnormalised 7x7 sum of two serial cumulative sums (BoxCA.cpp:5-13, GuidedFilter.cpp:29-122)
+ *   CSPM_CA_GF   GFCA:  GuidedFilter(I, p, 9, 0.0001f), colour branch with FAST_INV (GFCA.cpp:5-12, GuidedFilter.cpp:131-299)
+ *   CSPM_CA_BF   BFCA:  BilateralFilter(I, p, 35), colour branch, sig_sp 17.5, sig_clr 0.03, wrap-around borders (BFCA.cpp:5-13,
+ *                       BilateralFilter.cpp:51-97); its weights use the device's f64 exp
+ * Every op in the reference's order, no contraction.  A filtered slab needs min(w, h) >= 7 (BOX), 19 (GF), 17 (BF): below that the
+ * reference indexes outside the image; such a call fails with CSPM_ERR_ARG. */
+#define CSPM_CA_BOX 0
+#define CSPM_CA_GF 1
+#define CSPM_CA_BF 2
+/* CAMethod::aggreCV on host buffers: guide h*w*3 doubles as given, vol n_slices slabs of h*w, slices 1.. filtered in place */
+int cspm_aggregate_cv_host(int device, int method, const double *guide, int w, int h, int n_slices, double *vol);
+/* local stereo over the ctx's cost object: both views' plane fields; asynchronous on the ctx stream like cspm_patchmatch.
+ * PreSSPC / PreCSPC with a CAMethod between buildCV and the max-cost loop (pre_cs_pc.cc:57-84), then the cost of the fronto-parallel
+ * plane of every d = 1 .. max_dis-1 with the window reduced to its centre (pre_cs_pc.cc:157-183, pre_ss_pc.cc:99-111), then
+ * winner-take-all (the first d that reaches the minimum):
+ *   - per view v and level s: aggreCV over the raw cells 0 .. D_s (those cspm_get_cost_slab returns) with maxDis = D_s + 1, guided by
+ *     view v's level image, BGR -> RGB, each 8-bit value times (double)(1.0f/255.0f); M[v][s] = max(-1.0, max of the aggregated volume);
+ *   - cost(d) = sum over s of c_s * w_s, c_s = M[v][s] where f = (int)(d halved s times) is <= 0 or >= D_s, else the linear
+ *     interpolation between aggregated slices f and f+1 at (x>>s, y>>s);
+ *   - plane = Plane(Vec3d(0,0,1), Point3d(x, y, d*)), min_cost = cost(d*).
+ * The cost object is read, never written: cspm_get_disparity_*, cspm_postprocess(_device) and cspm_patchmatch work afterwards as usual.
+ * CSPM_ERR_STATE without a cost object or with a GrdPC / CSPC cost (no cells); CSPM_ERR_ARG for a bad method or a level too small.
+ * Its launches are timed under CSPM_K_MISC. */
+int cspm_local_stereo(cspm_ctx *ctx, int method);
+
 /* ---- measurement --------------------------------------------------------------------------------
  * When enabled, every kernel launch is bracketed by hipEvents on the ctx stream. */
 #define CSPM_K_GRD 0      /* cost-volume construction kernels */
