@@ -44,7 +44,7 @@ SYMBOLS = [
     "cspm_get_planes", "cspm_set_planes", "cspm_get_disparity_u8", "cspm_get_disparity_f64",
     "cspm_disparity_u8_device", "cspm_postprocess", "cspm_postprocess_device", "cspm_enable_timing", "cspm_reset_timing", "cspm_get_timing",
     "cspm_taps_per_view_pass", "cspm_row_engine_taps_per_view_pass", "cspm_fpm_begin", "cspm_fpm_candidates", "cspm_fpm_commit",
-    "cspm_aggregate_cv_host", "cspm_local_stereo",
+    "cspm_aggregate_cv_host", "cspm_local_stereo", "cspm_rescore_planes", "cspm_patchmatch_warm", "cspm_upsample_planes",
 ]
 
 
@@ -135,6 +135,9 @@ def load_library():
         "cspm_row_engine_taps_per_view_pass": (C.c_longlong, [vp]),
         "cspm_aggregate_cv_host": (C.c_int, [C.c_int, C.c_int, dp, C.c_int, C.c_int, C.c_int, dp]),
         "cspm_local_stereo": (C.c_int, [vp, C.c_int]),
+        "cspm_rescore_planes": (C.c_int, [vp]),
+        "cspm_patchmatch_warm": (C.c_int, [vp, C.c_int, pp]),
+        "cspm_upsample_planes": (C.c_int, [vp, vp]),
     }
     assert sorted(sig) == sorted(SYMBOLS)
     for name, (res, args) in sig.items():
@@ -317,6 +320,20 @@ class StereoContext:
         p = self.params(**kw)
         self._chk(self.L.cspm_pm_refine(self.p, it, C.byref(p)))
 
+    # ---- warm starts ----
+    def rescore_planes(self):
+        """min_cost of every stored plane under the current cost object (asynchronous); the planes are not changed"""
+        self._chk(self.L.cspm_rescore_planes(self.p))
+
+    def patchmatch_warm(self, iters=1, **kw):
+        """PatchMatch from the plane field already in the context: re-score (when the field is stale), then iterations 0 .. iters-1"""
+        p = self.params(**kw)
+        self._chk(self.L.cspm_patchmatch_warm(self.p, iters, C.byref(p)))
+
+    def upsample_planes_from(self, src):
+        """this context's plane field from src's, one pyramid level below (src is ((w+1)/2, (h+1)/2)); min_cost stays stale"""
+        self._chk(self.L.cspm_upsample_planes(self.p, src.p))
+
     def get_planes(self, view):
         npar = np.zeros((self.h, self.w, 6))
         cost = np.zeros((self.h, self.w))
@@ -385,3 +402,43 @@ def aggregate_cv_host(device, method, guide, vol):
     if rc != 0:
         raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
     return v
+
+
+def coarse_to_fine(l, r, max_dis, coarse_iters=3, fine_iters=1, cc="GRD", wnd_size=35, scale_num=5, reg_lambda=0.3, volumes=False,
+                   device=0, ctx=None, coarse_ctx=None, **pm_kw):
+    """PatchMatch on the half-size pair, then `fine_iters` warm iterations on the full pair from the upsampled planes.
+
+    The half-size images are the full cost object's level-1 images (pyrDown); the coarse run uses max_dis (max_dis + 1) // 2 and the
+    same cost settings.  ctx / coarse_ctx: contexts to reuse (created and, for the coarse one, closed here when None).  Returns the
+    full-size context with the warm run enqueued (asynchronous like patchmatch)."""
+    full = ctx if ctx is not None else StereoContext(device)
+    coarse = coarse_ctx if coarse_ctx is not None else StereoContext(device)
+
+    def build(c, md):
+        if cc == "GRD":
+            c.build_cost_grd(md, wnd_size, scale_num, reg_lambda, volumes=volumes)
+        elif cc == "CEN":
+            c.build_cost_cen(md, wnd_size, scale_num, reg_lambda, volumes=volumes)
+        elif cc == "IMG":
+            c.build_cost_img(md, wnd_size, scale_num, reg_lambda)
+        else:
+            raise ValueError(f"unknown cost {cc!r} (GRD, CEN or IMG)")
+
+    try:
+        full.set_images(l, r)
+        if scale_num < 2:  # a single-scale cost has no level 1: a two-level volume-free cost provides the pyrDown images
+            full.build_cost_img(max_dis, wnd_size, 2, 0.0)
+            half = [full.level_image(v, 1) for v in range(2)]
+            build(full, max_dis)
+        else:
+            build(full, max_dis)
+            half = [full.level_image(v, 1) for v in range(2)]
+        coarse.set_images(half[0], half[1])
+        build(coarse, (max_dis + 1) // 2)
+        coarse.patchmatch(coarse_iters, **pm_kw)
+        full.upsample_planes_from(coarse)
+        full.patchmatch_warm(fine_iters, **pm_kw)
+    finally:
+        if coarse_ctx is None:
+            coarse.close()
+    return full

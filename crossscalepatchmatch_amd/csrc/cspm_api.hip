@@ -130,6 +130,8 @@ struct cspm_ctx {
   bool phases_unchecked = false;      // single phases / cspm_set_planes / new inputs since then: no transparent retry
   int last_iters = 0;
   cspm_pm_params last_params{};
+  bool last_warm = false;             // that run was cspm_patchmatch_warm: a repeat starts from warm_snap, not from the init
+  double *warm_snap = nullptr;        // the starting field of the last warm run (both views, 7 arrays each), kept with the field
   long long sweep_fallbacks = 0;      // how often that happened (cspm_get_option)
   // asynchronous outputs (cspm_disparity_u8_device / cspm_postprocess_device) enqueued behind a run whose sweep has not been checked
   // yet: when that run is repeated after a timeout they are produced again from the repeated run's planes
@@ -283,6 +285,8 @@ void free_cost(cspm_ctx *c) {
 }
 void free_field(cspm_ctx *c) {
   if (c->field_mem) (void)hipFree(c->field_mem);
+  if (c->warm_snap) (void)hipFree(c->warm_snap);
+  c->warm_snap = nullptr;
   if (c->vc.cost) (void)hipFree(c->vc.cost);
   if (c->vc.c) (void)hipFree(c->vc.c);
   if (c->vc.cx) (void)hipFree(c->vc.cx);
@@ -733,6 +737,7 @@ Pm make_pm(cspm_ctx *c, const cspm_pm_params *p) {
 // once).  It is looked at by every call that synchronises with the host anyway (cspm_synchronize, the getters, the
 // single-phase entry cspm_pm_spatial): cspm_patchmatch itself stays asynchronous.
 int run_patchmatch(cspm_ctx *c, int iter_num, const cspm_pm_params *p);
+int run_warm_retry(cspm_ctx *c, int iter_num, const cspm_pm_params *p);
 int enqueue_disp_u8(cspm_ctx *c, int view, int dis_scale, void *d_out);
 int enqueue_postprocess_device(cspm_ctx *c, int dis_scale, void *d_l_out, void *d_r_out);
 
@@ -767,7 +772,7 @@ int check_sweep(cspm_ctx *c) {
     if (runs == 1 && !phases && c->cost_ready) {
       const long long keep = c->opt_raster_launches;
       c->opt_raster_launches = 1;
-      int rc = run_patchmatch(c, c->last_iters, &c->last_params);
+      int rc = c->last_warm ? run_warm_retry(c, c->last_iters, &c->last_params) : run_patchmatch(c, c->last_iters, &c->last_params);
       c->opt_raster_launches = keep;
       c->pm_runs_unchecked = 0;
       // the maps that were enqueued behind the aborted run were computed from its planes: produce them again
@@ -992,15 +997,53 @@ int do_refine(cspm_ctx *c, int iter, const cspm_pm_params *p) {
   return CSPM_OK;
 }
 
-int run_patchmatch(cspm_ctx *c, int iter_num, const cspm_pm_params *p) {
+int run_iterations(cspm_ctx *c, int iter_num, const cspm_pm_params *p) {
   int rc;
-  if ((rc = do_init(c, p))) return rc;                 // cs_patchmatch.cc:55
   for (int i = 0; i < iter_num; ++i) {                 // :65-102
     if ((rc = do_spatial(c, i, p))) return rc;
     if ((rc = do_view(c, i, p))) return rc;
     if ((rc = do_refine(c, i, p))) return rc;
   }
   return CSPM_OK;
+}
+
+int run_patchmatch(cspm_ctx *c, int iter_num, const cspm_pm_params *p) {
+  int rc;
+  if ((rc = do_init(c, p))) return rc;                 // cs_patchmatch.cc:55
+  return run_iterations(c, iter_num, p);
+}
+
+// the min_cost of every stored plane under the current cost object (k_rescore); makes the field consistent
+int do_rescore(cspm_ctx *c) {
+  const long long items = 2LL * c->W * c->H;
+  Pm pm = make_pm(c, &kDefaultParams);  // k_rescore reads the field and the geometry only
+  {
+    Timed t(c, CSPM_K_INIT, items);
+    const RowQueue rq = next_row_queue(c, 2);
+    LAUNCH_CS(k_rescore, dim3(row_grid(c, 2)), dim3(kRowBlock), row_shmem(c), c->cost, pm, rq, row_cap(c), row_ocap(c));
+  }
+  HIPCHK(c, hipGetLastError());
+  c->field_consistent = true;
+  return CSPM_OK;
+}
+
+// both views' 7 arrays, field -> snapshot (save) or back (restore); the snapshot is allocated by the first warm run and kept
+int warm_snapshot(cspm_ctx *c, bool save) {
+  const size_t bytes = sizeof(double) * 14 * (size_t)c->W * c->H;
+  if (!c->warm_snap) {
+    int rc = dalloc(c, &c->warm_snap, 14 * (size_t)c->W * c->H, nullptr);
+    if (rc) return rc;
+  }
+  HIPCHK(c, hipMemcpyAsync(save ? c->warm_snap : c->field_mem, save ? c->field_mem : c->warm_snap, bytes, hipMemcpyDeviceToDevice, c->stream));
+  return CSPM_OK;
+}
+
+// a warm run whose persistent sweep timed out: back to its (re-scored) starting field, then the same iterations again
+int run_warm_retry(cspm_ctx *c, int iter_num, const cspm_pm_params *p) {
+  int rc;
+  if ((rc = warm_snapshot(c, false))) return rc;
+  c->field_consistent = true;  // the snapshot was taken after the re-score
+  return run_iterations(c, iter_num, p);
 }
 
 // PlaneToDisp + PostProcessing (cs_patchmatch.cc:103-107, 508-588) enqueued on the ctx stream; results in c->d_dis[v]
@@ -1839,9 +1882,73 @@ int cspm_patchmatch(cspm_ctx *c, int iter_num, const cspm_pm_params *p) {
   if (iter_num < 0 || iter_num > 15) return fail(c, CSPM_ERR_ARG, "iter_num out of range");
   c->last_iters = iter_num;
   c->last_params = *p;
+  c->last_warm = false;
   c->out_reqs.clear();  // outputs requested behind an earlier run: that run can no longer be repeated (two runs unchecked = an error)
   ++c->pm_runs_unchecked;
   return run_patchmatch(c, iter_num, p);
+}
+
+int cspm_rescore_planes(cspm_ctx *c) {
+  if (!c) return CSPM_ERR_ARG;
+  if (!c->cost_ready) return fail(c, CSPM_ERR_STATE, "no plane cost built (cspm_build_cost_grd / cspm_finish_cost)");
+  if (!c->field_alloc) return fail(c, CSPM_ERR_STATE, "no plane field to re-score");
+  DevGuard guard_(c->device);
+  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  c->phases_unchecked = true;
+  return do_rescore(c);
+}
+
+// Asynchronous like cspm_patchmatch.  The starting field (re-scored when it is not consistent) is copied aside first, so that a
+// persistent sweep that times out can be repeated from it by the next synchronising call.
+int cspm_patchmatch_warm(cspm_ctx *c, int iter_num, const cspm_pm_params *p) {
+  if (!c) return CSPM_ERR_ARG;
+  if (!c->cost_ready) return fail(c, CSPM_ERR_STATE, "no plane cost built (cspm_build_cost_grd / cspm_finish_cost)");
+  if (!c->field_alloc) return fail(c, CSPM_ERR_STATE, "no plane field to start from (cspm_set_planes, cspm_local_stereo, cspm_upsample_planes or an earlier run)");
+  PM_ENTER();
+  if (iter_num < 0 || iter_num > 15) return fail(c, CSPM_ERR_ARG, "iter_num out of range");
+  if (!c->field_consistent && (rc = do_rescore(c))) return rc;
+  if ((rc = warm_snapshot(c, true))) return rc;
+  c->last_iters = iter_num;
+  c->last_params = *p;
+  c->last_warm = true;
+  c->out_reqs.clear();
+  ++c->pm_runs_unchecked;
+  return run_iterations(c, iter_num, p);
+}
+
+int cspm_upsample_planes(cspm_ctx *dst, cspm_ctx *src) {
+  if (!dst || !src || dst == src) return CSPM_ERR_ARG;
+  if (dst->device != src->device) return fail(dst, CSPM_ERR_ARG, "the two contexts are on different devices");
+  if (!src->field_alloc) return fail(dst, CSPM_ERR_STATE, "the source context has no plane field");
+  if (!dst->img0[0]) return fail(dst, CSPM_ERR_STATE, "cspm_set_images first");
+  if (src->W != (dst->W + 1) / 2 || src->H != (dst->H + 1) / 2)
+    return fail(dst, CSPM_ERR_ARG, "the source is " + std::to_string(src->W) + "x" + std::to_string(src->H) + ", one pyramid level below " +
+                                       std::to_string(dst->W) + "x" + std::to_string(dst->H) + " is " + std::to_string((dst->W + 1) / 2) + "x" +
+                                       std::to_string((dst->H + 1) / 2));
+  DevGuard guard_(dst->device);
+  if (!guard_.ok) return fail(dst, CSPM_ERR_HIP, "hipSetDevice failed");
+  int rc = check_sweep(src);  // a timed-out source run is repeated (or reported) before its planes are read
+  if (rc) return fail(dst, rc, "source context: " + src->err);
+  if ((rc = ensure_field(dst))) return rc;
+  // dst's stream waits for the source's work; the source's later work (or its destruction) waits for the copy
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  for (auto &e : ev) HIPCHK(dst, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  hipError_t e = hipEventRecord(ev[0], src->stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(dst->stream, ev[0], 0);
+  if (e == hipSuccess) {
+    Timed t(dst, CSPM_K_MISC, 0);
+    const long long n = (long long)dst->W * dst->H;
+    for (int v = 0; v < 2; ++v)
+      hipLaunchKernelGGL(k_upsample_planes, dim3(ew_grid(n)), dim3(256), 0, dst->stream, dst->f[v], src->f[v], dst->W, dst->H, src->W);
+  }
+  if (e == hipSuccess) e = hipGetLastError();
+  if (e == hipSuccess) e = hipEventRecord(ev[1], dst->stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(src->stream, ev[1], 0);
+  for (auto x : ev) (void)hipEventDestroy(x);
+  if (e != hipSuccess) return fail(dst, CSPM_ERR_HIP, std::string("cspm_upsample_planes: ") + hipGetErrorString(e));
+  dst->field_consistent = false;  // min_cost is stale until a re-score (cspm_patchmatch_warm does one)
+  if (dst->pm_runs_unchecked) dst->phases_unchecked = true;
+  return CSPM_OK;
 }
 
 int cspm_get_planes(cspm_ctx *c, int view, double *np_out, double *cost_out) {

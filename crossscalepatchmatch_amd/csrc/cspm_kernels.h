@@ -107,6 +107,24 @@ __global__ void k_plane_to_disp_f64(Pm pm, int v, double *__restrict__ out) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// A plane field carried up one pyramid level (an addition: coarse-to-fine warm starts).  dst is W x H, src the pyrDown size
+// ((W+1)/2, (H+1)/2); pixel (x, y) takes the plane of (x>>1, y>>1).  d(x, y) = 2 d_s(x/2, y/2) = a x + b y + 2c: the normal, a
+// and b are copied, c doubles (exact in binary).  min_cost is not written: the field is not consistent until it is re-scored.
+// ------------------------------------------------------------------------------------------------
+__global__ void k_upsample_planes(Field dst, Field src, int W, int H, int Ws) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)W * H) return;
+  const int y = (int)(i / W), x = (int)(i - (long long)y * W);
+  const long long s = (long long)(y >> 1) * Ws + (x >> 1);
+  dst.nx[i] = src.nx[s];
+  dst.ny[i] = src.ny[s];
+  dst.nz[i] = src.nz[s];
+  dst.a[i] = src.a[s];
+  dst.b[i] = src.b[s];
+  dst.c[i] = 2.0 * src.c[s];
+}
+
+// ------------------------------------------------------------------------------------------------
 // CSPatchMatch::PostProcessing (cs_patchmatch.cc:508-588) on the 8-bit maps, both views per launch.
 //   k_lr_check          one lane per pixel and view: the consistency flag
 //   k_fill_rows         one workgroup per image row and view: nearest consistent pixel on either side by a two-level scan

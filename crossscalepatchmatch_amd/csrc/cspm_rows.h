@@ -1413,6 +1413,36 @@ __global__ __launch_bounds__(kRowBlock, CSPM_INIT_MINW) void k_init(Cost cd, Pm 
 }
 
 // ------------------------------------------------------------------------------------------------
+// Re-score of a stored plane field (an addition: the start of a warm PatchMatch).  k_init with the stored plane of each pixel in
+// place of the random one: same evaluation, no threshold.  Only min_cost is written -- other waves still read the planes of the
+// pixels around theirs.  Re-scoring the field k_init just wrote gives k_init's costs bit for bit.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ RowPlane stored_plane(const Pm &pm, int v, int x, int y) {
+  const long long i = (long long)y * pm.W + x;
+  const Field &f = pm.f[v];
+  RowPlane p;
+  p.nx = f.nx[i]; p.ny = f.ny[i]; p.nz = f.nz[i];
+  p.a = f.a[i]; p.b = f.b[i]; p.c = f.c[i];
+  return p;
+}
+
+template <bool CS, int SRC>
+__global__ __launch_bounds__(kRowBlock, CSPM_INIT_MINW) void k_rescore(Cost cd, Pm pm, RowQueue rq, int cap, int ocap) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  LutMem &s_lut = *reinterpret_cast<LutMem *>(smem);
+  const Luts lut = load_luts(cd, s_lut);
+  RowItem it;
+  if (!row_item(pm.W, pm.H, 2, rq, it)) return;
+  const int lane = threadIdx.x & 63;
+  RowCtx ctx = make_row_ctx(smem, it.y, cap, ocap);
+  const bool live = it.x0 + lane < pm.W;
+  const int x = live ? it.x0 + lane : pm.W - 1;  // tail lanes shadow the last pixel
+  auto gen = [&](int xs) { return stored_plane(pm, it.v, xs, it.y); };
+  const double cost = eval_rows<CS, SRC>(cd, lut, ctx, it.v, x, gen, kDoubleMax, false);
+  if (live) pm.f[it.v].cost[(long long)it.y * pm.W + x] = cost;
+}
+
+// ------------------------------------------------------------------------------------------------
 // CSPatchMatch::PlaneRefinement  (cs_patchmatch.cc:292-345): several (by default all) halving steps of one iteration in
 // one launch.  A pixel's steps depend only on that pixel's own earlier steps; its current plane lives in the plane field
 // (global memory) and is re-read where it is needed.

@@ -26,6 +26,15 @@ class CSPatchMatch {
   // cspm_local_stereo); dis(), planes(), disparity() and use_pp as after PatchMatch.  Begin / End as above (End = PatchMatchEnd).
   void LocalStereo(const int &ca_method, const IPlaneCost *plane_cost, const bool &use_pp);
   void LocalStereoBegin(const int &ca_method, const IPlaneCost *plane_cost, const bool &use_pp);
+  // warm start (an addition): iter_num PatchMatch iterations from the plane field already in the device context of plane_cost --
+  // after LocalStereo, a previous pair's run, or the planes given to SetPlanes -- instead of InitRandomPlane.  The field is re-scored
+  // under plane_cost first (include/cspm.h cspm_patchmatch_warm).  Begin may follow a LocalStereoBegin on the same cost object
+  // without its End: the run is enqueued behind it.  One of this library's device costs only: a foreign IPlaneCost throws.
+  void PatchMatchFrom(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp);
+  void PatchMatchFromBegin(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp);
+  // the starting planes of a view for the next PatchMatchFrom (a previous frame's planes(), for example): wid x hei, row-major.
+  // Kept here and written into the cost object's context when PatchMatchFromBegin runs.
+  void SetPlanes(const RefView &view, const std::vector<Plane> &planes);
 
   // additions (the reference seeds from time(NULL) and has one schedule)
   void set_seed(uint64_t seed) { seed_ = seed; }
@@ -46,6 +55,7 @@ class CSPatchMatch {
   cspm_ctx *own_ctx_;  // foreign IPlaneCost: the context that holds the plane field
   cspm_ctx *pending_ctx_;  // PatchMatchBegin without its PatchMatchEnd yet
   bool pending_pp_;
+  std::vector<Plane> start_planes_[kViewNum];  // SetPlanes, not yet written into a context
   void PatchMatchForeign(int iter_num, const IPlaneCost *plane_cost, bool use_pp);
   CSPatchMatch(const CSPatchMatch &);
 };

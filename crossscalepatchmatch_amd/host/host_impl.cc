@@ -371,6 +371,44 @@ void CSPatchMatch::LocalStereo(const int &ca_method, const IPlaneCost *plane_cos
   PatchMatchEnd();
 }
 
+void CSPatchMatch::SetPlanes(const RefView &view, const std::vector<Plane> &planes) {
+  if (planes.size() != (size_t)wid_ * hei_) throw std::runtime_error("CSPatchMatch::SetPlanes: one plane per pixel (wid x hei) expected");
+  start_planes_[view] = planes;
+}
+
+void CSPatchMatch::PatchMatchFromBegin(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp) {
+  const IDevicePlaneCost *dev = dynamic_cast<const IDevicePlaneCost *>(plane_cost);
+  if (!dev) throw std::runtime_error("CSPatchMatch::PatchMatchFrom needs one of this library's device costs (a foreign IPlaneCost runs cold only: PatchMatch)");
+  cspm_ctx *ctx = dev->device_ctx();
+  if (pending_ctx_ && pending_ctx_ != ctx) throw std::runtime_error("CSPatchMatch::PatchMatchFromBegin: the previous run has not been ended");
+  for (int v = 0; v < kViewNum; ++v) {
+    if (start_planes_[v].empty()) continue;
+    const size_t n = start_planes_[v].size();
+    std::vector<double> np(6 * n), cost(n, 0.0);  // the costs are re-scored before the first iteration
+    for (size_t i = 0; i < n; ++i) {
+      const Vec3d nv = start_planes_[v][i].norm();
+      const Vec3d pv = start_planes_[v][i].param();
+      np[6 * i] = nv[0]; np[6 * i + 1] = nv[1]; np[6 * i + 2] = nv[2];
+      np[6 * i + 3] = pv[0]; np[6 * i + 4] = pv[1]; np[6 * i + 5] = pv[2];
+    }
+    check(cspm_set_planes(ctx, v, np.data(), cost.data()), ctx, "cspm_set_planes");
+    start_planes_[v].clear();
+  }
+  cspm_pm_params p;
+  cspm_pm_default_params(&p);
+  p.seed = seed_;
+  p.schedule = schedule_;
+  p.rb_rounds = rb_rounds_;
+  check(cspm_patchmatch_warm(ctx, iter_num, &p), ctx, "cspm_patchmatch_warm");  // asynchronous: enqueued on the context's stream
+  pending_ctx_ = ctx;
+  pending_pp_ = use_pp;
+}
+
+void CSPatchMatch::PatchMatchFrom(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp) {
+  PatchMatchFromBegin(iter_num, plane_cost, use_pp);
+  PatchMatchEnd();
+}
+
 void CSPatchMatch::PatchMatch(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp) {
   PatchMatchBegin(iter_num, plane_cost, use_pp);
   PatchMatchEnd();

@@ -1,6 +1,7 @@
 // main.cc -- command line with the reference's ten flags and defaults (CSPM/main.cc:23-34) and its flow
 // (main.cc:57-139): read the pair, construct the plane cost (timed), run PatchMatch, print "Total Time", write the
-// two 8-bit maps.  Runs on the GPU through the host layer.  Extra flags: --seed --schedule --device --iters --ca_name (local stereo).
+// two 8-bit maps.  Runs on the GPU through the host layer.  Extra flags: --seed --schedule --device --iters --ca_name (local stereo)
+// --warm_ca (local stereo, then --iters warm PatchMatch iterations).
 #include "../../include/cspm.h"
 #include "commfunc.h"
 #include "cs_patchmatch.h"
@@ -31,6 +32,8 @@ DEFINE_string(pc_name, "PRE", "plane cost family: PRE = PreSSPC / PreCSPC over -
                               "IMG = GrdPC / CSPC, the volume-free colour + gradient costs (main.cc:106-107, commented out there)");
 DEFINE_string(ca_name, "", "local stereo instead of PatchMatch: cost aggregation BOX | GF | BF over --cc_name's cost volumes, then "
               "cross-scale winner-take-all (empty: PatchMatch); not with --pc_name=IMG");
+DEFINE_string(warm_ca, "", "warm-started PatchMatch: local stereo with cost aggregation BOX | GF | BF (as --ca_name), then --iters PatchMatch "
+              "iterations from its plane field instead of the random init; needs --pc_name=PRE, not with --ca_name");
 DEFINE_bool(use_cs, false, "cross-scale aggregation over a 5-level pyramid (PreCSPC) instead of PreSSPC");
 DEFINE_bool(use_pp, false, "left-right check, hole filling and weighted median afterwards");
 DEFINE_double(reg_lambda, 0.0, "cross-scale regularisation weight");
@@ -88,11 +91,11 @@ void load(PairRun &p) {
   }
 }
 
-// --ca_name -> CSPM_CA_*, -1 for a name the library does not implement
-int ca_method() {
-  if (FLAGS_ca_name == "BOX") return CSPM_CA_BOX;
-  if (FLAGS_ca_name == "GF") return CSPM_CA_GF;
-  if (FLAGS_ca_name == "BF") return CSPM_CA_BF;
+// --ca_name / --warm_ca -> CSPM_CA_*, -1 for a name the library does not implement
+int ca_method(const string &name) {
+  if (name == "BOX") return CSPM_CA_BOX;
+  if (name == "GF") return CSPM_CA_GF;
+  if (name == "BF") return CSPM_CA_BF;
   return -1;
 }
 
@@ -111,8 +114,14 @@ void begin(PairRun &p, CCMethod *cost_fn) {
     p.matcher.reset(new CSPatchMatch(p.left, p.right, FLAGS_max_dis, FLAGS_dis_scale));
     p.matcher->set_seed(static_cast<uint64_t>(FLAGS_seed));
     p.matcher->set_schedule(FLAGS_schedule == "redblack" ? 1 : 0);
-    if (FLAGS_ca_name.empty()) p.matcher->PatchMatchBegin(FLAGS_iters, p.cost.get(), FLAGS_use_pp);
-    else p.matcher->LocalStereoBegin(ca_method(), p.cost.get(), FLAGS_use_pp);
+    if (!FLAGS_warm_ca.empty()) {  // the warm run is enqueued behind the local stereo on the cost object's stream
+      p.matcher->LocalStereoBegin(ca_method(FLAGS_warm_ca), p.cost.get(), FLAGS_use_pp);
+      p.matcher->PatchMatchFromBegin(FLAGS_iters, p.cost.get(), FLAGS_use_pp);
+    } else if (FLAGS_ca_name.empty()) {
+      p.matcher->PatchMatchBegin(FLAGS_iters, p.cost.get(), FLAGS_use_pp);
+    } else {
+      p.matcher->LocalStereoBegin(ca_method(FLAGS_ca_name), p.cost.get(), FLAGS_use_pp);
+    }
   } catch (const std::exception &e) {  // a bad pair must not take the batch down
     p.log << "Error: " << e.what() << "\n";
     p.rc = EXIT_FAILURE;
@@ -264,8 +273,16 @@ int run_batch(const std::vector<BatchJob> &jobs, int skipped, int bad_lines) {
 }
 
 int run() {
-  if (!FLAGS_ca_name.empty() && ca_method() < 0) {  // checked before anything opens a device
+  if (!FLAGS_ca_name.empty() && ca_method(FLAGS_ca_name) < 0) {  // checked before anything opens a device
     cout << "Error: --ca_name must be BOX, GF or BF (got " << FLAGS_ca_name << ")\n";
+    return EXIT_FAILURE;
+  }
+  if (!FLAGS_warm_ca.empty() && ca_method(FLAGS_warm_ca) < 0) {
+    cout << "Error: --warm_ca must be BOX, GF or BF (got " << FLAGS_warm_ca << ")\n";
+    return EXIT_FAILURE;
+  }
+  if (!FLAGS_warm_ca.empty() && (FLAGS_pc_name != "PRE" || !FLAGS_ca_name.empty())) {
+    cout << "Error: --warm_ca needs --pc_name=PRE (cost volumes to aggregate) and no --ca_name\n";
     return EXIT_FAILURE;
   }
   if (!FLAGS_ca_name.empty() && FLAGS_pc_name == "IMG") {

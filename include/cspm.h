@@ -221,6 +221,24 @@ int cspm_pm_refine(cspm_ctx *ctx, int iter, const cspm_pm_params *p);
 /* plane field in/out: 6 doubles per pixel (norm, param), row-major h*w; min_cost h*w doubles */
 int cspm_get_planes(cspm_ctx *ctx, int view, double *norm_param_out, double *min_cost_out);
 int cspm_set_planes(cspm_ctx *ctx, int view, const double *norm_param, const double *min_cost);
+/* ---- warm starts (an addition: PatchMatch from a plane field that is already there) -------------
+ * re-score: min_cost of every stored plane of both views under the ctx's cost object, the planes untouched; the same evaluation as
+ * the random init's, so re-scoring the field cspm_pm_init just wrote gives its costs bit for bit.  Asynchronous on the ctx stream.
+ * CSPM_ERR_STATE without a cost object or without a plane field.  Timed under CSPM_K_INIT. */
+int cspm_rescore_planes(cspm_ctx *ctx);
+/* cspm_patchmatch with the random init replaced by a re-score of the stored field (skipped when the field's min_costs already belong
+ * to this cost object: after a run, cspm_pm_init or a re-score).  Iterations 0 .. iter_num-1: the random streams and sweep directions
+ * of a cold run, so a warm run from the field cspm_pm_init wrote is the cold run.  Asynchronous like cspm_patchmatch, with the same
+ * transparent repeat after a sweep timeout: the starting field is copied aside on the device (both views, 14 doubles per pixel,
+ * allocated by the first warm run and kept with the field).  CSPM_ERR_STATE without a cost object or a plane field; CSPM_ERR_ARG
+ * for iter_num outside 0 .. 15 or bad params. */
+int cspm_patchmatch_warm(cspm_ctx *ctx, int iter_num, const cspm_pm_params *p);
+/* one pyramid level up: dst is w x h, src (same device) holds a plane field of exactly ((w+1)/2, (h+1)/2).  Every pixel (x, y) of
+ * both views takes src's plane at (x>>1, y>>1) with the normal, a and b as they are and c doubled (d(x,y) = 2 d_src(x/2, y/2)).
+ * min_cost is left stale (the field is not consistent: cspm_patchmatch_warm re-scores it).  Checks src's sweep first (like a getter),
+ * then is asynchronous on dst's stream, ordered after the work enqueued on src's stream; src's later work waits for the copy.
+ * CSPM_ERR_STATE when src has no plane field or dst no images; CSPM_ERR_ARG for other sizes or two devices. */
+int cspm_upsample_planes(cspm_ctx *dst, cspm_ctx *src);
 /* PlaneToDisp + dis() (cs_patchmatch.cc:590-601, 111-113): saturate_u8(Round2Int(d*dis_scale)) */
 int cspm_get_disparity_u8(cspm_ctx *ctx, int view, int dis_scale, uint8_t *out, size_t stride);
 int cspm_get_disparity_f64(cspm_ctx *ctx, int view, double *out); /* unquantised a*x+b*y+c */
