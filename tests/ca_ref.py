@@ -1,6 +1,12 @@
 """numpy restatement of the reference's cost aggregation (CSPM/ca_filter/) and of local stereo over an aggregated cost volume --
 the definitions tests/test_gpu_local_stereo.py holds the HIP kernels to.  Every elementwise step is one numpy operation (IEEE f64,
-no contraction), in the reference's order; np.add.accumulate sums serially, in the reference's order."""
+no contraction), in the reference's order; np.add.accumulate sums serially, in the reference's order.
+
+This file is itself held to the reference's own code: tests/test_reference_ca.py compares cumsum, box_filter and aggre_cv with what
+ca_filter/*.cpp, compiled unmodified against the test-only OpenCV stand-in, computed (tests/golden/refca_*.npz) -- bit for bit, BF
+within rtol 1e-12 (only exp differs; the largest difference seen is 4.3e-16).  One point stays unpinned: `/` is the plain IEEE
+quotient here, in the stand-in and in the kernels, while cv::divide of OpenCV 2.4 is believed to share a reciprocal across groups of
+elements and may differ in the last place (DESIGN.md sections 2 and 10)."""
 import numpy as np
 
 BOX_R, GF_R, GF_EPS = 3, 9, float(np.float32(0.0001))  # BoxCA.cpp:11; GuidedFilter.h:24 (eps is a float promoted to double)

@@ -7,6 +7,8 @@
 // and cv::RNG is the counter-based generator of DESIGN.md section 3.1 in its ROW_SHARED mode: the reference (USE_OMP,
 // commfunc.h:170) constructs `RNG rng(time(NULL))` once per image row (cs_patchmatch.cc:129-131, 308-310), so the n-th
 // construction after refcheck::begin() identifies (phase, iteration, halving step, view) and the n-th uniform() of a row its pixel.
+// The same header serves the reference's cost-aggregation filters (ca_filter/*.cpp, tests/test_reference_ca.py): Mat::ones / eye,
+// split, multiply and the elementwise Mat operators on CV_64FC1, each with its contract beside it.
 #pragma once
 #include <algorithm>
 #include <bitset>
@@ -64,6 +66,18 @@ class Mat {
   static Mat zeros(int r, int c, int type) {
     Mat m(r, c, type);
     std::memset(m.data, 0, m.step * r);
+    return m;
+  }
+  static Mat ones(int r, int c, int type) {  // CV_64FC1 only (GuidedFilter.cpp:114): every element exactly 1.0
+    if (type != CV_64FC1) throw std::runtime_error("refcheck stand-in: Mat::ones of CV_64FC1 only");
+    Mat m(r, c, type);
+    for (int i = 0; i < r * c; ++i) reinterpret_cast<double *>(m.data)[i] = 1.0;
+    return m;
+  }
+  static Mat eye(int r, int c, int type) {  // CV_64FC1 only (GuidedFilter.cpp:189; read only outside FAST_INV)
+    if (type != CV_64FC1) throw std::runtime_error("refcheck stand-in: Mat::eye of CV_64FC1 only");
+    Mat m = zeros(r, c, type);
+    for (int i = 0; i < std::min(r, c); ++i) m.at<double>(i, i) = 1.0;
     return m;
   }
   int type() const { return type_; }
@@ -161,6 +175,73 @@ class Mat {
   int type_ = 0;
   std::shared_ptr<uchar> buf_;
 };
+
+// ---- elementwise arithmetic on CV_64FC1, as ca_filter/GuidedFilter.cpp uses it (tests/test_reference_ca.py) ----
+// Every operation below is EAGER (OpenCV builds a MatExpr and evaluates it on assignment; on these expressions the result is the
+// same array) and is ONE IEEE f64 operation per element, no contraction (the checker is compiled with -ffp-contract=off).
+// One point this stand-in cannot pin: OpenCV 2.4's cv::divide on doubles is believed to share one reciprocal across a group of
+// elements (a single division of 1 by the product of several divisors, then multiplications), which may differ from the plain
+// quotient a / b in the last place.  Without an OpenCV 2.4 build that cannot be settled; `/` below is the plain quotient
+// (DESIGN.md sections 2 and 10).
+namespace refcheck {
+inline void same_f64(const Mat &a, const Mat &b) {
+  if (a.type() != CV_64FC1 || b.type() != CV_64FC1 || a.rows != b.rows || a.cols != b.cols)
+    throw std::runtime_error("refcheck stand-in: elementwise arithmetic on CV_64FC1 matrices of one size only");
+}
+template <class F> inline Mat binary(const Mat &a, const Mat &b, F f) {
+  same_f64(a, b);
+  Mat out(a.rows, a.cols, CV_64FC1);
+  for (int y = 0; y < a.rows; ++y) {
+    const double *pa = a.ptr<double>(y), *pb = b.ptr<double>(y);
+    double *po = out.ptr<double>(y);
+    for (int x = 0; x < a.cols; ++x) po[x] = f(pa[x], pb[x]);
+  }
+  return out;
+}
+template <class F> inline void inplace(Mat &a, const Mat &b, F f) {  // writes a's own buffer, as cv::Mat's compound operators do
+  same_f64(a, b);
+  for (int y = 0; y < a.rows; ++y) {
+    double *pa = a.ptr<double>(y);
+    const double *pb = b.ptr<double>(y);
+    for (int x = 0; x < a.cols; ++x) pa[x] = f(pa[x], pb[x]);
+  }
+}
+}  // namespace refcheck
+// cv::multiply(a, b, dst) with scale 1: dst[i] = a[i] * b[i], one rounding.  dst may be a or b.
+inline void multiply(const Mat &a, const Mat &b, Mat &dst) { dst = refcheck::binary(a, b, [](double p, double q) { return p * q; }); }
+// Mat + Mat, Mat - Mat: dst[i] = a[i] + b[i] / a[i] - b[i], one rounding
+inline Mat operator+(const Mat &a, const Mat &b) { return refcheck::binary(a, b, [](double p, double q) { return p + q; }); }
+inline Mat operator-(const Mat &a, const Mat &b) { return refcheck::binary(a, b, [](double p, double q) { return p - q; }); }
+// Mat / Mat (cv::divide with scale 1): the plain quotient a[i] / b[i], one rounding -- see the unpinned point above
+inline Mat operator/(const Mat &a, const Mat &b) { return refcheck::binary(a, b, [](double p, double q) { return p / q; }); }
+// Mat + double (cv::add with a Scalar): dst[i] = a[i] + s, one rounding; a float argument is promoted to double first, exactly
+inline Mat operator+(const Mat &a, double s) {
+  if (a.type() != CV_64FC1) throw std::runtime_error("refcheck stand-in: Mat + double on CV_64FC1 only");
+  Mat out(a.rows, a.cols, CV_64FC1);
+  for (int y = 0; y < a.rows; ++y)
+    for (int x = 0; x < a.cols; ++x) out.at<double>(y, x) = a.at<double>(y, x) + s;
+  return out;
+}
+// a += b, a -= b, a /= b: a[i] = a[i] (+ - /) b[i] in a's own buffer, one rounding (`/=`: the plain quotient, as above)
+inline Mat &operator+=(Mat &a, const Mat &b) { refcheck::inplace(a, b, [](double p, double q) { return p + q; }); return a; }
+inline Mat &operator-=(Mat &a, const Mat &b) { refcheck::inplace(a, b, [](double p, double q) { return p - q; }); return a; }
+inline Mat &operator/=(Mat &a, const Mat &b) { refcheck::inplace(a, b, [](double p, double q) { return p / q; }); return a; }
+// a *= s: a[i] = a[i] * s, one rounding (GuidedFilter.cpp:190, epsEye *= eps: read only outside FAST_INV)
+inline Mat &operator*=(Mat &a, double s) {
+  if (a.type() != CV_64FC1) throw std::runtime_error("refcheck stand-in: Mat *= double on CV_64FC1 only");
+  for (int y = 0; y < a.rows; ++y)
+    for (int x = 0; x < a.cols; ++x) a.at<double>(y, x) = a.at<double>(y, x) * s;
+  return a;
+}
+// cv::split of a CV_64FC3 image into three CV_64FC1 planes: copies, channel c of the interleaved pixel to plane c
+inline void split(const Mat &src, Mat *planes) {
+  if (src.type() != CV_64FC3) throw std::runtime_error("refcheck stand-in: split of CV_64FC3 only");
+  for (int c = 0; c < 3; ++c) {
+    planes[c] = Mat(src.rows, src.cols, CV_64FC1);
+    for (int y = 0; y < src.rows; ++y)
+      for (int x = 0; x < src.cols; ++x) planes[c].at<double>(y, x) = src.ptr<double>(y)[3 * x + c];
+  }
+}
 
 struct Vec3d {
   double val[3];
