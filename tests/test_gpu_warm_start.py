@@ -1,6 +1,7 @@
 """Warm-started PatchMatch: re-scoring a stored plane field (cspm_rescore_planes), PatchMatch from it (cspm_patchmatch_warm) and
-carrying a field up one pyramid level (cspm_upsample_planes), through the C ABI, the C++ host layer and the command line.  Everything
-is held to other GPU entries (the random init, the batch engine, the single phases) or to numpy: no whole-pair CPU oracle."""
+carrying a field up one pyramid level (cspm_upsample_planes), through the C ABI, the C++ host layer and the command line.  This
+module holds them to other GPU entries (the random init, the batch engine, the single phases) or to numpy: identities between GPU
+paths.  tests/test_gpu_warm_oracle.py holds the same entries to the CPU oracle restarted from the same fields (tests/warm_ref.py)."""
 import json
 import os
 import subprocess
