@@ -42,7 +42,8 @@ SYMBOLS = [
     "cspm_get_max_cost", "cspm_get_scale_weights", "cspm_grd_build_cv_host", "cspm_plane_cost_batch",
     "cspm_pm_default_params", "cspm_patchmatch", "cspm_pm_init", "cspm_pm_spatial", "cspm_pm_view", "cspm_pm_refine",
     "cspm_get_planes", "cspm_set_planes", "cspm_get_disparity_u8", "cspm_get_disparity_f64",
-    "cspm_disparity_u8_device", "cspm_postprocess", "cspm_postprocess_device", "cspm_enable_timing", "cspm_reset_timing", "cspm_get_timing",
+    "cspm_disparity_u8_device", "cspm_postprocess", "cspm_postprocess_device", "cspm_postprocess_f64", "cspm_postprocess_f64_device",
+    "cspm_enable_timing", "cspm_reset_timing", "cspm_get_timing",
     "cspm_taps_per_view_pass", "cspm_row_engine_taps_per_view_pass", "cspm_fpm_begin", "cspm_fpm_candidates", "cspm_fpm_commit",
     "cspm_aggregate_cv_host", "cspm_local_stereo", "cspm_rescore_planes", "cspm_patchmatch_warm", "cspm_upsample_planes",
 ]
@@ -125,6 +126,8 @@ def load_library():
         "cspm_disparity_u8_device": (C.c_int, [vp, C.c_int, C.c_int, vp]),
         "cspm_postprocess": (C.c_int, [vp, C.c_int, u8p, u8p, C.c_size_t]),
         "cspm_postprocess_device": (C.c_int, [vp, C.c_int, vp, vp]),
+        "cspm_postprocess_f64": (C.c_int, [vp, dp, dp, u8p, u8p]),
+        "cspm_postprocess_f64_device": (C.c_int, [vp, vp, vp]),
         "cspm_enable_timing": (C.c_int, [vp, C.c_int]),
         "cspm_reset_timing": (C.c_int, [vp]),
         "cspm_get_timing": (C.c_int, [vp, C.c_int, llp, dp, llp]),
@@ -368,6 +371,23 @@ class StereoContext:
     def postprocess_device(self, dis_scale, d_l_ptr, d_r_ptr):
         """PlaneToDisp + PostProcessing with device-resident outputs (asynchronous on the context's stream)"""
         self._chk(self.L.cspm_postprocess_device(self.p, dis_scale, C.c_void_p(d_l_ptr), C.c_void_p(d_r_ptr)))
+
+    def postprocess_f64(self, valid=False):
+        """sub-pixel PostProcessing: left-right check, fill and weighted median on the unquantised plane
+        disparities.  Returns (l, r) f64 maps, or (l, r, l_valid, r_valid) with the u8 left-right consistency masks."""
+        l = np.zeros((self.h, self.w))
+        r = np.zeros((self.h, self.w))
+        if not valid:
+            self._chk(self.L.cspm_postprocess_f64(self.p, _dp(l), _dp(r), None, None))
+            return l, r
+        lv = np.zeros((self.h, self.w), np.uint8)
+        rv = np.zeros((self.h, self.w), np.uint8)
+        self._chk(self.L.cspm_postprocess_f64(self.p, _dp(l), _dp(r), _u8(lv), _u8(rv)))
+        return l, r, lv, rv
+
+    def postprocess_f64_device(self, d_l_ptr, d_r_ptr):
+        """the same with device-resident outputs (packed h*w f64 each; asynchronous on the context's stream)"""
+        self._chk(self.L.cspm_postprocess_f64_device(self.p, C.c_void_p(d_l_ptr), C.c_void_p(d_r_ptr)))
 
     # ---- measurement ----
     def enable_timing(self, on=True):

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "cspm_kernels.h"
+#include "cspm_pp.h"
 #include "cspm_ca.h"
 
 using namespace cspm;
@@ -114,6 +115,7 @@ struct cspm_ctx {
   uint8_t *d_dis[2] = {nullptr, nullptr};
   uint8_t *d_valid[2] = {nullptr, nullptr};  // post-processing: left-right consistency flags
   unsigned int *d_todo = nullptr;            // post-processing: per view n indices of inconsistent pixels, then the two counts
+  double *d_pp[2] = {nullptr, nullptr};      // sub-pixel post-processing (cspm_postprocess_f64): the two f64 maps, allocated by its first call and kept
   // persistent raster sweep (k_spatial_sweep)
   unsigned int *d_sweep_ctrl = nullptr, *d_sweep_start = nullptr;
   unsigned long long *d_sweep_gran = nullptr;  // persistent sweep: 12 data-tagged granules per pixel and view (cspm_chain.h)
@@ -133,8 +135,9 @@ struct cspm_ctx {
   bool last_warm = false;             // that run was cspm_patchmatch_warm: a repeat starts from warm_snap, not from the init
   double *warm_snap = nullptr;        // the starting field of the last warm run (both views, 7 arrays each), kept with the field
   long long sweep_fallbacks = 0;      // how often that happened (cspm_get_option)
-  // asynchronous outputs (cspm_disparity_u8_device / cspm_postprocess_device) enqueued behind a run whose sweep has not been checked
-  // yet: when that run is repeated after a timeout they are produced again from the repeated run's planes
+  // asynchronous outputs (cspm_disparity_u8_device / cspm_postprocess_device / cspm_postprocess_f64_device) enqueued behind a run whose
+  // sweep has not been checked yet: when that run is repeated after a timeout they are produced again from the repeated run's planes.
+  // post: 0 = PlaneToDisp of one view, 1 = the 8-bit PostProcessing, 2 = the sub-pixel one
   struct OutReq { int post, view, dis_scale; void *o0, *o1; };
   std::vector<OutReq> out_reqs;
   // a later request for the same kind of map into the same buffer replaces the earlier one (the buffer ends up holding the later map)
@@ -299,6 +302,8 @@ void free_field(cspm_ctx *c) {
   }
   if (c->d_todo) (void)hipFree(c->d_todo);
   c->d_todo = nullptr;
+  if (c->d_pp[0]) (void)hipFree(c->d_pp[0]);  // one allocation holds both maps
+  c->d_pp[0] = c->d_pp[1] = nullptr;
   if (c->d_rowq) (void)hipFree(c->d_rowq);
   c->d_rowq = nullptr;
   if (c->fpm.xy) (void)hipFree(c->fpm.xy);
@@ -740,6 +745,7 @@ int run_patchmatch(cspm_ctx *c, int iter_num, const cspm_pm_params *p);
 int run_warm_retry(cspm_ctx *c, int iter_num, const cspm_pm_params *p);
 int enqueue_disp_u8(cspm_ctx *c, int view, int dis_scale, void *d_out);
 int enqueue_postprocess_device(cspm_ctx *c, int dis_scale, void *d_l_out, void *d_r_out);
+int enqueue_postprocess_f64_device(cspm_ctx *c, void *d_l_out, void *d_r_out);
 
 int check_sweep(cspm_ctx *c) {
   if (!c->sweep_pending) return CSPM_OK;
@@ -778,7 +784,9 @@ int check_sweep(cspm_ctx *c) {
       // the maps that were enqueued behind the aborted run were computed from its planes: produce them again
       for (const auto &q : reqs) {
         if (rc != CSPM_OK) break;
-        rc = q.post ? enqueue_postprocess_device(c, q.dis_scale, q.o0, q.o1) : enqueue_disp_u8(c, q.view, q.dis_scale, q.o0);
+        rc = q.post == 2 ? enqueue_postprocess_f64_device(c, q.o0, q.o1)
+             : q.post   ? enqueue_postprocess_device(c, q.dis_scale, q.o0, q.o1)
+                        : enqueue_disp_u8(c, q.view, q.dis_scale, q.o0);
       }
       if (rc == CSPM_OK) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1062,8 +1070,8 @@ int postprocess_enqueue(cspm_ctx *c, int dis_scale) {
                      c->d_valid[1]);
   // FillInvalid (:545): a workgroup per row and view
   if (fill_rows_shmem(c->W) > 160 * 1024) return fail(c, CSPM_ERR_ARG, "image too wide for the row scan of FillInvalid");
-  LAUNCH_ONE(k_fill_rows, dim3(2u * (unsigned)c->H), dim3(kFillBlock), fill_rows_shmem(c->W), pm, dis_scale, c->d_valid[0], c->d_valid[1], c->d_dis[0],
-             c->d_dis[1], c->d_todo, todo_cnt);
+  LAUNCH_ONE(k_fill_rows<FillU8>, dim3(2u * (unsigned)c->H), dim3(kFillBlock), fill_rows_shmem(c->W), pm, (FillU8{dis_scale, c->d_dis[0], c->d_dis[1]}),
+             c->d_valid[0], c->d_valid[1], c->d_todo, todo_cnt);
   // WeightedMedian(valid, 35, WMF_GAMMA) (:571-573): a wavefront per listed pixel; exp(-i/10) is the plane-cost LUT
   hipLaunchKernelGGL(k_weighted_median, dim3((unsigned)c->ncu * 8u), dim3(kMedianBlock), 0, c->stream, L0.pix[0], L0.pix[1], L0.Wp, L0.pad, c->W,
                      c->H, c->d_valid[0], c->d_valid[1], c->d_lut, c->d_dis[0], c->d_dis[1], c->d_todo, todo_cnt, 35 / 2);
@@ -1089,6 +1097,41 @@ int enqueue_postprocess_device(cspm_ctx *c, int dis_scale, void *d_l_out, void *
   void *outs[2] = {d_l_out, d_r_out};
   for (int v = 0; v < 2; ++v)
     HIPCHK(c, hipMemcpyAsync(outs[v], c->d_dis[v], (size_t)c->W * c->H, hipMemcpyDeviceToDevice, c->stream));
+  return CSPM_OK;
+}
+
+// sub-pixel PostProcessing (cspm_pp.h) enqueued on the ctx stream; maps in c->d_pp[v], flags in c->d_valid[v].
+// The 8-bit path's maps (c->d_dis) are not touched; the flags and the work list are scratch of whichever path runs.
+int postprocess_f64_enqueue(cspm_ctx *c) {
+  const long long n = (long long)c->W * c->H;
+  if (!c->d_pp[0]) {
+    int rc = dalloc(c, &c->d_pp[0], 2 * (size_t)n, nullptr);
+    if (rc) return rc;
+    c->d_pp[1] = c->d_pp[0] + n;
+  }
+  if (fill_rows_shmem(c->W) > 160 * 1024) return fail(c, CSPM_ERR_ARG, "image too wide for the row scan of FillInvalid");
+  Pm pm{};
+  pm.W = c->W; pm.H = c->H; pm.f[0] = c->f[0]; pm.f[1] = c->f[1];
+  const Level &L0 = c->cost.lv[0];
+  Timed t(c, CSPM_K_POST, 0);
+  for (int v = 0; v < 2; ++v)
+    hipLaunchKernelGGL(k_plane_to_disp_f64, dim3(ew_grid(n)), dim3(256), 0, c->stream, pm, v, c->d_pp[v]);
+  unsigned int *todo_cnt = c->d_todo + 2 * (size_t)n;
+  HIPCHK(c, hipMemsetAsync(todo_cnt, 0, 2 * sizeof(unsigned int), c->stream));
+  hipLaunchKernelGGL(k_lr_check_f64, dim3(ew_grid(2 * n)), dim3(256), 0, c->stream, c->d_pp[0], c->d_pp[1], c->W, c->H, c->d_valid[0], c->d_valid[1]);
+  LAUNCH_ONE(k_fill_rows<FillF64>, dim3(2u * (unsigned)c->H), dim3(kFillBlock), fill_rows_shmem(c->W), pm,
+             (FillF64{(double)c->max_dis, c->d_pp[0], c->d_pp[1]}), c->d_valid[0], c->d_valid[1], c->d_todo, todo_cnt);
+  hipLaunchKernelGGL(k_weighted_median_f64, dim3((unsigned)c->ncu * (unsigned)kPpGrid), dim3(kWave), 0, c->stream, L0.pix[0], L0.pix[1], L0.Wp, L0.pad,
+                     c->W, c->H, c->d_valid[0], c->d_valid[1], c->d_lut, c->d_pp[0], c->d_pp[1], c->d_todo, todo_cnt);
+  HIPCHK(c, hipGetLastError());
+  return CSPM_OK;
+}
+int enqueue_postprocess_f64_device(cspm_ctx *c, void *d_l_out, void *d_r_out) {
+  int rc = postprocess_f64_enqueue(c);
+  if (rc) return rc;
+  void *outs[2] = {d_l_out, d_r_out};
+  for (int v = 0; v < 2; ++v)
+    HIPCHK(c, hipMemcpyAsync(outs[v], c->d_pp[v], sizeof(double) * (size_t)c->W * c->H, hipMemcpyDeviceToDevice, c->stream));
   return CSPM_OK;
 }
 
@@ -2057,6 +2100,38 @@ int cspm_postprocess_device(cspm_ctx *c, int dis_scale, void *d_l_out, void *d_r
   if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
   if (c->sweep_pending) c->remember_output(cspm_ctx::OutReq{1, 0, dis_scale, d_l_out, d_r_out});  // see cspm_disparity_u8_device
   return enqueue_postprocess_device(c, dis_scale, d_l_out, d_r_out);
+}
+
+// sub-pixel PostProcessing: the f64 maps and, where asked for, the left-right consistency flags
+int cspm_postprocess_f64(cspm_ctx *c, double *l_out, double *r_out, uint8_t *l_valid_out, uint8_t *r_valid_out) {
+  if (!c) return CSPM_ERR_ARG;
+  if (!c->field_alloc || !c->cost_alloc) return fail(c, CSPM_ERR_STATE, "cspm_postprocess_f64 needs a finished PatchMatch");
+  if (!l_out || !r_out) return fail(c, CSPM_ERR_ARG, "bad outputs");
+  DevGuard guard_(c->device);
+  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  int rc = check_sweep(c);
+  if (rc) return rc;
+  if ((rc = postprocess_f64_enqueue(c))) return rc;
+  const size_t n = (size_t)c->W * c->H;
+  double *outs[2] = {l_out, r_out};
+  uint8_t *flags[2] = {l_valid_out, r_valid_out};
+  for (int v = 0; v < 2; ++v) {
+    HIPCHK(c, hipMemcpyAsync(outs[v], c->d_pp[v], sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    if (flags[v]) HIPCHK(c, hipMemcpyAsync(flags[v], c->d_valid[v], n, hipMemcpyDeviceToHost, c->stream));
+  }
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return CSPM_OK;
+}
+
+// the same with device-resident outputs (W*H f64 each, packed rows): asynchronous like cspm_postprocess_device
+int cspm_postprocess_f64_device(cspm_ctx *c, void *d_l_out, void *d_r_out) {
+  if (!c) return CSPM_ERR_ARG;
+  if (!c->field_alloc || !c->cost_alloc) return fail(c, CSPM_ERR_STATE, "cspm_postprocess_f64_device needs a finished PatchMatch");
+  if (!d_l_out || !d_r_out) return fail(c, CSPM_ERR_ARG, "bad outputs");
+  DevGuard guard_(c->device);
+  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  if (c->sweep_pending) c->remember_output(cspm_ctx::OutReq{2, 0, 0, d_l_out, d_r_out});  // see cspm_disparity_u8_device
+  return enqueue_postprocess_f64_device(c, d_l_out, d_r_out);
 }
 
 int cspm_enable_timing(cspm_ctx *c, int on) {

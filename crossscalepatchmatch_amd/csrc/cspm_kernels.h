@@ -166,8 +166,14 @@ inline size_t fill_rows_shmem(int W) { return (size_t)((W + 3) & ~3) + sizeof(in
 
 // FillInvalid (:370-428).  Grid = 2*H workgroups (view-major).  todo[v*n ...] receives the row-major indices of the view's
 // inconsistent pixels (rows in no particular order: the median treats them independently), todo_cnt[v] their number.
-__global__ __launch_bounds__(kFillBlock) void k_fill_rows(Pm pm, int dis_scale, const uint8_t *__restrict__ ok0, const uint8_t *__restrict__ ok1,
-                                                          uint8_t *__restrict__ dis0, uint8_t *__restrict__ dis1,
+// `Out` says what an inconsistent pixel receives: FillU8 the reference's whole-pixel 8-bit value, FillF64 (cspm_pp.h) the value itself.
+struct FillU8 {
+  int dis_scale;
+  uint8_t *dis0, *dis1;
+  __device__ __forceinline__ void store(int v, long long i, double d) const { (v ? dis1 : dis0)[i] = sat_u8(dis_scale * round2int(d)); }
+};
+template <class Out>
+__global__ __launch_bounds__(kFillBlock) void k_fill_rows(Pm pm, Out out_map, const uint8_t *__restrict__ ok0, const uint8_t *__restrict__ ok1,
                                                           unsigned int *__restrict__ todo, unsigned int *__restrict__ todo_cnt) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fill_smem[];
   const int W = pm.W, H = pm.H, t = (int)threadIdx.x;
@@ -177,7 +183,6 @@ __global__ __launch_bounds__(kFillBlock) void k_fill_rows(Pm pm, int dis_scale, 
   int *near_l = reinterpret_cast<int *>(fill_smem + ((W + 3) & ~3));
   int *run_l = near_l + W, *run_r = run_l + kFillBlock, *list_base = run_r + kFillBlock;
   const uint8_t *ok = (v ? ok1 : ok0) + row;
-  uint8_t *dis = (v ? dis1 : dis0) + row;
   for (int x = t; x < W; x += kFillBlock) flag[x] = ok[x];  // coalesced
   __syncthreads();
   // lane-private run [x0, x1): last consistent column in it, first consistent column in it, number of inconsistent ones
@@ -224,11 +229,11 @@ __global__ __launch_bounds__(kFillBlock) void k_fill_rows(Pm pm, int dis_scale, 
     const int l = near_l[x], r = carry;
     if (l >= 0 && r < W) {
       const double dl = plane_disp_at(f, row + l, x, y), dr = plane_disp_at(f, row + r, x, y);
-      dis[x] = sat_u8(dis_scale * round2int(dl <= dr ? dl : dr));
+      out_map.store(v, row + x, dl <= dr ? dl : dr);
     } else if (l >= 0) {
-      dis[x] = sat_u8(dis_scale * round2int(plane_disp_at(f, row + l, x, y)));
+      out_map.store(v, row + x, plane_disp_at(f, row + l, x, y));
     } else if (r < W) {
-      dis[x] = sat_u8(dis_scale * round2int(plane_disp_at(f, row + r, x, y)));
+      out_map.store(v, row + x, plane_disp_at(f, row + r, x, y));
     }
     *out++ = (unsigned int)(row + x);
   }

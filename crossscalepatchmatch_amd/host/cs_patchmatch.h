@@ -45,6 +45,10 @@ class CSPatchMatch {
   void planes(const RefView &view, std::vector<Plane> *out, std::vector<double> *min_cost) const;
   // unquantised disparity a*x+b*y+c of every pixel, row-major (what PlaneToDisp rounds, cs_patchmatch.cc:590-601)
   void disparity(const RefView &view, std::vector<double> *out) const;
+  // sub-pixel PostProcessing (an addition; include/cspm.h cspm_postprocess_f64): left-right check, fill and weighted median on the
+  // unquantised disparities of both views, row-major; either output may be NULL.  Needs the cost object's images like use_pp (a
+  // foreign IPlaneCost has them after a run with use_pp).  dis() and the plane field are not changed.
+  void PostProcessedDisparity(std::vector<double> *l_out, std::vector<double> *r_out) const;
 
  private:
   Mat img_[kViewNum], dis_[kViewNum];

@@ -421,6 +421,16 @@ void CSPatchMatch::disparity(const RefView &view, std::vector<double> *out) cons
   check(cspm_get_disparity_f64(last_ctx_, view, out->data()), last_ctx_, "cspm_get_disparity_f64");
 }
 
+void CSPatchMatch::PostProcessedDisparity(std::vector<double> *l_out, std::vector<double> *r_out) const {
+  if (!last_ctx_) throw std::runtime_error("CSPatchMatch::PostProcessedDisparity before PatchMatch");
+  if (!DevicePlaneCost::is_live(last_ctx_)) throw std::runtime_error("CSPatchMatch::PostProcessedDisparity: the plane cost PatchMatch ran on has been deleted");
+  if (!l_out && !r_out) return;
+  std::vector<double> unwanted;  // the library post-processes both views in one call
+  std::vector<double> *outs[kViewNum] = {l_out ? l_out : &unwanted, r_out ? r_out : &unwanted};
+  for (int v = 0; v < kViewNum; ++v) outs[v]->resize((size_t)wid_ * hei_);
+  check(cspm_postprocess_f64(last_ctx_, outs[kLeft]->data(), outs[kRight]->data(), NULL, NULL), last_ctx_, "cspm_postprocess_f64");
+}
+
 void CSPatchMatch::planes(const RefView &view, std::vector<Plane> *out, std::vector<double> *min_cost) const {
   if (!last_ctx_) throw std::runtime_error("CSPatchMatch::planes before PatchMatch");
   if (!DevicePlaneCost::is_live(last_ctx_)) throw std::runtime_error("CSPatchMatch::planes: the plane cost PatchMatch ran on has been deleted");

@@ -45,6 +45,8 @@ DEFINE_int32(iters, 3, "PatchMatch iterations (3 in the reference, main.cc:93)")
 DEFINE_string(l_disp_pfm, "", "also write the left sub-pixel disparity map as float32 PFM: the unquantised plane disparity a*x+b*y+c, "
                               "BEFORE post-processing (--use_pp changes the 8-bit maps only, as in the reference)");
 DEFINE_string(r_disp_pfm, "", "also write the right sub-pixel disparity map as float32 PFM (see --l_disp_pfm)");
+DEFINE_bool(pp_pfm, false, "with --use_pp: the PFM maps (--l_disp_pfm / --r_disp_pfm, or the batch list's) receive the sub-pixel post-processed "
+                           "disparities -- left-right check, fill and weighted median on a*x+b*y+c itself -- instead of the raw plane disparities");
 DEFINE_string(batch_list, "", "text file, one stereo pair per line: l_img r_img l_dis r_dis [l_pfm r_pfm]; all pairs run with the "
                               "matching flags of this command line on one device context (buffers are reused between pairs). A pair "
                               "that fails is reported and the batch goes on; the exit code is non-zero if any pair failed");
@@ -139,8 +141,13 @@ void finish(PairRun &p) {
               << "Total Time: " << seconds << "\n"
               << "--------------------------------------------------------\n";
       const string *pfm[kViewNum] = {&p.files.l_pfm, &p.files.r_pfm};
-      for (int v = 0; v < kViewNum; ++v)
-        if (!pfm[v]->empty()) p.matcher->disparity(v == 0 ? kLeft : kRight, &p.pfm[v]);  // reads the cost object's context: before it goes
+      if (FLAGS_pp_pfm) {  // one call post-processes both views
+        if (!pfm[0]->empty() || !pfm[1]->empty())
+          p.matcher->PostProcessedDisparity(pfm[0]->empty() ? NULL : &p.pfm[0], pfm[1]->empty() ? NULL : &p.pfm[1]);
+      } else {
+        for (int v = 0; v < kViewNum; ++v)
+          if (!pfm[v]->empty()) p.matcher->disparity(v == 0 ? kLeft : kRight, &p.pfm[v]);  // reads the cost object's context: before it goes
+      }
     } catch (const std::exception &e) {
       p.log << "Error: " << e.what() << "\n";
       p.rc = EXIT_FAILURE;
@@ -273,6 +280,10 @@ int run_batch(const std::vector<BatchJob> &jobs, int skipped, int bad_lines) {
 }
 
 int run() {
+  if (FLAGS_pp_pfm && !FLAGS_use_pp) {  // checked before anything opens a device
+    cout << "Error: --pp_pfm post-processes the PFM maps and needs --use_pp\n";
+    return EXIT_FAILURE;
+  }
   if (!FLAGS_ca_name.empty() && ca_method(FLAGS_ca_name) < 0) {  // checked before anything opens a device
     cout << "Error: --ca_name must be BOX, GF or BF (got " << FLAGS_ca_name << ")\n";
     return EXIT_FAILURE;
@@ -290,8 +301,8 @@ int run() {
     return EXIT_FAILURE;
   }
   DevicePlaneCost::device = FLAGS_device;
-  if (FLAGS_use_pp && !(FLAGS_l_disp_pfm.empty() && FLAGS_r_disp_pfm.empty()) && !FLAGS_quiet)
-    cout << "Note: the PFM maps hold the plane disparities before post-processing\n";
+  if (FLAGS_use_pp && !FLAGS_pp_pfm && !(FLAGS_l_disp_pfm.empty() && FLAGS_r_disp_pfm.empty()) && !FLAGS_quiet)
+    cout << "Note: the PFM maps hold the plane disparities before post-processing (--pp_pfm writes the post-processed ones)\n";
   if (FLAGS_batch_list.empty()) {
     const std::unique_ptr<CCMethod> cost_fn(GetCCType(FLAGS_cc_name));  // NULL for unknown names, rejected by the cost constructors
     if (!FLAGS_quiet) cout << "Load Image: " << FLAGS_l_img_file << " " << FLAGS_r_img_file << "\n";

@@ -245,7 +245,7 @@ int cspm_get_disparity_f64(cspm_ctx *ctx, int view, double *out); /* unquantised
 /* device-resident result (u8, packed w*h) for the batch driver.  Asynchronous; when the PatchMatch run in front of it is repeated
  * after a sweep timeout (CSPM_OPT_SWEEP_TIMEOUT_MS), the map is written again from the repeated run's planes before the
  * synchronising call returns success.
- * CONTRACT for every asynchronous output (this call and cspm_postprocess_device): the buffer must stay allocated, and its contents
+ * CONTRACT for every asynchronous output (this call, cspm_postprocess_device and cspm_postprocess_f64_device): the buffer must stay allocated, and its contents
  * must not be consumed, until a synchronising cspm_* call on this ctx (cspm_synchronize, any cspm_get_*, cspm_postprocess) has
  * returned CSPM_OK after the request.  Synchronising the stream or an event of your own is NOT enough: only the cspm_* call looks at
  * the sweep's error word, and if the sweep timed out the map that stream-side synchronisation sees was written from the aborted run
@@ -257,6 +257,15 @@ int cspm_postprocess(cspm_ctx *ctx, int dis_scale, uint8_t *l_out, uint8_t *r_ou
 /* the same with device-resident outputs (u8, packed w*h each); asynchronous on the ctx stream like cspm_patchmatch --
  * PatchMatch(iter_num, plane_cost, use_pp = true) without leaving the device (cs_patchmatch.cc:103-107) */
 int cspm_postprocess_device(cspm_ctx *ctx, int dis_scale, void *d_l_out, void *d_r_out);
+/* sub-pixel PostProcessing (an addition): the reference's three steps -- left-right check, fill, weighted
+ * median -- on the unquantised a*x+b*y+c of both views instead of the 8-bit maps.  Needs a plane field, a cost object and images,
+ * like cspm_postprocess.  l_out / r_out: w*h doubles each (packed rows); valid pixels hold what cspm_get_disparity_f64 returns,
+ * inconsistent ones the filled (clamped to [0, max_dis]) or median value.  l_valid_out / r_valid_out (w*h bytes each, 1 = the pixel
+ * passed the left-right check) may be NULL.  Synchronises.  The 8-bit maps are untouched: cspm_postprocess before or after this
+ * call gives what it gives alone, and vice versa. */
+int cspm_postprocess_f64(cspm_ctx *ctx, double *l_out, double *r_out, uint8_t *l_valid_out, uint8_t *r_valid_out);
+/* device-resident outputs (packed w*h f64 each), asynchronous on the ctx stream; the CONTRACT for asynchronous outputs above holds */
+int cspm_postprocess_f64_device(cspm_ctx *ctx, void *d_l_out, void *d_r_out);
 
 /* ---- CSPatchMatch::PatchMatch over a FOREIGN IPlaneCost (plane_cost/i_plane_cost.h:28-33) ------------------------------
  * Any object with a GetPlaneCost(x, y, plane, view) that is not one of this library's device costs: the reference drives it
