@@ -15,7 +15,7 @@ import os
 import numpy as np
 
 PARAM_KEYS = ("w", "h", "max_dis", "dis_scale", "scale_num", "reg_lambda", "iters", "seed", "schedule", "use_pp", "cc")
-CC_CODES = {"GRD": 0, "CEN": 1, "IMG": 2}  # params["cc"]: the cost family (cc/grd_cc, cc/cen_cc; IMG = GrdPC / CSPC)
+CC_CODES = {"GRD": 0, "CEN": 1, "IMG": 2, "CENGRD": 3}  # params["cc"]: the cost family (cc/grd_cc, cc/cen_cc; IMG = GrdPC / CSPC; cc/cengrd_cc)
 
 
 def partition(n_items, world, rank):
@@ -90,6 +90,8 @@ class HipPairFn:
             ctx.build_cost_img(*args)
         elif cc == CC_CODES["CEN"]:
             ctx.build_cost_cen(*args)
+        elif cc == CC_CODES["CENGRD"]:
+            ctx.build_cost_cengrd(*args)
         else:
             ctx.build_cost_grd(*args)
         ctx.patchmatch(int(p["iters"]), seed=int(p["seed"]), schedule=int(p["schedule"]))

@@ -33,11 +33,12 @@ OPT_VIEW_SORT = 17           # view propagation evaluates a row's proposals in t
 OPT_SWEEP_FOLD = 18          # cross-scale sweep workgroups of levels - 1 waves, the coarsest level folded onto them (default 1; identical planes)
 OPT_FAULT_VOLUME_ALLOC = 16  # write only, TEST HOOK: the n-th optional-volume allocation from now on fails
 CA_BOX, CA_GF, CA_BF = 0, 1, 2  # cost aggregation: BoxCA, GFCA, BFCA (ca_filter/)
+CENGRD_KAPPA, CENGRD_TAU = 0.0625, 32.0  # CSPM_CENGRD_KAPPA / CSPM_CENGRD_TAU: cell = fma(KAPPA, min(H, TAU), G)
 
 # every symbol include/cspm.h declares
 SYMBOLS = [
     "cspm_device_count", "cspm_create", "cspm_destroy", "cspm_last_error", "cspm_set_stream", "cspm_get_stream", "cspm_synchronize",
-    "cspm_set_images", "cspm_set_images_device", "cspm_build_cost_grd", "cspm_build_cost_cen", "cspm_build_cost_img", "cspm_cen_build_cv_host", "cspm_set_option", "cspm_get_option", "cspm_begin_cost", "cspm_upload_cost_slab",
+    "cspm_set_images", "cspm_set_images_device", "cspm_build_cost_grd", "cspm_build_cost_cen", "cspm_build_cost_cengrd", "cspm_build_cost_img", "cspm_cen_build_cv_host", "cspm_cengrd_build_cv_host", "cspm_set_option", "cspm_get_option", "cspm_begin_cost", "cspm_upload_cost_slab",
     "cspm_finish_cost", "cspm_get_levels", "cspm_get_level_dims", "cspm_get_level_image", "cspm_get_cost_slab",
     "cspm_get_max_cost", "cspm_get_scale_weights", "cspm_grd_build_cv_host", "cspm_plane_cost_batch",
     "cspm_pm_default_params", "cspm_patchmatch", "cspm_pm_init", "cspm_pm_spatial", "cspm_pm_view", "cspm_pm_refine",
@@ -100,8 +101,10 @@ def load_library():
         "cspm_set_option": (C.c_int, [vp, C.c_int, C.c_longlong]),
         "cspm_get_option": (C.c_int, [vp, C.c_int, llp]),
         "cspm_build_cost_cen": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double]),
+        "cspm_build_cost_cengrd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double]),
         "cspm_build_cost_img": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double]),
         "cspm_cen_build_cv_host": (C.c_int, [C.c_int, dp, dp, C.c_int, C.c_int, C.c_int, C.c_int, dp]),
+        "cspm_cengrd_build_cv_host": (C.c_int, [C.c_int, dp, dp, C.c_int, C.c_int, C.c_int, C.c_int, dp]),
         "cspm_begin_cost": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_double]),
         "cspm_upload_cost_slab": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, dp, C.c_size_t]),
         "cspm_finish_cost": (C.c_int, [vp]),
@@ -235,6 +238,10 @@ class StereoContext:
     def build_cost_cen(self, max_dis, wnd_size=35, scale_num=0, reg_lambda=0.0, volumes=False):
         self.set_option(OPT_GRD_VOLUMES, int(volumes))
         self._chk(self.L.cspm_build_cost_cen(self.p, max_dis, wnd_size, scale_num, reg_lambda))
+
+    def build_cost_cengrd(self, max_dis, wnd_size=35, scale_num=0, reg_lambda=0.0):
+        """CENGRD: census and GRD blended per cell; always materialised f64 volumes, whatever OPT_GRD_VOLUMES says"""
+        self._chk(self.L.cspm_build_cost_cengrd(self.p, max_dis, wnd_size, scale_num, reg_lambda))
 
     def build_cost_img(self, max_dis, wnd_size=35, scale_num=0, reg_lambda=0.0):
         """GrdPC (scale_num=0) / CSPC: the volume-free plane costs (plane_cost/grd_pc.cc, cspc.cc)"""
@@ -439,10 +446,12 @@ def coarse_to_fine(l, r, max_dis, coarse_iters=3, fine_iters=1, cc="GRD", wnd_si
             c.build_cost_grd(md, wnd_size, scale_num, reg_lambda, volumes=volumes)
         elif cc == "CEN":
             c.build_cost_cen(md, wnd_size, scale_num, reg_lambda, volumes=volumes)
+        elif cc == "CENGRD":
+            c.build_cost_cengrd(md, wnd_size, scale_num, reg_lambda)
         elif cc == "IMG":
             c.build_cost_img(md, wnd_size, scale_num, reg_lambda)
         else:
-            raise ValueError(f"unknown cost {cc!r} (GRD, CEN or IMG)")
+            raise ValueError(f"unknown cost {cc!r} (GRD, CEN, CENGRD or IMG)")
 
     try:
         full.set_images(l, r)

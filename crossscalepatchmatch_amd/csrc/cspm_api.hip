@@ -50,7 +50,7 @@ struct CostKey {
            with_pairs == o.with_pairs && with_cvol == o.with_cvol && with_px8 == o.with_px8;
   }
 };
-enum { kKindForeign = 0, kKindGrd = 1, kKindCen = 2, kKindImg = 3 };
+enum { kKindForeign = 0, kKindGrd = 1, kKindCen = 2, kKindImg = 3, kKindCenGrd = 4 };
 
 struct cspm_ctx {
   int device = 0, ncu = 256;
@@ -84,6 +84,7 @@ struct cspm_ctx {
   bool is_grd = false;           // cost built by cspm_build_cost_grd (gradients present)
   bool is_cen = false;           // cost built by cspm_build_cost_cen (census codes present)
   bool is_img = false;           // cost built by cspm_build_cost_img (GrdPC / CSPC: no cells, no volumes)
+  bool is_cengrd = false;        // cost built by cspm_build_cost_cengrd (gradients and census codes present, always volume-sourced)
   const uint32_t *cen_code[2][CSPM_MAX_LEVELS] = {{nullptr}};
   long long opt_grd_volumes = 0; // CSPM_OPT_GRD_VOLUMES
   long long opt_sweep_pairs = 0;   // CSPM_OPT_SWEEP_PAIRS: 0 = never (default: measured no faster), 1 = when they fit
@@ -552,6 +553,15 @@ int alloc_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg
           c->cen_gray[v][s] = gray;
           c->cen_code[v][s] = code;
           L.pc[v] = pc;
+        } else if (kind == kKindCenGrd) {  // what k_cengrd_volume reads: gradients, 8-bit gray and census codes; the tap engines read the volumes and, for the window weights, the colour elements L.px every kind has
+          double *g;
+          uint8_t *gray;
+          uint32_t *code;
+          if ((rc = dalloc(c, &g, ppx, &c->cost_allocs)) || (rc = dalloc(c, &gray, px, &c->cost_allocs)) || (rc = dalloc(c, &code, px * 3, &c->cost_allocs)))
+            return rc;
+          L.grd[v] = g;
+          c->cen_gray[v][s] = gray;
+          c->cen_code[v][s] = code;
         }
       }
     }
@@ -637,6 +647,7 @@ int alloc_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg
   c->is_grd = false;
   c->is_cen = false;
   c->is_img = false;
+  c->is_cengrd = false;
   c->sweep_pairs = false;
   c->sweep_packed = false;
   return CSPM_OK;
@@ -1566,6 +1577,43 @@ int cspm_build_cost_cen(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, d
   return finish_cost(c, false);
 }
 
+// CENGRD (include/cspm.h): per level the gradients of cspm_build_cost_grd and the census codes of
+// cspm_build_cost_cen, then ONE kernel per view that writes every cell fma(KAPPA, min(H, TAU_CEN), G) and reduces the max.  Always
+// volume-sourced: the PatchMatch kernels, local stereo and cspm_get_cost_slab read the volumes like any CCMethod's.
+int cspm_build_cost_cengrd(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg_lambda) {
+  if (!c) return CSPM_ERR_ARG;
+  DevGuard guard_(c->device);
+  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  int rc = alloc_cost(c, max_dis, wnd_size, scale_num, reg_lambda, true, kKindCenGrd);
+  if (rc == CSPM_ERR_HIP) return fail(c, rc, "cspm_build_cost_cengrd: device allocation failed (" + c->err + "): the cost needs its f64 volumes on the device, there is no CPU fallback");
+  if (rc) return rc;
+  Cost &cd = c->cost;
+  for (int s = 0; s < cd.levels; ++s) {
+    Level &L = cd.lv[s];
+    const long long px = (long long)L.W * L.H, ppx = (long long)L.Wp * L.H;
+    for (int v = 0; v < 2; ++v) {
+      double *g = const_cast<double *>(L.grd[v]);
+      uint8_t *gray = c->cen_gray[v][s];
+      uint32_t *code = const_cast<uint32_t *>(c->cen_code[v][s]);
+      Timed t(c, CSPM_K_GRD, 0);
+      hipLaunchKernelGGL(k_gradient<SrcU32>, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, SrcU32{L.pix[v], L.Wp, L.pad}, L.W, L.H, L.Wp, L.pad, g);
+      hipLaunchKernelGGL(k_gray8<SrcU32>, dim3(ew_grid(px)), dim3(256), 0, c->stream, SrcU32{L.pix[v], L.Wp, L.pad}, L.W, L.H, gray);
+      hipLaunchKernelGGL(k_census, dim3(ew_grid(px)), dim3(256), 0, c->stream, gray, L.W, L.H, code);
+      hipLaunchKernelGGL(k_make_aos, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, L.pix[v], (const double *)nullptr, ppx, (PixG *)L.px[v]);
+    }
+    for (int v = 0; v < 2; ++v) {
+      Timed t(c, CSPM_K_GRD, 0);
+      hipLaunchKernelGGL(k_cengrd_volume<SrcU32>, dim3(stride_grid(px * (L.D + 1))), dim3(256), 0, c->stream, SrcU32{L.pix[0], L.Wp, L.pad},
+                         SrcU32{L.pix[1], L.Wp, L.pad}, L.grd[0], L.grd[1], L.Wp, L.pad, c->cen_code[0][s], c->cen_code[1][s], L.W, L.H, 0, L.D + 1, v,
+                         (double *)L.vol[v], c->d_maxkeys + v * CSPM_MAX_LEVELS + s);
+    }
+  }
+  HIPCHK(c, hipGetLastError());
+  cd.fused = kSrcVolume;
+  c->is_cengrd = true;
+  return finish_cost(c, false);  // G >= 0 and KAPPA*min(H, TAU_CEN) >= 0: every cell is >= 0
+}
+
 // `new GrdPC(l, r, max_dis, wnd)` (scale_num == 0; plane_cost/grd_pc.cc:11-66) / `new CSPC(l, r, max_dis, wnd, scale_num,
 // reg_lambda)` (cspc.cc:11-93): pyramid, 8U gray and its x-gradient per level; no volumes, no CCMethod.  max_cost_ has no
 // counterpart in these classes: the "impossible disparity" cost is a constant (grd_pc.cc:131-132, cspc.cc:150-152).
@@ -1627,6 +1675,43 @@ int cspm_cen_build_cv_host(int device, const double *l_rgb, const double *r_rgb,
   return done(CSPM_OK);
 }
 
+// CenGrdCC::buildCV / buildRightCV on host buffers: the CENGRD cells (include/cspm.h) from CV_64FC3 images, gradients as
+// cspm_grd_build_cv_host derives them, census codes as cspm_cen_build_cv_host does
+int cspm_cengrd_build_cv_host(int device, const double *l_rgb, const double *r_rgb, int w, int h, int maxDis, int right_view, double *vol_out) {
+  if (!l_rgb || !r_rgb || !vol_out || w < 1 || h < 1 || maxDis < 1) return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
+  cspm_ctx *c = nullptr;
+  int rc = cspm_create(&c, device);
+  if (rc) return rc;
+  const size_t px = (size_t)w * h;
+  double *d[2] = {nullptr, nullptr}, *grd[2] = {nullptr, nullptr}, *vol = nullptr;
+  uint8_t *gray[2];
+  uint32_t *code[2];
+  std::vector<void *> tmp;
+  auto done = [&](int code_) {
+    if (code_) g_create_error = c->err;
+    for (void *p : tmp) (void)hipFree(p);
+    cspm_destroy(c);
+    return code_;
+  };
+  const double *src[2] = {l_rgb, r_rgb};
+  for (int v = 0; v < 2; ++v) {
+    if ((rc = dalloc(c, &d[v], px * 3, &tmp)) || (rc = dalloc(c, &grd[v], px, &tmp)) || (rc = dalloc(c, &gray[v], px, &tmp)) ||
+        (rc = dalloc(c, &code[v], px * 3, &tmp)))
+      return done(rc);
+    if (hipMemcpyAsync(d[v], src[v], sizeof(double) * px * 3, hipMemcpyHostToDevice, c->stream) != hipSuccess) return done(fail(c, CSPM_ERR_HIP, "upload failed"));
+    hipLaunchKernelGGL(k_gradient<SrcF64>, dim3(ew_grid((long long)px)), dim3(256), 0, c->stream, SrcF64{d[v], w}, w, h, w, 0, grd[v]);
+    hipLaunchKernelGGL(k_gray8<SrcF64>, dim3(ew_grid((long long)px)), dim3(256), 0, c->stream, SrcF64{d[v], w}, w, h, gray[v]);
+    hipLaunchKernelGGL(k_census, dim3(ew_grid((long long)px)), dim3(256), 0, c->stream, gray[v], w, h, code[v]);
+  }
+  if ((rc = dalloc(c, &vol, px * maxDis, &tmp))) return done(rc);
+  hipLaunchKernelGGL(k_cengrd_volume<SrcF64>, dim3(stride_grid((long long)px * maxDis)), dim3(256), 0, c->stream, SrcF64{d[0], w}, SrcF64{d[1], w}, grd[0],
+                     grd[1], w, 0, code[0], code[1], w, h, 0, maxDis, right_view, vol, (unsigned long long *)nullptr);
+  if (hipMemcpyAsync(vol_out, vol, sizeof(double) * px * maxDis, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess)
+    return done(fail(c, CSPM_ERR_HIP, "CENGRD volume kernel failed"));
+  return done(CSPM_OK);
+}
+
 int cspm_begin_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg_lambda) {
   if (!c) return CSPM_ERR_ARG;
   DevGuard guard_(c->device);
@@ -1645,7 +1730,7 @@ int cspm_begin_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, doubl
 
 int cspm_upload_cost_slab(cspm_ctx *c, int view, int level, int d, const double *slab, size_t stride_elems) {
   if (!c) return CSPM_ERR_ARG;
-  if (!c->cost_alloc || c->is_grd || c->is_cen || c->is_img || !c->cost.lv[0].vol[0]) return fail(c, CSPM_ERR_STATE, "cspm_begin_cost first");
+  if (!c->cost_alloc || c->is_grd || c->is_cen || c->is_img || c->is_cengrd || !c->cost.lv[0].vol[0]) return fail(c, CSPM_ERR_STATE, "cspm_begin_cost first");
   if (view < 0 || view > 1 || level < 0 || level >= c->cost.levels || !slab) return fail(c, CSPM_ERR_ARG, "bad view/level/slab");
   const Level &L = c->cost.lv[level];
   if (d < 0 || d > L.D || stride_elems < (size_t)L.W) return fail(c, CSPM_ERR_ARG, "bad slab index or stride");
@@ -1661,7 +1746,7 @@ int cspm_upload_cost_slab(cspm_ctx *c, int view, int level, int d, const double 
 
 int cspm_finish_cost(cspm_ctx *c) {
   if (!c) return CSPM_ERR_ARG;
-  if (!c->cost_alloc || c->is_grd || c->is_cen || c->is_img || !c->cost.lv[0].vol[0]) return fail(c, CSPM_ERR_STATE, "cspm_begin_cost first");
+  if (!c->cost_alloc || c->is_grd || c->is_cen || c->is_img || c->is_cengrd || !c->cost.lv[0].vol[0]) return fail(c, CSPM_ERR_STATE, "cspm_begin_cost first");
   DevGuard guard_(c->device);
   if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
   HIPCHK(c, hipMemsetAsync(c->d_maxkeys, 0, sizeof(unsigned long long) * 2 * CSPM_MAX_LEVELS, c->stream));
@@ -1802,7 +1887,7 @@ int cspm_aggregate_cv_host(int device, int method, const double *guide, int w, i
 int cspm_local_stereo(cspm_ctx *c, int method) {
   if (!c) return CSPM_ERR_ARG;
   if (method < CSPM_CA_BOX || method > CSPM_CA_BF) return fail(c, CSPM_ERR_ARG, "unknown aggregation method (CSPM_CA_BOX / GF / BF)");
-  if (!c->cost_alloc || !c->cost_ready) return fail(c, CSPM_ERR_STATE, "local stereo needs a cost object (cspm_build_cost_grd / _cen / cspm_finish_cost)");
+  if (!c->cost_alloc || !c->cost_ready) return fail(c, CSPM_ERR_STATE, "local stereo needs a cost object (cspm_build_cost_grd / _cen / _cengrd / cspm_finish_cost)");
   if (c->is_img) return fail(c, CSPM_ERR_STATE, "GrdPC / CSPC costs have no cost cells to aggregate");
   const Cost &cd = c->cost;
   if (cd.lv[0].D < 2) return fail(c, CSPM_ERR_ARG, "local stereo needs max_dis >= 2");

@@ -475,11 +475,39 @@ __global__ void k_gradient(Src s, int W, int H, int gWp, int gpad, double *__res
   grd[i] = g;
 }
 
+// one cell of GrdCC::buildCV / buildRightCV: myCostGrd (cc/grd_cc.cpp:4-35) of pixel (x, y) against the other view at disparity d
+//   left  view: other = right image at x-d, border branch when x-d < 0     (:88-100)
+//   right view: other = left image at x+d, border branch when x+d >= wid   (:134-147)
+// DEV as in k_grd_volume below, which documents the two forms.
+template <class Src, bool DEV>
+__device__ __forceinline__ double grd_volume_cell(const Src &l, const Src &r, const double *__restrict__ lG, const double *__restrict__ rG, int gWp,
+                                                  int gpad, int W, int x, int y, int d, int right_view) {
+  const int xo = right_view ? x + d : x - d;
+  const bool inside = right_view ? (xo < W) : (xo >= 0);
+  double c0, c1, c2, g0;  // own pixel
+  double o0, o1, o2, og;  // other-view pixel, or BORDER_THRES
+  const size_t grow = (size_t)y * gWp + gpad;
+  if (right_view) { r.rgb(x, y, c0, c1, c2); g0 = rG[grow + x]; } else { l.rgb(x, y, c0, c1, c2); g0 = lG[grow + x]; }
+  if (inside) {
+    if (right_view) { l.rgb(xo, y, o0, o1, o2); og = lG[grow + xo]; } else { r.rgb(xo, y, o0, o1, o2); og = rG[grow + xo]; }
+  } else {
+    o0 = o1 = o2 = 3.0; og = 3.0;  // BORDER_THRES (grd_cc.h:6)
+  }
+  // myCostGrd(lC, rC, lG, rG): differences are always left - right; fabs makes the sign irrelevant.
+  double clrDiff = 0;
+  clrDiff += fabs(c0 - o0);
+  clrDiff += fabs(c1 - o1);
+  clrDiff += fabs(c2 - o2);
+  clrDiff *= 0.3333333333;
+  double grdDiff = fabs(g0 - og);
+  clrDiff = clrDiff > 10.0 ? 10.0 : clrDiff;  // TAU_CLR
+  grdDiff = grdDiff > 2.0 ? 2.0 : grdDiff;    // TAU_GRD
+  return DEV ? __builtin_fma(1 - 0.1, grdDiff, 0.1 * clrDiff) : 0.1 * clrDiff + (1 - 0.1) * grdDiff;  // ALPHA
+}
+
 // GrdCC::buildCV / buildRightCV (cc/grd_cc.cpp:60-154) with myCostGrd (:4-35); one thread per cell,
 // slabs d-major as Mat costVol[d] (vol == nullptr: only the max is wanted).  Also reduces the max over
 // the volume (pre_cs_pc.cc:75-82).  d0/nd select a slab range (cspm_get_cost_slab in fused mode).
-//   left  view: other = right image at x-d, border branch when x-d < 0     (:88-100)
-//   right view: other = left image at x+d, border branch when x+d >= wid   (:134-147)
 // DEV = false: the reference's arithmetic to the last bit (the CCMethod::buildCV boundary, cspm_grd_build_cv_host).
 // DEV = true : the cells of the DEVICE order (cspm_tap.h grd_cell): the final multiply-add is one fma.  These are the cells the
 //              plane cost reads -- recomputed inside the tap engines by default, materialised with CSPM_OPT_GRD_VOLUMES -- and
@@ -494,31 +522,10 @@ __global__ __launch_bounds__(256) void k_grd_volume(Src l, Src r, const double *
   double best = -1.7976931348623157e308;
   // grid-stride: a bounded grid keeps the number of max-atomics (one per wave) small
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < cells; i += (long long)gridDim.x * blockDim.x) {
-    double cost;
     const int d = d0 + (int)(i / slab);
     const long long o = i - (long long)(d - d0) * slab;
     const int y = (int)(o / W), x = (int)(o - (long long)y * W);
-    const int xo = right_view ? x + d : x - d;
-    const bool inside = right_view ? (xo < W) : (xo >= 0);
-    double c0, c1, c2, g0;  // own pixel
-    double o0, o1, o2, og;  // other-view pixel, or BORDER_THRES
-    const size_t grow = (size_t)y * gWp + gpad;
-    if (right_view) { r.rgb(x, y, c0, c1, c2); g0 = rG[grow + x]; } else { l.rgb(x, y, c0, c1, c2); g0 = lG[grow + x]; }
-    if (inside) {
-      if (right_view) { l.rgb(xo, y, o0, o1, o2); og = lG[grow + xo]; } else { r.rgb(xo, y, o0, o1, o2); og = rG[grow + xo]; }
-    } else {
-      o0 = o1 = o2 = 3.0; og = 3.0;  // BORDER_THRES (grd_cc.h:6)
-    }
-    // myCostGrd(lC, rC, lG, rG): differences are always left - right; fabs makes the sign irrelevant.
-    double clrDiff = 0;
-    clrDiff += fabs(c0 - o0);
-    clrDiff += fabs(c1 - o1);
-    clrDiff += fabs(c2 - o2);
-    clrDiff *= 0.3333333333;
-    double grdDiff = fabs(g0 - og);
-    clrDiff = clrDiff > 10.0 ? 10.0 : clrDiff;  // TAU_CLR
-    grdDiff = grdDiff > 2.0 ? 2.0 : grdDiff;    // TAU_GRD
-    cost = DEV ? __builtin_fma(1 - 0.1, grdDiff, 0.1 * clrDiff) : 0.1 * clrDiff + (1 - 0.1) * grdDiff;  // ALPHA
+    const double cost = grd_volume_cell<Src, DEV>(l, r, lG, rG, gWp, gpad, W, x, y, d, right_view);
     if (vol) vol[i] = cost;
     if (cvol) cvol[((size_t)d * H + y) * cvW + cvpad + x] = cost;  // the padded volume the row engine's tables are DMA-filled from
     if (vol2) {  // the sweep's paired cells (kSrcVol2): slab d holds {cell(d), cell(d+1)}, d = 0 .. nd-2 (d0 == 0)
@@ -616,6 +623,46 @@ __global__ __launch_bounds__(256) void k_cen_volume(const uint32_t *__restrict__
       const uint32_t *a = (right_view ? rc : lc) + 3 * o, *b = (right_view ? lc : rc) + 3 * ((long long)y * W + xo);
       cost = (double)(__popc(a[0] ^ b[0]) + __popc(a[1] ^ b[1]) + __popc(a[2] ^ b[2]));
     }
+    if (vol) vol[i] = cost;
+    best = cost > best ? cost : best;
+  }
+  unsigned long long key = f64_key(best);
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1) {
+    const unsigned long long other = __shfl_xor(key, off, kWave);
+    key = other > key ? other : key;
+  }
+  if (max_key && (threadIdx.x & 63) == 0) atomicMax(max_key, key);
+}
+
+// ------------------------------------------------------------------------------------------------
+// CENGRD (an addition): cell = fma(KAPPA, min(H, TAU_CEN), G), G the DEVICE GRD cell (grd_volume_cell<.., true>,
+// border branch included), H the census cell of k_cen_volume (80 where the other view is outside).  KAPPA is a power of two and
+// min(H, TAU_CEN) an integer <= 32, so the product is exact and the fma rounds G + KAPPA*min(H, TAU_CEN) once.
+// One thread per cell, consecutive lanes = consecutive x (coalesced 8-byte stores, 512 B per wave), slabs d-major, d0/nd select a slab
+// range (i counts from slab d0; today's callers pass d0 = 0: the cost keeps its volumes, so cspm_get_cost_slab copies a slab instead of
+// recomputing it), max over the cells reduced per wave -> one atomic per wave: the shape of k_grd_volume / k_cen_volume.  The level's colours,
+// gradients and census codes are read directly (~50 B per cell, all of it L2 / Infinity Cache resident); no GRD or census volume is built.
+// ------------------------------------------------------------------------------------------------
+template <class Src>
+__global__ __launch_bounds__(256) void k_cengrd_volume(Src l, Src r, const double *__restrict__ lG, const double *__restrict__ rG, int gWp, int gpad,
+                                                       const uint32_t *__restrict__ lc, const uint32_t *__restrict__ rc, int W, int H, int d0, int nd,
+                                                       int right_view, double *__restrict__ vol, unsigned long long *max_key) {
+  const long long slab = (long long)W * H, cells = slab * nd;
+  double best = -1.7976931348623157e308;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < cells; i += (long long)gridDim.x * blockDim.x) {
+    const int d = d0 + (int)(i / slab);
+    const long long o = i - (long long)(d - d0) * slab;
+    const int y = (int)(o / W), x = (int)(o - (long long)y * W);
+    const double g = grd_volume_cell<Src, true>(l, r, lG, rG, gWp, gpad, W, x, y, d, right_view);
+    const int xo = right_view ? x + d : x - d;
+    int ham = 80;  // CENCUS_BIT
+    if (right_view ? (xo < W) : (xo >= 0)) {
+      const uint32_t *a = (right_view ? rc : lc) + 3 * o, *b = (right_view ? lc : rc) + 3 * ((long long)y * W + xo);
+      ham = __popc(a[0] ^ b[0]) + __popc(a[1] ^ b[1]) + __popc(a[2] ^ b[2]);
+    }
+    const double h = (double)ham;
+    const double cost = __builtin_fma(CSPM_CENGRD_KAPPA, h > CSPM_CENGRD_TAU ? CSPM_CENGRD_TAU : h, g);
     if (vol) vol[i] = cost;
     best = cost > best ? cost : best;
   }

@@ -3,12 +3,14 @@
 #pragma once
 #include "ca_method.h"
 #include "cc/cen_cc.h"
+#include "cc/cengrd_cc.h"
 #include "cc/grd_cc.h"
 #include "cc_method.h"
 
 inline CCMethod *getCCType(const string &name) {
   if (name == "GRD") return new GrdCC();
   if (name == "CEN") return new CenCC();
+  if (name == "CENGRD") return new CenGrdCC();  // not a reference name: the combined census + gradient cost (cc/cengrd_cc.h)
   return NULL;  // "BSM", "CG": NULL in the reference too (main.cc:47-54)
 }
 inline CCMethod *GetCCType(const string &name) { return getCCType(name); }  // spelling used by main.cc:39

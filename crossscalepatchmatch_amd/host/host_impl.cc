@@ -6,6 +6,7 @@
 #include "../../include/cspm.h"
 #include "ca_filter/device_ca.h"
 #include "cc/cen_cc.h"
+#include "cc/cengrd_cc.h"
 #include "cc/grd_cc.h"
 #include "cs_patchmatch.h"
 #include "plane_cost/device_plane_cost.h"
@@ -53,6 +54,21 @@ void CenCC::build(const Mat &lImg, const Mat &rImg, int maxDis, Mat *vol, int ri
 }
 void CenCC::buildCV(const Mat &lImg, const Mat &rImg, const int maxDis, Mat *costVol) { build(lImg, rImg, maxDis, costVol, 0); }
 void CenCC::buildRightCV(const Mat &lImg, const Mat &rImg, const int maxDis, Mat *rCostVol) { build(lImg, rImg, maxDis, rCostVol, 1); }
+
+// ---------------------------------------------------------------- CenGrdCC (CENGRD: include/cspm.h)
+void CenGrdCC::build(const Mat &lImg, const Mat &rImg, int maxDis, Mat *vol, int right) {
+  CV_Assert(lImg.type() == CV_64FC3 && rImg.type() == CV_64FC3);
+  CV_Assert(lImg.rows == rImg.rows && lImg.cols == rImg.cols && maxDis >= 1 && vol);
+  const int h = lImg.rows, w = lImg.cols;
+  std::vector<double> l = packed64(lImg), r = packed64(rImg), out((size_t)maxDis * h * w);
+  check(cspm_cengrd_build_cv_host(device_ >= 0 ? device_ : DeviceSlot::current().device(), l.data(), r.data(), w, h, maxDis, right, out.data()), NULL, "CenGrdCC");
+  for (int d = 0; d < maxDis; ++d) {
+    if (vol[d].rows != h || vol[d].cols != w || vol[d].type() != CV_64FC1) vol[d].create(h, w, CV_64FC1);
+    for (int y = 0; y < h; ++y) std::memcpy(vol[d].ptr<double>(y), &out[((size_t)d * h + y) * w], sizeof(double) * w);
+  }
+}
+void CenGrdCC::buildCV(const Mat &lImg, const Mat &rImg, const int maxDis, Mat *costVol) { build(lImg, rImg, maxDis, costVol, 0); }
+void CenGrdCC::buildRightCV(const Mat &lImg, const Mat &rImg, const int maxDis, Mat *rCostVol) { build(lImg, rImg, maxDis, rCostVol, 1); }
 
 // ---------------------------------------------------------------- BoxCA / GFCA / BFCA (ca_filter/*.cpp)
 void DeviceCA::aggreCV(const Mat &lImg, const Mat &rImg, const int maxDis, Mat *costVol) {
@@ -207,6 +223,8 @@ DevicePlaneCost::DevicePlaneCost(const Mat &l_img, const Mat &r_img, int max_dis
       check(cspm_build_cost_grd(ctx_, max_disp, wnd_size, scale_num, reg_lambda), ctx_, "cspm_build_cost_grd");
     } else if (dynamic_cast<CenCC *>(cc_method)) {
       check(cspm_build_cost_cen(ctx_, max_disp, wnd_size, scale_num, reg_lambda), ctx_, "cspm_build_cost_cen");
+    } else if (dynamic_cast<CenGrdCC *>(cc_method)) {
+      check(cspm_build_cost_cengrd(ctx_, max_disp, wnd_size, scale_num, reg_lambda), ctx_, "cspm_build_cost_cengrd");
     } else {
       // a foreign CCMethod: let it fill host volumes level by level exactly as pre_cs_pc.cc:57-74 does
       check(cspm_begin_cost(ctx_, max_disp, wnd_size, scale_num, reg_lambda), ctx_, "cspm_begin_cost");

@@ -27,7 +27,7 @@ DEFINE_string(r_dis_file, "r_dis.png", "right disparity map to write (8-bit)");
 // matching
 DEFINE_int32(max_dis, 0, "disparity search range");
 DEFINE_int32(dis_scale, 0, "factor applied to disparities before 8-bit quantisation");
-DEFINE_string(cc_name, "CCName", "matching cost: GRD | CEN");
+DEFINE_string(cc_name, "CCName", "matching cost: GRD | CEN | CENGRD (census and GRD blended per cell; not in the reference)");
 DEFINE_string(pc_name, "PRE", "plane cost family: PRE = PreSSPC / PreCSPC over --cc_name's cost volumes (the reference's main.cc); "
                               "IMG = GrdPC / CSPC, the volume-free colour + gradient costs (main.cc:106-107, commented out there)");
 DEFINE_string(ca_name, "", "local stereo instead of PatchMatch: cost aggregation BOX | GF | BF over --cc_name's cost volumes, then "

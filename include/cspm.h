@@ -169,6 +169,20 @@ int cspm_set_option(cspm_ctx *ctx, int key, long long value);
  * the device; Hamming cells are computed on the fly from the codes (default) or materialised as f64 volumes
  * (CSPM_OPT_GRD_VOLUMES = 1), exactly like the GRD cost. */
 int cspm_build_cost_cen(cspm_ctx *ctx, int max_dis, int wnd_size, int scale_num, double reg_lambda);
+/* CENGRD (an addition): census and GRD blended per cell.  The reference reserves the slot -- GetCCType("CG") /
+ * "BSM", main.cc:47-54 -- and defines nothing behind it; this is the library's own definition:
+ *     cell = fma(CSPM_CENGRD_KAPPA, min(H, CSPM_CENGRD_TAU), G)
+ * G = the GRD cell the device reads (what cspm_get_cost_slab returns after cspm_build_cost_grd: myCostGrd with its last multiply-add
+ * contracted, border branch included), H = the census cell of cspm_build_cost_cen at the same (view, level, x, y, d) (80 where the
+ * other view is outside).  KAPPA is a power of two and min(H, TAU) an integer, so the cell is G + KAPPA*min(H, TAU) rounded once.
+ * Both constants are documented defaults, chosen, not tuned: the census part spans [0, 2.0], the GRD part [0, 2.8].
+ * Same contract as the constructors above (everything on the ctx stream, buffers reused for an unchanged geometry, scale_num == 0 =
+ * single scale).  The cost is always volume-sourced -- d-major f64 volumes of D_s + 1 slabs per level and view, as
+ * CSPM_OPT_GRD_VOLUMES = 1 gives the other two; that option has no effect here -- so every consumer of a cost object works on it
+ * unchanged.  Volumes that do not fit fail the call with CSPM_ERR_HIP. */
+#define CSPM_CENGRD_KAPPA 0.0625 /* 2^-4 */
+#define CSPM_CENGRD_TAU 32.0
+int cspm_build_cost_cengrd(cspm_ctx *ctx, int max_dis, int wnd_size, int scale_num, double reg_lambda);
 /* The two volume-free IPlaneCost implementations the reference also ships (not instantiated by its main.cc):
  *   scale_num == 0 -> `new GrdPC(l_img, r_img, max_disp, wnd_size)`                          plane_cost/grd_pc.h:27-29, grd_pc.cc:11-66
  *   scale_num >= 1 -> `new CSPC(l_img, r_img, max_disp, wnd_size, scale_num, reg_lambda)`    plane_cost/cspc.h:21-23,  cspc.cc:11-93
@@ -197,6 +211,11 @@ int cspm_grd_build_cv_host(int device, const double *l_rgb, const double *r_rgb,
 /* CenCC::buildCV / buildRightCV on host buffers (cc/cen_cc.cc:4-70, 72-137), same contract as above */
 int cspm_cen_build_cv_host(int device, const double *l_rgb, const double *r_rgb, int w, int h, int maxDis,
                            int right_view, double *vol_out);
+
+/* The same boundary for the CENGRD cells (class CenGrdCC of the host layer): input contract of the two entries above, cells as
+ * defined at cspm_build_cost_cengrd -- the device form of G here too, so that there is one definition. */
+int cspm_cengrd_build_cv_host(int device, const double *l_rgb, const double *r_rgb, int w, int h, int maxDis,
+                              int right_view, double *vol_out);
 
 /* ---- IPlaneCost::GetPlaneCost, batched (plane_cost/i_plane_cost.h:28-33) ----------------------
  * xy: 2 ints per item; plane: 6 doubles per item = Plane::norm() then Plane::param().
