@@ -7,4 +7,4 @@ generator used for measurement (synth.py).  There is no CPU fallback: importing 
 every compute entry point raises when the HIP library or a gfx950 device is missing.
 """
 from .capi import (CspmError, StereoContext, PmParams, library_path, load_library, build_library,  # noqa: F401
-                   SCHED_RASTER, SCHED_REDBLACK, RNG_PER_PIXEL, RNG_ROW_SHARED, K_NAMES)
+                   SCHED_RASTER, SCHED_REDBLACK, SCHED_DIFFUSE, RNG_PER_PIXEL, RNG_ROW_SHARED, K_NAMES)

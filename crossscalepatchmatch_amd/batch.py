@@ -14,7 +14,8 @@ import os
 
 import numpy as np
 
-PARAM_KEYS = ("w", "h", "max_dis", "dis_scale", "scale_num", "reg_lambda", "iters", "seed", "schedule", "use_pp", "cc")
+PARAM_KEYS = ("w", "h", "max_dis", "dis_scale", "scale_num", "reg_lambda", "iters", "seed", "schedule", "use_pp", "cc", "neighbours")
+SCHEDULES = {"raster": 0, "redblack": 1, "diffuse": 2}  # capi.SCHED_*; params["neighbours"]: candidates per pixel under diffuse (0 / absent = 8)
 CC_CODES = {"GRD": 0, "CEN": 1, "IMG": 2, "CENGRD": 3}  # params["cc"]: the cost family (cc/grd_cc, cc/cen_cc; IMG = GrdPC / CSPC; cc/cengrd_cc)
 
 
@@ -94,7 +95,9 @@ class HipPairFn:
             ctx.build_cost_cengrd(*args)
         else:
             ctx.build_cost_grd(*args)
-        ctx.patchmatch(int(p["iters"]), seed=int(p["seed"]), schedule=int(p["schedule"]))
+        sched = int(p["schedule"])
+        nb = (int(p.get("neighbours", 0)) or 8) if sched == SCHEDULES["diffuse"] else 4
+        ctx.patchmatch(int(p["iters"]), seed=int(p["seed"]), schedule=sched, rb_neighbours=nb)
         if out is None:
             out = [torch.empty((h, w), dtype=torch.uint8, device=l.device) for _ in range(2)]
         assert all(o.is_contiguous() and o.device == self.device and o.dtype == torch.uint8 for o in out)
@@ -245,7 +248,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=8)
     ap.add_argument("--config", default="C3")
-    ap.add_argument("--schedule", type=int, default=0)
+    ap.add_argument("--schedule", type=lambda s: SCHEDULES[s] if s in SCHEDULES else int(s), default=0, help="raster | redblack | diffuse, or the number")
+    ap.add_argument("--neighbours", type=int, default=8, help="with --schedule diffuse: candidates per pixel (4, 8 or 20)")
     ap.add_argument("--use_pp", type=int, default=0)
     ap.add_argument("--cc", default="GRD", choices=sorted(CC_CODES))
     ap.add_argument("--in-flight", type=int, default=2)
@@ -263,7 +267,7 @@ def main():
         pairs = np.stack([np.stack(synth.make_pair(cfg["w"], cfg["h"], cfg["max_dis"], cfg["regions"], cfg["seed"] + i)[:2])
                           for i in range(args.pairs)])
         params = dict(w=cfg["w"], h=cfg["h"], max_dis=cfg["max_dis"], dis_scale=cfg["dis_scale"], scale_num=cfg["scale_num"],
-                      reg_lambda=cfg["reg_lambda"], iters=3, seed=12345, schedule=args.schedule, use_pp=args.use_pp, cc=CC_CODES[args.cc])
+                      reg_lambda=cfg["reg_lambda"], iters=3, seed=12345, schedule=args.schedule, use_pp=args.use_pp, cc=CC_CODES[args.cc], neighbours=args.neighbours)
     fn = HipPairFn(local_rank, in_flight=args.in_flight)
     torch.cuda.synchronize()
     t0 = time.perf_counter()

@@ -9,7 +9,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.environ.get("CSPM_LIB") or os.path.join(_HERE, "libcspm_hip.so")  # CSPM_LIB: an alternative build of the same library (tuning experiments)
 
-SCHED_RASTER, SCHED_REDBLACK = 0, 1
+SCHED_RASTER, SCHED_REDBLACK, SCHED_DIFFUSE = 0, 1, 2  # DIFFUSE: rb_neighbours is 4, 8 or 20 (include/cspm.h)
 RNG_PER_PIXEL, RNG_ROW_SHARED = 0, 1
 K_GRD, K_INIT, K_SPATIAL, K_VIEW, K_REFINE, K_MISC, K_POST = range(7)
 K_NAMES = ["grd", "init", "spatial", "view", "refine", "misc", "post"]

@@ -135,6 +135,7 @@ struct cspm_ctx {
   cspm_pm_params last_params{};
   bool last_warm = false;             // that run was cspm_patchmatch_warm: a repeat starts from warm_snap, not from the init
   double *warm_snap = nullptr;        // the starting field of the last warm run (both views, 7 arrays each), kept with the field
+  double *diffuse_snap = nullptr;     // CSPM_SCHED_DIFFUSE: the round's snapshot (both views, the 6 plane arrays each), allocated by the first such propagation and kept with the field
   long long sweep_fallbacks = 0;      // how often that happened (cspm_get_option)
   // asynchronous outputs (cspm_disparity_u8_device / cspm_postprocess_device / cspm_postprocess_f64_device) enqueued behind a run whose
   // sweep has not been checked yet: when that run is repeated after a timeout they are produced again from the repeated run's planes.
@@ -291,6 +292,8 @@ void free_field(cspm_ctx *c) {
   if (c->field_mem) (void)hipFree(c->field_mem);
   if (c->warm_snap) (void)hipFree(c->warm_snap);
   c->warm_snap = nullptr;
+  if (c->diffuse_snap) (void)hipFree(c->diffuse_snap);
+  c->diffuse_snap = nullptr;
   if (c->vc.cost) (void)hipFree(c->vc.cost);
   if (c->vc.c) (void)hipFree(c->vc.c);
   if (c->vc.cx) (void)hipFree(c->vc.cx);
@@ -817,8 +820,12 @@ int check_pm(cspm_ctx *c, const cspm_pm_params **p) {
   if (!c) return CSPM_ERR_ARG;
   if (!c->cost_ready) return fail(c, CSPM_ERR_STATE, "no plane cost built (cspm_build_cost_grd / cspm_finish_cost)");
   if (!*p) *p = &kDefaultParams;
-  if ((*p)->schedule != CSPM_SCHED_RASTER && (*p)->schedule != CSPM_SCHED_REDBLACK) return fail(c, CSPM_ERR_ARG, "bad schedule");
-  if ((*p)->rb_neighbours != 2 && (*p)->rb_neighbours != 4) return fail(c, CSPM_ERR_ARG, "rb_neighbours must be 2 or 4");
+  if ((*p)->schedule != CSPM_SCHED_RASTER && (*p)->schedule != CSPM_SCHED_REDBLACK && (*p)->schedule != CSPM_SCHED_DIFFUSE)
+    return fail(c, CSPM_ERR_ARG, "bad schedule");
+  if ((*p)->schedule == CSPM_SCHED_DIFFUSE) {
+    if ((*p)->rb_neighbours != 4 && (*p)->rb_neighbours != 8 && (*p)->rb_neighbours != 20)
+      return fail(c, CSPM_ERR_ARG, "rb_neighbours must be 4, 8 or 20 under CSPM_SCHED_DIFFUSE");
+  } else if ((*p)->rb_neighbours != 2 && (*p)->rb_neighbours != 4) return fail(c, CSPM_ERR_ARG, "rb_neighbours must be 2 or 4");
   if ((*p)->rb_rounds < 1) return fail(c, CSPM_ERR_ARG, "rb_rounds must be >= 1");
   return ensure_field(c);
 }
@@ -897,6 +904,39 @@ int do_spatial(cspm_ctx *c, int iter, const cspm_pm_params *p) {
         Timed t(c, CSPM_K_SPATIAL, items * p->rb_neighbours);
         LAUNCH_CS(k_spatial_rb, dim3(eval_grid(items)), dim3(kEvalBlock), 0, c->cost, pm, (hs + iter) & 1, inc, p->rb_neighbours);
       }
+  } else if (p->schedule == CSPM_SCHED_DIFFUSE) {
+    // per round: the twelve plane arrays go into the snapshot (one copy per view: a view's seventh array, min_cost, lies between
+    // them and is no part of it), then one row-engine launch reads candidates from the snapshot only and writes the live field only
+    static const signed char kOff4[4][2] = {CSPM_DIFFUSE_OFFSETS_4}, kOff8[8][2] = {CSPM_DIFFUSE_OFFSETS_8},
+                             kOff20[20][2] = {CSPM_DIFFUSE_OFFSETS_20};
+    const size_t n = (size_t)c->W * c->H;
+    if (!c->diffuse_snap) {
+      void *q = nullptr;
+      const hipError_t e = hipMalloc(&q, sizeof(double) * 12 * n);
+      if (e != hipSuccess)
+        return fail(c, CSPM_ERR_HIP, "CSPM_SCHED_DIFFUSE: no memory for the snapshot of the plane fields (" + std::to_string(sizeof(double) * 12 * n) +
+                                         " bytes): " + hipGetErrorString(e));
+      c->diffuse_snap = (double *)q;
+    }
+    Diffuse df{};
+    df.K = p->rb_neighbours;
+    const signed char(*off)[2] = df.K == 4 ? kOff4 : df.K == 8 ? kOff8 : kOff20;
+    for (int k = 0; k < df.K; ++k) {
+      df.off[k][0] = (signed char)(inc * off[k][0]);
+      df.off[k][1] = (signed char)(inc * off[k][1]);
+    }
+    for (int v = 0; v < 2; ++v) {
+      const double *b = c->diffuse_snap + (size_t)v * 6 * n;
+      df.s[v] = SnapField{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n};
+    }
+    const long long items = 2LL * c->W * c->H;
+    for (int r = 0; r < p->rb_rounds; ++r) {
+      Timed t(c, CSPM_K_SPATIAL, items * df.K);
+      for (int v = 0; v < 2; ++v)
+        HIPCHK(c, hipMemcpyAsync(c->diffuse_snap + (size_t)v * 6 * n, c->f[v].nx, sizeof(double) * 6 * n, hipMemcpyDeviceToDevice, c->stream));
+      const RowQueue rq = next_row_queue(c, 2);
+      LAUNCH_CS(k_spatial_diffuse, dim3(row_grid(c, 2)), dim3(kRowBlock), row_shmem(c), c->cost, pm, rq, df, row_cap(c), row_ocap(c));
+    }
   } else if (!c->opt_raster_launches) {
     // one persistent launch per sweep: 2 workgroups of 8 waves per CU pull pixels in diagonal-major order
     Sweep sw{};

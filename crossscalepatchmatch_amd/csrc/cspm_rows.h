@@ -1620,4 +1620,61 @@ __global__ __launch_bounds__(kRowBlock, CSPM_VIEW_MINW) void k_view_eval(Cost cd
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// SpatialPropagation under CSPM_SCHED_DIFFUSE (an addition; include/cspm.h): every pixel tries the planes
+// of K fixed near and far neighbours, read from a SNAPSHOT of both views' plane fields taken when the round starts -- k_refine
+// with the snapshot as generator.  No pixel depends on another one: the kernel reads planes from the snapshot only and writes the
+// live field only, each lane its own pixel.
+// ------------------------------------------------------------------------------------------------
+struct SnapField {
+  const double *nx, *ny, *nz, *a, *b, *c;  // the six plane arrays of a Field, no cost
+};
+struct Diffuse {
+  SnapField s[2];
+  int K;
+  signed char off[CSPM_DIFFUSE_MAX_NEIGHBOURS][2];  // (ox, oy) = inc * O_k, in the order of the accept loop
+};
+// the snapshot's plane at (x, y), both inside the image, taken whole: nothing is re-anchored (cs_patchmatch.cc:181-212)
+__device__ __forceinline__ RowPlane snap_plane(const SnapField &s, int W, int x, int y) {
+  const long long i = (long long)y * W + x;
+  RowPlane p;
+  p.nx = s.nx[i]; p.ny = s.ny[i]; p.nz = s.nz[i];
+  p.a = s.a[i]; p.b = s.b[i]; p.c = s.c[i];
+  return p;
+}
+
+template <bool CS, int SRC>
+__global__ __launch_bounds__(kRowBlock, CSPM_ROW_MINW) void k_spatial_diffuse(Cost cd, Pm pm, RowQueue rq, Diffuse df, int cap, int ocap) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  LutMem &s_lut = *reinterpret_cast<LutMem *>(smem);
+  const Luts lut = load_luts(cd, s_lut);
+  RowItem it;
+  if (!row_item(pm.W, pm.H, 2, rq, it)) return;
+  const int lane = threadIdx.x & 63;
+  RowCtx ctx = make_row_ctx(smem, it.y, cap, ocap);
+  const bool live = it.x0 + lane < pm.W;
+  const int x = live ? it.x0 + lane : pm.W - 1;  // tail lanes shadow the last pixel
+  const long long i = (long long)it.y * pm.W + x;
+  const Field &f = pm.f[it.v];
+  const SnapField &snap = df.s[it.v];
+  double cur_min = f.cost[i];
+  const bool use_thresh = pm.use_thresh != 0 && *cd.early_ok != 0;
+#ifdef CSPM_ROW_STATS
+  ctx.stat_slot = 15;
+#endif
+  for (int k = 0; k < df.K; ++k) {
+    const int ox = df.off[k][0], ny = it.y + df.off[k][1];
+    if (ny < 0 || ny >= pm.H) continue;  // the neighbour row is outside the image: no candidate k for the whole wave
+    const bool has_k = x + ox >= 0 && x + ox < pm.W;
+    // a lane whose neighbour column is outside evaluates the clamped one and never accepts
+    auto gen = [&](int xs) { return snap_plane(snap, pm.W, min(max(xs + ox, 0), pm.W - 1), ny); };
+    const double cost = eval_rows<CS, SRC>(cd, lut, ctx, it.v, x, gen, cur_min, use_thresh);
+    if (has_k && cost < cur_min) {
+      const RowPlane p = gen(x);
+      cur_min = cost;
+      if (live) store_plane(f, i, p.nx, p.ny, p.nz, p.a, p.b, p.c, cost);
+    }
+  }
+}
+
 }  // namespace cspm

@@ -38,7 +38,12 @@ class CSPatchMatch {
 
   // additions (the reference seeds from time(NULL) and has one schedule)
   void set_seed(uint64_t seed) { seed_ = seed; }
-  void set_schedule(int schedule, int rb_rounds = 1) { schedule_ = schedule; rb_rounds_ = rb_rounds; }
+  // schedule: CSPM_SCHED_*; rb_rounds: red-black / diffuse rounds per iteration; rb_neighbours: 2 or 4, under CSPM_SCHED_DIFFUSE 4, 8 or 20
+  void set_schedule(int schedule, int rb_rounds = 1, int rb_neighbours = 4) {
+    schedule_ = schedule;
+    rb_rounds_ = rb_rounds;
+    rb_neighbours_ = rb_neighbours;
+  }
   // final plane field of a view, for callers that want sub-pixel disparities.  Both read the device context of the plane cost
   // the last PatchMatch ran on: call them while that object is alive (they throw otherwise).  They return the PLANE field --
   // PostProcessing (use_pp) works on the 8-bit maps only (cs_patchmatch.cc:508-588) and does not change it.
@@ -54,7 +59,7 @@ class CSPatchMatch {
   Mat img_[kViewNum], dis_[kViewNum];
   int wid_, hei_, max_dis_, dis_scale_;
   uint64_t seed_;
-  int schedule_, rb_rounds_;
+  int schedule_, rb_rounds_, rb_neighbours_;
   cspm_ctx *last_ctx_;
   cspm_ctx *own_ctx_;  // foreign IPlaneCost: the context that holds the plane field
   cspm_ctx *pending_ctx_;  // PatchMatchBegin without its PatchMatchEnd yet

@@ -271,7 +271,7 @@ double DevicePlaneCost::GetPlaneCost(const int &ref_x, const int &ref_y, const P
 
 // ---------------------------------------------------------------- CSPatchMatch (cs_patchmatch.cc:3-109)
 CSPatchMatch::CSPatchMatch(const Mat &l_img, const Mat &r_img, const int &max_dis, const int &dis_scale)
-    : max_dis_(max_dis), dis_scale_(dis_scale), seed_(12345), schedule_(CSPM_SCHED_RASTER), rb_rounds_(1), last_ctx_(NULL), own_ctx_(NULL), pending_ctx_(NULL), pending_pp_(false) {
+    : max_dis_(max_dis), dis_scale_(dis_scale), seed_(12345), schedule_(CSPM_SCHED_RASTER), rb_rounds_(1), rb_neighbours_(4), last_ctx_(NULL), own_ctx_(NULL), pending_ctx_(NULL), pending_pp_(false) {
   CV_Assert(l_img.type() == CV_8UC3 && r_img.type() == CV_8UC3);  // cs_patchmatch.cc:8
   img_[kLeft] = l_img.clone();
   img_[kRight] = r_img.clone();
@@ -355,6 +355,7 @@ void CSPatchMatch::PatchMatchBegin(const int &iter_num, const IPlaneCost *plane_
   p.seed = seed_;
   p.schedule = schedule_;
   p.rb_rounds = rb_rounds_;
+  p.rb_neighbours = rb_neighbours_;
   check(cspm_patchmatch(ctx, iter_num, &p), ctx, "cspm_patchmatch");  // asynchronous: enqueued on the context's stream
   pending_ctx_ = ctx;
   pending_pp_ = use_pp;
@@ -417,6 +418,7 @@ void CSPatchMatch::PatchMatchFromBegin(const int &iter_num, const IPlaneCost *pl
   p.seed = seed_;
   p.schedule = schedule_;
   p.rb_rounds = rb_rounds_;
+  p.rb_neighbours = rb_neighbours_;
   check(cspm_patchmatch_warm(ctx, iter_num, &p), ctx, "cspm_patchmatch_warm");  // asynchronous: enqueued on the context's stream
   pending_ctx_ = ctx;
   pending_pp_ = use_pp;

@@ -1,6 +1,6 @@
 // main.cc -- command line with the reference's ten flags and defaults (CSPM/main.cc:23-34) and its flow
 // (main.cc:57-139): read the pair, construct the plane cost (timed), run PatchMatch, print "Total Time", write the
-// two 8-bit maps.  Runs on the GPU through the host layer.  Extra flags: --seed --schedule --device --iters --ca_name (local stereo)
+// two 8-bit maps.  Runs on the GPU through the host layer.  Extra flags: --seed --schedule --neighbours --device --iters --ca_name (local stereo)
 // --warm_ca (local stereo, then --iters warm PatchMatch iterations).
 #include "../../include/cspm.h"
 #include "commfunc.h"
@@ -39,7 +39,9 @@ DEFINE_bool(use_pp, false, "left-right check, hole filling and weighted median a
 DEFINE_double(reg_lambda, 0.0, "cross-scale regularisation weight");
 // not in the reference
 DEFINE_int32(seed, 12345, "random seed (the reference uses the wall clock)");
-DEFINE_string(schedule, "raster", "spatial propagation: raster (the reference's sweep) | redblack");
+DEFINE_string(schedule, "raster", "spatial propagation: raster (the reference's sweep) | redblack | diffuse (every pixel tries the planes of "
+                                  "--neighbours near and far neighbours, read from a snapshot of the field; not in the reference)");
+DEFINE_int32(neighbours, 8, "with --schedule=diffuse: candidates per pixel, 4 | 8 | 20 (include/cspm.h CSPM_SCHED_DIFFUSE); ignored by the other schedules");
 DEFINE_int32(device, 0, "GPU index");
 DEFINE_int32(iters, 3, "PatchMatch iterations (3 in the reference, main.cc:93)");
 DEFINE_string(l_disp_pfm, "", "also write the left sub-pixel disparity map as float32 PFM: the unquantised plane disparity a*x+b*y+c, "
@@ -115,7 +117,8 @@ void begin(PairRun &p, CCMethod *cost_fn) {
     p.cost.reset(pc);  // released on every path, exceptions included (batch mode goes on)
     p.matcher.reset(new CSPatchMatch(p.left, p.right, FLAGS_max_dis, FLAGS_dis_scale));
     p.matcher->set_seed(static_cast<uint64_t>(FLAGS_seed));
-    p.matcher->set_schedule(FLAGS_schedule == "redblack" ? 1 : 0);
+    if (FLAGS_schedule == "diffuse") p.matcher->set_schedule(CSPM_SCHED_DIFFUSE, 1, FLAGS_neighbours);
+    else p.matcher->set_schedule(FLAGS_schedule == "redblack" ? 1 : 0);
     if (!FLAGS_warm_ca.empty()) {  // the warm run is enqueued behind the local stereo on the cost object's stream
       p.matcher->LocalStereoBegin(ca_method(FLAGS_warm_ca), p.cost.get(), FLAGS_use_pp);
       p.matcher->PatchMatchFromBegin(FLAGS_iters, p.cost.get(), FLAGS_use_pp);

@@ -35,6 +35,23 @@ typedef struct cspm_ctx cspm_ctx;
 /* SpatialPropagation schedule (cs_patchmatch.cc:163-216) */
 #define CSPM_SCHED_RASTER 0   /* reference order: in-place raster sweep, run as an anti-diagonal wavefront */
 #define CSPM_SCHED_REDBLACK 1 /* checkerboard half-steps (option: fewer dependencies, clearly lower quality) */
+/* CSPM_SCHED_DIFFUSE (an addition): snapshot propagation.  One SpatialPropagation of iteration `iter` is
+ * rb_rounds rounds.  A round copies both views' plane fields (the six doubles nx, ny, nz, a, b, c per pixel, no costs) into a
+ * snapshot S; then every pixel (x, y) of every view v, independently of every other pixel, starts from m = its stored min_cost and
+ * walks k = 0 .. K-1 in this order: (ox, oy) = inc * O_k with inc = +1 for even iter, -1 for odd iter; a neighbour (x+ox, y+oy)
+ * outside the image is no candidate; otherwise the candidate is S[v][y+oy][x+ox] taken whole (normal and parameters as stored, nothing
+ * re-anchored: how cs_patchmatch.cc:181-212 adopts a neighbour's Plane), cost = GetPlaneCost(x, y, candidate, v) in the device order,
+ * and where cost < m (strict) the pixel's plane and min_cost become the candidate and its cost, and m = cost.
+ * K = rb_neighbours is 4, 8 or 20 under this schedule; O_0 .. O_{K-1} as (ox, oy) are the first K entries of the lists below
+ * (K = 20: the pattern of Galliani et al.'s Gipuma).  Needs a snapshot of 96 bytes per pixel, allocated by the first such call and
+ * kept with the plane field.  No spin-waits, no timeout, every cost object; the foreign-IPlaneCost protocol stays raster-only. */
+#define CSPM_SCHED_DIFFUSE 2
+#define CSPM_DIFFUSE_MAX_NEIGHBOURS 20
+#define CSPM_DIFFUSE_OFFSETS_4 {-1, 0}, {0, -1}, {1, 0}, {0, 1}
+#define CSPM_DIFFUSE_OFFSETS_8 CSPM_DIFFUSE_OFFSETS_4, {-5, 0}, {0, -5}, {5, 0}, {0, 5}
+#define CSPM_DIFFUSE_OFFSETS_20                                                                                     \
+  CSPM_DIFFUSE_OFFSETS_4, {-3, 0}, {0, -3}, {3, 0}, {0, 3}, {-5, 0}, {0, -5}, {5, 0}, {0, 5}, {-1, -2}, {1, -2}, {2, -1}, \
+      {2, 1}, {1, 2}, {-1, 2}, {-2, 1}, {-2, -1}
 
 /* rng flags */
 #define CSPM_RNG_PER_PIXEL 0
@@ -43,8 +60,8 @@ typedef struct cspm_ctx cspm_ctx;
 typedef struct cspm_pm_params {
   uint64_t seed;     /* replaces RNG(time(NULL)), cs_patchmatch.cc:32 */
   int schedule;      /* CSPM_SCHED_* */
-  int rb_rounds;     /* red-black rounds per iteration (>= 1) */
-  int rb_neighbours; /* 2 or 4 */
+  int rb_rounds;     /* red-black / diffuse rounds per iteration (>= 1) */
+  int rb_neighbours; /* 2 or 4; under CSPM_SCHED_DIFFUSE: 4, 8 or 20 */
   int rng_mode;      /* CSPM_RNG_* */
   int early_exit;    /* 1: stop a plane evaluation once its partial sum proves cost >= min_cost
                         (result-preserving; ignored when a scale weight or max_cost is negative) */

@@ -27,7 +27,7 @@ def stats(tag):
             row = [a[(slot * 8 + s) * 8 + b] for b in range(7)]
             tot = sum(row)
             if tot:
-                name = "init" if slot == 0 else "view" if slot == 1 else f"refine step {slot - 2}"
+                name = "init" if slot == 0 else "view" if slot == 1 else "diffuse" if slot == 15 else f"refine step {slot - 2}"
                 print(f"{tag:10s} {name:15s} level {s}: rows {tot:9d}  " + "  ".join(f"{NAMES[b]} {row[b] / tot:6.3f}" for b in range(7)))
 ctx.set_images(l, r)
 ctx.build_cost_grd(cfg["max_dis"], 35, cfg["scale_num"], cfg["reg_lambda"])
