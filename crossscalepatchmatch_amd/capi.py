@@ -32,6 +32,8 @@ OPT_VOLUME_RETRY_PAIRS = 15  # a cost object that runs without the optional volu
 OPT_VIEW_SORT = 17           # view propagation evaluates a row's proposals in target-column order (default 1; identical planes either way)
 OPT_SWEEP_FOLD = 18          # cross-scale sweep workgroups of levels - 1 waves, the coarsest level folded onto them (default 1; identical planes)
 OPT_FAULT_VOLUME_ALLOC = 16  # write only, TEST HOOK: the n-th optional-volume allocation from now on fails
+OPT_CENGRD_FUSED = 19        # set before build_cost_cengrd: 1 = no volumes, the cells are computed inside the PatchMatch kernels (default 0; identical planes)
+OPT_CENGRD_FUSED_ACTIVE = 20 # read only: the current cost object is a fused CENGRD one
 CA_BOX, CA_GF, CA_BF = 0, 1, 2  # cost aggregation: BoxCA, GFCA, BFCA (ca_filter/)
 CENGRD_KAPPA, CENGRD_TAU = 0.0625, 32.0  # CSPM_CENGRD_KAPPA / CSPM_CENGRD_TAU: cell = fma(KAPPA, min(H, TAU), G)
 
@@ -239,8 +241,12 @@ class StereoContext:
         self.set_option(OPT_GRD_VOLUMES, int(volumes))
         self._chk(self.L.cspm_build_cost_cen(self.p, max_dis, wnd_size, scale_num, reg_lambda))
 
-    def build_cost_cengrd(self, max_dis, wnd_size=35, scale_num=0, reg_lambda=0.0):
-        """CENGRD: census and GRD blended per cell; always materialised f64 volumes, whatever OPT_GRD_VOLUMES says"""
+    def build_cost_cengrd(self, max_dis, wnd_size=35, scale_num=0, reg_lambda=0.0, fused=None):
+        """CENGRD: census and GRD blended per cell; OPT_GRD_VOLUMES has no effect on it.
+        fused (CSPM_OPT_CENGRD_FUSED): None = leave the context's setting alone (the library's default: materialised f64 volumes);
+        True = no volumes, the PatchMatch kernels compute the cells (identical planes and costs); False = volumes."""
+        if fused is not None:
+            self.set_option(OPT_CENGRD_FUSED, int(bool(fused)))
         self._chk(self.L.cspm_build_cost_cengrd(self.p, max_dis, wnd_size, scale_num, reg_lambda))
 
     def build_cost_img(self, max_dis, wnd_size=35, scale_num=0, reg_lambda=0.0):
@@ -432,12 +438,12 @@ def aggregate_cv_host(device, method, guide, vol):
 
 
 def coarse_to_fine(l, r, max_dis, coarse_iters=3, fine_iters=1, cc="GRD", wnd_size=35, scale_num=5, reg_lambda=0.3, volumes=False,
-                   device=0, ctx=None, coarse_ctx=None, **pm_kw):
+                   device=0, ctx=None, coarse_ctx=None, fused=None, **pm_kw):
     """PatchMatch on the half-size pair, then `fine_iters` warm iterations on the full pair from the upsampled planes.
 
     The half-size images are the full cost object's level-1 images (pyrDown); the coarse run uses max_dis (max_dis + 1) // 2 and the
     same cost settings.  ctx / coarse_ctx: contexts to reuse (created and, for the coarse one, closed here when None).  Returns the
-    full-size context with the warm run enqueued (asynchronous like patchmatch)."""
+    full-size context with the warm run enqueued (asynchronous like patchmatch).  fused: passed to build_cost_cengrd (cc="CENGRD" only)."""
     full = ctx if ctx is not None else StereoContext(device)
     coarse = coarse_ctx if coarse_ctx is not None else StereoContext(device)
 
@@ -447,7 +453,7 @@ def coarse_to_fine(l, r, max_dis, coarse_iters=3, fine_iters=1, cc="GRD", wnd_si
         elif cc == "CEN":
             c.build_cost_cen(md, wnd_size, scale_num, reg_lambda, volumes=volumes)
         elif cc == "CENGRD":
-            c.build_cost_cengrd(md, wnd_size, scale_num, reg_lambda)
+            c.build_cost_cengrd(md, wnd_size, scale_num, reg_lambda, fused=fused)
         elif cc == "IMG":
             c.build_cost_img(md, wnd_size, scale_num, reg_lambda)
         else:

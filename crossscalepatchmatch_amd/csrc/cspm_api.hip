@@ -84,7 +84,8 @@ struct cspm_ctx {
   bool is_grd = false;           // cost built by cspm_build_cost_grd (gradients present)
   bool is_cen = false;           // cost built by cspm_build_cost_cen (census codes present)
   bool is_img = false;           // cost built by cspm_build_cost_img (GrdPC / CSPC: no cells, no volumes)
-  bool is_cengrd = false;        // cost built by cspm_build_cost_cengrd (gradients and census codes present, always volume-sourced)
+  bool is_cengrd = false;        // cost built by cspm_build_cost_cengrd (gradients and census codes present; volume-sourced, or fused: kSrcCenGrd)
+  long long opt_cengrd_fused = 0; // CSPM_OPT_CENGRD_FUSED
   const uint32_t *cen_code[2][CSPM_MAX_LEVELS] = {{nullptr}};
   long long opt_grd_volumes = 0; // CSPM_OPT_GRD_VOLUMES
   long long opt_sweep_pairs = 0;   // CSPM_OPT_SWEEP_PAIRS: 0 = never (default: measured no faster), 1 = when they fit
@@ -565,6 +566,11 @@ int alloc_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg
           L.grd[v] = g;
           c->cen_gray[v][s] = gray;
           c->cen_code[v][s] = code;
+          if (!with_vol) {  // fused cells (CSPM_OPT_CENGRD_FUSED; `with_vol` is part of the reuse key): the tap engines read the census elements and L.grd
+            PixC *pc;
+            if ((rc = dalloc(c, &pc, ppx, &c->cost_allocs))) return rc;
+            L.pc[v] = pc;
+          }
         }
       }
     }
@@ -849,11 +855,13 @@ inline void allow_lds(K kern, size_t shmem) {
     if (c->cost.cs) {                                                                                             \
       if (src_ == kSrcGrd) LAUNCH_ONE((kern<true, kSrcGrd>), grid, block, shmem, __VA_ARGS__);                    \
       else if (src_ == kSrcCen) LAUNCH_ONE((kern<true, kSrcCen>), grid, block, shmem, __VA_ARGS__);               \
+      else if (src_ == kSrcCenGrd) LAUNCH_ONE((kern<true, kSrcCenGrd>), grid, block, shmem, __VA_ARGS__);         \
       else if (src_ == kSrcImg) LAUNCH_ONE((kern<true, kSrcImg>), grid, block, shmem, __VA_ARGS__);               \
       else LAUNCH_ONE((kern<true, kSrcVolume>), grid, block, shmem, __VA_ARGS__);                                 \
     } else {                                                                                                      \
       if (src_ == kSrcGrd) LAUNCH_ONE((kern<false, kSrcGrd>), grid, block, shmem, __VA_ARGS__);                   \
       else if (src_ == kSrcCen) LAUNCH_ONE((kern<false, kSrcCen>), grid, block, shmem, __VA_ARGS__);              \
+      else if (src_ == kSrcCenGrd) LAUNCH_ONE((kern<false, kSrcCenGrd>), grid, block, shmem, __VA_ARGS__);        \
       else if (src_ == kSrcImg) LAUNCH_ONE((kern<false, kSrcImg>), grid, block, shmem, __VA_ARGS__);              \
       else LAUNCH_ONE((kern<false, kSrcVolume>), grid, block, shmem, __VA_ARGS__);                                \
     }                                                                                                             \
@@ -1255,6 +1263,10 @@ const double *ca_raw_cells(cspm_ctx *c, int v, int s, int d0, int n, double *scr
   if (c->is_cen)
     hipLaunchKernelGGL(k_cen_volume, dim3(stride_grid((long long)px * n)), dim3(256), 0, c->stream, c->cen_code[0][s], c->cen_code[1][s], L.W, L.H, d0,
                        n, v, scratch, (unsigned long long *)nullptr);
+  else if (c->is_cengrd)
+    hipLaunchKernelGGL(k_cengrd_volume<SrcU32>, dim3(stride_grid((long long)px * n)), dim3(256), 0, c->stream, SrcU32{L.pix[0], L.Wp, L.pad},
+                       SrcU32{L.pix[1], L.Wp, L.pad}, L.grd[0], L.grd[1], L.Wp, L.pad, c->cen_code[0][s], c->cen_code[1][s], L.W, L.H, d0, n, v, scratch,
+                       (unsigned long long *)nullptr);
   else
     hipLaunchKernelGGL((k_grd_volume<SrcU32, true>), dim3(stride_grid((long long)px * n)), dim3(256), 0, c->stream, SrcU32{L.pix[0], L.Wp, L.pad},
                        SrcU32{L.pix[1], L.Wp, L.pad}, L.grd[0], L.grd[1], L.Wp, L.pad, L.W, L.H, d0, n, v, scratch, (unsigned long long *)nullptr);
@@ -1495,6 +1507,7 @@ int cspm_set_option(cspm_ctx *c, int key, long long value) {
     case CSPM_OPT_TABLE_VOLUMES: c->opt_table_volumes = value ? 1 : 0; return CSPM_OK;
     case CSPM_OPT_SWEEP_PACKED: c->opt_sweep_packed = value ? 1 : 0; return CSPM_OK;
     case CSPM_OPT_SWEEP_FLOW: c->opt_sweep_flow = value ? 1 : 0; return CSPM_OK;
+    case CSPM_OPT_CENGRD_FUSED: c->opt_cengrd_fused = value ? 1 : 0; return CSPM_OK;
     case CSPM_OPT_SWEEP_WG: c->sweep_wg_per_cu = value < 0 ? 0 : (value > 16 ? 16 : (int)value); return CSPM_OK;
     case CSPM_OPT_VIEW_SORT: c->opt_view_sort = value ? 1 : 0; return CSPM_OK;
     case CSPM_OPT_SWEEP_FOLD: c->opt_sweep_fold = value ? 1 : 0; return CSPM_OK;
@@ -1527,6 +1540,8 @@ int cspm_get_option(cspm_ctx *c, int key, long long *value) {
     case CSPM_OPT_SWEEP_FLOW: *value = c->opt_sweep_flow; return CSPM_OK;
     case CSPM_OPT_SWEEP_WG: *value = c->sweep_wg_per_cu; return CSPM_OK;
     case CSPM_OPT_SWEEP_PACKED_ACTIVE: *value = c->sweep_packed ? 1 : 0; return CSPM_OK;
+    case CSPM_OPT_CENGRD_FUSED: *value = c->opt_cengrd_fused; return CSPM_OK;
+    case CSPM_OPT_CENGRD_FUSED_ACTIVE: *value = (c->cost_alloc && c->is_cengrd && c->cost.fused == kSrcCenGrd) ? 1 : 0; return CSPM_OK;
     case CSPM_OPT_SWEEP_PACKED_BAD: {  // synchronises: gradients the packer could not represent (always 0 for 8-bit images)
       if (!c->cost_alloc || !c->d_px8_bad) { *value = 0; return CSPM_OK; }
       DevGuard guard_(c->device);
@@ -1618,14 +1633,16 @@ int cspm_build_cost_cen(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, d
 }
 
 // CENGRD (include/cspm.h): per level the gradients of cspm_build_cost_grd and the census codes of
-// cspm_build_cost_cen, then ONE kernel per view that writes every cell fma(KAPPA, min(H, TAU_CEN), G) and reduces the max.  Always
-// volume-sourced: the PatchMatch kernels, local stereo and cspm_get_cost_slab read the volumes like any CCMethod's.
+// cspm_build_cost_cen, then ONE kernel per view that writes every cell fma(KAPPA, min(H, TAU_CEN), G) and reduces the max.  Volume-sourced
+// by default: the PatchMatch kernels, local stereo and cspm_get_cost_slab read the volumes like any CCMethod's.  With CSPM_OPT_CENGRD_FUSED
+// the kernel only reduces the max, no volume exists, and the tap engines compute the cells from Level::pc and Level::grd (kSrcCenGrd).
 int cspm_build_cost_cengrd(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg_lambda) {
   if (!c) return CSPM_ERR_ARG;
   DevGuard guard_(c->device);
   if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
-  int rc = alloc_cost(c, max_dis, wnd_size, scale_num, reg_lambda, true, kKindCenGrd);
-  if (rc == CSPM_ERR_HIP) return fail(c, rc, "cspm_build_cost_cengrd: device allocation failed (" + c->err + "): the cost needs its f64 volumes on the device, there is no CPU fallback");
+  const bool with_vol = c->opt_cengrd_fused == 0;
+  int rc = alloc_cost(c, max_dis, wnd_size, scale_num, reg_lambda, with_vol, kKindCenGrd);
+  if (rc == CSPM_ERR_HIP && with_vol) return fail(c, rc, "cspm_build_cost_cengrd: device allocation failed (" + c->err + "): the cost needs its f64 volumes on the device, there is no CPU fallback");
   if (rc) return rc;
   Cost &cd = c->cost;
   for (int s = 0; s < cd.levels; ++s) {
@@ -1640,8 +1657,9 @@ int cspm_build_cost_cengrd(cspm_ctx *c, int max_dis, int wnd_size, int scale_num
       hipLaunchKernelGGL(k_gray8<SrcU32>, dim3(ew_grid(px)), dim3(256), 0, c->stream, SrcU32{L.pix[v], L.Wp, L.pad}, L.W, L.H, gray);
       hipLaunchKernelGGL(k_census, dim3(ew_grid(px)), dim3(256), 0, c->stream, gray, L.W, L.H, code);
       hipLaunchKernelGGL(k_make_aos, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, L.pix[v], (const double *)nullptr, ppx, (PixG *)L.px[v]);
+      if (!with_vol) hipLaunchKernelGGL(k_make_aos_cen, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, L.pix[v], code, L.W, L.H, L.Wp, L.pad, (PixC *)L.pc[v]);
     }
-    for (int v = 0; v < 2; ++v) {
+    for (int v = 0; v < 2; ++v) {  // volumes unless fused (L.vol is null then), their max always
       Timed t(c, CSPM_K_GRD, 0);
       hipLaunchKernelGGL(k_cengrd_volume<SrcU32>, dim3(stride_grid(px * (L.D + 1))), dim3(256), 0, c->stream, SrcU32{L.pix[0], L.Wp, L.pad},
                          SrcU32{L.pix[1], L.Wp, L.pad}, L.grd[0], L.grd[1], L.Wp, L.pad, c->cen_code[0][s], c->cen_code[1][s], L.W, L.H, 0, L.D + 1, v,
@@ -1649,7 +1667,7 @@ int cspm_build_cost_cengrd(cspm_ctx *c, int max_dis, int wnd_size, int scale_num
     }
   }
   HIPCHK(c, hipGetLastError());
-  cd.fused = kSrcVolume;
+  cd.fused = with_vol ? kSrcVolume : kSrcCenGrd;
   c->is_cengrd = true;
   return finish_cost(c, false);  // G >= 0 and KAPPA*min(H, TAU_CEN) >= 0: every cell is >= 0
 }
@@ -1850,6 +1868,10 @@ int cspm_get_cost_slab(cspm_ctx *c, int view, int level, int d, double *out) {
   if (c->is_cen)
     hipLaunchKernelGGL(k_cen_volume, dim3(stride_grid((long long)px)), dim3(256), 0, c->stream, c->cen_code[0][level], c->cen_code[1][level], L.W,
                        L.H, d, 1, view, tmp, (unsigned long long *)nullptr);
+  else if (c->is_cengrd)
+    hipLaunchKernelGGL(k_cengrd_volume<SrcU32>, dim3(stride_grid((long long)px)), dim3(256), 0, c->stream, SrcU32{L.pix[0], L.Wp, L.pad},
+                       SrcU32{L.pix[1], L.Wp, L.pad}, L.grd[0], L.grd[1], L.Wp, L.pad, c->cen_code[0][level], c->cen_code[1][level], L.W, L.H, d, 1, view,
+                       tmp, (unsigned long long *)nullptr);
   else
   hipLaunchKernelGGL((k_grd_volume<SrcU32, true>), dim3(stride_grid((long long)px)), dim3(256), 0, c->stream, SrcU32{L.pix[0], L.Wp, L.pad},
                      SrcU32{L.pix[1], L.Wp, L.pad}, L.grd[0], L.grd[1], L.Wp, L.pad, L.W, L.H, d, 1, view, tmp,

@@ -37,6 +37,7 @@ struct ChainLevel {
   bool has_valid;
   double maxc;
   const char *px, *opx;  // own / other view elements
+  const char *gx, *ogx;  // kSrcCenGrd: the gradient arrays of the same pixels (doubles: half the elements' byte offsets)
   int dirE;              // byte step towards larger disparity in the other view: -E (left view) or +E
   double sgn;            // 2*view-1 as a double (GrdPC / CSPC: other_x = q_x + (2*view-1)*q_disp)
   const double *vol;
@@ -61,12 +62,14 @@ __device__ __forceinline__ ChainLevel make_chain_level(const Cost &cd, int s, in
   A.has_valid = L.D >= 2;
   A.maxc = cd.max_cost[view * CSPM_MAX_LEVELS + s];
   A.vol2 = nullptr;
+  A.gx = A.ogx = nullptr;
+  if (SRC == kSrcCenGrd) { A.gx = reinterpret_cast<const char *>(L.grd[view]); A.ogx = reinterpret_cast<const char *>(L.grd[1 - view]); }
   if (SRC == kSrcVol2) {
     A.px = reinterpret_cast<const char *>(L.pix[view]); A.opx = A.px;  // colours only: the guide weight
     A.Ip = L.pix[view][cy * L.Wp + L.pad + cx];
     A.vol2 = reinterpret_cast<const char *>(L.vol2[view]);
     A.Dm1 = max(L.D - 1, 1);  // a level with D < 2 has no valid tap (has_valid): the clamped disparity only forms an address, slab 1 exists
-  } else if (SRC == kSrcCen) {
+  } else if (census_elem<SRC>()) {
     A.px = reinterpret_cast<const char *>(L.pc[view]); A.opx = reinterpret_cast<const char *>(L.pc[1 - view]);
     A.Ip = L.pc[view][cy * L.Wp + L.pad + cx].pix;
   } else if (SRC == kSrcGrd8) {
@@ -271,7 +274,7 @@ __device__ __forceinline__ void chain_passes(const Cost &cd, const ChainLevel &A
   // that level runs without clamp, validity test and select (4 of ~29 instructions per tap and candidate; the margin covers the roundings
   // of the device-order disparity against the corner values, as in the row engine's all-valid rows).  True for most pixels of a sweep:
   // its candidates are the neighbours' settled planes.  Same arithmetic for the taps that were valid anyway: identical bits.
-  bool allv = (SRC == kSrcGrd || SRC == kSrcCen || SRC == kSrcGrd8 || SRC == kSrcVolume || SRC == kSrcVol2) && A.has_valid;
+  bool allv = (SRC == kSrcGrd || census_elem<SRC>() || SRC == kSrcGrd8 || SRC == kSrcVolume || SRC == kSrcVol2) && A.has_valid;
 #if defined(CSPM_STEP_TRACE) || !CSPM_CHAIN_ALLV
   allv = false;
 #endif
@@ -324,6 +327,8 @@ __device__ __forceinline__ void chain_passes(const Cost &cd, const ChainLevel &A
         P = uint4{0u, 0u, pix8_colour(e.y), 0u};
         XP = pix8_x(e.x, e.y);
       } else P = ld_elem<SRC>(A.px, ob + st * (kRowMod * E));  // always inside the padded allocation
+      [[maybe_unused]] double Pg = 0.0;  // kSrcCenGrd: the own element's gradient
+      if constexpr (SRC == kSrcCenGrd) Pg = ld_grad(A.gx, (ob + st * (kRowMod * E)) >> 1);
       const int sad0 = (int)__builtin_amdgcn_sad_u8(A.Ip, (SRC == kSrcVol2 || SRC == kSrcGrd8) ? P.z : pix_of<SRC>(P), 0u);
       const int sad = ok ? sad0 : lutzero;  // masked taps get weight entry kLutZero = 0.0: they add +0.0
       STEP_STAMP(1, sad0, P.z);             // the own element has arrived
@@ -366,6 +371,13 @@ __device__ __forceinline__ void chain_passes(const Cost &cd, const ChainLevel &A
           c0 = left ? chi : clo;
           c1 = left ? clo : chi;
           if (c == 0) STEP_STAMP(4, __double2hiint(c0), __double2hiint(c1));  // both cells (colour table round trip included)
+        } else if constexpr (SRC == kSrcCenGrd) {
+          // per element one 16-byte gather from Level::pc and one 8-byte gather from Level::grd
+          const int of = ob + st * (kRowMod * E) + __mul24(A.dirE, d.f);
+          const uint4 o0 = ld_elem<SRC>(A.opx, of), o1 = ld_elem<SRC>(A.opx, of + A.dirE);
+          const double g0 = ld_grad(A.ogx, of >> 1), g1 = ld_grad(A.ogx, (of + A.dirE) >> 1);
+          c0 = cengrd_cell(lut.a, P, Pg, o0, g0);
+          c1 = cengrd_cell(lut.a, P, Pg, o1, g1);
         } else {
           const int of = ob + st * (kRowMod * E) + __mul24(A.dirE, d.f);
 #if defined(CSPM_SWEEP_TRACE) && defined(CSPM_STEP_TRACE)

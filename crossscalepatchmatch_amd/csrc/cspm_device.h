@@ -56,6 +56,10 @@ enum { kSrcGrd8 = 5 };  // raster sweep only (chain engine), fused GRD: the same
                         // two adjacent other-view elements are 16 contiguous bytes = ONE dwordx4 gather, its own element one dwordx2 gather:
                         // 2 gathers / 24 B per tap instead of 3 / 36 B through the CU's L1 return path, which is what bounds the sweep
 
+enum { kSrcCenGrd = 6 };  // fused CENGRD (CSPM_OPT_CENGRD_FUSED): cell = fma(KAPPA, min(H, TAU_CEN), G) computed on the fly.  An element is 141 bits
+                          // (36 gradient + 24 colour + 80 code + pad flag) and does not fit 16 bytes: the census element PixC {code, pix} stays the
+                          // 16-byte element (Level::pc) and the gradient travels beside it as a parallel 8-byte array (Level::grd), same rows, same padding
+
 // The x-gradient of a GRD level (grd_cc.cpp:76-77) is gray[x+1] - gray[x-1] of the f32 gray image, and every f32 gray value of an
 // 8-bit colour is a multiple of 2^-27 below 256 (0.114f has ulp 2^-27; tests/test_oracle_primitives.py enumerates all 2^24 colours):
 // the gradient is an integer multiple of 2^-27 in (-256, 256) -- 36 bits.  With the 24 bits of colour that is a 60-bit pixel:
@@ -86,9 +90,9 @@ struct Level {
                           // the next column towards larger disparity (x-1 in the right image, x+1 in the left image)} -- the exact
                           // LDS image of a strip slot, so the row engine moves it global -> LDS by DMA (cspm_rows.h)
   const Pix8 *px8[2];     // GRD only: the packed 8-byte elements of kSrcGrd8 (raster sweep), H rows of Wp; null unless built
-  const PixC *pc[2];      // H rows of Wp (fused-census source)
+  const PixC *pc[2];      // H rows of Wp (fused-census and fused-CENGRD sources)
   const uint32_t *pix[2]; // packed colour only, H rows of Wp (pyramid construction, introspection)
-  const double *grd[2];   // x-gradient only, H rows of Wp (GRD volume / max kernels); GRD only
+  const double *grd[2];   // x-gradient only, H rows of Wp (GRD / CENGRD volume and max kernels; the gradient half of a kSrcCenGrd element); GRD and CENGRD
   const double *vol[2];   // cost_vol_[v][s]: (D+1) slabs of H*W doubles, d-major; null when fused
   const double *cvol[2];  // fused GRD only, when it fits the context's budget: the level's DEVICE cells (the bits of grd_cell()) as a volume of
                           // D+1 slabs x H rows x cvW columns, image column x at index cvpad + x (pad columns hold 0.0: only ever read under
@@ -100,7 +104,7 @@ struct Level {
 
 struct Cost {
   int cs;      // 0: PreSSPC::GetPlaneCost, 1: PreCSPC::GetPlaneCost
-  int fused;   // kSrcVolume: cells are read from vol; kSrcGrd / kSrcCen: computed on the fly from px / pc
+  int fused;   // kSrcVolume: cells are read from vol; kSrcGrd / kSrcCen / kSrcCenGrd: computed on the fly from px / pc / pc + grd
   int levels;
   int half;    // half_wnd_
   int n;       // 2*half+1

@@ -117,7 +117,8 @@ __device__ unsigned long long g_unionstat[8 * 8];
 
 // Two wave-private LDS strips per window row (sized by strip_capacity / own_capacity, carved from the launch's dynamic LDS):
 //   other view: 16-byte slots, see rd_cells();   own view: gradients (8 B) and colours (4 B) as two arrays (GRD, volumes),
-//   16-byte {code, colour} slots (census).
+//   16-byte {code, colour} slots (census).  Fused CENGRD (kSrcCenGrd): the census layout, followed by the gradients of the other-view slots
+//   (cap x 8 B) and of the own-view slots (ocap x 8 B) as two more arrays -- a tap reads a 16-byte slot and an 8-byte gradient, never 12 bytes.
 constexpr int kStripRegs = 6;                 // other-view elements a lane carries from global memory to LDS: strips of <= 384 slots
 constexpr int kOwnRegs = 2;                   // own-view elements per lane: 64 centres + window <= 128
 __host__ __device__ inline int strip_capacity(int max_dis, int half) {
@@ -133,6 +134,7 @@ __host__ __device__ inline int wave_lds_bytes(int cap, int ocap) {
   const int dbl = 2 * strip_set_bytes(cap, ocap), single = (cap + ocap) * 16;
   return dbl > single ? dbl : single;
 }
+// (kSrcCenGrd needs (cap + ocap) x 24 bytes: less than the two GRD strip sets, 32 cap + 24 ocap, that every launch is sized for)
 
 // LDS-DMA (gfx950): 64 lanes x 16 (or 4) bytes from per-lane global addresses `sbase + voff` straight into LDS at
 // [lds_dst + lane * 16 (4)) -- no VGPR carries the data, no ds_write is issued.  The compiler neither counts these loads nor
@@ -160,9 +162,10 @@ __device__ __forceinline__ const char *uniform_ptr(const char *p) {
 // what a lane holds of one element on its way from global memory to LDS
 template <int SRC> struct StripReg { typedef u32x3 type; };
 template <> struct StripReg<kSrcCen> { typedef uint4 type; };
+template <> struct StripReg<kSrcCenGrd> { typedef uint4 type; };
 template <int SRC>
 __device__ __forceinline__ typename StripReg<SRC>::type ld_strip(const char *row, int byte_off) {
-  if constexpr (SRC == kSrcCen) return *reinterpret_cast<const uint4 *>(row + (size_t)(unsigned)byte_off);
+  if constexpr (census_elem<SRC>()) return *reinterpret_cast<const uint4 *>(row + (size_t)(unsigned)byte_off);
   else return *reinterpret_cast<const u32x3_a4 *>(row + (size_t)(unsigned)byte_off);
 }
 
@@ -179,7 +182,7 @@ template <int SRC, int VIEW>
 __device__ __forceinline__ void rd_cells(int adr, uint4 &o0, uint4 &o1) {
   constexpr bool down = VIEW == 0 && SRC != kSrcImg;  // second cell one slot below the first
   constexpr int a0 = down ? 16 : 0, a1 = down ? 0 : 16;
-  if constexpr (SRC == kSrcCen) {
+  if constexpr (census_elem<SRC>()) {
     o0 = lds_ld<uint4>(adr + a0);
     o1 = lds_ld<uint4>(adr + a1);
   } else {
@@ -194,7 +197,7 @@ template <int SRC, int VIEW>
 __device__ __forceinline__ StageReg<SRC> ld_stage(const char *row, int byte_off) {
   constexpr int E = elem_size<SRC>();
   StageReg<SRC> r;
-  if constexpr (SRC == kSrcCen) {
+  if constexpr (census_elem<SRC>()) {
     r.v = *reinterpret_cast<const uint4 *>(row + (size_t)(unsigned)byte_off);
   } else {
     const u32x3 e = *reinterpret_cast<const u32x3_a4 *>(row + (size_t)(unsigned)byte_off);
@@ -207,7 +210,7 @@ __device__ __forceinline__ StageReg<SRC> ld_stage(const char *row, int byte_off)
 // adr_p the colour array (4-byte stride) -- consecutive lanes hit consecutive banks; census: adr_g addresses 16-byte slots.
 template <int SRC>
 __device__ __forceinline__ uint4 rd_own(int adr_g, int adr_p, int j) {
-  if constexpr (SRC == kSrcCen) {
+  if constexpr (census_elem<SRC>()) {
     return lds_ld<uint4>(adr_g + j * 16);
   } else {
     const uint32_t pix = lds_ld<uint32_t>(adr_p + j * 4);
@@ -225,7 +228,7 @@ __device__ __forceinline__ uint4 rd_own(int adr_g, int adr_p, int j) {
 }
 template <int SRC>
 __device__ __forceinline__ void wr_own(char *ostrip, int ocap, int idx, const typename StripReg<SRC>::type &e) {
-  if constexpr (SRC == kSrcCen) {
+  if constexpr (census_elem<SRC>()) {
     *reinterpret_cast<uint4 *>(ostrip + idx * 16) = e;
   } else {
     if constexpr (SRC == kSrcGrd || SRC == kSrcImg) *reinterpret_cast<uint2 *>(ostrip + idx * 8) = uint2{e.x, e.y};
@@ -287,8 +290,10 @@ struct RowSrc {
   // view, see rd_cells); own strip gradient / colour arrays
   int adr_o, adr_g, adr_p;
   int adr_g2, adr_g3;  // == adr_g, but opaque to the compiler (see tap_batch stage 1)
+  int adr_og, adr_gg;  // kSrcCenGrd: the gradient arrays of the two strips, addressed like adr_o / adr_g at half the stride
   // unstaged: image rows in global memory and the byte offset of the lane's window column 0
   const char *own_row, *oth_row;
+  const char *own_grow, *oth_grow;  // kSrcCenGrd: the same rows of the gradient arrays (half the byte offsets of the elements)
   int lane_off;
   // GrdPC / CSPC: the other view is addressed by image column fx (wave-uniform base, no per-lane part), clamped into the
   // range the strip / the padded row holds (only taps of the "impossible disparity" branch are ever clamped)
@@ -320,6 +325,7 @@ __device__ __forceinline__ void tap_batch(const RowLevel &A, const Luts &lut, co
   uint4 P[N], o0[N], o1[N];
   double fr[N], wgt[N], tmp[N];
   bool valid[N], in_img[N];
+  [[maybe_unused]] double Pg[N], og0[N], og1[N];  // kSrcCenGrd: the gradients of P, o0, o1 (8-byte reads beside the 16-byte ones)
   // stage 1: own elements.  (Two 8-byte reads off the same register would be merged into one ds_read2_b64, which runs at half the
   // rate of ds_read_b64: the gradient reads are volatile -- until round 4 they went through laundered copies of the base.)
   if constexpr (STAGED && CSPM_OWN_SINGLE && (SRC == kSrcGrd || SRC == kSrcImg)) {
@@ -335,6 +341,10 @@ __device__ __forceinline__ void tap_batch(const RowLevel &A, const Luts &lut, co
 #pragma unroll
     for (int k = 0; k < N; ++k)
       P[k] = STAGED ? rd_own<SRC>(CSPM_OWN_SINGLE || k == 0 ? adr_g : k == 1 ? adr_g2 : adr_g3, adr_p, J0 + k) : ld_elem<SRC>(R.own_row, off_g + (J0 + k) * E);
+    if constexpr (SRC == kSrcCenGrd) {
+#pragma unroll
+      for (int k = 0; k < N; ++k) Pg[k] = STAGED ? lds_ld_single(R.adr_gg + (g0 + J0 + k) * 8) : ld_grad(R.own_grow, (off_g + (J0 + k) * E) >> 1);
+    }
   }
   // stage 2: disparities (pure arithmetic), then the cells of the other view
 #pragma unroll
@@ -365,10 +375,19 @@ __device__ __forceinline__ void tap_batch(const RowLevel &A, const Luts &lut, co
       tmp[k] = lerp_cells(d.fr, v[0], v[A.slab]);
     } else if (STAGED) {
       rd_cells<SRC, VIEW>(mad_const<dirS>(d.f, adr_o) + j * 16, o0[k], o1[k]);
+      if constexpr (SRC == kSrcCenGrd) {  // the slots' gradients: the same two slots of the 8-byte array (rd_cells: the second cell one slot below for the left view)
+        const int ag = mad_const<dirS / 2>(d.f, R.adr_og) + (g0 + j) * 8;
+        og0[k] = lds_ld_single(ag + (VIEW == 0 ? 8 : 0));
+        og1[k] = lds_ld_single(ag + (VIEW == 0 ? 0 : 8));
+      }
     } else {
       const int of = mad_const<dirE>(d.f, off_g);
       o0[k] = ld_elem<SRC>(R.oth_row, of + j * E);
       o1[k] = ld_elem<SRC>(R.oth_row, of + j * E + dirE);
+      if constexpr (SRC == kSrcCenGrd) {
+        og0[k] = ld_grad(R.oth_grow, (of + j * E) >> 1);
+        og1[k] = ld_grad(R.oth_grow, (of + j * E + dirE) >> 1);
+      }
     }
   }
   // stage 3: guide weights (:161-164); outside the image: weight entry kLutZero = 0.0, the tap adds +0.0
@@ -383,6 +402,10 @@ __device__ __forceinline__ void tap_batch(const RowLevel &A, const Luts &lut, co
 #pragma unroll
     for (int k = 0; k < N; ++k)
       tmp[k] = img_cell(pix_of<SRC>(P[k]), g_of(P[k]), pix_of<SRC>(o0[k]), g_of(o0[k]), pix_of<SRC>(o1[k]), g_of(o1[k]), fr[k]);
+  } else if constexpr (SRC == kSrcCenGrd) {
+#pragma unroll
+    for (int k = 0; k < N; ++k)
+      tmp[k] = lerp_cells(fr[k], cengrd_cell(lut.a, P[k], Pg[k], o0[k], og0[k]), cengrd_cell(lut.a, P[k], Pg[k], o1[k], og1[k]));
   } else if (SRC != kSrcVolume) {
 #pragma unroll
     for (int k = 0; k < N; ++k) {
@@ -415,8 +438,8 @@ __device__ __forceinline__ void tap_group(const RowLevel &A, const Luts &lut, co
   const double qxg = qxg_d;
   qxg_d += (double)kRowMod;                          // exact: small integers
   // ga: the group's first window column as far as the addresses go (g0, or 0 when row_taps steps the bases itself)
-  const int adr_o = R.adr_o + ga * 16, adr_g = R.adr_g + ga * (SRC == kSrcCen ? 16 : 8), adr_p = R.adr_p + ga * 4, off_g = R.lane_off + ga * E;
-  const int adr_g2 = R.adr_g2 + ga * (SRC == kSrcCen ? 16 : 8), adr_g3 = R.adr_g3 + ga * (SRC == kSrcCen ? 16 : 8);
+  const int adr_o = R.adr_o + ga * 16, adr_g = R.adr_g + ga * (census_elem<SRC>() ? 16 : 8), adr_p = R.adr_p + ga * 4, off_g = R.lane_off + ga * E;
+  const int adr_g2 = R.adr_g2 + ga * (census_elem<SRC>() ? 16 : 8), adr_g3 = R.adr_g3 + ga * (census_elem<SRC>() ? 16 : 8);
   tap_batch<SRC, VIEW, EDGE, STAGED, ALLV, 0, (CNT < SUB ? CNT : SUB)>(A, lut, R, g0, adr_o, adr_g, adr_g2, adr_g3, adr_p, off_g, Ip, pa, Gg, qxg, e_rel, e_span, qy,
                                                                   cx_lane, S);
   if constexpr (CNT > SUB)
@@ -637,7 +660,7 @@ __device__ CSPM_LEVEL_INLINE double level_rows(const Cost &cd, const Luts &lut, 
   A.vol = L.vol[VIEW];
   A.slab = (size_t)L.W * (size_t)L.H;
   const char *px, *opx;
-  if (SRC == kSrcCen) {
+  if (census_elem<SRC>()) {
     px = reinterpret_cast<const char *>(L.pc[VIEW]); opx = reinterpret_cast<const char *>(L.pc[1 - VIEW]);
   } else {
     px = reinterpret_cast<const char *>(L.px[VIEW]); opx = reinterpret_cast<const char *>(L.px[1 - VIEW]);
@@ -657,16 +680,25 @@ __device__ CSPM_LEVEL_INLINE double level_rows(const Cost &cd, const Luts &lut, 
   RowSrc R;
   const int strip_a = lds_addr(ctx.strip), ostrip_a = lds_addr(ctx.ostrip);
   R.adr_o = strip_a + (L.pad + cx - A.half - s_lo) * 16 - ((VIEW == 0 && SRC != kSrcImg) ? 16 : 0);
-  R.adr_g = ostrip_a + (cx - cmin) * (SRC == kSrcCen ? 16 : 8);
+  R.adr_g = ostrip_a + (cx - cmin) * (census_elem<SRC>() ? 16 : 8);
   R.adr_p = ostrip_a + ctx.ocap * 8 + (cx - cmin) * 4;
   R.adr_g2 = R.adr_g3 = R.adr_g;
+  // kSrcCenGrd: gradient arrays behind the (cap + ocap) 16-byte slots, other view first; slot k of a strip <-> entry k of its array
+  char *gstrip = nullptr, *gostrip = nullptr;
+  R.adr_og = R.adr_gg = 0;
+  if constexpr (SRC == kSrcCenGrd) {
+    gstrip = ctx.strip + (size_t)(ctx.cap + ctx.ocap) * 16;
+    gostrip = gstrip + (size_t)ctx.cap * 8;
+    R.adr_og = lds_addr(gstrip) + (R.adr_o - strip_a) / 2;
+    R.adr_gg = lds_addr(gostrip) + (cx - cmin) * 8;
+  }
   asm volatile("" : "+v"(R.adr_g2));
   asm volatile("" : "+v"(R.adr_g3));
   R.lane_off = (L.pad + cx - A.half) * E;
   R.img_base = staged ? strip_a + (L.pad - s_lo) * 16 : L.pad * E;
   R.fx_lo = staged ? s_lo - L.pad : -L.pad;
   R.fx_hi = staged ? s_hi - 1 - L.pad : L.W + L.pad - 2;
-  const uint32_t Ip = SRC == kSrcCen ? L.pc[VIEW][cy * L.Wp + L.pad + cx].pix : L.px[VIEW][cy * L.Wp + L.pad + cx].pix;
+  const uint32_t Ip = census_elem<SRC>() ? L.pc[VIEW][cy * L.Wp + L.pad + cx].pix : L.px[VIEW][cy * L.Wp + L.pad + cx].pix;
   const double qx0_d = (double)(cx - A.half);
   const int e_lo = max(0, A.half - cx);                           // first window column inside the image
   const int e_span = min(A.n - 1, A.W - 1 - cx + A.half) - e_lo;  // last one, relative
@@ -1133,25 +1165,44 @@ __device__ CSPM_LEVEL_INLINE double level_rows(const Cost &cd, const Luts &lut, 
   const size_t row_stride = (size_t)L.Wp * E;
   R.own_row = px + (size_t)(cy - A.half + dy_lo) * row_stride;
   R.oth_row = opx + (size_t)(cy - A.half + dy_lo) * row_stride;
+  R.own_grow = R.oth_grow = nullptr;
+  const size_t grow_stride = SRC == kSrcCenGrd ? row_stride / 2 : 0;
+  [[maybe_unused]] double gpre[kStripRegs], gopre[kOwnRegs];  // kSrcCenGrd: the gradients of pre[] / opre[]
+  if constexpr (SRC == kSrcCenGrd) {
+    R.own_grow = reinterpret_cast<const char *>(L.grd[VIEW]) + (size_t)(cy - A.half + dy_lo) * grow_stride;
+    R.oth_grow = reinterpret_cast<const char *>(L.grd[1 - VIEW]) + (size_t)(cy - A.half + dy_lo) * grow_stride;
+  }
   const int pre_off = (s_lo + lane) * E, opre_off = (o_lo + lane) * E;
-  auto fetch = [&](const char *own_row, const char *oth_row) {
+  auto fetch = [&](const char *own_row, const char *oth_row, [[maybe_unused]] const char *own_grow, [[maybe_unused]] const char *oth_grow) {
 #pragma unroll
     for (int k = 0; k < kStripRegs; ++k)
-      if (lane + k * kWave < s_len) pre[k] = ld_stage<SRC, VIEW>(oth_row, pre_off + k * kWave * E);
+      if (lane + k * kWave < s_len) {
+        pre[k] = ld_stage<SRC, VIEW>(oth_row, pre_off + k * kWave * E);
+        if constexpr (SRC == kSrcCenGrd) gpre[k] = ld_grad(oth_grow, (pre_off + k * kWave * E) >> 1);
+      }
 #pragma unroll
     for (int k = 0; k < kOwnRegs; ++k)
-      if (lane + k * kWave < o_len) opre[k] = ld_strip<SRC>(own_row, opre_off + k * kWave * E);
+      if (lane + k * kWave < o_len) {
+        opre[k] = ld_strip<SRC>(own_row, opre_off + k * kWave * E);
+        if constexpr (SRC == kSrcCenGrd) gopre[k] = ld_grad(own_grow, (opre_off + k * kWave * E) >> 1);
+      }
   };
   auto commit = [&]() {
 #pragma unroll
     for (int k = 0; k < kStripRegs; ++k)
-      if (lane + k * kWave < s_len) *reinterpret_cast<uint4 *>(ctx.strip + (lane + k * kWave) * 16) = pre[k].v;
+      if (lane + k * kWave < s_len) {
+        *reinterpret_cast<uint4 *>(ctx.strip + (lane + k * kWave) * 16) = pre[k].v;
+        if constexpr (SRC == kSrcCenGrd) *reinterpret_cast<double *>(gstrip + (lane + k * kWave) * 8) = gpre[k];
+      }
 #pragma unroll
     for (int k = 0; k < kOwnRegs; ++k)
-      if (lane + k * kWave < o_len) wr_own<SRC>(ctx.ostrip, ctx.ocap, lane + k * kWave, opre[k]);
+      if (lane + k * kWave < o_len) {
+        wr_own<SRC>(ctx.ostrip, ctx.ocap, lane + k * kWave, opre[k]);
+        if constexpr (SRC == kSrcCenGrd) *reinterpret_cast<double *>(gostrip + (lane + k * kWave) * 8) = gopre[k];
+      }
   };
   if (staged) {
-    fetch(R.own_row, R.oth_row);
+    fetch(R.own_row, R.oth_row, R.own_grow, R.oth_grow);
     wave_lds_fence();  // the previous level's strip reads are done
     commit();
   }
@@ -1160,7 +1211,7 @@ __device__ CSPM_LEVEL_INLINE double level_rows(const Cost &cd, const Luts &lut, 
     const bool more = dy < dy_hi;
     if (staged) {
       wave_lds_fence();
-      if (more) fetch(R.own_row + row_stride, R.oth_row + row_stride);
+      if (more) fetch(R.own_row + row_stride, R.oth_row + row_stride, R.own_grow + grow_stride, R.oth_grow + grow_stride);
     }
     const double rowterm = b * (double)qy + c;  // q_disp_y, :155
     double Rsum;
@@ -1208,6 +1259,7 @@ __device__ CSPM_LEVEL_INLINE double level_rows(const Cost &cd, const Luts &lut, 
     }
     R.own_row += row_stride;
     R.oth_row += row_stride;
+    if constexpr (SRC == kSrcCenGrd) { R.own_grow += grow_stride; R.oth_grow += grow_stride; }
   }
   return tree.total(dy_hi + 1);
 }

@@ -48,15 +48,19 @@ typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 typedef u32x3 u32x3_a4 __attribute__((aligned(4)));
 // One element with ONE global load and a 32-bit byte offset (saddr + voffset addressing, no 64-bit address math):
 // PixG = dwordx3 {g.lo, g.hi, pix}, PixC = dwordx4 {code0, code1, code2, pix}.  Held as 4 dwords either way.
+// kSrcCen and kSrcCenGrd share the 16-byte census element; kSrcCenGrd reads the gradient of the same pixel from a parallel array of doubles
+// at HALF the element's byte offset (ld_grad)
+template <int SRC> constexpr bool census_elem() { return SRC == kSrcCen || SRC == kSrcCenGrd; }
 template <int SRC>
 __device__ __forceinline__ uint4 ld_elem(const char *base, int byte_off) {
-  if (SRC == kSrcCen) return *reinterpret_cast<const uint4 *>(base + (size_t)(unsigned)byte_off);
+  if (census_elem<SRC>()) return *reinterpret_cast<const uint4 *>(base + (size_t)(unsigned)byte_off);
   const u32x3 v = *reinterpret_cast<const u32x3_a4 *>(base + (size_t)(unsigned)byte_off);
   return uint4{v.x, v.y, v.z, 0u};
 }
-template <int SRC> constexpr int elem_size() { return SRC == kSrcCen ? 16 : SRC == kSrcGrd8 ? 8 : 12; }
+template <int SRC> constexpr int elem_size() { return census_elem<SRC>() ? 16 : SRC == kSrcGrd8 ? 8 : 12; }
 template <int SRC>
-__device__ __forceinline__ uint32_t pix_of(const uint4 &v) { return SRC == kSrcCen ? v.w : v.z; }
+__device__ __forceinline__ uint32_t pix_of(const uint4 &v) { return census_elem<SRC>() ? v.w : v.z; }
+__device__ __forceinline__ double ld_grad(const char *base, int byte_off) { return *reinterpret_cast<const double *>(base + (size_t)(unsigned)byte_off); }
 // kSrcGrd8 (cspm_device.h Pix8): one element = one dwordx2 load; TWO adjacent elements = one dwordx4 load (8-byte aligned)
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -99,6 +103,13 @@ __device__ __forceinline__ double cen_cell(const uint4 &q, const uint4 &o) {
   const int ham = __popc(q.x ^ o.x) + __popc(q.y ^ o.y) + __popc(q.z ^ o.z);
   const int cnt = ((int)o.w < 0) ? eighty : ham;
   return (double)cnt;
+}
+// CENGRD cell (include/cspm.h cspm_build_cost_cengrd; k_cengrd_volume writes the same bits): G = grd_cell() -- the other view's pad cells hold the
+// border colour and the border gradient, so the border branch of grd_volume_cell is the same arithmetic once the pad flag (bit 31 of the census
+// element's `pix`, which v_sad_u8 would count as a fourth channel) is masked -- and H = cen_cell(), 80 in those pad cells.
+__device__ __forceinline__ double cengrd_cell(const double *lut_a, const uint4 &q, double Gq, const uint4 &o, double Go) {
+  const double G = grd_cell(lut_a, q.w, Gq, o.w & 0x00FFFFFFu, Go);
+  return __builtin_fma(CSPM_CENGRD_KAPPA, __builtin_fmin(cen_cell(q, o), CSPM_CENGRD_TAU), G);
 }
 template <int SRC>
 __device__ __forceinline__ double cell_of(const double *lut_a, const uint4 &own, const uint4 &other) {

@@ -50,6 +50,10 @@ inline uint32_t ParseCommandLineFlags(int *argc, char ***argv, bool /*remove_fla
     size_t eq = a.find('=');
     if (eq != std::string::npos) { name = a.substr(0, eq); val = a.substr(eq + 1); has_val = true; }
     if (val.size() >= 2 && val.front() == '"' && val.back() == '"') val = val.substr(1, val.size() - 2);
+    if (name == "help" && !has_val) {  // like gflags: every flag with its description, then exit(1)
+      for (const auto &kv : registry()) std::printf("  --%s  %s\n", kv.first.c_str(), kv.second.help);
+      std::exit(1);
+    }
     auto it = registry().find(name);
     if (it == registry().end() && name.compare(0, 2, "no") == 0) {
       auto jt = registry().find(name.substr(2));

@@ -223,7 +223,9 @@ DevicePlaneCost::DevicePlaneCost(const Mat &l_img, const Mat &r_img, int max_dis
       check(cspm_build_cost_grd(ctx_, max_disp, wnd_size, scale_num, reg_lambda), ctx_, "cspm_build_cost_grd");
     } else if (dynamic_cast<CenCC *>(cc_method)) {
       check(cspm_build_cost_cen(ctx_, max_disp, wnd_size, scale_num, reg_lambda), ctx_, "cspm_build_cost_cen");
-    } else if (dynamic_cast<CenGrdCC *>(cc_method)) {
+    } else if (const CenGrdCC *cg = dynamic_cast<CenGrdCC *>(cc_method)) {
+      // set either way: a parked context keeps the option of the cost object before this one
+      check(cspm_set_option(ctx_, CSPM_OPT_CENGRD_FUSED, cg->fused() ? 1 : 0), ctx_, "cspm_set_option");
       check(cspm_build_cost_cengrd(ctx_, max_disp, wnd_size, scale_num, reg_lambda), ctx_, "cspm_build_cost_cengrd");
     } else {
       // a foreign CCMethod: let it fill host volumes level by level exactly as pre_cs_pc.cc:57-74 does

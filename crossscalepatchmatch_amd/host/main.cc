@@ -28,6 +28,8 @@ DEFINE_string(r_dis_file, "r_dis.png", "right disparity map to write (8-bit)");
 DEFINE_int32(max_dis, 0, "disparity search range");
 DEFINE_int32(dis_scale, 0, "factor applied to disparities before 8-bit quantisation");
 DEFINE_string(cc_name, "CCName", "matching cost: GRD | CEN | CENGRD (census and GRD blended per cell; not in the reference)");
+DEFINE_bool(cc_fused, false, "with --cc_name=CENGRD: compute the cells inside the PatchMatch kernels instead of materialising cost volumes "
+                             "(same maps, no volume memory); no effect with any other --cc_name");
 DEFINE_string(pc_name, "PRE", "plane cost family: PRE = PreSSPC / PreCSPC over --cc_name's cost volumes (the reference's main.cc); "
                               "IMG = GrdPC / CSPC, the volume-free colour + gradient costs (main.cc:106-107, commented out there)");
 DEFINE_string(ca_name, "", "local stereo instead of PatchMatch: cost aggregation BOX | GF | BF over --cc_name's cost volumes, then "
@@ -223,6 +225,7 @@ int run_batch(const std::vector<BatchJob> &jobs, int skipped, int bad_lines) {
     DeviceSlot slot(device, /*keep_context=*/true, /*shared_gpu=*/on_gpu[device] >= 2);
     DeviceSlot::Use use(slot);
     const std::unique_ptr<CCMethod> cost_fn(GetCCType(FLAGS_cc_name));  // NULL for unknown names, rejected by the cost constructors
+    if (CenGrdCC *cg = dynamic_cast<CenGrdCC *>(cost_fn.get())) cg->set_fused(FLAGS_cc_fused);
     // the next pair of the queue, decoded; a pair whose files cannot be read is reported at once and the worker moves on
     auto report = [&](PairRun &p) {
       if (p.rc != EXIT_SUCCESS) {
@@ -308,6 +311,7 @@ int run() {
     cout << "Note: the PFM maps hold the plane disparities before post-processing (--pp_pfm writes the post-processed ones)\n";
   if (FLAGS_batch_list.empty()) {
     const std::unique_ptr<CCMethod> cost_fn(GetCCType(FLAGS_cc_name));  // NULL for unknown names, rejected by the cost constructors
+    if (CenGrdCC *cg = dynamic_cast<CenGrdCC *>(cost_fn.get())) cg->set_fused(FLAGS_cc_fused);
     if (!FLAGS_quiet) cout << "Load Image: " << FLAGS_l_img_file << " " << FLAGS_r_img_file << "\n";
     PairRun p(PairFiles{FLAGS_l_img_file, FLAGS_r_img_file, FLAGS_l_dis_file, FLAGS_r_dis_file, FLAGS_l_disp_pfm, FLAGS_r_disp_pfm}, 0);
     load(p);

@@ -180,6 +180,16 @@ int cspm_build_cost_grd(cspm_ctx *ctx, int max_dis, int wnd_size, int scale_num,
 #define CSPM_OPT_SWEEP_PACKED 10
 #define CSPM_OPT_SWEEP_PACKED_ACTIVE 11
 #define CSPM_OPT_SWEEP_PACKED_BAD 12
+/* CSPM_OPT_CENGRD_FUSED (set before cspm_build_cost_cengrd; default 0): 0 = the CENGRD cost materialises its f64 volumes (see
+ * cspm_build_cost_cengrd).  1 = no volume is allocated: the PatchMatch kernels compute the cell defined at cspm_build_cost_cengrd from the
+ * level's colours, gradients and census codes as they go -- identical planes and costs, bit for bit -- and cspm_get_cost_slab, max_cost and
+ * cspm_local_stereo compute the cells they need slab by slab.  The fused form holds 40 bytes per padded pixel (row stride W_s + 2 * (D_s +
+ * wnd_size / 2 + 8)) and 13 per image pixel, per level and view; the volume form 24 and 13 + 8 * (D_s + 2).  The option is part of what a
+ * cost object's buffers are reused for: changing it between two builds rebuilds.  The GRD-only accelerators (CSPM_OPT_TABLE_VOLUMES,
+ * CSPM_OPT_SWEEP_PAIRS, CSPM_OPT_SWEEP_PACKED) do not apply; their _ACTIVE keys read 0.
+ * CSPM_OPT_CENGRD_FUSED_ACTIVE (read only): 1 when the current cost object is a fused CENGRD one. */
+#define CSPM_OPT_CENGRD_FUSED 19
+#define CSPM_OPT_CENGRD_FUSED_ACTIVE 20
 int cspm_get_option(cspm_ctx *ctx, int key, long long *value);
 int cspm_set_option(cspm_ctx *ctx, int key, long long value);
 /* The same constructors with `new CenCC` (main.cc:43-45; cc/cen_cc.cc:4-137): 9x9 census codes of every level built on
@@ -194,9 +204,9 @@ int cspm_build_cost_cen(cspm_ctx *ctx, int max_dis, int wnd_size, int scale_num,
  * other view is outside).  KAPPA is a power of two and min(H, TAU) an integer, so the cell is G + KAPPA*min(H, TAU) rounded once.
  * Both constants are documented defaults, chosen, not tuned: the census part spans [0, 2.0], the GRD part [0, 2.8].
  * Same contract as the constructors above (everything on the ctx stream, buffers reused for an unchanged geometry, scale_num == 0 =
- * single scale).  The cost is always volume-sourced -- d-major f64 volumes of D_s + 1 slabs per level and view, as
+ * single scale).  By default the cost is volume-sourced -- d-major f64 volumes of D_s + 1 slabs per level and view, as
  * CSPM_OPT_GRD_VOLUMES = 1 gives the other two; that option has no effect here -- so every consumer of a cost object works on it
- * unchanged.  Volumes that do not fit fail the call with CSPM_ERR_HIP. */
+ * unchanged.  Volumes that do not fit fail the call with CSPM_ERR_HIP; CSPM_OPT_CENGRD_FUSED = 1 builds the same cost without them. */
 #define CSPM_CENGRD_KAPPA 0.0625 /* 2^-4 */
 #define CSPM_CENGRD_TAU 32.0
 int cspm_build_cost_cengrd(cspm_ctx *ctx, int max_dis, int wnd_size, int scale_num, double reg_lambda);

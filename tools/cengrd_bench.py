@@ -1,10 +1,13 @@
 """Cost and accuracy of the CENGRD matching cost next to GRD and CEN at the C3 geometry: one JSON line per cost and measurement.
 
-    python tools/cengrd_bench.py [--costs GRD,CEN,CENGRD] [--modes ctor,run,quality] [--pairs 20] [--inflight 2] [--repeats 3]
+    python tools/cengrd_bench.py [--costs GRD,CEN,CENGRD,GRD_fused,CEN_fused,CENGRD_fused] [--modes ctor,run,quality] [--pairs 20] [--inflight 2] [--repeats 3]
                                  [--quality-pairs 6] [--config C3] [--no-motorcycle]
 
 Costs: GRD and CEN are built with CSPM_OPT_GRD_VOLUMES = 1 (materialised f64 volumes: the PatchMatch kernels are then the same
-volume-sourced instantiations CENGRD runs); GRD_fused is the default fused GRD cost (the bench.py headline).
+volume-sourced instantiations CENGRD runs); GRD_fused is the default fused GRD cost (the bench.py headline), CEN_fused the fused census
+cost, CENGRD_fused the CENGRD cost with CSPM_OPT_CENGRD_FUSED = 1 (no volumes: the cells are computed inside the PatchMatch kernels).
+The fused-CENGRD comparison of DESIGN.md section 13 is ONE run of
+    python tools/cengrd_bench.py --costs CENGRD,CENGRD_fused,GRD_fused,CEN_fused --modes run
 Modes:
   ctor     the cost constructor alone, per pair, on one context: host clock around build + synchronise (images already on the device),
            and the summed device time of the constructor's kernels (CSPM_K_GRD).  For the per-kernel split run this mode alone under
@@ -70,10 +73,14 @@ def main():
             ctx.build_cost_grd(*a, volumes=False)
         elif cost == "CEN":
             ctx.build_cost_cen(*a, volumes=True)
+        elif cost == "CEN_fused":
+            ctx.build_cost_cen(*a, volumes=False)
         elif cost == "CENGRD":
-            ctx.build_cost_cengrd(*a)
+            ctx.build_cost_cengrd(*a, fused=False)
+        elif cost == "CENGRD_fused":
+            ctx.build_cost_cengrd(*a, fused=True)
         else:
-            raise ValueError(f"unknown cost {cost!r} (GRD, GRD_fused, CEN or CENGRD)")
+            raise ValueError(f"unknown cost {cost!r} (GRD, GRD_fused, CEN, CEN_fused, CENGRD or CENGRD_fused)")
 
     def run(k, c, l, r, cost, iters=3):
         ctx = ctxs[k]
