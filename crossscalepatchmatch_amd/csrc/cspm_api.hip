@@ -42,15 +42,20 @@ struct DevGuard {
   }
 };
 
-// what the buffers of a cost object were sized for: an identical request reuses them (no hipMalloc / hipFree per pair)
+// who built the cost object: cspm_begin_cost (uploaded volumes), cspm_build_cost_grd / _cen / _img (GrdPC / CSPC: no cells, no volumes) / _cengrd
+enum CostKind { kKindNone = -1, kKindForeign = 0, kKindGrd = 1, kKindCen = 2, kKindImg = 3, kKindCenGrd = 4 };
+
+// what the buffers of a cost object were sized for: an identical request reuses them (no hipMalloc / hipFree per pair).
+// `kind` is also THE kind of the context's cost object (alloc_cost sets it, free_cost clears it); whether its cells come from volumes
+// or are computed on the fly is Cost::fused
 struct CostKey {
-  int W = 0, H = 0, max_dis = 0, wnd = 0, scale_num = -1, with_vol = 0, kind = -1, with_pairs = 0, with_cvol = 0, with_px8 = 0;
+  int W = 0, H = 0, max_dis = 0, wnd = 0, scale_num = -1, with_vol = 0, with_pairs = 0, with_cvol = 0, with_px8 = 0;
+  CostKind kind = kKindNone;
   bool operator==(const CostKey &o) const {
     return W == o.W && H == o.H && max_dis == o.max_dis && wnd == o.wnd && scale_num == o.scale_num && with_vol == o.with_vol && kind == o.kind &&
            with_pairs == o.with_pairs && with_cvol == o.with_cvol && with_px8 == o.with_px8;
   }
 };
-enum { kKindForeign = 0, kKindGrd = 1, kKindCen = 2, kKindImg = 3, kKindCenGrd = 4 };
 
 struct cspm_ctx {
   int device = 0, ncu = 256;
@@ -81,10 +86,6 @@ struct cspm_ctx {
   int *d_early_ok = nullptr;      // device flag: every max_cost (and, for uploaded volumes, every min) is >= 0
   uint8_t *cen_gray[2][CSPM_MAX_LEVELS] = {{nullptr}};
   double *d_lut = nullptr, *d_lut_a = nullptr, *d_maxcost = nullptr;
-  bool is_grd = false;           // cost built by cspm_build_cost_grd (gradients present)
-  bool is_cen = false;           // cost built by cspm_build_cost_cen (census codes present)
-  bool is_img = false;           // cost built by cspm_build_cost_img (GrdPC / CSPC: no cells, no volumes)
-  bool is_cengrd = false;        // cost built by cspm_build_cost_cengrd (gradients and census codes present; volume-sourced, or fused: kSrcCenGrd)
   long long opt_cengrd_fused = 0; // CSPM_OPT_CENGRD_FUSED
   const uint32_t *cen_code[2][CSPM_MAX_LEVELS] = {{nullptr}};
   long long opt_grd_volumes = 0; // CSPM_OPT_GRD_VOLUMES
@@ -186,6 +187,12 @@ int fail(cspm_ctx *c, int code, const std::string &msg) {
     if (e_ != hipSuccess)                                                                            \
       return fail(ctx, CSPM_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));             \
   } while (0)
+
+// run the rest of the enclosing scope on the context's device (DevGuard); ON_DEVICE_ID: before a context exists
+#define ON_DEVICE_ID(ctx, dev) \
+  DevGuard guard_(dev);        \
+  if (!guard_.ok) return fail(ctx, CSPM_ERR_HIP, "hipSetDevice failed")
+#define ON_DEVICE(ctx) ON_DEVICE_ID(ctx, (ctx)->device)
 
 template <class T>
 int dalloc(cspm_ctx *c, T **p, size_t n, std::vector<void *> *track) {
@@ -431,7 +438,7 @@ void launch_pyramid(cspm_ctx *c) {
 // allocate the (padded) pyramid images, the per-kind side arrays (gradients / census codes) and, when `with_vol`, the
 // cost volumes; fill Cost (everything except gradients / volume contents / max_cost).  An identical request (same
 // image size, max_dis, window, levels, kind, volumes) reuses every buffer: no allocator call, no host synchronisation.
-int alloc_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg_lambda, bool with_vol, int kind, bool want_pairs = false,
+int alloc_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg_lambda, bool with_vol, CostKind kind, bool want_pairs = false,
                bool want_cvol = false) {
   if (!c->img0[0]) return fail(c, CSPM_ERR_STATE, "cspm_set_images must precede cost construction");
   if (max_dis < 1 || wnd_size < 1 || wnd_size > kMaxWnd || scale_num < 0 || scale_num > CSPM_MAX_LEVELS)
@@ -475,6 +482,14 @@ int alloc_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg
   key.with_cvol = with_cvol;
   const bool with_px8 = kind == kKindGrd && !with_vol && c->opt_sweep_packed != 0;
   key.with_px8 = with_px8;
+  // the side arrays of a kind, per level and view: gradients (GRD, CENGRD: what the cell kernels read; the tap engines of a fused cost too), GRD's
+  // paired elements, 8-bit gray (census input; GrdPC / CSPC's x-gradient input), census codes, and the census elements the tap engines read
+  // for fused census cells (CEN always; CENGRD with CSPM_OPT_CENGRD_FUSED: `with_vol` is part of the reuse key).  The colour elements L.px
+  // (window weights) every kind has
+  const bool need_grd = kind == kKindGrd || kind == kKindCenGrd, need_px16 = kind == kKindGrd;
+  const size_t grd_slack = kind == kKindGrd ? 64 : 0;  // a strip's last DMA piece may start inside the last row
+  const bool need_gray = kind == kKindImg || kind == kKindCen || kind == kKindCenGrd, need_code = kind == kKindCen || kind == kKindCenGrd;
+  const bool need_pc = kind == kKindCen || (kind == kKindCenGrd && !with_vol);
   bool reuse = c->cost_alloc && key == c->cost_key;
   // A cost object that wanted optional volumes and did not get them (free-memory veto, failed hipMalloc) is reused as it is, but not for
   // ever: every volume_retry_pairs-th reuse allocates afresh and asks again, so that one transient shortage -- another context was
@@ -531,46 +546,35 @@ int alloc_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg
           if ((rc = dalloc(c, &vol, (size_t)(D + 2) * px, &c->cost_allocs))) return rc;  // D+1 slabs and one guard slab (clamped taps of a level with D < 2)
           L.vol[v] = vol;
         }
-        if (kind == kKindGrd) {
+        if (need_grd) {
           double *g;
-          if ((rc = dalloc(c, &g, ppx + 64, &c->cost_allocs))) return rc;  // + slack: a strip's last DMA piece may start inside the last row
+          if ((rc = dalloc(c, &g, ppx + grd_slack, &c->cost_allocs))) return rc;
           L.grd[v] = g;
+        }
+        if (need_px16) {
           uint4 *p16;
           if ((rc = dalloc(c, &p16, ppx + 64, &c->cost_allocs))) return rc;
           L.px16[v] = p16;
-          if (with_px8) {
-            Pix8 *p8;
-            if ((rc = dalloc(c, &p8, ppx + 64, &c->cost_allocs))) return rc;  // + slack: a pair load at the last element reads one element beyond
-            L.px8[v] = p8;
-          }
-        } else if (kind == kKindImg) {
+        }
+        if (with_px8) {
+          Pix8 *p8;
+          if ((rc = dalloc(c, &p8, ppx + 64, &c->cost_allocs))) return rc;  // + slack: a pair load at the last element reads one element beyond
+          L.px8[v] = p8;
+        }
+        if (need_gray) {
           uint8_t *gray;
           if ((rc = dalloc(c, &gray, px, &c->cost_allocs))) return rc;
           c->cen_gray[v][s] = gray;
-        } else if (kind == kKindCen) {
-          uint8_t *gray;
+        }
+        if (need_code) {
           uint32_t *code;
+          if ((rc = dalloc(c, &code, px * 3, &c->cost_allocs))) return rc;
+          c->cen_code[v][s] = code;
+        }
+        if (need_pc) {
           PixC *pc;
-          if ((rc = dalloc(c, &gray, px, &c->cost_allocs)) || (rc = dalloc(c, &code, px * 3, &c->cost_allocs)) ||
-              (rc = dalloc(c, &pc, ppx, &c->cost_allocs)))
-            return rc;
-          c->cen_gray[v][s] = gray;
-          c->cen_code[v][s] = code;
+          if ((rc = dalloc(c, &pc, ppx, &c->cost_allocs))) return rc;
           L.pc[v] = pc;
-        } else if (kind == kKindCenGrd) {  // what k_cengrd_volume reads: gradients, 8-bit gray and census codes; the tap engines read the volumes and, for the window weights, the colour elements L.px every kind has
-          double *g;
-          uint8_t *gray;
-          uint32_t *code;
-          if ((rc = dalloc(c, &g, ppx, &c->cost_allocs)) || (rc = dalloc(c, &gray, px, &c->cost_allocs)) || (rc = dalloc(c, &code, px * 3, &c->cost_allocs)))
-            return rc;
-          L.grd[v] = g;
-          c->cen_gray[v][s] = gray;
-          c->cen_code[v][s] = code;
-          if (!with_vol) {  // fused cells (CSPM_OPT_CENGRD_FUSED; `with_vol` is part of the reuse key): the tap engines read the census elements and L.grd
-            PixC *pc;
-            if ((rc = dalloc(c, &pc, ppx, &c->cost_allocs))) return rc;
-            L.pc[v] = pc;
-          }
         }
       }
     }
@@ -653,10 +657,6 @@ int alloc_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg
   HIPCHK(c, hipMemsetAsync(c->d_maxkeys, 0, sizeof(unsigned long long) * 2 * CSPM_MAX_LEVELS, c->stream));
   HIPCHK(c, hipMemsetAsync(c->d_maxkeys + 2 * CSPM_MAX_LEVELS, 0xFF, sizeof(unsigned long long) * 2 * CSPM_MAX_LEVELS, c->stream));
   cd.fused = kSrcVolume;
-  c->is_grd = false;
-  c->is_cen = false;
-  c->is_img = false;
-  c->is_cengrd = false;
   c->sweep_pairs = false;
   c->sweep_packed = false;
   return CSPM_OK;
@@ -683,6 +683,127 @@ int fetch_max_cost(cspm_ctx *c) {
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->max_cost_fetched = true;
   return CSPM_OK;
+}
+
+// The cell kernel of the context's cost kind for slabs d0 .. d0+n-1 of level s, view v: the cells go to `out` (null: none are stored),
+// their max is reduced into `max_key` (null: not reduced).  `optional_volumes`: GRD's constructor also fills Level::vol2 / cvol, where held.
+void launch_cells(cspm_ctx *c, int s, int v, int d0, int n, double *out, unsigned long long *max_key, bool optional_volumes = false) {
+  const Level &L = c->cost.lv[s];
+  const dim3 grid(stride_grid((long long)L.W * L.H * n)), block(256);
+  const SrcU32 l{L.pix[0], L.Wp, L.pad}, r{L.pix[1], L.Wp, L.pad};
+  switch (c->cost_key.kind) {
+    case kKindGrd:
+      hipLaunchKernelGGL((k_grd_volume<SrcU32, true>), grid, block, 0, c->stream, l, r, L.grd[0], L.grd[1], L.Wp, L.pad, L.W, L.H, d0, n, v, out, max_key,
+                         optional_volumes ? (double2 *)L.vol2[v] : nullptr, optional_volumes ? (double *)L.cvol[v] : nullptr,
+                         optional_volumes ? L.cvW : 0, optional_volumes ? L.cvpad : 0);
+      break;
+    case kKindCen:
+      hipLaunchKernelGGL(k_cen_volume, grid, block, 0, c->stream, c->cen_code[0][s], c->cen_code[1][s], L.W, L.H, d0, n, v, out, max_key);
+      break;
+    case kKindCenGrd:
+      hipLaunchKernelGGL(k_cengrd_volume<SrcU32>, grid, block, 0, c->stream, l, r, L.grd[0], L.grd[1], L.Wp, L.pad, c->cen_code[0][s], c->cen_code[1][s],
+                         L.W, L.H, d0, n, v, out, max_key);
+      break;
+    default: break;  // uploaded volumes are read where they are; GrdPC / CSPC have no cells
+  }
+}
+
+// the preparation launches of the constructors, each for level s, view v; g: the gradients to put into the colour elements, or null
+void prep_gradient(cspm_ctx *c, const Level &L, int v) {
+  hipLaunchKernelGGL(k_gradient<SrcU32>, dim3(ew_grid((long long)L.Wp * L.H)), dim3(256), 0, c->stream, SrcU32{L.pix[v], L.Wp, L.pad}, L.W, L.H, L.Wp,
+                     L.pad, const_cast<double *>(L.grd[v]));
+}
+void prep_census(cspm_ctx *c, int s, int v) {
+  const Level &L = c->cost.lv[s];
+  const long long px = (long long)L.W * L.H;
+  hipLaunchKernelGGL(k_gray8<SrcU32>, dim3(ew_grid(px)), dim3(256), 0, c->stream, SrcU32{L.pix[v], L.Wp, L.pad}, L.W, L.H, c->cen_gray[v][s]);
+  hipLaunchKernelGGL(k_census, dim3(ew_grid(px)), dim3(256), 0, c->stream, c->cen_gray[v][s], L.W, L.H, const_cast<uint32_t *>(c->cen_code[v][s]));
+}
+void prep_aos(cspm_ctx *c, const Level &L, int v, const double *g) {
+  const long long ppx = (long long)L.Wp * L.H;
+  hipLaunchKernelGGL(k_make_aos, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, L.pix[v], g, ppx, (PixG *)L.px[v]);
+}
+void prep_aos_cen(cspm_ctx *c, int s, int v) {
+  const Level &L = c->cost.lv[s];
+  hipLaunchKernelGGL(k_make_aos_cen, dim3(ew_grid((long long)L.Wp * L.H)), dim3(256), 0, c->stream, L.pix[v], c->cen_code[v][s], L.W, L.H, L.Wp, L.pad,
+                     (PixC *)L.pc[v]);
+}
+
+// The constructors cspm_build_cost_grd / _cen / _cengrd / _img: per level the side arrays of both views, then the cells of both views
+// (pre_cs_pc.cc:57-84) -- stored as volumes when `with_vol`, otherwise only their max is reduced (pre_cs_pc.cc:75-82) and the PatchMatch
+// kernels compute cells on the fly.
+int build_cost(cspm_ctx *c, CostKind kind, int max_dis, int wnd_size, int scale_num, double reg_lambda) {
+  if (!c) return CSPM_ERR_ARG;
+  ON_DEVICE(c);
+  bool with_vol = false, want_pairs = false, want_cvol = false;
+  int fused = kSrcImg;        // the cell source without volumes
+  double floor_val = -1.0;    // finish_cost: max_cost when no cells exist
+  switch (kind) {
+    case kKindGrd:
+      with_vol = c->opt_grd_volumes != 0;
+      want_pairs = !with_vol && c->opt_sweep_pairs != 0;
+      want_cvol = !with_vol && c->opt_table_volumes != 0;
+      fused = kSrcGrd;
+      break;
+    case kKindCen:
+      with_vol = c->opt_grd_volumes != 0;
+      fused = kSrcCen;
+      break;
+    case kKindCenGrd:
+      with_vol = c->opt_cengrd_fused == 0;
+      fused = kSrcCenGrd;
+      break;
+    default: {  // kKindImg
+      const double alpha = 0.1, tau_clr = 10.0, tau_grd = 2.0;
+      floor_val = alpha * tau_clr + (1 - alpha) * tau_grd;
+    }
+  }
+  int rc = alloc_cost(c, max_dis, wnd_size, scale_num, reg_lambda, with_vol, kind, want_pairs, want_cvol);
+  if (rc == CSPM_ERR_HIP && kind == kKindCenGrd && with_vol)
+    return fail(c, rc, "cspm_build_cost_cengrd: device allocation failed (" + c->err + "): the cost needs its f64 volumes on the device, there is no CPU fallback");
+  if (rc) return rc;
+  Cost &cd = c->cost;
+  for (int s = 0; s < cd.levels; ++s) {
+    Level &L = cd.lv[s];
+    const long long px = (long long)L.W * L.H, ppx = (long long)L.Wp * L.H;
+    for (int v = 0; v < 2; ++v) {
+      Timed t(c, CSPM_K_GRD, 0);
+      switch (kind) {
+        case kKindGrd:  // gradients of both views per level (grd_cc.cpp:70-77)
+          prep_gradient(c, L, v);
+          prep_aos(c, L, v, L.grd[v]);
+          // image v is the other view of view 1-v: the left view (0) reads the right image at x-f, x-f-1; the right view the left image at x+f, x+f+1
+          hipLaunchKernelGGL(k_make_px16, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, L.pix[v], L.grd[v], L.Wp, L.H, v == 1 ? -1 : 1, (uint4 *)L.px16[v]);
+          if (L.px8[v])
+            hipLaunchKernelGGL(k_make_px8, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, L.pix[v], L.grd[v], ppx, (Pix8 *)L.px8[v], c->d_px8_bad);
+          break;
+        case kKindCen:
+          prep_census(c, s, v);
+          prep_aos_cen(c, s, v);
+          prep_aos(c, L, v, nullptr);
+          break;
+        case kKindCenGrd:
+          prep_gradient(c, L, v);
+          prep_census(c, s, v);
+          prep_aos(c, L, v, nullptr);
+          if (!with_vol) prep_aos_cen(c, s, v);
+          break;
+        default:  // kKindImg: 8U gray and its x-gradient in the colour elements
+          hipLaunchKernelGGL(k_gray8_u8, dim3(ew_grid(px)), dim3(256), 0, c->stream, L.pix[v], L.W, L.H, L.Wp, L.pad, c->cen_gray[v][s]);
+          hipLaunchKernelGGL(k_make_aos_img, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, L.pix[v], (const uint8_t *)c->cen_gray[v][s], L.W, L.H, L.Wp,
+                             L.pad, (PixG *)L.px[v]);
+      }
+    }
+    for (int v = 0; v < 2 && kind != kKindImg; ++v) {  // volumes when asked for (L.vol is null otherwise), their max always
+      Timed t(c, CSPM_K_GRD, 0);
+      launch_cells(c, s, v, 0, L.D + 1, (double *)L.vol[v], c->d_maxkeys + v * CSPM_MAX_LEVELS + s, true);
+    }
+  }
+  HIPCHK(c, hipGetLastError());
+  cd.fused = with_vol ? kSrcVolume : fused;
+  c->sweep_pairs = cd.lv[0].vol2[0] != nullptr;                // GRD only: alloc_cost gives no other kind these buffers
+  c->sweep_packed = !with_vol && cd.lv[0].px8[0] != nullptr;
+  return finish_cost(c, false, floor_val);  // every cell of these kinds is >= 0 (CENGRD: G >= 0 and KAPPA*min(H, TAU_CEN) >= 0)
 }
 
 int ensure_field(cspm_ctx *c) {
@@ -1260,16 +1381,7 @@ const double *ca_raw_cells(cspm_ctx *c, int v, int s, int d0, int n, double *scr
   const size_t px = (size_t)L.W * L.H;
   if (L.vol[v]) return L.vol[v] + (size_t)d0 * px;
   Timed t(c, CSPM_K_MISC, 0);
-  if (c->is_cen)
-    hipLaunchKernelGGL(k_cen_volume, dim3(stride_grid((long long)px * n)), dim3(256), 0, c->stream, c->cen_code[0][s], c->cen_code[1][s], L.W, L.H, d0,
-                       n, v, scratch, (unsigned long long *)nullptr);
-  else if (c->is_cengrd)
-    hipLaunchKernelGGL(k_cengrd_volume<SrcU32>, dim3(stride_grid((long long)px * n)), dim3(256), 0, c->stream, SrcU32{L.pix[0], L.Wp, L.pad},
-                       SrcU32{L.pix[1], L.Wp, L.pad}, L.grd[0], L.grd[1], L.Wp, L.pad, c->cen_code[0][s], c->cen_code[1][s], L.W, L.H, d0, n, v, scratch,
-                       (unsigned long long *)nullptr);
-  else
-    hipLaunchKernelGGL((k_grd_volume<SrcU32, true>), dim3(stride_grid((long long)px * n)), dim3(256), 0, c->stream, SrcU32{L.pix[0], L.Wp, L.pad},
-                       SrcU32{L.pix[1], L.Wp, L.pad}, L.grd[0], L.grd[1], L.Wp, L.pad, L.W, L.H, d0, n, v, scratch, (unsigned long long *)nullptr);
+  launch_cells(c, s, v, d0, n, scratch, nullptr);
   return scratch;
 }
 
@@ -1370,8 +1482,7 @@ int cspm_create(cspm_ctx **out, int device) {
   if (e != hipSuccess || n <= 0)
     return fail(nullptr, CSPM_ERR_HIP, std::string("no HIP device: ") + (e != hipSuccess ? hipGetErrorString(e) : "count=0"));
   if (device < 0 || device >= n) return fail(nullptr, CSPM_ERR_ARG, "device index out of range");
-  DevGuard guard_(device);
-  if (!guard_.ok) return fail(nullptr, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE_ID(nullptr, device);
   hipDeviceProp_t prop;
   if ((e = hipGetDeviceProperties(&prop, device)) != hipSuccess) return fail(nullptr, CSPM_ERR_HIP, hipGetErrorString(e));
   if (std::string(prop.gcnArchName).rfind("gfx950", 0) != 0)
@@ -1420,8 +1531,7 @@ const char *cspm_last_error(const cspm_ctx *c) { return c ? c->err.c_str() : g_c
 
 int cspm_set_stream(cspm_ctx *c, void *s) {
   if (!c) return CSPM_ERR_ARG;
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->stream = s ? (hipStream_t)s : c->own_stream;
   return CSPM_OK;
@@ -1435,8 +1545,7 @@ int cspm_get_stream(cspm_ctx *c, void **out) {
 
 int cspm_synchronize(cspm_ctx *c) {
   if (!c) return CSPM_ERR_ARG;
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   int rc = check_sweep(c);  // also surfaces a timed-out raster sweep of an asynchronous cspm_patchmatch
   if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1449,8 +1558,7 @@ int cspm_synchronize(cspm_ctx *c) {
 static int set_images_impl(cspm_ctx *c, const void *l, const void *r, int w, int h, size_t stride, bool on_device) {
   if (!c) return CSPM_ERR_ARG;
   if (!l || !r || w < 1 || h < 1 || stride < (size_t)w * 3) return fail(c, CSPM_ERR_ARG, "bad image arguments");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   if (w != c->W || h != c->H) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     free_cost(c);
@@ -1541,7 +1649,7 @@ int cspm_get_option(cspm_ctx *c, int key, long long *value) {
     case CSPM_OPT_SWEEP_WG: *value = c->sweep_wg_per_cu; return CSPM_OK;
     case CSPM_OPT_SWEEP_PACKED_ACTIVE: *value = c->sweep_packed ? 1 : 0; return CSPM_OK;
     case CSPM_OPT_CENGRD_FUSED: *value = c->opt_cengrd_fused; return CSPM_OK;
-    case CSPM_OPT_CENGRD_FUSED_ACTIVE: *value = (c->cost_alloc && c->is_cengrd && c->cost.fused == kSrcCenGrd) ? 1 : 0; return CSPM_OK;
+    case CSPM_OPT_CENGRD_FUSED_ACTIVE: *value = (c->cost_alloc && c->cost.fused == kSrcCenGrd) ? 1 : 0; return CSPM_OK;
     case CSPM_OPT_SWEEP_PACKED_BAD: {  // synchronises: gradients the packer could not represent (always 0 for 8-bit images)
       if (!c->cost_alloc || !c->d_px8_bad) { *value = 0; return CSPM_OK; }
       DevGuard guard_(c->device);
@@ -1555,81 +1663,15 @@ int cspm_get_option(cspm_ctx *c, int key, long long *value) {
   }
 }
 
+// GRD cells: stored as volumes when CSPM_OPT_GRD_VOLUMES, otherwise only their max is reduced and the PatchMatch kernels recompute them
 int cspm_build_cost_grd(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg_lambda) {
-  if (!c) return CSPM_ERR_ARG;
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
-  const bool with_vol = c->opt_grd_volumes != 0;
-  int rc = alloc_cost(c, max_dis, wnd_size, scale_num, reg_lambda, with_vol, kKindGrd, !with_vol && c->opt_sweep_pairs != 0,
-                      !with_vol && c->opt_table_volumes != 0);
-  if (rc) return rc;
-  Cost &cd = c->cost;
-  // gradients of both views per level (grd_cc.cpp:70-77); then the GRD cells of both views
-  // (pre_cs_pc.cc:57-84): stored as volumes when CSPM_OPT_GRD_VOLUMES, otherwise only their max is
-  // reduced (pre_cs_pc.cc:75-82) and the PatchMatch kernels recompute cells on the fly.
-  for (int s = 0; s < cd.levels; ++s) {
-    Level &L = cd.lv[s];
-    const long long ppx = (long long)L.Wp * L.H;
-    for (int v = 0; v < 2; ++v) {
-      double *g = const_cast<double *>(L.grd[v]);
-      Timed t(c, CSPM_K_GRD, 0);
-      hipLaunchKernelGGL(k_gradient<SrcU32>, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, SrcU32{L.pix[v], L.Wp, L.pad}, L.W, L.H,
-                         L.Wp, L.pad, g);
-      hipLaunchKernelGGL(k_make_aos, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, L.pix[v], (const double *)g, ppx, (PixG *)L.px[v]);
-      // image v is the other view of view 1-v: the left view (0) reads the right image at x-f, x-f-1; the right view the left image at x+f, x+f+1
-      hipLaunchKernelGGL(k_make_px16, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, L.pix[v], (const double *)g, L.Wp, L.H, v == 1 ? -1 : 1,
-                         (uint4 *)L.px16[v]);
-      if (L.px8[v])
-        hipLaunchKernelGGL(k_make_px8, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, L.pix[v], (const double *)g, ppx, (Pix8 *)L.px8[v], c->d_px8_bad);
-    }
-    const long long cells = (long long)L.W * L.H * (L.D + 1);
-    for (int v = 0; v < 2; ++v) {
-      Timed t(c, CSPM_K_GRD, 0);
-      hipLaunchKernelGGL((k_grd_volume<SrcU32, true>), dim3(stride_grid(cells)), dim3(256), 0, c->stream, SrcU32{L.pix[0], L.Wp, L.pad},
-                         SrcU32{L.pix[1], L.Wp, L.pad}, L.grd[0], L.grd[1], L.Wp, L.pad, L.W, L.H, 0, L.D + 1, v,
-                         (double *)L.vol[v], c->d_maxkeys + v * CSPM_MAX_LEVELS + s, (double2 *)L.vol2[v], (double *)L.cvol[v], L.cvW, L.cvpad);
-    }
-  }
-  HIPCHK(c, hipGetLastError());
-  cd.fused = with_vol ? kSrcVolume : kSrcGrd;
-  c->sweep_pairs = cd.lv[0].vol2[0] != nullptr;
-  c->sweep_packed = !with_vol && cd.lv[0].px8[0] != nullptr;
-  c->is_grd = true;
-  return finish_cost(c, false);
+  return build_cost(c, kKindGrd, max_dis, wnd_size, scale_num, reg_lambda);
 }
 
 // `new PreSSPC/PreCSPC(l, r, max_dis, wnd, [scale_num,] new CenCC, [reg_lambda])`: census volumes of every level
 // built on the device (cc/cen_cc.cc:4-137), then read by the PatchMatch kernels like any CCMethod's volumes.
 int cspm_build_cost_cen(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg_lambda) {
-  if (!c) return CSPM_ERR_ARG;
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
-  const bool with_vol = c->opt_grd_volumes != 0;
-  int rc = alloc_cost(c, max_dis, wnd_size, scale_num, reg_lambda, with_vol, kKindCen);
-  if (rc) return rc;
-  Cost &cd = c->cost;
-  for (int s = 0; s < cd.levels; ++s) {
-    Level &L = cd.lv[s];
-    const long long px = (long long)L.W * L.H, ppx = (long long)L.Wp * L.H;
-    for (int v = 0; v < 2; ++v) {
-      uint8_t *gray = c->cen_gray[v][s];
-      uint32_t *code = const_cast<uint32_t *>(c->cen_code[v][s]);
-      Timed t(c, CSPM_K_GRD, 0);
-      hipLaunchKernelGGL(k_gray8<SrcU32>, dim3(ew_grid(px)), dim3(256), 0, c->stream, SrcU32{L.pix[v], L.Wp, L.pad}, L.W, L.H, gray);
-      hipLaunchKernelGGL(k_census, dim3(ew_grid(px)), dim3(256), 0, c->stream, gray, L.W, L.H, code);
-      hipLaunchKernelGGL(k_make_aos_cen, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, L.pix[v], code, L.W, L.H, L.Wp, L.pad, (PixC *)L.pc[v]);
-      hipLaunchKernelGGL(k_make_aos, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, L.pix[v], (const double *)nullptr, ppx, (PixG *)L.px[v]);
-    }
-    for (int v = 0; v < 2; ++v) {  // volumes when asked for, their max (pre_cs_pc.cc:75-82) always
-      Timed t(c, CSPM_K_GRD, 0);
-      hipLaunchKernelGGL(k_cen_volume, dim3(stride_grid(px * (L.D + 1))), dim3(256), 0, c->stream, c->cen_code[0][s], c->cen_code[1][s], L.W, L.H,
-                         0, L.D + 1, v, (double *)L.vol[v], c->d_maxkeys + v * CSPM_MAX_LEVELS + s);
-    }
-  }
-  HIPCHK(c, hipGetLastError());
-  cd.fused = with_vol ? kSrcVolume : kSrcCen;
-  c->is_cen = true;
-  return finish_cost(c, false);
+  return build_cost(c, kKindCen, max_dis, wnd_size, scale_num, reg_lambda);
 }
 
 // CENGRD (include/cspm.h): per level the gradients of cspm_build_cost_grd and the census codes of
@@ -1637,143 +1679,99 @@ int cspm_build_cost_cen(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, d
 // by default: the PatchMatch kernels, local stereo and cspm_get_cost_slab read the volumes like any CCMethod's.  With CSPM_OPT_CENGRD_FUSED
 // the kernel only reduces the max, no volume exists, and the tap engines compute the cells from Level::pc and Level::grd (kSrcCenGrd).
 int cspm_build_cost_cengrd(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg_lambda) {
-  if (!c) return CSPM_ERR_ARG;
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
-  const bool with_vol = c->opt_cengrd_fused == 0;
-  int rc = alloc_cost(c, max_dis, wnd_size, scale_num, reg_lambda, with_vol, kKindCenGrd);
-  if (rc == CSPM_ERR_HIP && with_vol) return fail(c, rc, "cspm_build_cost_cengrd: device allocation failed (" + c->err + "): the cost needs its f64 volumes on the device, there is no CPU fallback");
-  if (rc) return rc;
-  Cost &cd = c->cost;
-  for (int s = 0; s < cd.levels; ++s) {
-    Level &L = cd.lv[s];
-    const long long px = (long long)L.W * L.H, ppx = (long long)L.Wp * L.H;
-    for (int v = 0; v < 2; ++v) {
-      double *g = const_cast<double *>(L.grd[v]);
-      uint8_t *gray = c->cen_gray[v][s];
-      uint32_t *code = const_cast<uint32_t *>(c->cen_code[v][s]);
-      Timed t(c, CSPM_K_GRD, 0);
-      hipLaunchKernelGGL(k_gradient<SrcU32>, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, SrcU32{L.pix[v], L.Wp, L.pad}, L.W, L.H, L.Wp, L.pad, g);
-      hipLaunchKernelGGL(k_gray8<SrcU32>, dim3(ew_grid(px)), dim3(256), 0, c->stream, SrcU32{L.pix[v], L.Wp, L.pad}, L.W, L.H, gray);
-      hipLaunchKernelGGL(k_census, dim3(ew_grid(px)), dim3(256), 0, c->stream, gray, L.W, L.H, code);
-      hipLaunchKernelGGL(k_make_aos, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, L.pix[v], (const double *)nullptr, ppx, (PixG *)L.px[v]);
-      if (!with_vol) hipLaunchKernelGGL(k_make_aos_cen, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, L.pix[v], code, L.W, L.H, L.Wp, L.pad, (PixC *)L.pc[v]);
-    }
-    for (int v = 0; v < 2; ++v) {  // volumes unless fused (L.vol is null then), their max always
-      Timed t(c, CSPM_K_GRD, 0);
-      hipLaunchKernelGGL(k_cengrd_volume<SrcU32>, dim3(stride_grid(px * (L.D + 1))), dim3(256), 0, c->stream, SrcU32{L.pix[0], L.Wp, L.pad},
-                         SrcU32{L.pix[1], L.Wp, L.pad}, L.grd[0], L.grd[1], L.Wp, L.pad, c->cen_code[0][s], c->cen_code[1][s], L.W, L.H, 0, L.D + 1, v,
-                         (double *)L.vol[v], c->d_maxkeys + v * CSPM_MAX_LEVELS + s);
-    }
-  }
-  HIPCHK(c, hipGetLastError());
-  cd.fused = with_vol ? kSrcVolume : kSrcCenGrd;
-  c->is_cengrd = true;
-  return finish_cost(c, false);  // G >= 0 and KAPPA*min(H, TAU_CEN) >= 0: every cell is >= 0
+  return build_cost(c, kKindCenGrd, max_dis, wnd_size, scale_num, reg_lambda);
 }
 
 // `new GrdPC(l, r, max_dis, wnd)` (scale_num == 0; plane_cost/grd_pc.cc:11-66) / `new CSPC(l, r, max_dis, wnd, scale_num,
 // reg_lambda)` (cspc.cc:11-93): pyramid, 8U gray and its x-gradient per level; no volumes, no CCMethod.  max_cost_ has no
 // counterpart in these classes: the "impossible disparity" cost is a constant (grd_pc.cc:131-132, cspc.cc:150-152).
 int cspm_build_cost_img(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg_lambda) {
-  if (!c) return CSPM_ERR_ARG;
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
-  int rc = alloc_cost(c, max_dis, wnd_size, scale_num, reg_lambda, false, kKindImg);
+  return build_cost(c, kKindImg, max_dis, wnd_size, scale_num, reg_lambda);
+}
+
+// The one-shot host entries (CCMethod::buildCV, CAMethod::aggreCV on caller-owned buffers) work on a temporary context and device buffers
+// of their own: both go when the call returns, and the message of a failure stays behind as the thread's creation error.
+struct Scratch {
+  cspm_ctx *c = nullptr;
+  std::vector<void *> tmp;
+  int done(int code) {
+    if (code) g_create_error = c->err;
+    return code;
+  }
+  ~Scratch() {
+    for (void *p : tmp) (void)hipFree(p);
+    cspm_destroy(c);
+  }
+};
+
+// CCMethod::buildCV / buildRightCV on host buffers (cc_method.h:31-32): the cells of slabs 0 .. maxDis-1 from CV_64FC3 images
+static int build_cv_host(CostKind kind, int device, const double *l_rgb, const double *r_rgb, int w, int h, int maxDis, int right_view, double *vol_out) {
+  if (!l_rgb || !r_rgb || !vol_out || w < 1 || h < 1 || maxDis < 1) return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
+  Scratch S;
+  int rc = cspm_create(&S.c, device);
   if (rc) return rc;
-  Cost &cd = c->cost;
-  for (int s = 0; s < cd.levels; ++s) {
-    Level &L = cd.lv[s];
-    const long long px = (long long)L.W * L.H, ppx = (long long)L.Wp * L.H;
-    for (int v = 0; v < 2; ++v) {
-      uint8_t *gray = c->cen_gray[v][s];
-      Timed t(c, CSPM_K_GRD, 0);
-      hipLaunchKernelGGL(k_gray8_u8, dim3(ew_grid(px)), dim3(256), 0, c->stream, L.pix[v], L.W, L.H, L.Wp, L.pad, gray);
-      hipLaunchKernelGGL(k_make_aos_img, dim3(ew_grid(ppx)), dim3(256), 0, c->stream, L.pix[v], (const uint8_t *)gray, L.W, L.H, L.Wp, L.pad,
-                         (PixG *)L.px[v]);
+  cspm_ctx *c = S.c;
+  const size_t px = (size_t)w * h;
+  const bool need_grd = kind != kKindCen, need_code = kind != kKindGrd;
+  double *d[2] = {nullptr, nullptr}, *grd[2] = {nullptr, nullptr}, *vol = nullptr;
+  uint8_t *gray[2] = {nullptr, nullptr};
+  uint32_t *code[2] = {nullptr, nullptr};
+  unsigned long long *key = nullptr;  // k_grd_volume<SrcF64, false> reduces its max: it gets a zeroed key, the other two kernels none
+  const double *src[2] = {l_rgb, r_rgb};
+  for (int v = 0; v < 2; ++v) {
+    if ((rc = dalloc(c, &d[v], px * 3, &S.tmp)) || (need_grd && (rc = dalloc(c, &grd[v], px, &S.tmp))) ||
+        (need_code && ((rc = dalloc(c, &gray[v], px, &S.tmp)) || (rc = dalloc(c, &code[v], px * 3, &S.tmp)))))
+      return S.done(rc);
+    if (hipMemcpyAsync(d[v], src[v], sizeof(double) * px * 3, hipMemcpyHostToDevice, c->stream) != hipSuccess) return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  }
+  if ((rc = dalloc(c, &vol, px * maxDis, &S.tmp)) || (kind == kKindGrd && (rc = dalloc(c, &key, 1, &S.tmp)))) return S.done(rc);
+  if (key && hipMemsetAsync(key, 0, sizeof *key, c->stream) != hipSuccess) return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  const dim3 ew(ew_grid((long long)px)), grid(stride_grid((long long)px * maxDis)), block(256);
+  for (int v = 0; v < 2; ++v) {
+    if (need_grd) hipLaunchKernelGGL(k_gradient<SrcF64>, ew, block, 0, c->stream, SrcF64{d[v], w}, w, h, w, 0, grd[v]);
+    if (need_code) {
+      hipLaunchKernelGGL(k_gray8<SrcF64>, ew, block, 0, c->stream, SrcF64{d[v], w}, w, h, gray[v]);
+      hipLaunchKernelGGL(k_census, ew, block, 0, c->stream, gray[v], w, h, code[v]);
     }
   }
-  HIPCHK(c, hipGetLastError());
-  cd.fused = kSrcImg;
-  c->is_img = true;
-  const double alpha = 0.1, tau_clr = 10.0, tau_grd = 2.0;
-  return finish_cost(c, false, alpha * tau_clr + (1 - alpha) * tau_grd);
+  const SrcF64 l{d[0], w}, r{d[1], w};
+  const char *what;
+  if (kind == kKindGrd) {
+    what = "GRD volume kernel failed";
+    hipLaunchKernelGGL((k_grd_volume<SrcF64, false>), grid, block, 0, c->stream, l, r, grd[0], grd[1], w, 0, w, h, 0, maxDis, right_view, vol, key);
+  } else if (kind == kKindCen) {
+    what = "census volume kernel failed";
+    hipLaunchKernelGGL(k_cen_volume, grid, block, 0, c->stream, code[0], code[1], w, h, 0, maxDis, right_view, vol, (unsigned long long *)nullptr);
+  } else {
+    what = "CENGRD volume kernel failed";
+    hipLaunchKernelGGL(k_cengrd_volume<SrcF64>, grid, block, 0, c->stream, l, r, grd[0], grd[1], w, 0, code[0], code[1], w, h, 0, maxDis, right_view, vol,
+                       (unsigned long long *)nullptr);
+  }
+  if (hipMemcpyAsync(vol_out, vol, sizeof(double) * px * maxDis, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, what));
+  return S.done(CSPM_OK);
+}
+
+// GrdCC::buildCV / buildRightCV on host buffers
+int cspm_grd_build_cv_host(int device, const double *l_rgb, const double *r_rgb, int w, int h, int maxDis, int right_view, double *vol_out) {
+  return build_cv_host(kKindGrd, device, l_rgb, r_rgb, w, h, maxDis, right_view, vol_out);
 }
 
 // CenCC::buildCV / buildRightCV on host buffers (cc_method.h:31-32, cc/cen_cc.cc:4-137)
 int cspm_cen_build_cv_host(int device, const double *l_rgb, const double *r_rgb, int w, int h, int maxDis, int right_view, double *vol_out) {
-  if (!l_rgb || !r_rgb || !vol_out || w < 1 || h < 1 || maxDis < 1) return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
-  cspm_ctx *c = nullptr;
-  int rc = cspm_create(&c, device);
-  if (rc) return rc;
-  const size_t px = (size_t)w * h;
-  double *d[2] = {nullptr, nullptr}, *vol = nullptr;
-  uint8_t *gray[2];
-  uint32_t *code[2];
-  std::vector<void *> tmp;
-  auto done = [&](int code_) {
-    if (code_) g_create_error = c->err;
-    for (void *p : tmp) (void)hipFree(p);
-    cspm_destroy(c);
-    return code_;
-  };
-  const double *src[2] = {l_rgb, r_rgb};
-  for (int v = 0; v < 2; ++v) {
-    if ((rc = dalloc(c, &d[v], px * 3, &tmp)) || (rc = dalloc(c, &gray[v], px, &tmp)) || (rc = dalloc(c, &code[v], px * 3, &tmp))) return done(rc);
-    if (hipMemcpyAsync(d[v], src[v], sizeof(double) * px * 3, hipMemcpyHostToDevice, c->stream) != hipSuccess) return done(fail(c, CSPM_ERR_HIP, "upload failed"));
-    hipLaunchKernelGGL(k_gray8<SrcF64>, dim3(ew_grid((long long)px)), dim3(256), 0, c->stream, SrcF64{d[v], w}, w, h, gray[v]);
-    hipLaunchKernelGGL(k_census, dim3(ew_grid((long long)px)), dim3(256), 0, c->stream, gray[v], w, h, code[v]);
-  }
-  if ((rc = dalloc(c, &vol, px * maxDis, &tmp))) return done(rc);
-  hipLaunchKernelGGL(k_cen_volume, dim3(stride_grid((long long)px * maxDis)), dim3(256), 0, c->stream, code[0], code[1], w, h, 0, maxDis, right_view,
-                     vol, (unsigned long long *)nullptr);
-  if (hipMemcpyAsync(vol_out, vol, sizeof(double) * px * maxDis, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess)
-    return done(fail(c, CSPM_ERR_HIP, "census volume kernel failed"));
-  return done(CSPM_OK);
+  return build_cv_host(kKindCen, device, l_rgb, r_rgb, w, h, maxDis, right_view, vol_out);
 }
 
 // CenGrdCC::buildCV / buildRightCV on host buffers: the CENGRD cells (include/cspm.h) from CV_64FC3 images, gradients as
 // cspm_grd_build_cv_host derives them, census codes as cspm_cen_build_cv_host does
 int cspm_cengrd_build_cv_host(int device, const double *l_rgb, const double *r_rgb, int w, int h, int maxDis, int right_view, double *vol_out) {
-  if (!l_rgb || !r_rgb || !vol_out || w < 1 || h < 1 || maxDis < 1) return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
-  cspm_ctx *c = nullptr;
-  int rc = cspm_create(&c, device);
-  if (rc) return rc;
-  const size_t px = (size_t)w * h;
-  double *d[2] = {nullptr, nullptr}, *grd[2] = {nullptr, nullptr}, *vol = nullptr;
-  uint8_t *gray[2];
-  uint32_t *code[2];
-  std::vector<void *> tmp;
-  auto done = [&](int code_) {
-    if (code_) g_create_error = c->err;
-    for (void *p : tmp) (void)hipFree(p);
-    cspm_destroy(c);
-    return code_;
-  };
-  const double *src[2] = {l_rgb, r_rgb};
-  for (int v = 0; v < 2; ++v) {
-    if ((rc = dalloc(c, &d[v], px * 3, &tmp)) || (rc = dalloc(c, &grd[v], px, &tmp)) || (rc = dalloc(c, &gray[v], px, &tmp)) ||
-        (rc = dalloc(c, &code[v], px * 3, &tmp)))
-      return done(rc);
-    if (hipMemcpyAsync(d[v], src[v], sizeof(double) * px * 3, hipMemcpyHostToDevice, c->stream) != hipSuccess) return done(fail(c, CSPM_ERR_HIP, "upload failed"));
-    hipLaunchKernelGGL(k_gradient<SrcF64>, dim3(ew_grid((long long)px)), dim3(256), 0, c->stream, SrcF64{d[v], w}, w, h, w, 0, grd[v]);
-    hipLaunchKernelGGL(k_gray8<SrcF64>, dim3(ew_grid((long long)px)), dim3(256), 0, c->stream, SrcF64{d[v], w}, w, h, gray[v]);
-    hipLaunchKernelGGL(k_census, dim3(ew_grid((long long)px)), dim3(256), 0, c->stream, gray[v], w, h, code[v]);
-  }
-  if ((rc = dalloc(c, &vol, px * maxDis, &tmp))) return done(rc);
-  hipLaunchKernelGGL(k_cengrd_volume<SrcF64>, dim3(stride_grid((long long)px * maxDis)), dim3(256), 0, c->stream, SrcF64{d[0], w}, SrcF64{d[1], w}, grd[0],
-                     grd[1], w, 0, code[0], code[1], w, h, 0, maxDis, right_view, vol, (unsigned long long *)nullptr);
-  if (hipMemcpyAsync(vol_out, vol, sizeof(double) * px * maxDis, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess)
-    return done(fail(c, CSPM_ERR_HIP, "CENGRD volume kernel failed"));
-  return done(CSPM_OK);
+  return build_cv_host(kKindCenGrd, device, l_rgb, r_rgb, w, h, maxDis, right_view, vol_out);
 }
 
 int cspm_begin_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg_lambda) {
   if (!c) return CSPM_ERR_ARG;
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   int rc = alloc_cost(c, max_dis, wnd_size, scale_num, reg_lambda, true, kKindForeign);
   if (rc) return rc;
   for (int s = 0; s < c->cost.levels; ++s)
@@ -1788,12 +1786,11 @@ int cspm_begin_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, doubl
 
 int cspm_upload_cost_slab(cspm_ctx *c, int view, int level, int d, const double *slab, size_t stride_elems) {
   if (!c) return CSPM_ERR_ARG;
-  if (!c->cost_alloc || c->is_grd || c->is_cen || c->is_img || c->is_cengrd || !c->cost.lv[0].vol[0]) return fail(c, CSPM_ERR_STATE, "cspm_begin_cost first");
+  if (!c->cost_alloc || c->cost_key.kind != kKindForeign) return fail(c, CSPM_ERR_STATE, "cspm_begin_cost first");
   if (view < 0 || view > 1 || level < 0 || level >= c->cost.levels || !slab) return fail(c, CSPM_ERR_ARG, "bad view/level/slab");
   const Level &L = c->cost.lv[level];
   if (d < 0 || d > L.D || stride_elems < (size_t)L.W) return fail(c, CSPM_ERR_ARG, "bad slab index or stride");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   double *dst = (double *)L.vol[view] + (size_t)d * L.W * L.H;
   HIPCHK(c, hipMemcpy2DAsync(dst, sizeof(double) * L.W, slab, sizeof(double) * stride_elems, sizeof(double) * L.W, L.H,
                              hipMemcpyHostToDevice, c->stream));
@@ -1804,9 +1801,8 @@ int cspm_upload_cost_slab(cspm_ctx *c, int view, int level, int d, const double 
 
 int cspm_finish_cost(cspm_ctx *c) {
   if (!c) return CSPM_ERR_ARG;
-  if (!c->cost_alloc || c->is_grd || c->is_cen || c->is_img || c->is_cengrd || !c->cost.lv[0].vol[0]) return fail(c, CSPM_ERR_STATE, "cspm_begin_cost first");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  if (!c->cost_alloc || c->cost_key.kind != kKindForeign) return fail(c, CSPM_ERR_STATE, "cspm_begin_cost first");
+  ON_DEVICE(c);
   HIPCHK(c, hipMemsetAsync(c->d_maxkeys, 0, sizeof(unsigned long long) * 2 * CSPM_MAX_LEVELS, c->stream));
   HIPCHK(c, hipMemsetAsync(c->d_maxkeys + 2 * CSPM_MAX_LEVELS, 0xFF, sizeof(unsigned long long) * 2 * CSPM_MAX_LEVELS, c->stream));
   for (int s = 0; s < c->cost.levels; ++s)
@@ -1835,8 +1831,7 @@ int cspm_get_level_dims(const cspm_ctx *c, int level, int *w, int *h, int *max_d
 int cspm_get_level_image(cspm_ctx *c, int view, int level, uint8_t *out) {
   if (!c || !out) return CSPM_ERR_ARG;
   if (!c->cost_alloc || view < 0 || view > 1 || level < 0 || level >= c->cost.levels) return fail(c, CSPM_ERR_ARG, "bad view/level");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   const Level &L = c->cost.lv[level];
   const size_t px = (size_t)L.W * L.H;
   uint8_t *tmp;
@@ -1853,29 +1848,18 @@ int cspm_get_cost_slab(cspm_ctx *c, int view, int level, int d, double *out) {
   if (!c->cost_alloc || view < 0 || view > 1 || level < 0 || level >= c->cost.levels) return fail(c, CSPM_ERR_ARG, "bad view/level");
   const Level &L = c->cost.lv[level];
   if (d < 0 || d > L.D) return fail(c, CSPM_ERR_ARG, "bad slab index");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   const size_t px = (size_t)L.W * L.H;
   if (L.vol[view]) {
     HIPCHK(c, hipMemcpyAsync(out, L.vol[view] + (size_t)d * px, sizeof(double) * px, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return CSPM_OK;
   }
-  if (c->is_img) return fail(c, CSPM_ERR_STATE, "GrdPC / CSPC have no cost volumes");
+  if (c->cost_key.kind == kKindImg) return fail(c, CSPM_ERR_STATE, "GrdPC / CSPC have no cost volumes");
   // fused cost: materialise the requested slab with the volume kernel
   double *tmp;
   HIPCHK(c, hipMalloc((void **)&tmp, sizeof(double) * px));
-  if (c->is_cen)
-    hipLaunchKernelGGL(k_cen_volume, dim3(stride_grid((long long)px)), dim3(256), 0, c->stream, c->cen_code[0][level], c->cen_code[1][level], L.W,
-                       L.H, d, 1, view, tmp, (unsigned long long *)nullptr);
-  else if (c->is_cengrd)
-    hipLaunchKernelGGL(k_cengrd_volume<SrcU32>, dim3(stride_grid((long long)px)), dim3(256), 0, c->stream, SrcU32{L.pix[0], L.Wp, L.pad},
-                       SrcU32{L.pix[1], L.Wp, L.pad}, L.grd[0], L.grd[1], L.Wp, L.pad, c->cen_code[0][level], c->cen_code[1][level], L.W, L.H, d, 1, view,
-                       tmp, (unsigned long long *)nullptr);
-  else
-  hipLaunchKernelGGL((k_grd_volume<SrcU32, true>), dim3(stride_grid((long long)px)), dim3(256), 0, c->stream, SrcU32{L.pix[0], L.Wp, L.pad},
-                     SrcU32{L.pix[1], L.Wp, L.pad}, L.grd[0], L.grd[1], L.Wp, L.pad, L.W, L.H, d, 1, view, tmp,
-                     (unsigned long long *)nullptr);
+  launch_cells(c, level, view, d, 1, tmp, nullptr);
   hipError_t e = hipMemcpyAsync(out, tmp, sizeof(double) * px, hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   (void)hipFree(tmp);
@@ -1886,8 +1870,7 @@ int cspm_get_cost_slab(cspm_ctx *c, int view, int level, int d, double *out) {
 int cspm_get_max_cost(cspm_ctx *c, int view, int level, double *out) {
   if (!c || !out) return CSPM_ERR_ARG;
   if (!c->cost_ready || view < 0 || view > 1 || level < 0 || level >= c->cost.levels) return fail(c, CSPM_ERR_STATE, "cost not ready or bad view/level");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   int rc = fetch_max_cost(c);
   if (rc) return rc;
   *out = c->host_max_cost[view * CSPM_MAX_LEVELS + level];
@@ -1908,41 +1891,35 @@ int cspm_aggregate_cv_host(int device, int method, const double *guide, int w, i
     return fail(nullptr, CSPM_ERR_ARG, std::string(ca_name(method)) + " needs min(w, h) >= " + std::to_string(ca_min_size(method)) + ", the slabs are " +
                                            std::to_string(w) + "x" + std::to_string(h));
   if (n_slices == 1) return CSPM_OK;
-  cspm_ctx *c = nullptr;
-  int rc = cspm_create(&c, device);
+  Scratch S;
+  int rc = cspm_create(&S.c, device);
   if (rc) return rc;
-  std::vector<void *> tmp;
-  auto done = [&](int code) {
-    if (code) g_create_error = c->err;
-    for (void *p : tmp) (void)hipFree(p);
-    cspm_destroy(c);
-    return code;
-  };
+  cspm_ctx *c = S.c;
   const size_t px = (size_t)w * h;
   const int nb = ca_batch(px);
   CaWork wk;
   double *dv = nullptr, *dout = nullptr;
-  if ((rc = ca_alloc_work(c, px, nb, &wk, &tmp)) || (rc = dalloc(c, &dv, (size_t)(n_slices - 1) * px, &tmp)) ||
-      (rc = dalloc(c, &dout, (size_t)nb * px, &tmp)))
-    return done(rc);
+  if ((rc = ca_alloc_work(c, px, nb, &wk, &S.tmp)) || (rc = dalloc(c, &dv, (size_t)(n_slices - 1) * px, &S.tmp)) ||
+      (rc = dalloc(c, &dout, (size_t)nb * px, &S.tmp)))
+    return S.done(rc);
   std::vector<double> gn(3 * px);  // channel-major, the values as given
   for (size_t i = 0; i < px; ++i)
     for (int k = 0; k < 3; ++k) gn[k * px + i] = guide[3 * i + k];
   if (hipMemcpyAsync(wk.gn, gn.data(), sizeof(double) * 3 * px, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
       hipMemcpyAsync(dv, vol + px, sizeof(double) * (n_slices - 1) * px, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-    return done(fail(c, CSPM_ERR_HIP, "upload failed"));
+    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
   ca_prepare_guide(c, method, wk, w, h);
   for (int d0 = 0; d0 < n_slices - 1; d0 += nb) {
     const int n = std::min(nb, n_slices - 1 - d0);
     ca_filter(c, method, wk, w, h, dv + (size_t)d0 * px, n, dout);
     if (hipMemcpyAsync(dv + (size_t)d0 * px, dout, sizeof(double) * n * px, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-      return done(fail(c, CSPM_ERR_HIP, "copy failed"));
+      return S.done(fail(c, CSPM_ERR_HIP, "copy failed"));
   }
   if (hipGetLastError() != hipSuccess ||
       hipMemcpyAsync(vol + px, dv, sizeof(double) * (n_slices - 1) * px, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
       hipStreamSynchronize(c->stream) != hipSuccess)
-    return done(fail(c, CSPM_ERR_HIP, "aggregation kernels failed"));
-  return done(CSPM_OK);
+    return S.done(fail(c, CSPM_ERR_HIP, "aggregation kernels failed"));
+  return S.done(CSPM_OK);
 }
 
 // local stereo over the ctx's cost object (cspm.h): asynchronous on the ctx stream like cspm_patchmatch
@@ -1950,15 +1927,14 @@ int cspm_local_stereo(cspm_ctx *c, int method) {
   if (!c) return CSPM_ERR_ARG;
   if (method < CSPM_CA_BOX || method > CSPM_CA_BF) return fail(c, CSPM_ERR_ARG, "unknown aggregation method (CSPM_CA_BOX / GF / BF)");
   if (!c->cost_alloc || !c->cost_ready) return fail(c, CSPM_ERR_STATE, "local stereo needs a cost object (cspm_build_cost_grd / _cen / _cengrd / cspm_finish_cost)");
-  if (c->is_img) return fail(c, CSPM_ERR_STATE, "GrdPC / CSPC costs have no cost cells to aggregate");
+  if (c->cost_key.kind == kKindImg) return fail(c, CSPM_ERR_STATE, "GrdPC / CSPC costs have no cost cells to aggregate");
   const Cost &cd = c->cost;
   if (cd.lv[0].D < 2) return fail(c, CSPM_ERR_ARG, "local stereo needs max_dis >= 2");
   for (int s = 0; s < cd.levels; ++s)
     if (cd.lv[s].D >= 1 && std::min(cd.lv[s].W, cd.lv[s].H) < ca_min_size(method))
       return fail(c, CSPM_ERR_ARG, std::string(ca_name(method)) + " needs min(w, h) >= " + std::to_string(ca_min_size(method)) + "; level " +
                                        std::to_string(s) + " is " + std::to_string(cd.lv[s].W) + "x" + std::to_string(cd.lv[s].H));
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   int rc;
   if ((rc = ensure_field(c)) || (rc = ca_ensure(c))) return rc;
   c->field_consistent = false;  // min_cost is the local-stereo cost, not the plane cost of this cost object
@@ -1968,38 +1944,6 @@ int cspm_local_stereo(cspm_ctx *c, int method) {
   return CSPM_OK;
 }
 
-int cspm_grd_build_cv_host(int device, const double *l_rgb, const double *r_rgb, int w, int h, int maxDis, int right_view, double *vol_out) {
-  if (!l_rgb || !r_rgb || !vol_out || w < 1 || h < 1 || maxDis < 1) return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
-  cspm_ctx *c = nullptr;
-  int rc = cspm_create(&c, device);
-  if (rc) return rc;
-  const size_t px = (size_t)w * h;
-  double *dl = nullptr, *dr = nullptr, *gl = nullptr, *gr = nullptr, *vol = nullptr;
-  unsigned long long *key = nullptr;
-  std::vector<void *> tmp;
-  auto done = [&](int code) {
-    if (code) g_create_error = c->err;
-    for (void *p : tmp) (void)hipFree(p);
-    cspm_destroy(c);
-    return code;
-  };
-  if ((rc = dalloc(c, &dl, px * 3, &tmp)) || (rc = dalloc(c, &dr, px * 3, &tmp)) || (rc = dalloc(c, &gl, px, &tmp)) ||
-      (rc = dalloc(c, &gr, px, &tmp)) || (rc = dalloc(c, &vol, px * maxDis, &tmp)) || (rc = dalloc(c, &key, 1, &tmp)))
-    return done(rc);
-  if (hipMemcpyAsync(dl, l_rgb, sizeof(double) * px * 3, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipMemcpyAsync(dr, r_rgb, sizeof(double) * px * 3, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipMemsetAsync(key, 0, sizeof *key, c->stream) != hipSuccess)
-    return done(fail(c, CSPM_ERR_HIP, "upload failed"));
-  hipLaunchKernelGGL(k_gradient<SrcF64>, dim3(ew_grid((long long)px)), dim3(256), 0, c->stream, SrcF64{dl, w}, w, h, w, 0, gl);
-  hipLaunchKernelGGL(k_gradient<SrcF64>, dim3(ew_grid((long long)px)), dim3(256), 0, c->stream, SrcF64{dr, w}, w, h, w, 0, gr);
-  hipLaunchKernelGGL((k_grd_volume<SrcF64, false>), dim3(stride_grid((long long)px * maxDis)), dim3(256), 0, c->stream, SrcF64{dl, w}, SrcF64{dr, w},
-                     gl, gr, w, 0, w, h, 0, maxDis, right_view, vol, key);
-  if (hipMemcpyAsync(vol_out, vol, sizeof(double) * px * maxDis, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess)
-    return done(fail(c, CSPM_ERR_HIP, "GRD volume kernel failed"));
-  return done(CSPM_OK);
-}
-
 int cspm_plane_cost_batch(cspm_ctx *c, int view, int n, const int *xy, const double *np, double *out) {
   if (!c) return CSPM_ERR_ARG;
   if (!c->cost_ready) return fail(c, CSPM_ERR_STATE, "no plane cost built");
@@ -2007,8 +1951,7 @@ int cspm_plane_cost_batch(cspm_ctx *c, int view, int n, const int *xy, const dou
   if (n == 0) return CSPM_OK;
   for (int i = 0; i < n; ++i)
     if (xy[2 * i] < 0 || xy[2 * i] >= c->W || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= c->H) return fail(c, CSPM_ERR_ARG, "pixel outside the image");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   int *dxy = nullptr;
   double *dnp = nullptr, *dout = nullptr;
   std::vector<void *> tmp;
@@ -2038,8 +1981,7 @@ int cspm_pm_default_params(cspm_pm_params *p) {
 
 #define PM_ENTER()                                                            \
   if (!c) return CSPM_ERR_ARG;                                                \
-  DevGuard guard_(c->device);                                                 \
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");        \
+  ON_DEVICE(c);                                                               \
   int rc = check_pm(c, &p);                                                   \
   if (rc) return rc
 
@@ -2082,8 +2024,7 @@ int cspm_rescore_planes(cspm_ctx *c) {
   if (!c) return CSPM_ERR_ARG;
   if (!c->cost_ready) return fail(c, CSPM_ERR_STATE, "no plane cost built (cspm_build_cost_grd / cspm_finish_cost)");
   if (!c->field_alloc) return fail(c, CSPM_ERR_STATE, "no plane field to re-score");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   c->phases_unchecked = true;
   return do_rescore(c);
 }
@@ -2115,8 +2056,7 @@ int cspm_upsample_planes(cspm_ctx *dst, cspm_ctx *src) {
     return fail(dst, CSPM_ERR_ARG, "the source is " + std::to_string(src->W) + "x" + std::to_string(src->H) + ", one pyramid level below " +
                                        std::to_string(dst->W) + "x" + std::to_string(dst->H) + " is " + std::to_string((dst->W + 1) / 2) + "x" +
                                        std::to_string((dst->H + 1) / 2));
-  DevGuard guard_(dst->device);
-  if (!guard_.ok) return fail(dst, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(dst);
   int rc = check_sweep(src);  // a timed-out source run is repeated (or reported) before its planes are read
   if (rc) return fail(dst, rc, "source context: " + src->err);
   if ((rc = ensure_field(dst))) return rc;
@@ -2144,8 +2084,7 @@ int cspm_upsample_planes(cspm_ctx *dst, cspm_ctx *src) {
 int cspm_get_planes(cspm_ctx *c, int view, double *np_out, double *cost_out) {
   if (!c || view < 0 || view > 1) return CSPM_ERR_ARG;
   if (!c->field_alloc) return fail(c, CSPM_ERR_STATE, "no plane field yet");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   {
     int rc = check_sweep(c);
     if (rc) return rc;
@@ -2164,8 +2103,7 @@ int cspm_get_planes(cspm_ctx *c, int view, double *np_out, double *cost_out) {
 int cspm_set_planes(cspm_ctx *c, int view, const double *np, const double *cost) {
   if (!c || view < 0 || view > 1 || !np || !cost) return CSPM_ERR_ARG;
   if (!c->img0[0]) return fail(c, CSPM_ERR_STATE, "cspm_set_images first");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   int rc = ensure_field(c);
   if (rc) return rc;
   const size_t n = (size_t)c->W * c->H;
@@ -2183,8 +2121,7 @@ int cspm_set_planes(cspm_ctx *c, int view, const double *np, const double *cost)
 int cspm_disparity_u8_device(cspm_ctx *c, int view, int dis_scale, void *d_out) {
   if (!c || view < 0 || view > 1 || !d_out) return CSPM_ERR_ARG;
   if (!c->field_alloc) return fail(c, CSPM_ERR_STATE, "no plane field yet");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   // asynchronous: when the run in front of it has an unchecked sweep, remember the request -- a repeated run (sweep timeout)
   // writes the map again from ITS planes, so the caller never reads a map of the aborted run after a successful check
   if (c->sweep_pending) c->remember_output(cspm_ctx::OutReq{0, view, dis_scale, d_out, nullptr});
@@ -2194,8 +2131,7 @@ int cspm_disparity_u8_device(cspm_ctx *c, int view, int dis_scale, void *d_out) 
 int cspm_get_disparity_u8(cspm_ctx *c, int view, int dis_scale, uint8_t *out, size_t stride) {
   if (!c || !out || view < 0 || view > 1 || stride < (size_t)c->W) return CSPM_ERR_ARG;
   if (!c->field_alloc) return fail(c, CSPM_ERR_STATE, "no plane field yet");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   int rc = check_sweep(c);  // BEFORE PlaneToDisp: a run repeated after a sweep timeout must be the one the map is computed from
   if (rc) return rc;
   if ((rc = enqueue_disp_u8(c, view, dis_scale, c->d_dis[view]))) return rc;
@@ -2207,8 +2143,7 @@ int cspm_get_disparity_u8(cspm_ctx *c, int view, int dis_scale, uint8_t *out, si
 int cspm_get_disparity_f64(cspm_ctx *c, int view, double *out) {
   if (!c || view < 0 || view > 1 || !out) return CSPM_ERR_ARG;
   if (!c->field_alloc) return fail(c, CSPM_ERR_STATE, "no plane field yet");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   {
     int rc = check_sweep(c);
     if (rc) return rc;
@@ -2226,8 +2161,7 @@ int cspm_postprocess(cspm_ctx *c, int dis_scale, uint8_t *l_out, uint8_t *r_out,
   if (!c) return CSPM_ERR_ARG;
   if (!c->field_alloc || !c->cost_alloc) return fail(c, CSPM_ERR_STATE, "cspm_postprocess needs a finished PatchMatch");
   if (dis_scale < 1 || stride < (size_t)c->W || !l_out || !r_out) return fail(c, CSPM_ERR_ARG, "bad dis_scale / stride / outputs");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   int rc = check_sweep(c);
   if (rc) return rc;
   if ((rc = postprocess_enqueue(c, dis_scale))) return rc;
@@ -2243,8 +2177,7 @@ int cspm_postprocess_device(cspm_ctx *c, int dis_scale, void *d_l_out, void *d_r
   if (!c) return CSPM_ERR_ARG;
   if (!c->field_alloc || !c->cost_alloc) return fail(c, CSPM_ERR_STATE, "cspm_postprocess_device needs a finished PatchMatch");
   if (dis_scale < 1 || !d_l_out || !d_r_out) return fail(c, CSPM_ERR_ARG, "bad dis_scale / outputs");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   if (c->sweep_pending) c->remember_output(cspm_ctx::OutReq{1, 0, dis_scale, d_l_out, d_r_out});  // see cspm_disparity_u8_device
   return enqueue_postprocess_device(c, dis_scale, d_l_out, d_r_out);
 }
@@ -2254,8 +2187,7 @@ int cspm_postprocess_f64(cspm_ctx *c, double *l_out, double *r_out, uint8_t *l_v
   if (!c) return CSPM_ERR_ARG;
   if (!c->field_alloc || !c->cost_alloc) return fail(c, CSPM_ERR_STATE, "cspm_postprocess_f64 needs a finished PatchMatch");
   if (!l_out || !r_out) return fail(c, CSPM_ERR_ARG, "bad outputs");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   int rc = check_sweep(c);
   if (rc) return rc;
   if ((rc = postprocess_f64_enqueue(c))) return rc;
@@ -2275,8 +2207,7 @@ int cspm_postprocess_f64_device(cspm_ctx *c, void *d_l_out, void *d_r_out) {
   if (!c) return CSPM_ERR_ARG;
   if (!c->field_alloc || !c->cost_alloc) return fail(c, CSPM_ERR_STATE, "cspm_postprocess_f64_device needs a finished PatchMatch");
   if (!d_l_out || !d_r_out) return fail(c, CSPM_ERR_ARG, "bad outputs");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   if (c->sweep_pending) c->remember_output(cspm_ctx::OutReq{2, 0, 0, d_l_out, d_r_out});  // see cspm_disparity_u8_device
   return enqueue_postprocess_f64_device(c, d_l_out, d_r_out);
 }
@@ -2288,16 +2219,14 @@ int cspm_enable_timing(cspm_ctx *c, int on) {
 }
 int cspm_reset_timing(cspm_ctx *c) {
   if (!c) return CSPM_ERR_ARG;
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   int rc = drain_timing(c);
   for (int k = 0; k < CSPM_K_COUNT; ++k) { c->acc_ms[k] = 0; c->acc_launch[k] = 0; c->acc_evals[k] = 0; }
   return rc;
 }
 int cspm_get_timing(cspm_ctx *c, int k, long long *launches, double *total_ms, long long *evals) {
   if (!c || k < 0 || k >= CSPM_K_COUNT) return CSPM_ERR_ARG;
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   int rc = drain_timing(c);
   if (launches) *launches = c->acc_launch[k];
   if (total_ms) *total_ms = c->acc_ms[k];
@@ -2365,8 +2294,7 @@ int cspm_debug_alive_hist(unsigned long long *out120, int reset) {  // [3 groups
 int cspm_fpm_begin(cspm_ctx *c, int w, int h, int max_dis) {
   if (!c) return CSPM_ERR_ARG;
   if (w < 1 || h < 1 || max_dis < 1) return fail(c, CSPM_ERR_ARG, "bad w / h / max_dis");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   if (w != c->W || h != c->H) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     free_cost(c);
@@ -2400,8 +2328,7 @@ int cspm_fpm_candidates(cspm_ctx *c, int phase, int iter, int step, const cspm_p
   if (!c->fpm_cap) return fail(c, CSPM_ERR_STATE, "cspm_fpm_begin first");
   if (!p) p = &kDefaultParams;
   if (p->schedule != CSPM_SCHED_RASTER) return fail(c, CSPM_ERR_ARG, "a foreign IPlaneCost runs the reference's raster schedule only");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   Pm pm = make_pm(c, p);
   const long long n = (long long)c->W * c->H;
   long long count = 0;
@@ -2445,8 +2372,7 @@ int cspm_fpm_candidates(cspm_ctx *c, int phase, int iter, int step, const cspm_p
 int cspm_fpm_commit(cspm_ctx *c, const double *cost) {
   if (!c || !cost) return CSPM_ERR_ARG;
   if (c->fpm_phase < 0) return fail(c, CSPM_ERR_STATE, "no candidate batch pending (cspm_fpm_candidates)");
-  DevGuard guard_(c->device);
-  if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+  ON_DEVICE(c);
   Pm pm = make_pm(c, &c->fpm_params);
   const long long count = c->fpm_count;
   HIPCHK(c, hipMemcpyAsync(c->fpm.cost, cost, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));

@@ -260,3 +260,118 @@ def test_census_cost(gpu_ctx, request, pairname, scale_num, lam, volumes):
             assert L.cspm_cen_build_cv_host(0, dp(l), dp(r), w, h, D, right, dp(a)) == 0
             (lib.csor_cen_build_right_cv if right else lib.csor_cen_build_cv)(dp(l), dp(r), w, h, D, dp(b))
             np.testing.assert_array_equal(a, b)
+
+
+# ---- the state around cost kinds: 65 x 33 (63 x 21 for the slabs), max_dis 8, two levels, window 5 ----------------------------------
+
+ERR_STATE = -3  # CSPM_ERR_STATE
+KIND_ARGS = (8, 5, 2, 0.3)  # max_dis, wnd_size, scale_num, reg_lambda
+KIND_BUILDS = {
+    "grd": lambda c: c.build_cost_grd(*KIND_ARGS),
+    "grd_volumes": lambda c: c.build_cost_grd(*KIND_ARGS, volumes=True),
+    "cen": lambda c: c.build_cost_cen(*KIND_ARGS),
+    "cen_volumes": lambda c: c.build_cost_cen(*KIND_ARGS, volumes=True),
+    "cengrd": lambda c: c.build_cost_cengrd(*KIND_ARGS, fused=False),
+    "cengrd_fused": lambda c: c.build_cost_cengrd(*KIND_ARGS, fused=True),
+    "img": lambda c: c.build_cost_img(*KIND_ARGS),
+}
+
+
+def _kind_images(w, h):
+    from crossscalepatchmatch_amd import synth
+    return synth.make_pair(w, h, KIND_ARGS[0], regions=3, seed=17)[:2]
+
+
+@pytest.fixture
+def kind_ctx(_gpu_ctx_session):
+    """a context of its own (after the session's: torch initialises first), so that no option set here reaches another test"""
+    import crossscalepatchmatch_amd as cs
+    ctx = cs.StereoContext(0)
+    yield ctx
+    ctx.close()
+
+
+def _last_error(ctx):
+    return ctx.L.cspm_last_error(ctx.p).decode()
+
+
+@pytest.mark.parametrize("kind", ["grd", "cen", "cengrd", "cengrd_fused", "img"])
+def test_upload_and_finish_need_begin_cost(kind_ctx, kind):
+    """only a cspm_begin_cost object takes slabs: after every constructor cspm_upload_cost_slab and cspm_finish_cost are state errors"""
+    import ctypes as C
+    ctx = kind_ctx
+    ctx.set_images(*_kind_images(65, 33))
+    KIND_BUILDS[kind](ctx)
+    slab = np.zeros((33, 65))
+    assert ctx.L.cspm_upload_cost_slab(ctx.p, 0, 0, 0, slab.ctypes.data_as(C.POINTER(C.c_double)), 65) == ERR_STATE
+    assert _last_error(ctx) == "cspm_begin_cost first"
+    ctx.L.cspm_set_option(ctx.p, -1, 0)  # another message in between
+    assert ctx.L.cspm_finish_cost(ctx.p) == ERR_STATE
+    assert _last_error(ctx) == "cspm_begin_cost first"
+    ctx.begin_cost(*KIND_ARGS)
+    ctx.upload_cost_slab(0, 0, 0, slab)
+    ctx.finish_cost()
+
+
+def test_img_cost_has_no_cells(kind_ctx):
+    from crossscalepatchmatch_amd import capi
+    import ctypes as C
+    ctx = kind_ctx
+    ctx.set_images(*_kind_images(65, 33))
+    KIND_BUILDS["img"](ctx)
+    out = np.zeros((33, 65))
+    assert ctx.L.cspm_get_cost_slab(ctx.p, 0, 0, 0, out.ctypes.data_as(C.POINTER(C.c_double))) == ERR_STATE
+    assert _last_error(ctx) == "GrdPC / CSPC have no cost volumes"
+    assert ctx.L.cspm_local_stereo(ctx.p, capi.CA_BOX) == ERR_STATE
+    assert _last_error(ctx) == "GrdPC / CSPC costs have no cost cells to aggregate"
+
+
+def test_kinds_in_turn_on_one_context(kind_ctx):
+    """GRD fused -> CEN fused -> IMG -> CENGRD fused -> the CENGRD cells uploaded -> GRD volumes on one context, one PatchMatch
+    iteration after each: planes, costs and max_cost equal a fresh context's that was built with that kind alone -- nothing of the
+    previous object (its kind, its cell source) is left"""
+    import crossscalepatchmatch_amd as cs
+    l, r = _kind_images(65, 33)
+    cells = {}
+
+    def foreign(c):
+        c.begin_cost(*KIND_ARGS)
+        for (v, s), vol in cells.items():
+            for d in range(vol.shape[0]):
+                c.upload_cost_slab(v, s, d, vol[d])
+        c.finish_cost()
+
+    def state(c, build):
+        c.set_images(l, r)
+        build(c)
+        c.patchmatch(1, seed=9)
+        return [c.get_planes(v) for v in (0, 1)], [c.max_cost(v, s) for v in (0, 1) for s in range(c.levels)]
+
+    for kind in ("grd", "cen", "img", "cengrd_fused", "foreign", "grd_volumes"):
+        build = foreign if kind == "foreign" else KIND_BUILDS[kind]
+        got, got_max = state(kind_ctx, build)
+        if kind == "cengrd_fused":
+            cells.update({(v, s): kind_ctx.cost_volume(v, s) for v in (0, 1) for s in range(kind_ctx.levels)})
+        fresh = cs.StereoContext(0)
+        try:
+            want, want_max = state(fresh, build)
+        finally:
+            fresh.close()
+        assert got_max == want_max, kind
+        for v in (0, 1):
+            np.testing.assert_array_equal(got[v][0], want[v][0], err_msg=f"{kind}: planes, view {v}")
+            np.testing.assert_array_equal(got[v][1], want[v][1], err_msg=f"{kind}: min_cost, view {v}")
+
+
+@pytest.mark.parametrize("kind", ["grd", "cen", "cengrd"])
+def test_fused_slabs_equal_the_volumes(kind_ctx, kind):
+    """cspm_get_cost_slab on a fused object launches the cell kernel for one slab (63 x 21: the grid-stride loop has a tail)"""
+    ctx = kind_ctx
+    ctx.set_images(*_kind_images(63, 21))
+    fused, volumes = {"grd": ("grd", "grd_volumes"), "cen": ("cen", "cen_volumes"), "cengrd": ("cengrd_fused", "cengrd")}[kind]
+    KIND_BUILDS[fused](ctx)
+    assert ctx.levels == 2
+    got = {(v, s): ctx.cost_volume(v, s) for v in (0, 1) for s in (0, 1)}
+    KIND_BUILDS[volumes](ctx)
+    for (v, s), vol in got.items():
+        np.testing.assert_array_equal(vol, ctx.cost_volume(v, s), err_msg=f"{kind}: view {v}, level {s}")
