@@ -49,6 +49,7 @@ SYMBOLS = [
     "cspm_enable_timing", "cspm_reset_timing", "cspm_get_timing",
     "cspm_taps_per_view_pass", "cspm_row_engine_taps_per_view_pass", "cspm_fpm_begin", "cspm_fpm_candidates", "cspm_fpm_commit",
     "cspm_aggregate_cv_host", "cspm_local_stereo", "cspm_rescore_planes", "cspm_patchmatch_warm", "cspm_upsample_planes",
+    "cspm_merge_planes", "cspm_merge_planes_host", "cspm_pm_init_keep",
 ]
 
 
@@ -146,6 +147,9 @@ def load_library():
         "cspm_rescore_planes": (C.c_int, [vp]),
         "cspm_patchmatch_warm": (C.c_int, [vp, C.c_int, pp]),
         "cspm_upsample_planes": (C.c_int, [vp, vp]),
+        "cspm_merge_planes": (C.c_int, [vp, vp]),
+        "cspm_merge_planes_host": (C.c_int, [vp, C.c_int, dp, u8p]),
+        "cspm_pm_init_keep": (C.c_int, [vp, pp]),
     }
     assert sorted(sig) == sorted(SYMBOLS)
     for name, (res, args) in sig.items():
@@ -350,6 +354,30 @@ class StereoContext:
         """this context's plane field from src's, one pyramid level below (src is ((w+1)/2, (h+1)/2)); min_cost stays stale"""
         self._chk(self.L.cspm_upsample_planes(self.p, src.p))
 
+    # ---- candidate fields (include/cspm.h "candidate fields") ----
+    def merge_planes_from(self, src):
+        """src's plane field offered to both views of this context: a pixel takes src's plane where it costs less (asynchronous)"""
+        self._chk(self.L.cspm_merge_planes(self.p, src.p))
+
+    def merge_planes(self, view, field, mask=None):
+        """field (h, w, 6) offered to one view; mask (h, w), 0 = no candidate, None = every pixel.  Non-finite planes are no candidates."""
+        f = np.ascontiguousarray(field, dtype=np.float64)
+        assert f.shape == (self.h, self.w, 6), f.shape
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+            assert m.shape == (self.h, self.w), m.shape
+        self._chk(self.L.cspm_merge_planes_host(self.p, view, _dp(f), _u8(m) if m is not None else None))
+
+    def merge_disparity(self, view, disp):
+        """a disparity map (h, w) offered as the fronto-parallel planes (0, 0, 1, 0, 0, d); a non-finite d is no candidate"""
+        self.merge_planes(view, disparity_planes(disp))
+
+    def pm_init_keep(self, **kw):
+        """the random init as a challenger: a pixel takes its InitRandomPlane plane only where it costs less than the stored one"""
+        p = self.params(**kw)
+        self._chk(self.L.cspm_pm_init_keep(self.p, C.byref(p)))
+
     def get_planes(self, view):
         npar = np.zeros((self.h, self.w, 6))
         cost = np.zeros((self.h, self.w))
@@ -435,6 +463,30 @@ def aggregate_cv_host(device, method, guide, vol):
     if rc != 0:
         raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
     return v
+
+
+def disparity_planes(disp):
+    """(h, w) disparities -> the (h, w, 6) fronto-parallel planes (0, 0, 1, 0, 0, d)"""
+    d = np.asarray(disp, dtype=np.float64)
+    f = np.zeros(d.shape + (6,))
+    f[..., 2] = 1.0
+    f[..., 5] = d
+    return f
+
+
+def seeded_patchmatch(ctx, iters, seeds=(), **kw):
+    """PatchMatch whose random start field competes with the caller's hypotheses: pm_init, then every seed merged in turn, then
+    `iters` iterations (patchmatch_warm: a cold run's streams).  A seed is a StereoContext (its plane field, both views) or a tuple
+    (view, field[, mask]) as for merge_planes.  Asynchronous like patchmatch; ctx has its images and cost object."""
+    init_kw = {k: kw[k] for k in ("seed", "rng_mode", "early_exit") if k in kw}
+    ctx.pm_init(**init_kw)
+    for s in seeds:
+        if isinstance(s, StereoContext):
+            ctx.merge_planes_from(s)
+        else:
+            ctx.merge_planes(*s)
+    ctx.patchmatch_warm(iters, **kw)
+    return ctx
 
 
 def coarse_to_fine(l, r, max_dis, coarse_iters=3, fine_iters=1, cc="GRD", wnd_size=35, scale_num=5, reg_lambda=0.3, volumes=False,

@@ -137,6 +137,7 @@ struct cspm_ctx {
   cspm_pm_params last_params{};
   bool last_warm = false;             // that run was cspm_patchmatch_warm: a repeat starts from warm_snap, not from the init
   double *warm_snap = nullptr;        // the starting field of the last warm run (both views, 7 arrays each), kept with the field
+  double *cand_mem = nullptr;         // cspm_merge_planes_host: one view's candidate planes (6 arrays) and, behind them, its mask bytes; allocated by the first such call and kept with the field
   double *diffuse_snap = nullptr;     // CSPM_SCHED_DIFFUSE: the round's snapshot (both views, the 6 plane arrays each), allocated by the first such propagation and kept with the field
   long long sweep_fallbacks = 0;      // how often that happened (cspm_get_option)
   // asynchronous outputs (cspm_disparity_u8_device / cspm_postprocess_device / cspm_postprocess_f64_device) enqueued behind a run whose
@@ -302,6 +303,8 @@ void free_field(cspm_ctx *c) {
   c->warm_snap = nullptr;
   if (c->diffuse_snap) (void)hipFree(c->diffuse_snap);
   c->diffuse_snap = nullptr;
+  if (c->cand_mem) (void)hipFree(c->cand_mem);
+  c->cand_mem = nullptr;
   if (c->vc.cost) (void)hipFree(c->vc.cost);
   if (c->vc.c) (void)hipFree(c->vc.c);
   if (c->vc.cx) (void)hipFree(c->vc.cx);
@@ -1215,6 +1218,20 @@ int do_rescore(cspm_ctx *c) {
   return CSPM_OK;
 }
 
+// candidate-field merging (k_merge / k_merge_keep) of views view0 .. view0 + views - 1: cf == nullptr is keep-init.
+// The field has to be consistent (the callers re-score first) and stays so: an accepted candidate is stored with its own cost.
+int do_merge(cspm_ctx *c, const CandField *cf, const cspm_pm_params *p, int view0, int views, long long evals) {
+  Pm pm = make_pm(c, p);
+  {
+    Timed t(c, CSPM_K_INIT, evals);
+    const RowQueue rq = next_row_queue(c, views);
+    if (cf) LAUNCH_CS(k_merge, dim3(row_grid(c, views)), dim3(kRowBlock), row_shmem(c), c->cost, pm, rq, *cf, view0, views, row_cap(c), row_ocap(c));
+    else LAUNCH_CS(k_merge_keep, dim3(row_grid(c, views)), dim3(kRowBlock), row_shmem(c), c->cost, pm, rq, CandInit{}, view0, views, row_cap(c), row_ocap(c));
+  }
+  HIPCHK(c, hipGetLastError());
+  return CSPM_OK;
+}
+
 // both views' 7 arrays, field -> snapshot (save) or back (restore); the snapshot is allocated by the first warm run and kept
 int warm_snapshot(cspm_ctx *c, bool save) {
   const size_t bytes = sizeof(double) * 14 * (size_t)c->W * c->H;
@@ -2079,6 +2096,81 @@ int cspm_upsample_planes(cspm_ctx *dst, cspm_ctx *src) {
   dst->field_consistent = false;  // min_cost is stale until a re-score (cspm_patchmatch_warm does one)
   if (dst->pm_runs_unchecked) dst->phases_unchecked = true;
   return CSPM_OK;
+}
+
+inline SnapField snap_of(const Field &f) { return SnapField{f.nx, f.ny, f.nz, f.a, f.b, f.c}; }
+
+int cspm_merge_planes(cspm_ctx *dst, cspm_ctx *src) {
+  if (!dst || !src || dst == src) return dst ? fail(dst, CSPM_ERR_ARG, "cspm_merge_planes needs two different contexts") : CSPM_ERR_ARG;
+  if (dst->device != src->device) return fail(dst, CSPM_ERR_ARG, "the two contexts are on different devices");
+  if (!src->field_alloc) return fail(dst, CSPM_ERR_STATE, "the source context has no plane field");
+  if (!dst->img0[0]) return fail(dst, CSPM_ERR_STATE, "cspm_set_images first");
+  if (!dst->cost_ready) return fail(dst, CSPM_ERR_STATE, "no plane cost built (cspm_build_cost_grd / cspm_finish_cost)");
+  if (!dst->field_alloc) return fail(dst, CSPM_ERR_STATE, "no plane field to merge into (cspm_pm_init, cspm_set_planes, cspm_local_stereo or an earlier run)");
+  if (src->W != dst->W || src->H != dst->H)
+    return fail(dst, CSPM_ERR_ARG, "the source is " + std::to_string(src->W) + "x" + std::to_string(src->H) + ", the destination " +
+                                       std::to_string(dst->W) + "x" + std::to_string(dst->H));
+  ON_DEVICE(dst);
+  int rc = check_sweep(src);  // a timed-out source run is repeated (or reported) before its planes are read
+  if (rc) return fail(dst, rc, "source context: " + src->err);
+  if (!dst->field_consistent && (rc = do_rescore(dst))) return rc;
+  // dst's stream waits for the source's work; the source's later work (or its destruction) waits for the merge
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  for (auto &e : ev) HIPCHK(dst, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  hipError_t e = hipEventRecord(ev[0], src->stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(dst->stream, ev[0], 0);
+  if (e == hipSuccess) {
+    const CandField cf{{snap_of(src->f[0]), snap_of(src->f[1])}, {nullptr, nullptr}};
+    rc = do_merge(dst, &cf, &kDefaultParams, 0, 2, 2LL * dst->W * dst->H);
+  }
+  if (e == hipSuccess) e = hipEventRecord(ev[1], dst->stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(src->stream, ev[1], 0);
+  for (auto x : ev) (void)hipEventDestroy(x);
+  if (e != hipSuccess) return fail(dst, CSPM_ERR_HIP, std::string("cspm_merge_planes: ") + hipGetErrorString(e));
+  if (dst->pm_runs_unchecked) dst->phases_unchecked = true;  // an unchecked run can no longer be repeated over these planes
+  return rc;
+}
+
+int cspm_merge_planes_host(cspm_ctx *c, int view, const double *np, const uint8_t *mask) {
+  if (!c) return CSPM_ERR_ARG;
+  if (view < 0 || view > 1 || !np) return fail(c, CSPM_ERR_ARG, "cspm_merge_planes_host: bad view or no candidate field");
+  if (!c->cost_ready) return fail(c, CSPM_ERR_STATE, "no plane cost built (cspm_build_cost_grd / cspm_finish_cost)");
+  if (!c->field_alloc) return fail(c, CSPM_ERR_STATE, "no plane field to merge into (cspm_pm_init, cspm_set_planes, cspm_local_stereo or an earlier run)");
+  ON_DEVICE(c);
+  int rc;
+  const size_t n = (size_t)c->W * c->H;
+  if (!c->cand_mem && (rc = dalloc(c, &c->cand_mem, 6 * n + (n + 7) / 8, nullptr))) return rc;  // 48 + 1 bytes per pixel
+  unsigned char *d_mask = reinterpret_cast<unsigned char *>(c->cand_mem + 6 * n);
+  std::vector<double> h(6 * n);
+  long long evals = 0;  // pixels that have a candidate
+  for (size_t i = 0; i < n; ++i) {
+    bool has = !mask || mask[i] != 0;
+    for (int k = 0; k < 6; ++k) {
+      h[k * n + i] = np[6 * i + k];
+      has = has && std::isfinite(np[6 * i + k]);
+    }
+    evals += has;
+  }
+  // the copies out of caller memory are complete when the call returns; the merge itself is asynchronous
+  HIPCHK(c, hipMemcpyAsync(c->cand_mem, h.data(), sizeof(double) * 6 * n, hipMemcpyHostToDevice, c->stream));
+  if (mask) HIPCHK(c, hipMemcpyAsync(d_mask, mask, n, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (!c->field_consistent && (rc = do_rescore(c))) return rc;
+  CandField cf{};
+  const double *b = c->cand_mem;
+  cf.s[view] = SnapField{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n};
+  cf.mask[view] = mask ? d_mask : nullptr;
+  if (c->pm_runs_unchecked) c->phases_unchecked = true;
+  return do_merge(c, &cf, &kDefaultParams, view, 1, evals);
+}
+
+int cspm_pm_init_keep(cspm_ctx *c, const cspm_pm_params *p) {
+  const bool had_field = c && c->field_alloc;
+  PM_ENTER();
+  if (c->pm_runs_unchecked) c->phases_unchecked = true;
+  if (!had_field) return do_init(c, p);  // nothing to keep
+  if (!c->field_consistent && (rc = do_rescore(c))) return rc;
+  return do_merge(c, nullptr, p, 0, 2, 2LL * c->W * c->H);
 }
 
 int cspm_get_planes(cspm_ctx *c, int view, double *np_out, double *cost_out) {

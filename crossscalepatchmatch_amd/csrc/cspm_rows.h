@@ -1729,4 +1729,67 @@ __global__ __launch_bounds__(kRowBlock, CSPM_ROW_MINW) void k_spatial_diffuse(Co
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Candidate-field merging (an addition; include/cspm.h "candidate fields"): every pixel tries ONE candidate plane,
+// taken whole, against its stored min_cost -- k_refine's accept rule with the candidate read from a caller's field (k_merge) or
+// drawn by InitRandomPlane (k_merge_keep: the stored field is the seed, the random field the challenger).  One body, the candidate
+// source is the functor.  A lane without a candidate (mask 0, a non-finite value) still walks eval_rows with its own stored plane --
+// the wave's reductions need every lane -- and never stores.  The store is safe: the generator reads the candidate field, the random
+// stream and, for a lane without a candidate, that lane's own pixel, which is then not written; never a plane another lane writes.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool finite_bits(double v) { return (__double_as_longlong(v) & 0x7ff0000000000000LL) != 0x7ff0000000000000LL; }
+
+struct CandField {          // a candidate plane field per view, laid out like a Field without costs
+  SnapField s[2];
+  const unsigned char *mask[2];  // per pixel, 0 = no candidate; null: every pixel has one
+  __device__ __forceinline__ bool operator()(const Pm &pm, int v, int x, int y, RowPlane &p) const {
+    p = snap_plane(s[v], pm.W, x, y);
+    const bool fin = finite_bits(p.nx) && finite_bits(p.ny) && finite_bits(p.nz) && finite_bits(p.a) && finite_bits(p.b) && finite_bits(p.c);
+    return fin && (!mask[v] || mask[v][(long long)y * pm.W + x] != 0);
+  }
+};
+struct CandInit {           // the plane InitRandomPlane draws for the pixel: every pixel has one
+  __device__ __forceinline__ bool operator()(const Pm &pm, int v, int x, int y, RowPlane &p) const {
+    p = init_plane(pm, v, x, y);
+    return true;
+  }
+};
+
+// items cover views view0 .. view0 + views - 1
+template <bool CS, int SRC, class Cand>
+__device__ __forceinline__ void merge_rows(const Cost &cd, const Pm &pm, const RowQueue &rq, const Cand &cand, int view0, int views, int cap, int ocap) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  LutMem &s_lut = *reinterpret_cast<LutMem *>(smem);
+  const Luts lut = load_luts(cd, s_lut);
+  RowItem it;
+  if (!row_item(pm.W, pm.H, views, rq, it)) return;
+  const int v = view0 + it.v;
+  const int lane = threadIdx.x & 63;
+  RowCtx ctx = make_row_ctx(smem, it.y, cap, ocap);
+  const bool live = it.x0 + lane < pm.W;
+  const int x = live ? it.x0 + lane : pm.W - 1;  // tail lanes shadow the last pixel
+  const long long i = (long long)it.y * pm.W + x;
+  const Field &f = pm.f[v];
+  const double cur_min = f.cost[i];
+  const bool use_thresh = pm.use_thresh != 0 && *cd.early_ok != 0;
+  auto gen = [&](int xs) {
+    RowPlane p;
+    if (!cand(pm, v, xs, it.y, p)) p = stored_plane(pm, v, xs, it.y);  // no candidate: the lane's own plane, result discarded
+    return p;
+  };
+  const double cost = eval_rows<CS, SRC>(cd, lut, ctx, v, x, gen, cur_min, use_thresh);
+  RowPlane p;
+  const bool has = cand(pm, v, x, it.y, p);
+  if (has && live && cost < cur_min) store_plane(f, i, p.nx, p.ny, p.nz, p.a, p.b, p.c, cost);
+}
+
+template <bool CS, int SRC>
+__global__ __launch_bounds__(kRowBlock, CSPM_INIT_MINW) void k_merge(Cost cd, Pm pm, RowQueue rq, CandField cand, int view0, int views, int cap, int ocap) {
+  merge_rows<CS, SRC>(cd, pm, rq, cand, view0, views, cap, ocap);
+}
+template <bool CS, int SRC>
+__global__ __launch_bounds__(kRowBlock, CSPM_INIT_MINW) void k_merge_keep(Cost cd, Pm pm, RowQueue rq, CandInit cand, int view0, int views, int cap, int ocap) {
+  merge_rows<CS, SRC>(cd, pm, rq, cand, view0, views, cap, ocap);
+}
+
 }  // namespace cspm

@@ -35,6 +35,20 @@ class CSPatchMatch {
   // the starting planes of a view for the next PatchMatchFrom (a previous frame's planes(), for example): wid x hei, row-major.
   // Kept here and written into the cost object's context when PatchMatchFromBegin runs.
   void SetPlanes(const RefView &view, const std::vector<Plane> &planes);
+  // seeded starts (an addition; include/cspm.h "candidate fields"): hypotheses that win only where they cost less than what is there.
+  // AddCandidates: one plane per pixel of a view (wid x hei, row-major; a plane with a non-finite value is no candidate);
+  // AddCandidateDisparity: a CV_32FC1 / CV_64FC1 map offered as fronto-parallel planes, a non-finite or negative value being no
+  // candidate.  Any number per view; kept here until the next PatchMatchSeeded / PatchMatchKeep, which merges them in this order.
+  void AddCandidates(const RefView &view, const std::vector<Plane> &planes);
+  void AddCandidateDisparity(const RefView &view, const Mat &disp);
+  // PatchMatchSeeded: InitRandomPlane, then the candidates merged, then iter_num iterations (cspm_pm_init, cspm_merge_planes_host,
+  // cspm_patchmatch_warm).  PatchMatchKeep: the field already in the device context of plane_cost (LocalStereo, the previous frame's
+  // run, SetPlanes) stays wherever InitRandomPlane's plane costs no less (cspm_pm_init_keep), then the candidates, then the iterations.
+  // Begin / End as for PatchMatchFrom; one of this library's device costs only: a foreign IPlaneCost throws.
+  void PatchMatchSeeded(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp);
+  void PatchMatchSeededBegin(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp);
+  void PatchMatchKeep(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp);
+  void PatchMatchKeepBegin(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp);
 
   // additions (the reference seeds from time(NULL) and has one schedule)
   void set_seed(uint64_t seed) { seed_ = seed; }
@@ -65,6 +79,13 @@ class CSPatchMatch {
   cspm_ctx *pending_ctx_;  // PatchMatchBegin without its PatchMatchEnd yet
   bool pending_pp_;
   std::vector<Plane> start_planes_[kViewNum];  // SetPlanes, not yet written into a context
+  struct Candidates {  // AddCandidates / AddCandidateDisparity, not yet merged: 6 doubles per pixel and a mask (empty: every pixel)
+    std::vector<double> norm_param;
+    std::vector<uint8_t> mask;
+  };
+  std::vector<Candidates> candidates_[kViewNum];
+  void WriteStartPlanes(cspm_ctx *ctx);
+  void SeededBegin(bool keep, int iter_num, const IPlaneCost *plane_cost, bool use_pp);
   void PatchMatchForeign(int iter_num, const IPlaneCost *plane_cost, bool use_pp);
   CSPatchMatch(const CSPatchMatch &);
 };

@@ -397,15 +397,12 @@ void CSPatchMatch::SetPlanes(const RefView &view, const std::vector<Plane> &plan
   start_planes_[view] = planes;
 }
 
-void CSPatchMatch::PatchMatchFromBegin(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp) {
-  const IDevicePlaneCost *dev = dynamic_cast<const IDevicePlaneCost *>(plane_cost);
-  if (!dev) throw std::runtime_error("CSPatchMatch::PatchMatchFrom needs one of this library's device costs (a foreign IPlaneCost runs cold only: PatchMatch)");
-  cspm_ctx *ctx = dev->device_ctx();
-  if (pending_ctx_ && pending_ctx_ != ctx) throw std::runtime_error("CSPatchMatch::PatchMatchFromBegin: the previous run has not been ended");
+// SetPlanes' fields into the context (their costs are re-scored before anything compares against them)
+void CSPatchMatch::WriteStartPlanes(cspm_ctx *ctx) {
   for (int v = 0; v < kViewNum; ++v) {
     if (start_planes_[v].empty()) continue;
     const size_t n = start_planes_[v].size();
-    std::vector<double> np(6 * n), cost(n, 0.0);  // the costs are re-scored before the first iteration
+    std::vector<double> np(6 * n), cost(n, 0.0);
     for (size_t i = 0; i < n; ++i) {
       const Vec3d nv = start_planes_[v][i].norm();
       const Vec3d pv = start_planes_[v][i].param();
@@ -415,6 +412,14 @@ void CSPatchMatch::PatchMatchFromBegin(const int &iter_num, const IPlaneCost *pl
     check(cspm_set_planes(ctx, v, np.data(), cost.data()), ctx, "cspm_set_planes");
     start_planes_[v].clear();
   }
+}
+
+void CSPatchMatch::PatchMatchFromBegin(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp) {
+  const IDevicePlaneCost *dev = dynamic_cast<const IDevicePlaneCost *>(plane_cost);
+  if (!dev) throw std::runtime_error("CSPatchMatch::PatchMatchFrom needs one of this library's device costs (a foreign IPlaneCost runs cold only: PatchMatch)");
+  cspm_ctx *ctx = dev->device_ctx();
+  if (pending_ctx_ && pending_ctx_ != ctx) throw std::runtime_error("CSPatchMatch::PatchMatchFromBegin: the previous run has not been ended");
+  WriteStartPlanes(ctx);
   cspm_pm_params p;
   cspm_pm_default_params(&p);
   p.seed = seed_;
@@ -424,6 +429,84 @@ void CSPatchMatch::PatchMatchFromBegin(const int &iter_num, const IPlaneCost *pl
   check(cspm_patchmatch_warm(ctx, iter_num, &p), ctx, "cspm_patchmatch_warm");  // asynchronous: enqueued on the context's stream
   pending_ctx_ = ctx;
   pending_pp_ = use_pp;
+}
+
+void CSPatchMatch::AddCandidates(const RefView &view, const std::vector<Plane> &planes) {
+  const size_t n = (size_t)wid_ * hei_;
+  if (planes.size() != n) throw std::runtime_error("CSPatchMatch::AddCandidates: one plane per pixel (wid x hei) expected");
+  Candidates c;
+  c.norm_param.resize(6 * n);
+  for (size_t i = 0; i < n; ++i) {
+    const Vec3d nv = planes[i].norm();
+    const Vec3d pv = planes[i].param();
+    double *q = &c.norm_param[6 * i];
+    q[0] = nv[0]; q[1] = nv[1]; q[2] = nv[2];
+    q[3] = pv[0]; q[4] = pv[1]; q[5] = pv[2];
+  }
+  candidates_[view].push_back(c);
+}
+
+void CSPatchMatch::AddCandidateDisparity(const RefView &view, const Mat &disp) {
+  if (disp.cols != wid_ || disp.rows != hei_ || (disp.type() != CV_32FC1 && disp.type() != CV_64FC1))
+    throw std::runtime_error("CSPatchMatch::AddCandidateDisparity: a CV_32FC1 or CV_64FC1 map of the image size expected");
+  const size_t n = (size_t)wid_ * hei_;
+  Candidates c;
+  c.norm_param.assign(6 * n, 0.0);
+  c.mask.assign(n, 0);
+  for (int y = 0; y < hei_; ++y)
+    for (int x = 0; x < wid_; ++x) {
+      const double d = disp.type() == CV_32FC1 ? (double)disp.at<float>(y, x) : disp.at<double>(y, x);
+      const size_t i = (size_t)y * wid_ + x;
+      if (!std::isfinite(d) || d < 0.0) continue;  // no candidate
+      c.norm_param[6 * i + 2] = 1.0;  // the fronto-parallel plane (0, 0, 1, 0, 0, d)
+      c.norm_param[6 * i + 5] = d;
+      c.mask[i] = 1;
+    }
+  candidates_[view].push_back(c);
+}
+
+void CSPatchMatch::SeededBegin(bool keep, int iter_num, const IPlaneCost *plane_cost, bool use_pp) {
+  const IDevicePlaneCost *dev = dynamic_cast<const IDevicePlaneCost *>(plane_cost);
+  if (!dev) throw std::runtime_error("CSPatchMatch::PatchMatchSeeded / PatchMatchKeep need one of this library's device costs (a foreign IPlaneCost runs cold only: PatchMatch)");
+  cspm_ctx *ctx = dev->device_ctx();
+  if (pending_ctx_ && pending_ctx_ != ctx) throw std::runtime_error("CSPatchMatch::PatchMatchSeededBegin / PatchMatchKeepBegin: the previous run has not been ended");
+  cspm_pm_params p;
+  cspm_pm_default_params(&p);
+  p.seed = seed_;
+  p.schedule = schedule_;
+  p.rb_rounds = rb_rounds_;
+  p.rb_neighbours = rb_neighbours_;
+  if (keep) {
+    WriteStartPlanes(ctx);
+    check(cspm_pm_init_keep(ctx, &p), ctx, "cspm_pm_init_keep");
+  } else {
+    check(cspm_pm_init(ctx, &p), ctx, "cspm_pm_init");
+  }
+  for (int v = 0; v < kViewNum; ++v) {
+    for (size_t k = 0; k < candidates_[v].size(); ++k) {
+      const Candidates &c = candidates_[v][k];
+      check(cspm_merge_planes_host(ctx, v, c.norm_param.data(), c.mask.empty() ? NULL : c.mask.data()), ctx, "cspm_merge_planes_host");
+    }
+    candidates_[v].clear();
+  }
+  check(cspm_patchmatch_warm(ctx, iter_num, &p), ctx, "cspm_patchmatch_warm");  // asynchronous: enqueued on the context's stream
+  pending_ctx_ = ctx;
+  pending_pp_ = use_pp;
+}
+
+void CSPatchMatch::PatchMatchSeededBegin(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp) {
+  SeededBegin(false, iter_num, plane_cost, use_pp);
+}
+void CSPatchMatch::PatchMatchSeeded(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp) {
+  SeededBegin(false, iter_num, plane_cost, use_pp);
+  PatchMatchEnd();
+}
+void CSPatchMatch::PatchMatchKeepBegin(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp) {
+  SeededBegin(true, iter_num, plane_cost, use_pp);
+}
+void CSPatchMatch::PatchMatchKeep(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp) {
+  SeededBegin(true, iter_num, plane_cost, use_pp);
+  PatchMatchEnd();
 }
 
 void CSPatchMatch::PatchMatchFrom(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp) {

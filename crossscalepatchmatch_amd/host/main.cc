@@ -1,7 +1,8 @@
 // main.cc -- command line with the reference's ten flags and defaults (CSPM/main.cc:23-34) and its flow
 // (main.cc:57-139): read the pair, construct the plane cost (timed), run PatchMatch, print "Total Time", write the
 // two 8-bit maps.  Runs on the GPU through the host layer.  Extra flags: --seed --schedule --neighbours --device --iters --ca_name (local stereo)
-// --warm_ca (local stereo, then --iters warm PatchMatch iterations).
+// --warm_ca (local stereo, then --iters warm PatchMatch iterations) --l_seed_pfm --r_seed_pfm (disparity maps offered to the random start
+// field as candidates) --seed_ca (local stereo, kept wherever the random start plane costs no less, then --iters iterations).
 #include "../../include/cspm.h"
 #include "commfunc.h"
 #include "cs_patchmatch.h"
@@ -36,6 +37,13 @@ DEFINE_string(ca_name, "", "local stereo instead of PatchMatch: cost aggregation
               "cross-scale winner-take-all (empty: PatchMatch); not with --pc_name=IMG");
 DEFINE_string(warm_ca, "", "warm-started PatchMatch: local stereo with cost aggregation BOX | GF | BF (as --ca_name), then --iters PatchMatch "
               "iterations from its plane field instead of the random init; needs --pc_name=PRE, not with --ca_name");
+DEFINE_string(seed_ca, "", "seeded PatchMatch: local stereo with cost aggregation BOX | GF | BF (as --warm_ca), then the random start planes "
+              "compete with its field pixel by pixel and the cheaper plane stays (keep-init), then --iters iterations; needs --pc_name=PRE, "
+              "not with --warm_ca or --ca_name");
+DEFINE_string(l_seed_pfm, "", "a float32 PFM disparity map of the left view offered to PatchMatch as candidates: after the random init (or the "
+                              "keep-init of --seed_ca) a pixel takes the fronto-parallel plane of its value where that costs less; non-finite "
+                              "or negative values are no candidates.  Not with --ca_name, --warm_ca or --batch_list");
+DEFINE_string(r_seed_pfm, "", "the same for the right view (see --l_seed_pfm)");
 DEFINE_bool(use_cs, false, "cross-scale aggregation over a 5-level pyramid (PreCSPC) instead of PreSSPC");
 DEFINE_bool(use_pp, false, "left-right check, hole filling and weighted median afterwards");
 DEFINE_double(reg_lambda, 0.0, "cross-scale regularisation weight");
@@ -121,7 +129,23 @@ void begin(PairRun &p, CCMethod *cost_fn) {
     p.matcher->set_seed(static_cast<uint64_t>(FLAGS_seed));
     if (FLAGS_schedule == "diffuse") p.matcher->set_schedule(CSPM_SCHED_DIFFUSE, 1, FLAGS_neighbours);
     else p.matcher->set_schedule(FLAGS_schedule == "redblack" ? 1 : 0);
-    if (!FLAGS_warm_ca.empty()) {  // the warm run is enqueued behind the local stereo on the cost object's stream
+    const string *seed_pfm[kViewNum] = {&FLAGS_l_seed_pfm, &FLAGS_r_seed_pfm};
+    for (int v = 0; v < kViewNum; ++v) {
+      if (seed_pfm[v]->empty()) continue;
+      std::vector<double> d;
+      int w = 0, h = 0;
+      if (!ReadPFM(*seed_pfm[v], &d, &w, &h) || w != p.left.cols || h != p.left.rows)
+        throw std::runtime_error("can not read " + *seed_pfm[v] + " as a single-channel PFM of the image size");
+      Mat m(h, w, CV_64FC1);
+      for (int y = 0; y < h; ++y) std::copy(d.begin() + (size_t)y * w, d.begin() + (size_t)(y + 1) * w, m.ptr<double>(y));
+      p.matcher->AddCandidateDisparity(v == 0 ? kLeft : kRight, m);
+    }
+    if (!FLAGS_seed_ca.empty()) {  // keep-init and the iterations are enqueued behind the local stereo on the cost object's stream
+      p.matcher->LocalStereoBegin(ca_method(FLAGS_seed_ca), p.cost.get(), FLAGS_use_pp);
+      p.matcher->PatchMatchKeepBegin(FLAGS_iters, p.cost.get(), FLAGS_use_pp);
+    } else if (!FLAGS_l_seed_pfm.empty() || !FLAGS_r_seed_pfm.empty()) {
+      p.matcher->PatchMatchSeededBegin(FLAGS_iters, p.cost.get(), FLAGS_use_pp);
+    } else if (!FLAGS_warm_ca.empty()) {  // the warm run is enqueued behind the local stereo on the cost object's stream
       p.matcher->LocalStereoBegin(ca_method(FLAGS_warm_ca), p.cost.get(), FLAGS_use_pp);
       p.matcher->PatchMatchFromBegin(FLAGS_iters, p.cost.get(), FLAGS_use_pp);
     } else if (FLAGS_ca_name.empty()) {
@@ -300,6 +324,31 @@ int run() {
   }
   if (!FLAGS_warm_ca.empty() && (FLAGS_pc_name != "PRE" || !FLAGS_ca_name.empty())) {
     cout << "Error: --warm_ca needs --pc_name=PRE (cost volumes to aggregate) and no --ca_name\n";
+    return EXIT_FAILURE;
+  }
+  if (!FLAGS_seed_ca.empty() && ca_method(FLAGS_seed_ca) < 0) {
+    cout << "Error: --seed_ca must be BOX, GF or BF (got " << FLAGS_seed_ca << ")\n";
+    return EXIT_FAILURE;
+  }
+  if (!FLAGS_seed_ca.empty() && (!FLAGS_warm_ca.empty() || !FLAGS_ca_name.empty())) {
+    cout << "Error: --seed_ca is a start of its own: not with --warm_ca or --ca_name\n";
+    return EXIT_FAILURE;
+  }
+  if (!FLAGS_seed_ca.empty() && FLAGS_pc_name != "PRE") {
+    cout << "Error: --seed_ca needs --pc_name=PRE (cost volumes to aggregate)\n";
+    return EXIT_FAILURE;
+  }
+  const bool seed_pfm = !FLAGS_l_seed_pfm.empty() || !FLAGS_r_seed_pfm.empty();
+  if (seed_pfm && (!FLAGS_warm_ca.empty() || !FLAGS_ca_name.empty())) {
+    cout << "Error: --l_seed_pfm / --r_seed_pfm are merged after a random init: not with --warm_ca or --ca_name\n";
+    return EXIT_FAILURE;
+  }
+  if (seed_pfm && !FLAGS_batch_list.empty()) {
+    cout << "Error: --l_seed_pfm / --r_seed_pfm belong to one pair: not with --batch_list\n";
+    return EXIT_FAILURE;
+  }
+  if ((seed_pfm || !FLAGS_seed_ca.empty()) && FLAGS_pc_name != "PRE" && FLAGS_pc_name != "IMG") {
+    cout << "Error: seeded starts need one of this library's plane costs (--pc_name=PRE or IMG), not " << FLAGS_pc_name << "\n";
     return EXIT_FAILURE;
   }
   if (!FLAGS_ca_name.empty() && FLAGS_pc_name == "IMG") {

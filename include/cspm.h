@@ -285,6 +285,35 @@ int cspm_patchmatch_warm(cspm_ctx *ctx, int iter_num, const cspm_pm_params *p);
  * then is asynchronous on dst's stream, ordered after the work enqueued on src's stream; src's later work waits for the copy.
  * CSPM_ERR_STATE when src has no plane field or dst no images; CSPM_ERR_ARG for other sizes or two devices. */
 int cspm_upsample_planes(cspm_ctx *dst, cspm_ctx *src);
+/* ---- candidate fields (an addition): hypotheses that win only where they are better ---------------------------
+ * MERGE.  A view has a candidate plane field C (six doubles per pixel, norm then param, the layout of cspm_get_planes) and optionally a
+ * mask.  Every pixel (x, y), independently of every other pixel: m = its stored min_cost; the candidate is C[y][x] taken whole (nothing
+ * is re-anchored: how CSPM_SCHED_DIFFUSE adopts a neighbour); cost = GetPlaneCost(x, y, candidate, view) in the device order; where
+ * cost < m (strict) the pixel's plane and min_cost become the candidate and its cost.  A pixel whose mask byte is 0, or whose six
+ * candidate values are not all finite, has no candidate and is left unchanged.  The evaluation stops early exactly as plane refinement's
+ * does (early_exit of the default parameters and the cost object's licence): result-preserving.
+ * KEEP-INIT.  The same rule with the candidate being the plane InitRandomPlane draws for (x, y, view) under the given parameters (seed,
+ * rng_mode: the streams of cspm_pm_init); the stored plane stays on a tie.  The merge seen from the other side: the stored field is the
+ * seed, the random field the challenger.
+ * Both need m to be the stored plane's cost under the current cost object: a field that is not consistent (after cspm_set_planes,
+ * cspm_local_stereo, cspm_upsample_planes, a new cost object) is re-scored first, the rule of cspm_patchmatch_warm; both leave the field
+ * consistent.  cspm_pm_init -> merge(s) -> cspm_patchmatch_warm(n), and cspm_pm_init_keep -> cspm_patchmatch_warm(n), are therefore
+ * whole pipelines: the warm call skips its re-score and runs iterations 0 .. n-1 with a cold run's streams from the merged field.
+ * All three are asynchronous on the ctx stream and timed under CSPM_K_INIT, one evaluation per pixel that has a candidate.
+ *
+ * cspm_merge_planes: both views, candidates = src's stored plane field (its min_costs are not used).  Same w x h, same device, src != dst.
+ * Checks src's sweep first (like a getter), then is ordered after the work enqueued on src's stream; src's later work waits for the
+ * merge.  CSPM_ERR_STATE when src has no plane field or dst lacks images, a cost object or a plane field; CSPM_ERR_ARG for a size
+ * mismatch, two devices or src == dst. */
+int cspm_merge_planes(cspm_ctx *dst, cspm_ctx *src);
+/* one view, candidates from caller memory: norm_param h*w*6 doubles, mask h*w bytes or NULL (every pixel).  They are copied into a
+ * ctx-owned candidate buffer (48 + 1 bytes per pixel, allocated by the first such call and kept with the plane field); the host buffers
+ * are free for reuse when the call returns.  CSPM_ERR_STATE without a cost object or a plane field; CSPM_ERR_ARG for a bad view or a
+ * NULL norm_param. */
+int cspm_merge_planes_host(cspm_ctx *ctx, int view, const double *norm_param, const uint8_t *mask);
+/* keep-init over both views.  Without a plane field it is cspm_pm_init (nothing is there to keep); CSPM_ERR_STATE without a cost
+ * object; params as for cspm_pm_init. */
+int cspm_pm_init_keep(cspm_ctx *ctx, const cspm_pm_params *p);
 /* PlaneToDisp + dis() (cs_patchmatch.cc:590-601, 111-113): saturate_u8(Round2Int(d*dis_scale)) */
 int cspm_get_disparity_u8(cspm_ctx *ctx, int view, int dis_scale, uint8_t *out, size_t stride);
 int cspm_get_disparity_f64(cspm_ctx *ctx, int view, double *out); /* unquantised a*x+b*y+c */
