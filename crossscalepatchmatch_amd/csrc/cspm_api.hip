@@ -57,6 +57,62 @@ struct CostKey {
   }
 };
 
+// an asynchronous output (cspm_disparity_u8_device / cspm_postprocess_device / cspm_postprocess_f64_device)
+enum OutKind { kOutDisp, kOutPost8, kOutPostF64 };  // PlaneToDisp of one view, the 8-bit PostProcessing, the sub-pixel one
+struct OutReq { OutKind kind; int view, dis_scale; void *o0, *o1; };
+
+// WHEN A RUN IS REPEATED AFTER A SWEEP TIMEOUT.  A persistent raster sweep that gives up waiting raises a sticky error word, which the
+// next call that synchronises with the host anyway looks at (check_sweep).  A timeout is slowness, not a wrong result: when exactly ONE
+// whole run (cspm_patchmatch / cspm_patchmatch_warm) began since the last check and nothing tainted it, it is repeated with per-diagonal
+// launches, and so are the outputs enqueued behind it; anything else is an error.  Only the operations below touch the fields.
+// The two taints differ on purpose:
+//   taint()               stays until the next check that finds a sweep pending.  For what no whole run can stand for: the single phases
+//                         cspm_pm_init / _spatial / _view / _refine, cspm_rescore_planes, cspm_set_planes (the caller's costs) and
+//                         cspm_fpm_begin (a foreign cost drives the field).
+//   taint_unchecked_run() counts only behind a run that has not been checked: its inputs (alloc_cost, set_images_impl) or its planes
+//                         (cspm_local_stereo, cspm_upsample_planes, cspm_merge_planes, cspm_merge_planes_host, cspm_pm_init_keep) are no
+//                         longer what it ran on.  In front of a run they are its start -- a warm run snapshots it -- and taint nothing.
+// Known limit: take() is not called while no sweep is pending, so a taint() outlives its call and blocks the repeat of the NEXT run:
+// a timeout behind cspm_pm_init or cspm_set_planes + cspm_patchmatch_warm is an error, behind cspm_pm_init_keep or cspm_local_stereo +
+// cspm_patchmatch_warm it is repeated.
+struct Repeat {
+  struct Record {
+    int runs = 0;  // whole runs begun since the last check
+    bool tainted = false;
+    bool warm = false;  // the last run was cspm_patchmatch_warm: a repeat starts from warm_snap, not from the init
+    int iters = 0;
+    cspm_pm_params params{};
+    std::vector<OutReq> outs;
+  };
+  // a whole run begins; the outputs behind an earlier run go, that run can no longer be repeated (two runs unchecked = an error)
+  void begin_run(bool warm, int iters, const cspm_pm_params &params) {
+    r_.warm = warm; r_.iters = iters; r_.params = params;
+    r_.outs.clear();
+    ++r_.runs;
+  }
+  void sweep_enqueued() { pending_ = true; }  // a persistent sweep's error word has not been checked yet
+  bool pending() const { return pending_; }
+  void taint() { r_.tainted = true; }
+  void taint_unchecked_run() { r_.tainted = r_.tainted || r_.runs > 0; }
+  // while a sweep is pending: a later request for the same kind of map into the same buffers replaces the earlier one
+  void remember_output(const OutReq &q) {
+    for (auto it = r_.outs.begin(); it != r_.outs.end(); ++it)
+      if (it->kind == q.kind && it->o0 == q.o0 && it->o1 == q.o1 && (q.kind != kOutDisp || it->view == q.view)) { r_.outs.erase(it); break; }
+    r_.outs.push_back(q);
+  }
+  // the pending sweep has been checked: what ran since the check before, and a clean record
+  Record take() {
+    const Record out = r_;
+    r_ = Record{};
+    pending_ = false;
+    return out;
+  }
+
+ private:
+  bool pending_ = false;
+  Record r_;
+};
+
 struct cspm_ctx {
   int device = 0, ncu = 256;
   // persistent sweep: workgroups launched per CU (env CSPM_SWEEP_WG).  2..6 take the same time when the pair is alone (the sweep
@@ -128,29 +184,11 @@ struct cspm_ctx {
   unsigned int sweep_epoch = 0;
   long long opt_raster_launches = 0;  // CSPM_OPT_RASTER_LAUNCHES
   long long sweep_timeout_ms = 3000;  // CSPM_OPT_SWEEP_TIMEOUT_MS (env CSPM_SWEEP_TIMEOUT_MS): bound of one wait for a predecessor pixel
-  bool sweep_pending = false;         // a sweep's error word has not been checked yet
-  // what ran since the sweep error word was last looked at: exactly one whole cspm_patchmatch (on inputs that are still in
-  // place) can be repeated with per-diagonal launches when its persistent sweep timed out
-  int pm_runs_unchecked = 0;
-  bool phases_unchecked = false;      // single phases / cspm_set_planes / new inputs since then: no transparent retry
-  int last_iters = 0;
-  cspm_pm_params last_params{};
-  bool last_warm = false;             // that run was cspm_patchmatch_warm: a repeat starts from warm_snap, not from the init
+  Repeat repeat;                      // when a run is repeated after a sweep timeout
   double *warm_snap = nullptr;        // the starting field of the last warm run (both views, 7 arrays each), kept with the field
   double *cand_mem = nullptr;         // cspm_merge_planes_host: one view's candidate planes (6 arrays) and, behind them, its mask bytes; allocated by the first such call and kept with the field
   double *diffuse_snap = nullptr;     // CSPM_SCHED_DIFFUSE: the round's snapshot (both views, the 6 plane arrays each), allocated by the first such propagation and kept with the field
   long long sweep_fallbacks = 0;      // how often that happened (cspm_get_option)
-  // asynchronous outputs (cspm_disparity_u8_device / cspm_postprocess_device / cspm_postprocess_f64_device) enqueued behind a run whose
-  // sweep has not been checked yet: when that run is repeated after a timeout they are produced again from the repeated run's planes.
-  // post: 0 = PlaneToDisp of one view, 1 = the 8-bit PostProcessing, 2 = the sub-pixel one
-  struct OutReq { int post, view, dis_scale; void *o0, *o1; };
-  std::vector<OutReq> out_reqs;
-  // a later request for the same kind of map into the same buffer replaces the earlier one (the buffer ends up holding the later map)
-  void remember_output(const OutReq &q) {
-    for (auto it = out_reqs.begin(); it != out_reqs.end(); ++it)
-      if (it->post == q.post && it->o0 == q.o0 && it->o1 == q.o1 && (q.post || it->view == q.view)) { out_reqs.erase(it); break; }
-    out_reqs.push_back(q);
-  }
   // CSPatchMatch over a foreign IPlaneCost (cspm_fpm_*): candidate buffers and what the pending batch was
   FpmCand fpm{nullptr, nullptr, nullptr, nullptr};
   long long fpm_cap = 0;
@@ -297,58 +335,46 @@ void free_cost(cspm_ctx *c) {
   c->cost_key = CostKey{};
   memset(&c->cost, 0, sizeof c->cost);
 }
+// hipFree of a pointer that may not be set; the pointer is null afterwards
+template <class T>
+void dfree(T *&p) {
+  if (p) (void)hipFree((void *)p);
+  p = nullptr;
+}
 void free_field(cspm_ctx *c) {
-  if (c->field_mem) (void)hipFree(c->field_mem);
-  if (c->warm_snap) (void)hipFree(c->warm_snap);
-  c->warm_snap = nullptr;
-  if (c->diffuse_snap) (void)hipFree(c->diffuse_snap);
-  c->diffuse_snap = nullptr;
-  if (c->cand_mem) (void)hipFree(c->cand_mem);
-  c->cand_mem = nullptr;
-  if (c->vc.cost) (void)hipFree(c->vc.cost);
-  if (c->vc.c) (void)hipFree(c->vc.c);
-  if (c->vc.cx) (void)hipFree(c->vc.cx);
-  if (c->vc.perm) (void)hipFree(c->vc.perm);
+  dfree(c->field_mem);
+  dfree(c->warm_snap);
+  dfree(c->diffuse_snap);
+  dfree(c->cand_mem);
+  dfree(c->vc.cost);
+  dfree(c->vc.c);
+  dfree(c->vc.cx);
+  dfree(c->vc.perm);
   for (int v = 0; v < 2; ++v) {
-    if (c->d_dis[v]) (void)hipFree(c->d_dis[v]);
-    if (c->d_valid[v]) (void)hipFree(c->d_valid[v]);
-    c->d_dis[v] = nullptr;
-    c->d_valid[v] = nullptr;
+    dfree(c->d_dis[v]);
+    dfree(c->d_valid[v]);
   }
-  if (c->d_todo) (void)hipFree(c->d_todo);
-  c->d_todo = nullptr;
-  if (c->d_pp[0]) (void)hipFree(c->d_pp[0]);  // one allocation holds both maps
-  c->d_pp[0] = c->d_pp[1] = nullptr;
-  if (c->d_rowq) (void)hipFree(c->d_rowq);
-  c->d_rowq = nullptr;
-  if (c->fpm.xy) (void)hipFree(c->fpm.xy);
-  if (c->fpm.view) (void)hipFree(c->fpm.view);
-  if (c->fpm.plane) (void)hipFree(c->fpm.plane);
-  if (c->fpm.cost) (void)hipFree(c->fpm.cost);
-  c->fpm = FpmCand{nullptr, nullptr, nullptr, nullptr};
+  dfree(c->d_todo);
+  dfree(c->d_pp[0]);  // one allocation holds both maps
+  c->d_pp[1] = nullptr;
+  dfree(c->d_rowq);
+  dfree(c->fpm.xy);
+  dfree(c->fpm.view);
+  dfree(c->fpm.plane);
+  dfree(c->fpm.cost);
   c->fpm_cap = 0;
   c->fpm_phase = -1;
-  if (c->d_sweep_ctrl) (void)hipFree(c->d_sweep_ctrl);
-  if (c->d_sweep_gran) (void)hipFree(c->d_sweep_gran);
-  if (c->d_sweep_start) (void)hipFree(c->d_sweep_start);
-  if (c->d_sweep_ready) (void)hipFree(c->d_sweep_ready);
-  if (c->d_sweep_qctl) (void)hipFree(c->d_sweep_qctl);
-  if (c->d_sweep_queue) (void)hipFree(c->d_sweep_queue);
-  c->d_sweep_ready = c->d_sweep_qctl = nullptr;
-  c->d_sweep_queue = nullptr;
-  c->d_sweep_ctrl = c->d_sweep_start = nullptr;
-  c->d_sweep_gran = nullptr;
-  c->field_mem = nullptr;
-  c->vc = ViewCand{nullptr, nullptr, nullptr, nullptr};
+  dfree(c->d_sweep_ctrl);
+  dfree(c->d_sweep_gran);
+  dfree(c->d_sweep_start);
+  dfree(c->d_sweep_ready);
+  dfree(c->d_sweep_qctl);
+  dfree(c->d_sweep_queue);
   c->field_alloc = false;
 }
 void free_images(cspm_ctx *c) {
-  for (int v = 0; v < 2; ++v) {
-    if (c->img0[v]) (void)hipFree(c->img0[v]);
-    c->img0[v] = nullptr;
-  }
-  if (c->stage) (void)hipFree(c->stage);
-  c->stage = nullptr;
+  for (int v = 0; v < 2; ++v) dfree(c->img0[v]);
+  dfree(c->stage);
   c->stage_bytes = 0;
   c->W = c->H = 0;
 }
@@ -507,7 +533,7 @@ int alloc_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg
   c->cost_ready = false;
   c->max_cost_fetched = false;
   c->field_consistent = false;  // stored min_costs belong to the previous cost object: only InitRandomPlane re-establishes them
-  if (c->pm_runs_unchecked) c->phases_unchecked = true;  // an unchecked run's inputs are being replaced: no transparent retry for it
+  c->repeat.taint_unchecked_run();  // its inputs are being replaced
   int rc;
   if (!reuse) {
     cd.cs = scale_num > 0;
@@ -870,85 +896,36 @@ int ensure_flow(cspm_ctx *c) {
   return CSPM_OK;
 }
 
-Pm make_pm(cspm_ctx *c, const cspm_pm_params *p) {
+// the geometry and the two plane fields: all that the kernels which only read or convert planes look at
+Pm field_pm(const cspm_ctx *c) {
   Pm pm{};
-  pm.W = c->W; pm.H = c->H; pm.max_dis = c->max_dis;
-  pm.seed = p->seed;
-  pm.rng_row_shared = p->rng_mode == CSPM_RNG_ROW_SHARED;
-  pm.trust_cost = c->field_consistent ? 1 : 0;
-  pm.use_thresh = p->early_exit ? 1 : 0;  // and-ed with the cost object's device-side licence (Cost::early_ok) in the kernels
+  pm.W = c->W; pm.H = c->H;
   pm.f[0] = c->f[0];
   pm.f[1] = c->f[1];
   return pm;
 }
-
-// A persistent sweep's bounded spins raise the STICKY error word ctrl[1] instead of hanging (later sweeps then drain at
-// once).  It is looked at by every call that synchronises with the host anyway (cspm_synchronize, the getters, the
-// single-phase entry cspm_pm_spatial): cspm_patchmatch itself stays asynchronous.
-int run_patchmatch(cspm_ctx *c, int iter_num, const cspm_pm_params *p);
-int run_warm_retry(cspm_ctx *c, int iter_num, const cspm_pm_params *p);
-int enqueue_disp_u8(cspm_ctx *c, int view, int dis_scale, void *d_out);
-int enqueue_postprocess_device(cspm_ctx *c, int dis_scale, void *d_l_out, void *d_r_out);
-int enqueue_postprocess_f64_device(cspm_ctx *c, void *d_l_out, void *d_r_out);
-
-int check_sweep(cspm_ctx *c) {
-  if (!c->sweep_pending) return CSPM_OK;
-  unsigned int ctrl[2] = {0, 0}, px8_bad = 0;
-  HIPCHK(c, hipMemcpyAsync(ctrl, c->d_sweep_ctrl, sizeof ctrl, hipMemcpyDeviceToHost, c->stream));
-  const bool packed = c->sweep_packed && c->cost_alloc && c->d_px8_bad;
-  if (packed) HIPCHK(c, hipMemcpyAsync(&px8_bad, c->d_px8_bad, sizeof px8_bad, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->sweep_pending = false;
-  // CSPM_OPT_SWEEP_PACKED: a gradient the 36-bit fixed-point field cannot hold was packed as 0 and the sweep read a wrong cell.  Cannot
-  // happen for 8-bit images (cspm.h); if it ever does, the planes are wrong and the caller must hear about it, not only a counter.
-  if (packed && px8_bad) {
-    c->pm_runs_unchecked = 0;
-    c->phases_unchecked = false;
-    c->out_reqs.clear();
-    return fail(c, CSPM_ERR_HIP, "CSPM_OPT_SWEEP_PACKED: " + std::to_string(px8_bad) + " gradients could not be packed exactly; the raster sweep's planes are not valid");
-  }
-  const int runs = c->pm_runs_unchecked;
-  const bool phases = c->phases_unchecked;
-  c->pm_runs_unchecked = 0;
-  c->phases_unchecked = false;
-  const std::vector<cspm_ctx::OutReq> reqs = c->out_reqs;
-  c->out_reqs.clear();
-  if (ctrl[1]) {
-    (void)hipMemsetAsync(c->d_sweep_ctrl, 0, 2 * sizeof(unsigned int), c->stream);
-    // A timeout is slowness (a shared or oversubscribed GPU, a profiler attached, many contexts in flight), not a wrong
-    // result waiting to happen: the per-diagonal sweep needs no inter-workgroup hand-off and gives the same planes bit for
-    // bit.  When exactly one whole PatchMatch ran since the last check -- its inputs are still in place -- it is repeated
-    // that way and the caller never sees the hiccup; anything else (several pairs enqueued, single phases) is an error.
-    if (runs == 1 && !phases && c->cost_ready) {
-      const long long keep = c->opt_raster_launches;
-      c->opt_raster_launches = 1;
-      int rc = c->last_warm ? run_warm_retry(c, c->last_iters, &c->last_params) : run_patchmatch(c, c->last_iters, &c->last_params);
-      c->opt_raster_launches = keep;
-      c->pm_runs_unchecked = 0;
-      // the maps that were enqueued behind the aborted run were computed from its planes: produce them again
-      for (const auto &q : reqs) {
-        if (rc != CSPM_OK) break;
-        rc = q.post == 2 ? enqueue_postprocess_f64_device(c, q.o0, q.o1)
-             : q.post   ? enqueue_postprocess_device(c, q.dis_scale, q.o0, q.o1)
-                        : enqueue_disp_u8(c, q.view, q.dis_scale, q.o0);
-      }
-      if (rc == CSPM_OK) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        ++c->sweep_fallbacks;
-        return CSPM_OK;
-      }
-      return rc;
-    }
-    return fail(c, CSPM_ERR_HIP, "raster sweep timed out waiting for a predecessor pixel (inter-workgroup hand-off)");
-  }
-  return CSPM_OK;
+Pm make_pm(cspm_ctx *c, const cspm_pm_params *p) {
+  Pm pm = field_pm(c);
+  pm.max_dis = c->max_dis;
+  pm.seed = p->seed;
+  pm.rng_row_shared = p->rng_mode == CSPM_RNG_ROW_SHARED;
+  pm.trust_cost = c->field_consistent ? 1 : 0;
+  pm.use_thresh = p->early_exit ? 1 : 0;  // and-ed with the cost object's device-side licence (Cost::early_ok) in the kernels
+  return pm;
 }
 
 const cspm_pm_params kDefaultParams = {12345ULL, CSPM_SCHED_RASTER, 1, 4, CSPM_RNG_PER_PIXEL, 1};
 
+// preconditions of the entries that run on the plane field
+int need_cost(cspm_ctx *c) {
+  return c->cost_ready ? CSPM_OK : fail(c, CSPM_ERR_STATE, "no plane cost built (cspm_build_cost_grd / cspm_finish_cost)");
+}
+int need_field(cspm_ctx *c, const char *msg) { return c->field_alloc ? CSPM_OK : fail(c, CSPM_ERR_STATE, msg); }
+const char *const kNoMergeTarget = "no plane field to merge into (cspm_pm_init, cspm_set_planes, cspm_local_stereo or an earlier run)";
+
 int check_pm(cspm_ctx *c, const cspm_pm_params **p) {
   if (!c) return CSPM_ERR_ARG;
-  if (!c->cost_ready) return fail(c, CSPM_ERR_STATE, "no plane cost built (cspm_build_cost_grd / cspm_finish_cost)");
+  if (int rc = need_cost(c)) return rc;
   if (!*p) *p = &kDefaultParams;
   if ((*p)->schedule != CSPM_SCHED_RASTER && (*p)->schedule != CSPM_SCHED_REDBLACK && (*p)->schedule != CSPM_SCHED_DIFFUSE)
     return fail(c, CSPM_ERR_ARG, "bad schedule");
@@ -1005,14 +982,18 @@ inline void allow_lds(K kern, size_t shmem) {
     }                                                                                                             \
   } while (0)
 
+// one row-engine launch over `views` views, timed as `kclass` with `evals` evaluations: the claim counters, then the kernel with the
+// arguments every row kernel takes around its own (`pm` is the caller's)
+#define LAUNCH_ROWS(kclass, evals, views, kern, ...)                                                                          \
+  do {                                                                                                                        \
+    Timed t_(c, kclass, evals);                                                                                               \
+    const RowQueue rq_ = next_row_queue(c, views);                                                                            \
+    LAUNCH_CS(kern, dim3(row_grid(c, views)), dim3(kRowBlock), row_shmem(c), c->cost, pm, rq_, ##__VA_ARGS__, row_cap(c), row_ocap(c)); \
+  } while (0)
+
 int do_init(cspm_ctx *c, const cspm_pm_params *p) {
-  const long long items = 2LL * c->W * c->H;
   Pm pm = make_pm(c, p);
-  {
-    Timed t(c, CSPM_K_INIT, items);
-    const RowQueue rq = next_row_queue(c, 2);
-    LAUNCH_CS(k_init, dim3(row_grid(c, 2)), dim3(kRowBlock), row_shmem(c), c->cost, pm, rq, row_cap(c), row_ocap(c));
-  }
+  LAUNCH_ROWS(CSPM_K_INIT, 2LL * c->W * c->H, 2, k_init);
   HIPCHK(c, hipGetLastError());
   c->field_consistent = true;
   return CSPM_OK;
@@ -1063,7 +1044,7 @@ int do_spatial(cspm_ctx *c, int iter, const cspm_pm_params *p) {
     }
     const long long items = 2LL * c->W * c->H;
     for (int r = 0; r < p->rb_rounds; ++r) {
-      Timed t(c, CSPM_K_SPATIAL, items * df.K);
+      Timed t(c, CSPM_K_SPATIAL, items * df.K);  // the snapshot copies are part of the round's time: not LAUNCH_ROWS, which times the launch alone
       for (int v = 0; v < 2; ++v)
         HIPCHK(c, hipMemcpyAsync(c->diffuse_snap + (size_t)v * 6 * n, c->f[v].nx, sizeof(double) * 6 * n, hipMemcpyDeviceToDevice, c->stream));
       const RowQueue rq = next_row_queue(c, 2);
@@ -1128,7 +1109,7 @@ int do_spatial(cspm_ctx *c, int iter, const cspm_pm_params *p) {
       if (flow) LAUNCH_SWEEP(k_spatial_flow, dim3(grid), dim3(waves * kWave), sweep_lds(c), c->cost, pm, sw, inc);
       else LAUNCH_SWEEP(k_spatial_sweep, dim3(grid), dim3(waves * kWave), sweep_lds(c), c->cost, pm, sw, inc);
     }
-    c->sweep_pending = true;
+    c->repeat.sweep_enqueued();
   } else {
     for (int k = 1; k <= c->W + c->H - 2; ++k) {
       const int ys_lo = std::max(0, k - (c->W - 1)), ys_hi = std::min(c->H - 1, k);
@@ -1154,11 +1135,7 @@ int do_view(cspm_ctx *c, int iter, const cspm_pm_params *p) {
       Timed t(c, CSPM_K_MISC, 0);
       LAUNCH_ONE(k_view_sort, dim3(c->H), dim3(256), sort_shmem, pm, v, vc);
     }
-    {
-      Timed t(c, CSPM_K_VIEW, items);
-      const RowQueue rq = next_row_queue(c, 1);
-      LAUNCH_CS(k_view_eval, dim3(row_grid(c, 1)), dim3(kRowBlock), row_shmem(c), c->cost, pm, rq, v, vc, row_cap(c), row_ocap(c));
-    }
+    LAUNCH_ROWS(CSPM_K_VIEW, items, 1, k_view_eval, v, vc);
     {
       Timed t(c, CSPM_K_MISC, 0);
       LAUNCH_ONE(k_view_resolve, dim3(c->H), dim3(256), shmem, pm, v, iter % 2 == 0 ? 0 : 1, c->vc);
@@ -1179,9 +1156,7 @@ int do_refine(cspm_ctx *c, int iter, const cspm_pm_params *p) {
   double z = z_iter, nn = n_iter;
   for (int first = 0; first < steps; first += c->refine_chunk) {
     const int cnt = std::min(c->refine_chunk, steps - first);
-    Timed t(c, CSPM_K_REFINE, items * cnt);
-    const RowQueue rq = next_row_queue(c, 2);
-    LAUNCH_CS(k_refine, dim3(row_grid(c, 2)), dim3(kRowBlock), row_shmem(c), c->cost, pm, rq, iter, first, cnt, z, nn, row_cap(c), row_ocap(c));
+    LAUNCH_ROWS(CSPM_K_REFINE, items * cnt, 2, k_refine, iter, first, cnt, z, nn);
     for (int k = 0; k < cnt; ++k) { z /= 2.0; nn /= 2.0; }
   }
   HIPCHK(c, hipGetLastError());
@@ -1206,28 +1181,21 @@ int run_patchmatch(cspm_ctx *c, int iter_num, const cspm_pm_params *p) {
 
 // the min_cost of every stored plane under the current cost object (k_rescore); makes the field consistent
 int do_rescore(cspm_ctx *c) {
-  const long long items = 2LL * c->W * c->H;
   Pm pm = make_pm(c, &kDefaultParams);  // k_rescore reads the field and the geometry only
-  {
-    Timed t(c, CSPM_K_INIT, items);
-    const RowQueue rq = next_row_queue(c, 2);
-    LAUNCH_CS(k_rescore, dim3(row_grid(c, 2)), dim3(kRowBlock), row_shmem(c), c->cost, pm, rq, row_cap(c), row_ocap(c));
-  }
+  LAUNCH_ROWS(CSPM_K_INIT, 2LL * c->W * c->H, 2, k_rescore);
   HIPCHK(c, hipGetLastError());
   c->field_consistent = true;
   return CSPM_OK;
 }
 
+inline int ensure_consistent(cspm_ctx *c) { return c->field_consistent ? CSPM_OK : do_rescore(c); }
+
 // candidate-field merging (k_merge / k_merge_keep) of views view0 .. view0 + views - 1: cf == nullptr is keep-init.
 // The field has to be consistent (the callers re-score first) and stays so: an accepted candidate is stored with its own cost.
 int do_merge(cspm_ctx *c, const CandField *cf, const cspm_pm_params *p, int view0, int views, long long evals) {
   Pm pm = make_pm(c, p);
-  {
-    Timed t(c, CSPM_K_INIT, evals);
-    const RowQueue rq = next_row_queue(c, views);
-    if (cf) LAUNCH_CS(k_merge, dim3(row_grid(c, views)), dim3(kRowBlock), row_shmem(c), c->cost, pm, rq, *cf, view0, views, row_cap(c), row_ocap(c));
-    else LAUNCH_CS(k_merge_keep, dim3(row_grid(c, views)), dim3(kRowBlock), row_shmem(c), c->cost, pm, rq, CandInit{}, view0, views, row_cap(c), row_ocap(c));
-  }
+  if (cf) LAUNCH_ROWS(CSPM_K_INIT, evals, views, k_merge, *cf, view0, views);
+  else LAUNCH_ROWS(CSPM_K_INIT, evals, views, k_merge_keep, CandInit{}, view0, views);
   HIPCHK(c, hipGetLastError());
   return CSPM_OK;
 }
@@ -1253,8 +1221,7 @@ int run_warm_retry(cspm_ctx *c, int iter_num, const cspm_pm_params *p) {
 
 // PlaneToDisp + PostProcessing (cs_patchmatch.cc:103-107, 508-588) enqueued on the ctx stream; results in c->d_dis[v]
 int postprocess_enqueue(cspm_ctx *c, int dis_scale) {
-  Pm pm{};
-  pm.W = c->W; pm.H = c->H; pm.f[0] = c->f[0]; pm.f[1] = c->f[1];
+  const Pm pm = field_pm(c);
   const long long n = (long long)c->W * c->H;
   const Level &L0 = c->cost.lv[0];
   Timed t(c, CSPM_K_POST, 0);
@@ -1278,22 +1245,13 @@ int postprocess_enqueue(cspm_ctx *c, int dis_scale) {
 
 // PlaneToDisp of one view into a device buffer (u8, packed W*H), enqueued on the ctx stream
 int enqueue_disp_u8(cspm_ctx *c, int view, int dis_scale, void *d_out) {
-  Pm pm{};
-  pm.W = c->W; pm.H = c->H; pm.f[0] = c->f[0]; pm.f[1] = c->f[1];
+  const Pm pm = field_pm(c);
   {
     Timed t(c, CSPM_K_MISC, 0);
     hipLaunchKernelGGL(k_plane_to_disp_u8, dim3(ew_grid((long long)c->W * c->H)), dim3(256), 0, c->stream, pm, view, dis_scale,
                        (uint8_t *)d_out, (size_t)c->W);
   }
   HIPCHK(c, hipGetLastError());
-  return CSPM_OK;
-}
-int enqueue_postprocess_device(cspm_ctx *c, int dis_scale, void *d_l_out, void *d_r_out) {
-  int rc = postprocess_enqueue(c, dis_scale);
-  if (rc) return rc;
-  void *outs[2] = {d_l_out, d_r_out};
-  for (int v = 0; v < 2; ++v)
-    HIPCHK(c, hipMemcpyAsync(outs[v], c->d_dis[v], (size_t)c->W * c->H, hipMemcpyDeviceToDevice, c->stream));
   return CSPM_OK;
 }
 
@@ -1307,8 +1265,7 @@ int postprocess_f64_enqueue(cspm_ctx *c) {
     c->d_pp[1] = c->d_pp[0] + n;
   }
   if (fill_rows_shmem(c->W) > 160 * 1024) return fail(c, CSPM_ERR_ARG, "image too wide for the row scan of FillInvalid");
-  Pm pm{};
-  pm.W = c->W; pm.H = c->H; pm.f[0] = c->f[0]; pm.f[1] = c->f[1];
+  const Pm pm = field_pm(c);
   const Level &L0 = c->cost.lv[0];
   Timed t(c, CSPM_K_POST, 0);
   for (int v = 0; v < 2; ++v)
@@ -1323,13 +1280,84 @@ int postprocess_f64_enqueue(cspm_ctx *c) {
   HIPCHK(c, hipGetLastError());
   return CSPM_OK;
 }
-int enqueue_postprocess_f64_device(cspm_ctx *c, void *d_l_out, void *d_r_out) {
-  int rc = postprocess_f64_enqueue(c);
-  if (rc) return rc;
-  void *outs[2] = {d_l_out, d_r_out};
+
+// An asynchronous output, enqueued on the ctx stream: the map of one view, or both post-processed maps copied to the caller's buffers.
+// request_output: when the run in front of it has an unchecked sweep the request is remembered -- a repeated run (sweep timeout) writes
+// the map again from ITS planes, so the caller never reads a map of the aborted run after a successful check.
+int enqueue_output(cspm_ctx *c, const OutReq &q) {
+  if (q.kind == kOutDisp) return enqueue_disp_u8(c, q.view, q.dis_scale, q.o0);
+  const bool f64 = q.kind == kOutPostF64;
+  if (int rc = f64 ? postprocess_f64_enqueue(c) : postprocess_enqueue(c, q.dis_scale)) return rc;
+  void *outs[2] = {q.o0, q.o1};
+  const size_t bytes = (f64 ? sizeof(double) : 1) * (size_t)c->W * c->H;
   for (int v = 0; v < 2; ++v)
-    HIPCHK(c, hipMemcpyAsync(outs[v], c->d_pp[v], sizeof(double) * (size_t)c->W * c->H, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(outs[v], f64 ? (const void *)c->d_pp[v] : (const void *)c->d_dis[v], bytes, hipMemcpyDeviceToDevice, c->stream));
   return CSPM_OK;
+}
+int request_output(cspm_ctx *c, const OutReq &q) {
+  if (c->repeat.pending()) c->repeat.remember_output(q);
+  return enqueue_output(c, q);
+}
+
+// The run whose persistent sweep timed out, again with per-diagonal launches -- they need no inter-workgroup hand-off and give the same
+// planes bit for bit -- and then the maps that were enqueued behind it: those were computed from the aborted run's planes.
+int replay(cspm_ctx *c, const Repeat::Record &rec) {
+  const long long keep = c->opt_raster_launches;
+  c->opt_raster_launches = 1;
+  int rc = rec.warm ? run_warm_retry(c, rec.iters, &rec.params) : run_patchmatch(c, rec.iters, &rec.params);
+  c->opt_raster_launches = keep;
+  for (size_t i = 0; rc == CSPM_OK && i < rec.outs.size(); ++i) rc = enqueue_output(c, rec.outs[i]);
+  if (rc != CSPM_OK) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  ++c->sweep_fallbacks;
+  return CSPM_OK;
+}
+
+// A persistent sweep's bounded spins raise the STICKY error word ctrl[1] instead of hanging (later sweeps then drain at
+// once).  It is looked at by every call that synchronises with the host anyway (cspm_synchronize, the getters, the
+// single-phase entry cspm_pm_spatial): cspm_patchmatch itself stays asynchronous.  What a timeout leads to is Repeat's rule.
+int check_sweep(cspm_ctx *c) {
+  if (!c->repeat.pending()) return CSPM_OK;
+  unsigned int ctrl[2] = {0, 0}, px8_bad = 0;
+  HIPCHK(c, hipMemcpyAsync(ctrl, c->d_sweep_ctrl, sizeof ctrl, hipMemcpyDeviceToHost, c->stream));
+  if (c->sweep_packed && c->cost_alloc && c->d_px8_bad)
+    HIPCHK(c, hipMemcpyAsync(&px8_bad, c->d_px8_bad, sizeof px8_bad, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const Repeat::Record rec = c->repeat.take();
+  // CSPM_OPT_SWEEP_PACKED: a gradient the 36-bit fixed-point field cannot hold was packed as 0 and the sweep read a wrong cell.  Cannot
+  // happen for 8-bit images (cspm.h); if it ever does, the planes are wrong and the caller must hear about it, not only a counter.
+  if (px8_bad)
+    return fail(c, CSPM_ERR_HIP, "CSPM_OPT_SWEEP_PACKED: " + std::to_string(px8_bad) + " gradients could not be packed exactly; the raster sweep's planes are not valid");
+  if (!ctrl[1]) return CSPM_OK;
+  (void)hipMemsetAsync(c->d_sweep_ctrl, 0, 2 * sizeof(unsigned int), c->stream);
+  if (rec.runs == 1 && !rec.tainted && c->cost_ready) return replay(c, rec);
+  return fail(c, CSPM_ERR_HIP, "raster sweep timed out waiting for a predecessor pixel (inter-workgroup hand-off)");
+}
+
+// Work of `dst` that reads the planes of `src`, another context on the same device.
+// source_check: a timed-out source run is repeated (or reported) before its planes are read.
+int source_check(cspm_ctx *dst, cspm_ctx *src) {
+  const int rc = check_sweep(src);
+  return rc ? fail(dst, rc, "source context: " + src->err) : CSPM_OK;
+}
+// with_source: dst's stream waits for the source's work, `body` enqueues on dst's stream, and the source's later work (or its
+// destruction) waits for that.  A HIP error is reported under `entry`; otherwise what body returned.
+template <class Body>
+int with_source(cspm_ctx *dst, cspm_ctx *src, const char *entry, Body body) {
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  for (auto &e : ev) HIPCHK(dst, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  int rc = CSPM_OK;
+  hipError_t e = hipEventRecord(ev[0], src->stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(dst->stream, ev[0], 0);
+  if (e == hipSuccess) {
+    rc = body();
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipEventRecord(ev[1], dst->stream);
+  if (e == hipSuccess) e = hipStreamWaitEvent(src->stream, ev[1], 0);
+  for (auto x : ev) (void)hipEventDestroy(x);
+  if (e != hipSuccess) return fail(dst, CSPM_ERR_HIP, std::string(entry) + ": " + hipGetErrorString(e));
+  return rc;
 }
 
 // ---- cost aggregation (cspm_ca.h) ----------------------------------------------------------------------------------------------
@@ -1589,12 +1617,11 @@ static int set_images_impl(cspm_ctx *c, const void *l, const void *r, int w, int
     c->cost_ready = false;
   }
   c->field_consistent = false;
-  if (c->pm_runs_unchecked) c->phases_unchecked = true;
+  c->repeat.taint_unchecked_run();  // its inputs are being replaced
   const void *src[2] = {l, r};
   const size_t row = (size_t)w * 3;
   if (!on_device && c->stage_bytes < 2 * row * h) {
-    if (c->stage) (void)hipFree(c->stage);
-    c->stage = nullptr;
+    dfree(c->stage);
     c->stage_bytes = 0;
     HIPCHK(c, hipMalloc((void **)&c->stage, 2 * row * h));
     c->stage_bytes = 2 * row * h;
@@ -1955,7 +1982,7 @@ int cspm_local_stereo(cspm_ctx *c, int method) {
   int rc;
   if ((rc = ensure_field(c)) || (rc = ca_ensure(c))) return rc;
   c->field_consistent = false;  // min_cost is the local-stereo cost, not the plane cost of this cost object
-  if (c->pm_runs_unchecked) c->phases_unchecked = true;  // an unchecked PatchMatch run can no longer be repeated over these planes
+  c->repeat.taint_unchecked_run();  // it can no longer be repeated over these planes
   for (int v = 0; v < 2; ++v)
     if ((rc = ca_local_view(c, method, v))) return rc;
   return CSPM_OK;
@@ -2004,23 +2031,23 @@ int cspm_pm_default_params(cspm_pm_params *p) {
 
 int cspm_pm_init(cspm_ctx *c, const cspm_pm_params *p) {
   PM_ENTER();
-  c->phases_unchecked = true;
+  c->repeat.taint();
   return do_init(c, p);
 }
 int cspm_pm_spatial(cspm_ctx *c, int iter, const cspm_pm_params *p) {
   PM_ENTER();
-  c->phases_unchecked = true;
+  c->repeat.taint();
   if ((rc = do_spatial(c, iter, p))) return rc;
   return check_sweep(c);
 }
 int cspm_pm_view(cspm_ctx *c, int iter, const cspm_pm_params *p) {
   PM_ENTER();
-  c->phases_unchecked = true;
+  c->repeat.taint();
   return do_view(c, iter, p);
 }
 int cspm_pm_refine(cspm_ctx *c, int iter, const cspm_pm_params *p) {
   PM_ENTER();
-  c->phases_unchecked = true;
+  c->repeat.taint();
   return do_refine(c, iter, p);
 }
 
@@ -2029,20 +2056,16 @@ int cspm_pm_refine(cspm_ctx *c, int iter, const cspm_pm_params *p) {
 int cspm_patchmatch(cspm_ctx *c, int iter_num, const cspm_pm_params *p) {
   PM_ENTER();
   if (iter_num < 0 || iter_num > 15) return fail(c, CSPM_ERR_ARG, "iter_num out of range");
-  c->last_iters = iter_num;
-  c->last_params = *p;
-  c->last_warm = false;
-  c->out_reqs.clear();  // outputs requested behind an earlier run: that run can no longer be repeated (two runs unchecked = an error)
-  ++c->pm_runs_unchecked;
+  c->repeat.begin_run(false, iter_num, *p);
   return run_patchmatch(c, iter_num, p);
 }
 
 int cspm_rescore_planes(cspm_ctx *c) {
   if (!c) return CSPM_ERR_ARG;
-  if (!c->cost_ready) return fail(c, CSPM_ERR_STATE, "no plane cost built (cspm_build_cost_grd / cspm_finish_cost)");
-  if (!c->field_alloc) return fail(c, CSPM_ERR_STATE, "no plane field to re-score");
+  int rc;
+  if ((rc = need_cost(c)) || (rc = need_field(c, "no plane field to re-score"))) return rc;
   ON_DEVICE(c);
-  c->phases_unchecked = true;
+  c->repeat.taint();
   return do_rescore(c);
 }
 
@@ -2050,17 +2073,12 @@ int cspm_rescore_planes(cspm_ctx *c) {
 // persistent sweep that times out can be repeated from it by the next synchronising call.
 int cspm_patchmatch_warm(cspm_ctx *c, int iter_num, const cspm_pm_params *p) {
   if (!c) return CSPM_ERR_ARG;
-  if (!c->cost_ready) return fail(c, CSPM_ERR_STATE, "no plane cost built (cspm_build_cost_grd / cspm_finish_cost)");
-  if (!c->field_alloc) return fail(c, CSPM_ERR_STATE, "no plane field to start from (cspm_set_planes, cspm_local_stereo, cspm_upsample_planes or an earlier run)");
+  if (int e = need_cost(c)) return e;
+  if (int e = need_field(c, "no plane field to start from (cspm_set_planes, cspm_local_stereo, cspm_upsample_planes or an earlier run)")) return e;
   PM_ENTER();
   if (iter_num < 0 || iter_num > 15) return fail(c, CSPM_ERR_ARG, "iter_num out of range");
-  if (!c->field_consistent && (rc = do_rescore(c))) return rc;
-  if ((rc = warm_snapshot(c, true))) return rc;
-  c->last_iters = iter_num;
-  c->last_params = *p;
-  c->last_warm = true;
-  c->out_reqs.clear();
-  ++c->pm_runs_unchecked;
+  if ((rc = ensure_consistent(c)) || (rc = warm_snapshot(c, true))) return rc;
+  c->repeat.begin_run(true, iter_num, *p);
   return run_iterations(c, iter_num, p);
 }
 
@@ -2074,28 +2092,17 @@ int cspm_upsample_planes(cspm_ctx *dst, cspm_ctx *src) {
                                        std::to_string(dst->W) + "x" + std::to_string(dst->H) + " is " + std::to_string((dst->W + 1) / 2) + "x" +
                                        std::to_string((dst->H + 1) / 2));
   ON_DEVICE(dst);
-  int rc = check_sweep(src);  // a timed-out source run is repeated (or reported) before its planes are read
-  if (rc) return fail(dst, rc, "source context: " + src->err);
-  if ((rc = ensure_field(dst))) return rc;
-  // dst's stream waits for the source's work; the source's later work (or its destruction) waits for the copy
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  for (auto &e : ev) HIPCHK(dst, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  hipError_t e = hipEventRecord(ev[0], src->stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(dst->stream, ev[0], 0);
-  if (e == hipSuccess) {
+  int rc;
+  if ((rc = source_check(dst, src)) || (rc = ensure_field(dst))) return rc;
+  return with_source(dst, src, "cspm_upsample_planes", [&] {
     Timed t(dst, CSPM_K_MISC, 0);
     const long long n = (long long)dst->W * dst->H;
     for (int v = 0; v < 2; ++v)
       hipLaunchKernelGGL(k_upsample_planes, dim3(ew_grid(n)), dim3(256), 0, dst->stream, dst->f[v], src->f[v], dst->W, dst->H, src->W);
-  }
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e == hipSuccess) e = hipEventRecord(ev[1], dst->stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(src->stream, ev[1], 0);
-  for (auto x : ev) (void)hipEventDestroy(x);
-  if (e != hipSuccess) return fail(dst, CSPM_ERR_HIP, std::string("cspm_upsample_planes: ") + hipGetErrorString(e));
-  dst->field_consistent = false;  // min_cost is stale until a re-score (cspm_patchmatch_warm does one)
-  if (dst->pm_runs_unchecked) dst->phases_unchecked = true;
-  return CSPM_OK;
+    dst->field_consistent = false;  // min_cost is stale until a re-score (cspm_patchmatch_warm does one)
+    dst->repeat.taint_unchecked_run();
+    return CSPM_OK;
+  });
 }
 
 inline SnapField snap_of(const Field &f) { return SnapField{f.nx, f.ny, f.nz, f.a, f.b, f.c}; }
@@ -2105,39 +2112,27 @@ int cspm_merge_planes(cspm_ctx *dst, cspm_ctx *src) {
   if (dst->device != src->device) return fail(dst, CSPM_ERR_ARG, "the two contexts are on different devices");
   if (!src->field_alloc) return fail(dst, CSPM_ERR_STATE, "the source context has no plane field");
   if (!dst->img0[0]) return fail(dst, CSPM_ERR_STATE, "cspm_set_images first");
-  if (!dst->cost_ready) return fail(dst, CSPM_ERR_STATE, "no plane cost built (cspm_build_cost_grd / cspm_finish_cost)");
-  if (!dst->field_alloc) return fail(dst, CSPM_ERR_STATE, "no plane field to merge into (cspm_pm_init, cspm_set_planes, cspm_local_stereo or an earlier run)");
+  if (int e = need_cost(dst)) return e;
+  if (int e = need_field(dst, kNoMergeTarget)) return e;
   if (src->W != dst->W || src->H != dst->H)
     return fail(dst, CSPM_ERR_ARG, "the source is " + std::to_string(src->W) + "x" + std::to_string(src->H) + ", the destination " +
                                        std::to_string(dst->W) + "x" + std::to_string(dst->H));
   ON_DEVICE(dst);
-  int rc = check_sweep(src);  // a timed-out source run is repeated (or reported) before its planes are read
-  if (rc) return fail(dst, rc, "source context: " + src->err);
-  if (!dst->field_consistent && (rc = do_rescore(dst))) return rc;
-  // dst's stream waits for the source's work; the source's later work (or its destruction) waits for the merge
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  for (auto &e : ev) HIPCHK(dst, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  hipError_t e = hipEventRecord(ev[0], src->stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(dst->stream, ev[0], 0);
-  if (e == hipSuccess) {
+  int rc;
+  if ((rc = source_check(dst, src)) || (rc = ensure_consistent(dst))) return rc;
+  return with_source(dst, src, "cspm_merge_planes", [&] {
     const CandField cf{{snap_of(src->f[0]), snap_of(src->f[1])}, {nullptr, nullptr}};
-    rc = do_merge(dst, &cf, &kDefaultParams, 0, 2, 2LL * dst->W * dst->H);
-  }
-  if (e == hipSuccess) e = hipEventRecord(ev[1], dst->stream);
-  if (e == hipSuccess) e = hipStreamWaitEvent(src->stream, ev[1], 0);
-  for (auto x : ev) (void)hipEventDestroy(x);
-  if (e != hipSuccess) return fail(dst, CSPM_ERR_HIP, std::string("cspm_merge_planes: ") + hipGetErrorString(e));
-  if (dst->pm_runs_unchecked) dst->phases_unchecked = true;  // an unchecked run can no longer be repeated over these planes
-  return rc;
+    dst->repeat.taint_unchecked_run();  // it can no longer be repeated over these planes
+    return do_merge(dst, &cf, &kDefaultParams, 0, 2, 2LL * dst->W * dst->H);
+  });
 }
 
 int cspm_merge_planes_host(cspm_ctx *c, int view, const double *np, const uint8_t *mask) {
   if (!c) return CSPM_ERR_ARG;
   if (view < 0 || view > 1 || !np) return fail(c, CSPM_ERR_ARG, "cspm_merge_planes_host: bad view or no candidate field");
-  if (!c->cost_ready) return fail(c, CSPM_ERR_STATE, "no plane cost built (cspm_build_cost_grd / cspm_finish_cost)");
-  if (!c->field_alloc) return fail(c, CSPM_ERR_STATE, "no plane field to merge into (cspm_pm_init, cspm_set_planes, cspm_local_stereo or an earlier run)");
-  ON_DEVICE(c);
   int rc;
+  if ((rc = need_cost(c)) || (rc = need_field(c, kNoMergeTarget))) return rc;
+  ON_DEVICE(c);
   const size_t n = (size_t)c->W * c->H;
   if (!c->cand_mem && (rc = dalloc(c, &c->cand_mem, 6 * n + (n + 7) / 8, nullptr))) return rc;  // 48 + 1 bytes per pixel
   unsigned char *d_mask = reinterpret_cast<unsigned char *>(c->cand_mem + 6 * n);
@@ -2155,21 +2150,21 @@ int cspm_merge_planes_host(cspm_ctx *c, int view, const double *np, const uint8_
   HIPCHK(c, hipMemcpyAsync(c->cand_mem, h.data(), sizeof(double) * 6 * n, hipMemcpyHostToDevice, c->stream));
   if (mask) HIPCHK(c, hipMemcpyAsync(d_mask, mask, n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (!c->field_consistent && (rc = do_rescore(c))) return rc;
+  if ((rc = ensure_consistent(c))) return rc;
   CandField cf{};
   const double *b = c->cand_mem;
   cf.s[view] = SnapField{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n};
   cf.mask[view] = mask ? d_mask : nullptr;
-  if (c->pm_runs_unchecked) c->phases_unchecked = true;
+  c->repeat.taint_unchecked_run();
   return do_merge(c, &cf, &kDefaultParams, view, 1, evals);
 }
 
 int cspm_pm_init_keep(cspm_ctx *c, const cspm_pm_params *p) {
   const bool had_field = c && c->field_alloc;
   PM_ENTER();
-  if (c->pm_runs_unchecked) c->phases_unchecked = true;
+  c->repeat.taint_unchecked_run();
   if (!had_field) return do_init(c, p);  // nothing to keep
-  if (!c->field_consistent && (rc = do_rescore(c))) return rc;
+  if ((rc = ensure_consistent(c))) return rc;
   return do_merge(c, nullptr, p, 0, 2, 2LL * c->W * c->H);
 }
 
@@ -2177,10 +2172,7 @@ int cspm_get_planes(cspm_ctx *c, int view, double *np_out, double *cost_out) {
   if (!c || view < 0 || view > 1) return CSPM_ERR_ARG;
   if (!c->field_alloc) return fail(c, CSPM_ERR_STATE, "no plane field yet");
   ON_DEVICE(c);
-  {
-    int rc = check_sweep(c);
-    if (rc) return rc;
-  }
+  if (int rc = check_sweep(c)) return rc;
   const size_t n = (size_t)c->W * c->H;
   std::vector<double> h(7 * n);
   HIPCHK(c, hipMemcpyAsync(h.data(), c->f[view].nx, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, c->stream));
@@ -2206,7 +2198,7 @@ int cspm_set_planes(cspm_ctx *c, int view, const double *np, const double *cost)
   HIPCHK(c, hipMemcpyAsync(c->f[view].nx, h.data(), sizeof(double) * 7 * n, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->field_consistent = false;  // min_cost is whatever the caller says: the sweep may not assume cost(plane) == min_cost
-  c->phases_unchecked = true;
+  c->repeat.taint();
   return CSPM_OK;
 }
 
@@ -2214,10 +2206,7 @@ int cspm_disparity_u8_device(cspm_ctx *c, int view, int dis_scale, void *d_out) 
   if (!c || view < 0 || view > 1 || !d_out) return CSPM_ERR_ARG;
   if (!c->field_alloc) return fail(c, CSPM_ERR_STATE, "no plane field yet");
   ON_DEVICE(c);
-  // asynchronous: when the run in front of it has an unchecked sweep, remember the request -- a repeated run (sweep timeout)
-  // writes the map again from ITS planes, so the caller never reads a map of the aborted run after a successful check
-  if (c->sweep_pending) c->remember_output(cspm_ctx::OutReq{0, view, dis_scale, d_out, nullptr});
-  return enqueue_disp_u8(c, view, dis_scale, d_out);
+  return request_output(c, OutReq{kOutDisp, view, dis_scale, d_out, nullptr});
 }
 
 int cspm_get_disparity_u8(cspm_ctx *c, int view, int dis_scale, uint8_t *out, size_t stride) {
@@ -2236,12 +2225,8 @@ int cspm_get_disparity_f64(cspm_ctx *c, int view, double *out) {
   if (!c || view < 0 || view > 1 || !out) return CSPM_ERR_ARG;
   if (!c->field_alloc) return fail(c, CSPM_ERR_STATE, "no plane field yet");
   ON_DEVICE(c);
-  {
-    int rc = check_sweep(c);
-    if (rc) return rc;
-  }
-  Pm pm{};
-  pm.W = c->W; pm.H = c->H; pm.f[0] = c->f[0]; pm.f[1] = c->f[1];
+  if (int rc = check_sweep(c)) return rc;
+  const Pm pm = field_pm(c);
   const size_t n = (size_t)c->W * c->H;
   hipLaunchKernelGGL(k_plane_to_disp_f64, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, pm, view, c->vc.cost);
   HIPCHK(c, hipMemcpyAsync(out, c->vc.cost, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
@@ -2270,8 +2255,7 @@ int cspm_postprocess_device(cspm_ctx *c, int dis_scale, void *d_l_out, void *d_r
   if (!c->field_alloc || !c->cost_alloc) return fail(c, CSPM_ERR_STATE, "cspm_postprocess_device needs a finished PatchMatch");
   if (dis_scale < 1 || !d_l_out || !d_r_out) return fail(c, CSPM_ERR_ARG, "bad dis_scale / outputs");
   ON_DEVICE(c);
-  if (c->sweep_pending) c->remember_output(cspm_ctx::OutReq{1, 0, dis_scale, d_l_out, d_r_out});  // see cspm_disparity_u8_device
-  return enqueue_postprocess_device(c, dis_scale, d_l_out, d_r_out);
+  return request_output(c, OutReq{kOutPost8, 0, dis_scale, d_l_out, d_r_out});
 }
 
 // sub-pixel PostProcessing: the f64 maps and, where asked for, the left-right consistency flags
@@ -2300,8 +2284,7 @@ int cspm_postprocess_f64_device(cspm_ctx *c, void *d_l_out, void *d_r_out) {
   if (!c->field_alloc || !c->cost_alloc) return fail(c, CSPM_ERR_STATE, "cspm_postprocess_f64_device needs a finished PatchMatch");
   if (!d_l_out || !d_r_out) return fail(c, CSPM_ERR_ARG, "bad outputs");
   ON_DEVICE(c);
-  if (c->sweep_pending) c->remember_output(cspm_ctx::OutReq{2, 0, 0, d_l_out, d_r_out});  // see cspm_disparity_u8_device
-  return enqueue_postprocess_f64_device(c, d_l_out, d_r_out);
+  return request_output(c, OutReq{kOutPostF64, 0, 0, d_l_out, d_r_out});
 }
 
 int cspm_enable_timing(cspm_ctx *c, int on) {
@@ -2400,7 +2383,7 @@ int cspm_fpm_begin(cspm_ctx *c, int w, int h, int max_dis) {
   }
   c->max_dis = max_dis;
   c->field_consistent = false;
-  c->phases_unchecked = true;
+  c->repeat.taint();
   int rc = ensure_field(c);
   if (rc) return rc;
   const long long need = std::max(2LL * w * h, 4LL * std::min(w, h));  // a diagonal batch holds 4 per pixel (tiny images)
