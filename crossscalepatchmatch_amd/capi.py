@@ -34,6 +34,7 @@ OPT_SWEEP_FOLD = 18          # cross-scale sweep workgroups of levels - 1 waves,
 OPT_FAULT_VOLUME_ALLOC = 16  # write only, TEST HOOK: the n-th optional-volume allocation from now on fails
 OPT_CENGRD_FUSED = 19        # set before build_cost_cengrd: 1 = no volumes, the cells are computed inside the PatchMatch kernels (default 0; identical planes)
 OPT_CENGRD_FUSED_ACTIVE = 20 # read only: the current cost object is a fused CENGRD one
+OPT_PP_SPECKLE_REMOVED = 21  # read only, synchronises: pixels the speckle filter removed from both masks in the last post-processing
 CA_BOX, CA_GF, CA_BF = 0, 1, 2  # cost aggregation: BoxCA, GFCA, BFCA (ca_filter/)
 CENGRD_KAPPA, CENGRD_TAU = 0.0625, 32.0  # CSPM_CENGRD_KAPPA / CSPM_CENGRD_TAU: cell = fma(KAPPA, min(H, TAU), G)
 
@@ -50,6 +51,7 @@ SYMBOLS = [
     "cspm_taps_per_view_pass", "cspm_row_engine_taps_per_view_pass", "cspm_fpm_begin", "cspm_fpm_candidates", "cspm_fpm_commit",
     "cspm_aggregate_cv_host", "cspm_local_stereo", "cspm_rescore_planes", "cspm_patchmatch_warm", "cspm_upsample_planes",
     "cspm_merge_planes", "cspm_merge_planes_host", "cspm_pm_init_keep",
+    "cspm_set_pp_speckle", "cspm_get_pp_speckle", "cspm_filter_speckles_host",
 ]
 
 
@@ -150,6 +152,9 @@ def load_library():
         "cspm_merge_planes": (C.c_int, [vp, vp]),
         "cspm_merge_planes_host": (C.c_int, [vp, C.c_int, dp, u8p]),
         "cspm_pm_init_keep": (C.c_int, [vp, pp]),
+        "cspm_set_pp_speckle": (C.c_int, [vp, C.c_int, C.c_double]),
+        "cspm_get_pp_speckle": (C.c_int, [vp, ip, dp]),
+        "cspm_filter_speckles_host": (C.c_int, [C.c_int, dp, u8p, C.c_int, C.c_int, C.c_int, C.c_double, u8p, C.POINTER(C.c_int32)]),
     }
     assert sorted(sig) == sorted(SYMBOLS)
     for name, (res, args) in sig.items():
@@ -426,6 +431,17 @@ class StereoContext:
         self._chk(self.L.cspm_postprocess_f64(self.p, _dp(l), _dp(r), _u8(lv), _u8(rv)))
         return l, r, lv, rv
 
+    def set_pp_speckle(self, max_size, max_diff=1.0):
+        """speckle filter of every post-processing entry: after the left-right check, connected components
+        (4-neighbours whose disparities differ by at most max_diff) of at most max_size pixels leave the consistency mask and are
+        filled and medianed like any inconsistent pixel.  max_size = 0 (the default) = no filter."""
+        self._chk(self.L.cspm_set_pp_speckle(self.p, int(max_size), float(max_diff)))
+
+    def get_pp_speckle(self):
+        n, x = C.c_int(), C.c_double()
+        self._chk(self.L.cspm_get_pp_speckle(self.p, C.byref(n), C.byref(x)))
+        return n.value, x.value
+
     def postprocess_f64_device(self, d_l_ptr, d_r_ptr):
         """the same with device-resident outputs (packed h*w f64 each; asynchronous on the context's stream)"""
         self._chk(self.L.cspm_postprocess_f64_device(self.p, C.c_void_p(d_l_ptr), C.c_void_p(d_r_ptr)))
@@ -463,6 +479,26 @@ def aggregate_cv_host(device, method, guide, vol):
     if rc != 0:
         raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
     return v
+
+
+def filter_speckles(device, disp, valid, max_size, max_diff):
+    """the speckle filter alone on a host map: disp (h, w) f64, valid (h, w) or None (every pixel).  Returns
+    (valid_out u8, sizes int32): the mask without the components of at most max_size pixels, and every pixel's component size
+    (0 outside the mask)."""
+    L = load_library()
+    d = np.ascontiguousarray(disp, dtype=np.float64)
+    assert d.ndim == 2
+    m = None
+    if valid is not None:
+        m = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+        assert m.shape == d.shape, m.shape
+    out = np.zeros(d.shape, np.uint8)
+    sizes = np.zeros(d.shape, np.int32)
+    rc = L.cspm_filter_speckles_host(device, _dp(d), _u8(m) if m is not None else None, d.shape[1], d.shape[0], int(max_size), float(max_diff),
+                                     _u8(out), sizes.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    return out, sizes
 
 
 def disparity_planes(disp):

@@ -12,6 +12,7 @@
 
 #include "cspm_kernels.h"
 #include "cspm_pp.h"
+#include "cspm_speckle.h"
 #include "cspm_ca.h"
 
 using namespace cspm;
@@ -175,6 +176,10 @@ struct cspm_ctx {
   uint8_t *d_valid[2] = {nullptr, nullptr};  // post-processing: left-right consistency flags
   unsigned int *d_todo = nullptr;            // post-processing: per view n indices of inconsistent pixels, then the two counts
   double *d_pp[2] = {nullptr, nullptr};      // sub-pixel post-processing (cspm_postprocess_f64): the two f64 maps, allocated by its first call and kept
+  int pp_speckle_size = 0;                   // cspm_set_pp_speckle: 0 = no speckle filter (no launch, no scratch)
+  double pp_speckle_diff = 1.0;
+  int *d_speckle = nullptr;                  // speckle filter: per view n parents, then per view n counts, then the removed-pixel counter; allocated by the first filtered call and kept
+  bool speckle_ran = false;                  // the last post-processing enqueued ran the filter (CSPM_OPT_PP_SPECKLE_REMOVED reads its counter)
   // persistent raster sweep (k_spatial_sweep)
   unsigned int *d_sweep_ctrl = nullptr, *d_sweep_start = nullptr;
   unsigned long long *d_sweep_gran = nullptr;  // persistent sweep: 12 data-tagged granules per pixel and view (cspm_chain.h)
@@ -355,6 +360,8 @@ void free_field(cspm_ctx *c) {
     dfree(c->d_valid[v]);
   }
   dfree(c->d_todo);
+  dfree(c->d_speckle);
+  c->speckle_ran = false;
   dfree(c->d_pp[0]);  // one allocation holds both maps
   c->d_pp[1] = nullptr;
   dfree(c->d_rowq);
@@ -1219,6 +1226,44 @@ int run_warm_retry(cspm_ctx *c, int iter_num, const cspm_pm_params *p) {
   return run_iterations(c, iter_num, p);
 }
 
+// The speckle filter's four launches (cspm_speckle.h) for `views` views (1 or 2) of w x h, n = w * h < 2^31.  scratch: views * n parents,
+// then views * n counts.  size_out (one view only) may be null.
+template <class T>
+void speckle_launch(hipStream_t stream, const T *const *d, uint8_t *const *valid, int views, int w, int h, int max_size, double thr, int *scratch,
+                    unsigned int *removed, int *size_out) {
+  const long long n = (long long)w * h;
+  SpkViews<T> vs;
+  for (int v = 0; v < 2; ++v) {
+    const int u = v < views ? v : 0;
+    vs.v[v] = SpkView<T>{d[u], valid[u], scratch + u * n, scratch + (views + u) * n};
+  }
+  const unsigned tiles = (unsigned)(((w + kSpkTileW - 1) / kSpkTileW) * (long long)((h + kSpkTileH - 1) / kSpkTileH));
+  const dim3 px_grid((unsigned)((n + 255) / 256), (unsigned)views);
+  hipLaunchKernelGGL(k_speckle_tiles<T>, dim3(tiles, (unsigned)views), dim3(kSpkBlock), 0, stream, vs, w, h, thr);
+  hipLaunchKernelGGL(k_speckle_borders<T>, px_grid, dim3(256), 0, stream, vs, w, h, thr);
+  hipLaunchKernelGGL(k_speckle_sizes, px_grid, dim3(256), 0, stream, vs.v[0].parent, vs.v[1].parent, vs.v[0].cnt, vs.v[1].cnt, n);
+  hipLaunchKernelGGL(k_speckle_apply, px_grid, dim3(256), 0, stream, vs.v[0].parent, vs.v[1].parent, vs.v[0].cnt, vs.v[1].cnt, vs.v[0].valid,
+                     vs.v[1].valid, n, max_size, removed, size_out);
+}
+
+// PostProcessing's speckle filter on c->d_valid, between LeftRightCheck and FillInvalid; nothing at all when off
+template <class T>
+int speckle_enqueue(cspm_ctx *c, const T *d0, const T *d1, double thr) {
+  c->speckle_ran = c->pp_speckle_size > 0;
+  if (!c->speckle_ran) return CSPM_OK;
+  const long long n = (long long)c->W * c->H;
+  if (n >= (1LL << 31)) return fail(c, CSPM_ERR_ARG, "image too large for the speckle filter's 32-bit labels");
+  if (!c->d_speckle) {
+    int rc = dalloc(c, &c->d_speckle, 4 * (size_t)n + 1, nullptr);
+    if (rc) return rc;
+  }
+  unsigned int *removed = (unsigned int *)(c->d_speckle + 4 * n);
+  HIPCHK(c, hipMemsetAsync(removed, 0, sizeof(unsigned int), c->stream));
+  const T *d[2] = {d0, d1};
+  speckle_launch<T>(c->stream, d, c->d_valid, 2, c->W, c->H, c->pp_speckle_size, thr, c->d_speckle, removed, nullptr);
+  return CSPM_OK;
+}
+
 // PlaneToDisp + PostProcessing (cs_patchmatch.cc:103-107, 508-588) enqueued on the ctx stream; results in c->d_dis[v]
 int postprocess_enqueue(cspm_ctx *c, int dis_scale) {
   const Pm pm = field_pm(c);
@@ -1232,6 +1277,7 @@ int postprocess_enqueue(cspm_ctx *c, int dis_scale) {
   // LeftRightCheck of both views (:516) on the maps as PlaneToDisp left them
   hipLaunchKernelGGL(k_lr_check, dim3(ew_grid(2 * n)), dim3(256), 0, c->stream, c->d_dis[0], c->d_dis[1], c->W, c->H, dis_scale, c->d_valid[0],
                      c->d_valid[1]);
+  if (int rc = speckle_enqueue<uint8_t>(c, c->d_dis[0], c->d_dis[1], c->pp_speckle_diff * (double)dis_scale)) return rc;
   // FillInvalid (:545): a workgroup per row and view
   if (fill_rows_shmem(c->W) > 160 * 1024) return fail(c, CSPM_ERR_ARG, "image too wide for the row scan of FillInvalid");
   LAUNCH_ONE(k_fill_rows<FillU8>, dim3(2u * (unsigned)c->H), dim3(kFillBlock), fill_rows_shmem(c->W), pm, (FillU8{dis_scale, c->d_dis[0], c->d_dis[1]}),
@@ -1273,6 +1319,7 @@ int postprocess_f64_enqueue(cspm_ctx *c) {
   unsigned int *todo_cnt = c->d_todo + 2 * (size_t)n;
   HIPCHK(c, hipMemsetAsync(todo_cnt, 0, 2 * sizeof(unsigned int), c->stream));
   hipLaunchKernelGGL(k_lr_check_f64, dim3(ew_grid(2 * n)), dim3(256), 0, c->stream, c->d_pp[0], c->d_pp[1], c->W, c->H, c->d_valid[0], c->d_valid[1]);
+  if (int rc = speckle_enqueue<double>(c, c->d_pp[0], c->d_pp[1], c->pp_speckle_diff)) return rc;
   LAUNCH_ONE(k_fill_rows<FillF64>, dim3(2u * (unsigned)c->H), dim3(kFillBlock), fill_rows_shmem(c->W), pm,
              (FillF64{(double)c->max_dis, c->d_pp[0], c->d_pp[1]}), c->d_valid[0], c->d_valid[1], c->d_todo, todo_cnt);
   hipLaunchKernelGGL(k_weighted_median_f64, dim3((unsigned)c->ncu * (unsigned)kPpGrid), dim3(kWave), 0, c->stream, L0.pix[0], L0.pix[1], L0.Wp, L0.pad,
@@ -1673,6 +1720,20 @@ int cspm_set_option(cspm_ctx *c, int key, long long value) {
   }
 }
 
+int cspm_set_pp_speckle(cspm_ctx *c, int max_size, double max_diff) {
+  if (!c) return CSPM_ERR_ARG;
+  if (max_size < 0 || !(max_diff >= 0.0) || !std::isfinite(max_diff)) return fail(c, CSPM_ERR_ARG, "speckle filter: max_size >= 0 and a finite max_diff >= 0");
+  c->pp_speckle_size = max_size;
+  c->pp_speckle_diff = max_diff;
+  return CSPM_OK;
+}
+int cspm_get_pp_speckle(cspm_ctx *c, int *max_size, double *max_diff) {
+  if (!c) return CSPM_ERR_ARG;
+  if (max_size) *max_size = c->pp_speckle_size;
+  if (max_diff) *max_diff = c->pp_speckle_diff;
+  return CSPM_OK;
+}
+
 int cspm_get_option(cspm_ctx *c, int key, long long *value) {
   if (!c || !value) return CSPM_ERR_ARG;
   switch (key) {
@@ -1694,6 +1755,17 @@ int cspm_get_option(cspm_ctx *c, int key, long long *value) {
     case CSPM_OPT_SWEEP_PACKED_ACTIVE: *value = c->sweep_packed ? 1 : 0; return CSPM_OK;
     case CSPM_OPT_CENGRD_FUSED: *value = c->opt_cengrd_fused; return CSPM_OK;
     case CSPM_OPT_CENGRD_FUSED_ACTIVE: *value = (c->cost_alloc && c->cost.fused == kSrcCenGrd) ? 1 : 0; return CSPM_OK;
+    case CSPM_OPT_PP_SPECKLE_REMOVED: {  // synchronises: pixels the speckle filter took out of both masks in the last post-processing
+      if (c->pp_speckle_size == 0 || !c->speckle_ran || !c->d_speckle) { *value = 0; return CSPM_OK; }  // off, or nothing filtered yet
+      DevGuard guard_(c->device);
+      if (!guard_.ok) return fail(c, CSPM_ERR_HIP, "hipSetDevice failed");
+      if (int rc = check_sweep(c)) return rc;  // a repeated run replays the post-processing behind it: the count is the replay's
+      unsigned int removed = 0;
+      HIPCHK(c, hipMemcpyAsync(&removed, c->d_speckle + 4 * (size_t)c->W * c->H, sizeof removed, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      *value = removed;
+      return CSPM_OK;
+    }
     case CSPM_OPT_SWEEP_PACKED_BAD: {  // synchronises: gradients the packer could not represent (always 0 for 8-bit images)
       if (!c->cost_alloc || !c->d_px8_bad) { *value = 0; return CSPM_OK; }
       DevGuard guard_(c->device);
@@ -1963,6 +2035,35 @@ int cspm_aggregate_cv_host(int device, int method, const double *guide, int w, i
       hipMemcpyAsync(vol + px, dv, sizeof(double) * (n_slices - 1) * px, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
       hipStreamSynchronize(c->stream) != hipSuccess)
     return S.done(fail(c, CSPM_ERR_HIP, "aggregation kernels failed"));
+  return S.done(CSPM_OK);
+}
+
+// the speckle filter alone on caller maps: the launches PostProcessing enqueues, on one view
+int cspm_filter_speckles_host(int device, const double *disp, const uint8_t *valid, int w, int h, int max_size, double max_diff, uint8_t *valid_out,
+                              int32_t *size_out) {
+  if (!disp || !valid_out || w < 1 || h < 1 || max_size < 0 || !(max_diff >= 0.0)) return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
+  const long long n = (long long)w * h;
+  if (n >= (1LL << 31)) return fail(nullptr, CSPM_ERR_ARG, "w * h must be below 2^31: labels are 32-bit pixel indices");
+  Scratch S;
+  int rc = cspm_create(&S.c, device);
+  if (rc) return rc;
+  cspm_ctx *c = S.c;
+  double *dd = nullptr;
+  uint8_t *dv = nullptr;
+  int *scratch = nullptr;  // parents, counts, n(p), the removed-pixel counter
+  if ((rc = dalloc(c, &dd, (size_t)n, &S.tmp)) || (rc = dalloc(c, &dv, (size_t)n, &S.tmp)) || (rc = dalloc(c, &scratch, 3 * (size_t)n + 1, &S.tmp)))
+    return S.done(rc);
+  if (hipMemcpyAsync(dd, disp, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      (valid ? hipMemcpyAsync(dv, valid, (size_t)n, hipMemcpyHostToDevice, c->stream) : hipMemsetAsync(dv, 1, (size_t)n, c->stream)) != hipSuccess ||
+      hipMemsetAsync(scratch + 3 * n, 0, sizeof(int), c->stream) != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  const double *d[1] = {dd};
+  uint8_t *v[1] = {dv};
+  speckle_launch<double>(c->stream, d, v, 1, w, h, max_size, max_diff, scratch, (unsigned int *)(scratch + 3 * n), scratch + 2 * n);
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(valid_out, dv, (size_t)n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      (size_out && hipMemcpyAsync(size_out, scratch + 2 * n, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, "speckle filter kernels failed"));
   return S.done(CSPM_OK);
 }
 

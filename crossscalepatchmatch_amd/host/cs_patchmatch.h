@@ -68,6 +68,12 @@ class CSPatchMatch {
   // unquantised disparities of both views, row-major; either output may be NULL.  Needs the cost object's images like use_pp (a
   // foreign IPlaneCost has them after a run with use_pp).  dis() and the plane field are not changed.
   void PostProcessedDisparity(std::vector<double> *l_out, std::vector<double> *r_out) const;
+  // speckle filter of PostProcessing (an addition; include/cspm.h cspm_set_pp_speckle): between the left-right check and the fill,
+  // connected components (4-neighbours whose disparities differ by at most max_diff) of at most max_size consistent pixels leave the
+  // consistency mask, in use_pp's 8-bit maps and in PostProcessedDisparity alike.  max_size == 0 (the default) = no filter.  Kept
+  // here and written into the cost object's context by every post-processing of this object.  Throws for max_size < 0 and for a
+  // max_diff that is negative or not finite.
+  void SetSpeckleFilter(int max_size, double max_diff);
 
  private:
   Mat img_[kViewNum], dis_[kViewNum];
@@ -78,6 +84,9 @@ class CSPatchMatch {
   cspm_ctx *own_ctx_;  // foreign IPlaneCost: the context that holds the plane field
   cspm_ctx *pending_ctx_;  // PatchMatchBegin without its PatchMatchEnd yet
   bool pending_pp_;
+  int speckle_size_;
+  double speckle_diff_;
+  void ApplySpeckleFilter(cspm_ctx *ctx) const;
   std::vector<Plane> start_planes_[kViewNum];  // SetPlanes, not yet written into a context
   struct Candidates {  // AddCandidates / AddCandidateDisparity, not yet merged: 6 doubles per pixel and a mask (empty: every pixel)
     std::vector<double> norm_param;

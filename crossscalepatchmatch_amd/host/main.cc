@@ -14,6 +14,7 @@
 #include "pfm_io.h"
 
 #include <atomic>
+#include <cmath>
 #include <fstream>
 #include <memory>
 #include <mutex>
@@ -59,6 +60,11 @@ DEFINE_string(l_disp_pfm, "", "also write the left sub-pixel disparity map as fl
 DEFINE_string(r_disp_pfm, "", "also write the right sub-pixel disparity map as float32 PFM (see --l_disp_pfm)");
 DEFINE_bool(pp_pfm, false, "with --use_pp: the PFM maps (--l_disp_pfm / --r_disp_pfm, or the batch list's) receive the sub-pixel post-processed "
                            "disparities -- left-right check, fill and weighted median on a*x+b*y+c itself -- instead of the raw plane disparities");
+DEFINE_int32(pp_speckle_size, 0, "with --use_pp: speckle filter between the left-right check and the fill -- connected components of at most "
+                                 "this many consistent pixels are treated as inconsistent (filled and medianed); 0 = no filter.  Applies to the "
+                                 "8-bit maps and, with --pp_pfm, to the PFM maps");
+DEFINE_double(pp_speckle_diff, 1.0, "with --pp_speckle_size: two neighbouring pixels belong to one component when their disparities differ by at "
+                                    "most this much (in disparity units, before --dis_scale)");
 DEFINE_string(batch_list, "", "text file, one stereo pair per line: l_img r_img l_dis r_dis [l_pfm r_pfm]; all pairs run with the "
                               "matching flags of this command line on one device context (buffers are reused between pairs). A pair "
                               "that fails is reported and the batch goes on; the exit code is non-zero if any pair failed");
@@ -127,6 +133,7 @@ void begin(PairRun &p, CCMethod *cost_fn) {
     p.cost.reset(pc);  // released on every path, exceptions included (batch mode goes on)
     p.matcher.reset(new CSPatchMatch(p.left, p.right, FLAGS_max_dis, FLAGS_dis_scale));
     p.matcher->set_seed(static_cast<uint64_t>(FLAGS_seed));
+    p.matcher->SetSpeckleFilter(FLAGS_pp_speckle_size, FLAGS_pp_speckle_diff);
     if (FLAGS_schedule == "diffuse") p.matcher->set_schedule(CSPM_SCHED_DIFFUSE, 1, FLAGS_neighbours);
     else p.matcher->set_schedule(FLAGS_schedule == "redblack" ? 1 : 0);
     const string *seed_pfm[kViewNum] = {&FLAGS_l_seed_pfm, &FLAGS_r_seed_pfm};
@@ -312,6 +319,14 @@ int run_batch(const std::vector<BatchJob> &jobs, int skipped, int bad_lines) {
 int run() {
   if (FLAGS_pp_pfm && !FLAGS_use_pp) {  // checked before anything opens a device
     cout << "Error: --pp_pfm post-processes the PFM maps and needs --use_pp\n";
+    return EXIT_FAILURE;
+  }
+  if (FLAGS_pp_speckle_size != 0 && !FLAGS_use_pp) {
+    cout << "Error: --pp_speckle_size filters the post-processing's consistency masks and needs --use_pp\n";
+    return EXIT_FAILURE;
+  }
+  if (FLAGS_pp_speckle_size < 0 || !(FLAGS_pp_speckle_diff >= 0.0) || !std::isfinite(FLAGS_pp_speckle_diff)) {
+    cout << "Error: --pp_speckle_size must be >= 0 and --pp_speckle_diff finite and >= 0\n";
     return EXIT_FAILURE;
   }
   if (!FLAGS_ca_name.empty() && ca_method(FLAGS_ca_name) < 0) {  // checked before anything opens a device

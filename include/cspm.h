@@ -190,6 +190,9 @@ int cspm_build_cost_grd(cspm_ctx *ctx, int max_dis, int wnd_size, int scale_num,
  * CSPM_OPT_CENGRD_FUSED_ACTIVE (read only): 1 when the current cost object is a fused CENGRD one. */
 #define CSPM_OPT_CENGRD_FUSED 19
 #define CSPM_OPT_CENGRD_FUSED_ACTIVE 20
+/* CSPM_OPT_PP_SPECKLE_REMOVED (read only; synchronises): pixels the speckle filter (cspm_set_pp_speckle) took out of the two consistency
+ * masks, both views together, in the context's last post-processing; 0 when that ran without the filter. */
+#define CSPM_OPT_PP_SPECKLE_REMOVED 21
 int cspm_get_option(cspm_ctx *ctx, int key, long long *value);
 int cspm_set_option(cspm_ctx *ctx, int key, long long value);
 /* The same constructors with `new CenCC` (main.cc:43-45; cc/cen_cc.cc:4-137): 9x9 census codes of every level built on
@@ -341,6 +344,23 @@ int cspm_postprocess_device(cspm_ctx *ctx, int dis_scale, void *d_l_out, void *d
 int cspm_postprocess_f64(cspm_ctx *ctx, double *l_out, double *r_out, uint8_t *l_valid_out, uint8_t *r_valid_out);
 /* device-resident outputs (packed w*h f64 each), asynchronous on the ctx stream; the CONTRACT for asynchronous outputs above holds */
 int cspm_postprocess_f64_device(cspm_ctx *ctx, void *d_l_out, void *d_r_out);
+
+/* speckle filter (an addition), a step of all four post-processing entries above, between the left-right check
+ * and the fill.  S(D, V, max_size, max_diff) -> V' on one view's map D and its consistency mask V: nodes are the pixels with V = 1; two
+ * nodes are joined when they are 4-neighbours and |D[p] - D[q]| <= max_diff (in f64; false when either is NaN; pairwise, not against a
+ * seed); n(p) = size of p's connected component, 0 for a non-node; V'[p] = V[p] && n(p) > max_size.  Fill and weighted median then see
+ * V' as they see V without the filter (a removed pixel is filled, is medianed and does not vote), and the masks cspm_postprocess_f64
+ * returns are V'.  The f64 entries filter the unquantised a*x+b*y+c maps; the 8-bit entries (double)byte with the threshold
+ * max_diff * dis_scale (one f64 product).  max_size == 0 (the default; max_diff defaults to 1.0) = no filter: no launch, no memory.
+ * Scratch: two int32 per pixel and view (and one counter), allocated by the first filtered post-processing and kept with the plane field.
+ * Timed under CSPM_K_POST.  CSPM_ERR_ARG for max_size < 0 or a max_diff that is negative or not finite; the getter's outputs may be NULL. */
+int cspm_set_pp_speckle(cspm_ctx *ctx, int max_size, double max_diff);
+int cspm_get_pp_speckle(cspm_ctx *ctx, int *max_size, double *max_diff);
+/* the filter alone on caller maps, no context needed: disp w*h doubles, valid w*h bytes (NULL = every pixel is a node), valid_out w*h
+ * bytes = V', size_out (may be NULL) w*h int32 = n(p).  max_diff may be +infinity here (the mask's own components).  CSPM_ERR_ARG for
+ * max_size < 0, a negative or NaN max_diff, or w*h >= 2^31 (labels are 32-bit pixel indices). */
+int cspm_filter_speckles_host(int device, const double *disp, const uint8_t *valid, int w, int h, int max_size, double max_diff,
+                              uint8_t *valid_out, int32_t *size_out);
 
 /* ---- CSPatchMatch::PatchMatch over a FOREIGN IPlaneCost (plane_cost/i_plane_cost.h:28-33) ------------------------------
  * Any object with a GetPlaneCost(x, y, plane, view) that is not one of this library's device costs: the reference drives it
