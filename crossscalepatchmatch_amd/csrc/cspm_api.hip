@@ -298,20 +298,18 @@ int drain_timing(cspm_ctx *c) {
 // row engine: one wave per 64-pixel run of an image row, kRowWaves waves per workgroup, grid a multiple of 8 (XCD bands)
 // a row-kernel launch: claimed column bands when it runs for several rounds of resident waves, interleaved row blocks otherwise
 // (cspm_rows.h row_item); workgroups of kRowWaves waves, grid a multiple of 8
-inline bool row_claimed_w(const cspm_ctx *c, int W, int views) {
-  const long long items = row_items(W, c->H, views);
+inline bool row_claimed(const cspm_ctx *c, int views) {
+  const long long items = row_items(c->W, c->H, views);
   if (items >= (1LL << 31)) return false;
   if (c->row_claim >= 0) return c->row_claim != 0;
   return items >= 2LL * c->ncu * 12;  // two rounds of the 12 waves a CU holds (a KITTI-size pair: every row kernel; a 450 x 375 pair: none)
 }
-inline unsigned row_grid_w(const cspm_ctx *c, int W, int views) {
-  const bool claimed = row_claimed_w(c, W, views);
-  long long per_xcd = (row_items_per_xcd(W, c->H, views, claimed) + kRowWaves - 1) / kRowWaves;
+inline unsigned row_grid(const cspm_ctx *c, int views) {
+  const bool claimed = row_claimed(c, views);
+  long long per_xcd = (row_items_per_xcd(c->W, c->H, views, claimed) + kRowWaves - 1) / kRowWaves;
   if (claimed) per_xcd += per_xcd / 4 + 1;  // the surplus workgroups of the XCDs that finish first take over the others' bands
   return (unsigned)(per_xcd * 8);
 }
-inline bool row_claimed(const cspm_ctx *c, int views) { return row_claimed_w(c, c->W, views); }
-inline unsigned row_grid(const cspm_ctx *c, int views) { return row_grid_w(c, c->W, views); }
 inline int row_cap(const cspm_ctx *c) { return strip_capacity(c->max_dis, c->cost.half); }
 inline int row_ocap(const cspm_ctx *c) { return own_capacity(c->cost.half); }
 inline size_t row_shmem(const cspm_ctx *c) { return sizeof(LutMem) + (size_t)kRowWaves * wave_lds_bytes(row_cap(c), row_ocap(c)); }
@@ -1007,10 +1005,10 @@ int do_init(cspm_ctx *c, const cspm_pm_params *p) {
 }
 
 // waves of a sweep workgroup: cross-scale -> one per pyramid level; single-scale -> one per chain pass of a full window
-inline bool sweep_folded(const cspm_ctx *c) { return c->cost.cs && kSweepWpl == 1 && c->opt_sweep_fold != 0 && c->cost.levels >= 4; }
+inline bool sweep_folded(const cspm_ctx *c) { return c->cost.cs && c->opt_sweep_fold != 0 && c->cost.levels >= 4; }
 inline unsigned sweep_waves(const cspm_ctx *c) {
   if (sweep_folded(c)) return (unsigned)(c->cost.levels - 1);  // the last level is folded onto the waves of levels 1 .. (cspm_chain.h eval_pixel_pair)
-  return c->cost.cs ? (unsigned)(c->cost.levels * kSweepWpl) : (unsigned)((c->cost.n + kChainRows - 1) / kChainRows);
+  return c->cost.cs ? (unsigned)c->cost.levels : (unsigned)((c->cost.n + kChainRows - 1) / kChainRows);
 }
 inline size_t sweep_lds(const cspm_ctx *c) { return sweep_shared_bytes((int)sweep_waves(c) + (sweep_folded(c) ? 1 : 0)); }
 

@@ -114,14 +114,8 @@ __device__ __forceinline__ unsigned long long step_stamp(unsigned dep0, unsigned
 // MEASURED (profiles/r05_sweep_*): a sweep pixel's evaluation drops from 8.3 to 6.3 us -- and the sweep takes the same 20 ms: its anti-
 // diagonals advance at the pace of the SLOWEST pixels on the critical path through the dependency lattice (two-candidate pixels,
 // hand-over), not of the median one, and the pipelined kernel needs 97-109 VGPRs against 81, which other pairs' kernels would use.
-// So the raster sweep keeps the plain loop (CSPM_SWEEP_PIPE = 0); single evaluations (cspm_plane_cost_batch, the red-black option)
+// So the raster sweep keeps the plain loop (the pipelined one lost there); single evaluations (cspm_plane_cost_batch, the red-black option)
 // run the pipelined one, which keeps it compiled and tested: two schedules of the same arithmetic that must agree bit for bit.
-#ifndef CSPM_SWEEP_PIPE
-#define CSPM_SWEEP_PIPE 0
-#endif
-#ifndef CSPM_CHAIN_ALLV
-#define CSPM_CHAIN_ALLV 1
-#endif
 
 // a value that is the same in every lane of the wave (the candidate planes of a pixel, the window centre's colour): telling the compiler
 // so moves it to scalar registers -- the software-pipelined steps need the vector registers (two workgroups of five waves are resident
@@ -274,8 +268,9 @@ __device__ __forceinline__ void chain_passes(const Cost &cd, const ChainLevel &A
   // that level runs without clamp, validity test and select (4 of ~29 instructions per tap and candidate; the margin covers the roundings
   // of the device-order disparity against the corner values, as in the row engine's all-valid rows).  True for most pixels of a sweep:
   // its candidates are the neighbours' settled planes.  Same arithmetic for the taps that were valid anyway: identical bits.
+  // (The general taps on every level lost.)
   bool allv = (SRC == kSrcGrd || census_elem<SRC>() || SRC == kSrcGrd8 || SRC == kSrcVolume || SRC == kSrcVol2) && A.has_valid;
-#if defined(CSPM_STEP_TRACE) || !CSPM_CHAIN_ALLV
+#if defined(CSPM_STEP_TRACE)
   allv = false;
 #endif
   if (allv) {
@@ -522,17 +517,17 @@ __global__ __launch_bounds__(kEvalBlock) void k_spatial_rb(Cost cd, Pm pm, int c
 // every tap is computed once).  Work split: cross-scale -> one wave per pyramid level; single-scale -> one wave per
 // chain pass.  No early exit: both candidate costs are needed in full when accepted.
 // ------------------------------------------------------------------------------------------------
-#ifndef CSPM_SWEEP_POLL_SLEEP
-#define CSPM_SWEEP_POLL_SLEEP 1  // s_sleep argument (x 64 cycles) between two polls of a predecessor's granules
-#endif
-#ifndef CSPM_SWEEP_PRIO
-#define CSPM_SWEEP_PRIO 3
-#endif
-#ifndef CSPM_SWEEP_WPL
-#define CSPM_SWEEP_WPL 1
-#endif
-constexpr int kSweepWpl = CSPM_SWEEP_WPL;  // waves per pyramid level in a cross-scale sweep workgroup
-constexpr int kSweepMaxWaves = CSPM_MAX_LEVELS * kSweepWpl > kMaxPasses ? CSPM_MAX_LEVELS * kSweepWpl : kMaxPasses;  // cross-scale: a wave per level (x kSweepWpl); single scale: a wave per chain pass
+// minimum waves per SIMD the register allocator leaves room for in the two persistent sweep kernels (2nd __launch_bounds__ argument).  A sweep workgroup
+// is five waves (one per pyramid level), which the dispatcher places 2+1+1+1 on the CU's four SIMDs -- and the next workgroup the same
+// way: TWO resident workgroups per CU need FOUR wave slots on the first SIMD, i.e. <= 128 VGPRs (measured in round 5: at 137-155 VGPRs
+// only one workgroup per CU is resident and a sweep takes 38 ms instead of 20; it is also why 3 or 4 workgroups per CU never differed
+// from 2: at 95 VGPRs = 5 slots per SIMD the third workgroup would need a sixth).
+constexpr int kSweepMinWaves = 4;   // (2nd __launch_bounds__ argument of k_spatial_sweep and k_spatial_flow; 5 lost, see k_spatial_flow)
+constexpr int kSweepPollSleep = 1;  // s_sleep argument (x 64 cycles) between two polls of a predecessor's granules (8 made no difference to a
+                                    // refinement running beside the sweep, profiles/r06_corun.txt)
+constexpr int kSweepPrio = 3;       // s_setprio of the sweep's waves (0 made no difference there either)
+// cross-scale: a wave per level (two waves per level lost twice); single scale: a wave per chain pass
+constexpr int kSweepMaxWaves = CSPM_MAX_LEVELS > kMaxPasses ? CSPM_MAX_LEVELS : kMaxPasses;
 
 // views into the dynamic LDS of a sweep launch: sized by the waves actually launched (sweep_shared_bytes), so that a second
 // kernel -- another stereo pair's refinement -- still finds LDS on the CU
@@ -557,10 +552,9 @@ __device__ __forceinline__ SweepShared sweep_shared(unsigned char *smem) {
 template <bool CS, int SRC>
 __device__ __forceinline__ ChainLevel sweep_level_setup(const Cost &cd, int v, int x, int y, int wave) {
   if (CS) {
-    const int level = wave / kSweepWpl;
     int cur_x = x, cur_y = y;
-    for (int s = 0; s < level; ++s) { cur_y /= 2; cur_x /= 2; }
-    return make_chain_level<SRC>(cd, level < cd.levels ? level : 0, v, cur_x, cur_y);
+    for (int s = 0; s < wave; ++s) { cur_y /= 2; cur_x /= 2; }
+    return make_chain_level<SRC>(cd, wave < cd.levels ? wave : 0, v, cur_x, cur_y);
   }
   return make_chain_level<SRC>(cd, 0, v, x, y);
 }
@@ -569,14 +563,12 @@ template <bool CS, int SRC>
 __device__ __forceinline__ void eval_pixel_pair(const Cost &cd, const Luts &lut, const SweepShared &sh, int v, int x, int y, const Cand &c0,
                                                 const Cand &c1, bool both, int wave, int lane, double &cost0, double &cost1, const ChainLevel &A) {
   if (CS) {
-    // kSweepWpl waves per pyramid level share its chain passes (a sweep pixel is latency-bound: its evaluation is on the
-    // critical path of the whole sweep).  Level of this wave: (cur_x, cur_y, cur_disp) after `level` halvings
-    // (pre_cs_pc.cc:139-140,183-185).
-    const int level = wave / kSweepWpl, part_of = wave - level * kSweepWpl;
+    // One wave per pyramid level.  Level of this wave: (cur_x, cur_y, cur_disp) after `level` halvings (pre_cs_pc.cc:139-140,183-185).
+    const int level = wave;
     double d0 = c0.a * (double)x + c0.b * (double)y + c0.c, d1 = c1.a * (double)x + c1.b * (double)y + c1.c;
     int cur_x = x, cur_y = y;
     for (int s = 0; s < level; ++s) { cur_y /= 2; cur_x /= 2; d0 /= 2.0; d1 /= 2.0; }
-    double *part0 = sh.m[level * kSweepWpl].part[0], *part1 = sh.m[level * kSweepWpl].part[1];  // the level's first wave's scratch serves all its waves
+    double *part0 = sh.m[level].part[0], *part1 = sh.m[level].part[1];
     if (level < cd.levels) {
       ChainPlane pl[2];
       plane_param(c0.nx, c0.ny, c0.nz, (double)cur_x, (double)cur_y, d0, pl[0].a, pl[0].b, pl[0].c);  // :144-149
@@ -586,36 +578,19 @@ __device__ __forceinline__ void eval_pixel_pair(const Cost &cd, const Luts &lut,
         pl[1].a = wave_uniform(pl[1].a); pl[1].b = wave_uniform(pl[1].b); pl[1].c = wave_uniform(pl[1].c);
         EVAL_STAMP(4);
         double *const parts[2] = {part0, part1};
-        chain_passes<SRC, 2, CSPM_SWEEP_PIPE != 0>(cd, A, lut, pl, lane, part_of, kSweepWpl, parts);
+        chain_passes<SRC, 2>(cd, A, lut, pl, lane, 0, 1, parts);
         EVAL_STAMP(5);
-        if (kSweepWpl == 1) {
-          wave_lds_fence();
-          const double s0 = finish_level(A, part0, lane);
-          const double s1 = finish_level(A, part1, lane);
-          if (lane == 0) { sh.lvl[0][level] = s0; sh.lvl[1][level] = s1; }
-        }
+        wave_lds_fence();
+        const double s0 = finish_level(A, part0, lane);
+        const double s1 = finish_level(A, part1, lane);
+        if (lane == 0) { sh.lvl[0][level] = s0; sh.lvl[1][level] = s1; }
       } else {
         const ChainPlane p1[1] = {pl[0]};
         double *const parts[1] = {part0};
-        chain_passes<SRC, 1, CSPM_SWEEP_PIPE != 0>(cd, A, lut, p1, lane, part_of, kSweepWpl, parts);
-        if (kSweepWpl == 1) {
-          wave_lds_fence();
-          const double s0 = finish_level(A, part0, lane);
-          if (lane == 0) { sh.lvl[0][level] = s0; sh.lvl[1][level] = s0; }
-        }
-      }
-    }
-    if (kSweepWpl > 1) {
-      __syncthreads();  // the chain sums of every level are complete
-      if (level < cd.levels) {
-        // candidate 0 is finished by the level's first wave, candidate 1 by its second
-        if (part_of == 0) {
-          const double s0 = finish_level(A, part0, lane);
-          if (lane == 0) { sh.lvl[0][level] = s0; if (!both) sh.lvl[1][level] = s0; }
-        } else if (part_of == 1 && both) {
-          const double s1 = finish_level(A, part1, lane);
-          if (lane == 0) sh.lvl[1][level] = s1;
-        }
+        chain_passes<SRC, 1>(cd, A, lut, p1, lane, 0, 1, parts);
+        wave_lds_fence();
+        const double s0 = finish_level(A, part0, lane);
+        if (lane == 0) { sh.lvl[0][level] = s0; sh.lvl[1][level] = s0; }
       }
     }
     // FOLDED last level (round 6, CSPM_OPT_SWEEP_FOLD): a workgroup launched with ONE WAVE FEWER than the cost has levels -- four waves,
@@ -626,7 +601,7 @@ __device__ __forceinline__ void eval_pixel_pair(const Cost &cd, const Luts &lut,
     // pair's refinement (168 VGPRs) where three run on an empty CU; two four-wave sweep workgroups leave room for TWO
     // (profiles/r06_corun.txt: the refinement runs at 36 % of its speed beside a sweep, the sweep is not slowed at all).
     const int nw = (int)(blockDim.x >> 6);
-    if (kSweepWpl == 1 && cd.levels == nw + 1) {
+    if (cd.levels == nw + 1) {
       const int last = cd.levels - 1;
       double *fold0 = sh.m[nw].part[0], *fold1 = sh.m[nw].part[1];
       ChainLevel B = A;
@@ -642,11 +617,11 @@ __device__ __forceinline__ void eval_pixel_pair(const Cost &cd, const Luts &lut,
           plane_param(c1.nx, c1.ny, c1.nz, (double)lx, (double)ly, e1, pl[1].a, pl[1].b, pl[1].c);
           pl[1].a = wave_uniform(pl[1].a); pl[1].b = wave_uniform(pl[1].b); pl[1].c = wave_uniform(pl[1].c);
           double *const parts[2] = {fold0, fold1};
-          chain_passes<SRC, 2, CSPM_SWEEP_PIPE != 0>(cd, B, lut, pl, lane, wave - 1, nw - 1, parts);
+          chain_passes<SRC, 2>(cd, B, lut, pl, lane, wave - 1, nw - 1, parts);
         } else {
           const ChainPlane p1[1] = {pl[0]};
           double *const parts[1] = {fold0};
-          chain_passes<SRC, 1, CSPM_SWEEP_PIPE != 0>(cd, B, lut, p1, lane, wave - 1, nw - 1, parts);
+          chain_passes<SRC, 1>(cd, B, lut, p1, lane, wave - 1, nw - 1, parts);
         }
       }
       __syncthreads();  // the folded level's chain sums are complete
@@ -672,11 +647,11 @@ __device__ __forceinline__ void eval_pixel_pair(const Cost &cd, const Luts &lut,
     const ChainPlane pl[2] = {{wave_uniform(c0.a), wave_uniform(c0.b), wave_uniform(c0.c)}, {wave_uniform(c1.a), wave_uniform(c1.b), wave_uniform(c1.c)}};
     double *const parts[2] = {sh.m[0].part[0], sh.m[0].part[1]};  // the chain sums of all waves meet in wave 0's scratch
     if (both) {
-      chain_passes<SRC, 2, CSPM_SWEEP_PIPE != 0>(cd, A, lut, pl, lane, wave, nw, parts);
+      chain_passes<SRC, 2>(cd, A, lut, pl, lane, wave, nw, parts);
     } else {
       const ChainPlane p1[1] = {pl[0]};
       double *const parts1[1] = {parts[0]};
-      chain_passes<SRC, 1, CSPM_SWEEP_PIPE != 0>(cd, A, lut, p1, lane, wave, nw, parts1);
+      chain_passes<SRC, 1>(cd, A, lut, p1, lane, wave, nw, parts1);
     }
     __syncthreads();
     cost0 = cost1 = 0.0;
@@ -784,7 +759,7 @@ __device__ __forceinline__ bool wait_granules(const unsigned long long *p, bool 
     if (need) g = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const bool ready = !need || (unsigned int)(g >> 32) == epoch;
     if (__builtin_amdgcn_ballot_w64(!ready) == 0ull) return true;
-    __builtin_amdgcn_s_sleep(CSPM_SWEEP_POLL_SLEEP);
+    __builtin_amdgcn_s_sleep(kSweepPollSleep);
     if ((spins & 255u) == 0u) {
       if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return false;
       if (wall_clock64() - t0 > timeout_ticks) {  // CSPM_OPT_SWEEP_TIMEOUT_MS, default 3 s
@@ -796,18 +771,16 @@ __device__ __forceinline__ bool wait_granules(const unsigned long long *p, bool 
 }
 
 template <bool CS, int SRC>
-__global__ __launch_bounds__(kSweepMaxWaves *kWave, CSPM_SWEEP_MINW) void k_spatial_sweep(Cost cd, Pm pm, Sweep sw, int inc) {
+__global__ __launch_bounds__(kSweepMaxWaves *kWave, kSweepMinWaves) void k_spatial_sweep(Cost cd, Pm pm, Sweep sw, int inc) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const SweepShared sh = sweep_shared(smem);
   __shared__ double s_plane[2][6];
   __shared__ unsigned int s_item;
   __shared__ int s_ok;
   const Luts lut = load_luts(cd, sh.lut);
-#if CSPM_SWEEP_PRIO
   // The sweep is a chain of 1 616 dependent pixel evaluations with few waves: when it shares SIMDs with the throughput kernels
   // of other pairs in flight, its instructions go first.
-  __builtin_amdgcn_s_setprio(CSPM_SWEEP_PRIO);
-#endif
+  __builtin_amdgcn_s_setprio(kSweepPrio);
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = threadIdx.x & 63;
   const int ndiag = pm.W + pm.H - 1;
@@ -986,22 +959,17 @@ __device__ __forceinline__ int flow_pop(const Sweep &sw) {
 #endif
 
 // Residency (tools/ubench/residency.hip): five-wave workgroups leave one workgroup's worth of wave slots unused -- two are resident per CU
-// at 97-128 VGPRs, three at <= 96.  Measured with this kernel capped at 96 (CSPM_FLOW_MINW = 5): the compiler's code under that cap
+// at 97-128 VGPRs, three at <= 96.  Measured with this kernel capped at 96 (five waves per SIMD in its launch bounds): the compiler's code under that cap
 // evaluates a pixel in 9.3 us instead of 5.4 even on an empty GPU, and three workgroups that all COMPUTE oversubscribe the CU (23 us per
-// pixel, 52 ms per sweep).  So: the cap of the ordered sweep, two workgroups per CU.
-#ifndef CSPM_FLOW_MINW
-#define CSPM_FLOW_MINW CSPM_SWEEP_MINW
-#endif
+// pixel, 52 ms per sweep).  So: the cap of the ordered sweep (kSweepMinWaves), two workgroups per CU.
 template <bool CS, int SRC>
-__global__ __launch_bounds__(kSweepMaxWaves *kWave, CSPM_FLOW_MINW) void k_spatial_flow(Cost cd, Pm pm, Sweep sw, int inc) {
+__global__ __launch_bounds__(kSweepMaxWaves *kWave, kSweepMinWaves) void k_spatial_flow(Cost cd, Pm pm, Sweep sw, int inc) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const SweepShared sh = sweep_shared(smem);
   __shared__ double s_plane[2][6];  // [0] the x-predecessor's final plane, [1] the y-predecessor's
   __shared__ int s_item, s_from, s_ok;
   const Luts lut = load_luts(cd, sh.lut);
-#if CSPM_SWEEP_PRIO
-  __builtin_amdgcn_s_setprio(CSPM_SWEEP_PRIO);
-#endif
+  __builtin_amdgcn_s_setprio(kSweepPrio);
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int lane = threadIdx.x & 63;
   const unsigned int npix = (unsigned int)pm.W * (unsigned int)pm.H;

@@ -18,15 +18,6 @@
 #pragma once
 #include "cspm_device.h"
 
-// minimum waves per SIMD the register allocator leaves room for in the sweep kernel (2nd __launch_bounds__ argument).  A sweep workgroup
-// is five waves (one per pyramid level), which the dispatcher places 2+1+1+1 on the CU's four SIMDs -- and the next workgroup the same
-// way: TWO resident workgroups per CU need FOUR wave slots on the first SIMD, i.e. <= 128 VGPRs (measured in round 5: at 137-155 VGPRs
-// only one workgroup per CU is resident and a sweep takes 38 ms instead of 20; it is also why 3 or 4 workgroups per CU never differed
-// from 2: at 95 VGPRs = 5 slots per SIMD the third workgroup would need a sixth).
-#ifndef CSPM_SWEEP_MINW
-#define CSPM_SWEEP_MINW 4
-#endif
-
 #include "cspm_chain.h"
 #include "cspm_rows.h"
 #include "cspm_tap.h"

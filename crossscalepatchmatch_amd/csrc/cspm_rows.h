@@ -28,68 +28,12 @@
 
 namespace cspm {
 
-#ifndef CSPM_ROW_WAVES
-#define CSPM_ROW_WAVES 4
-#endif
-constexpr int kRowWaves = CSPM_ROW_WAVES;     // waves per workgroup (they share the two lookup tables)
-#ifndef CSPM_ROW_MINW
-#define CSPM_ROW_MINW 3                       // waves per SIMD the register allocator must leave room for: 168 VGPRs (157 used, no
-                                              // scratch).  Measured in round 2 (C3, ms per k_refine launch): 2 waves 66.1, 3 waves
-                                              // 55.7, 4 waves 58.3 (128 VGPRs), 5 waves 64.3, 6 waves 67.2; round 3: 4 waves per SIMD
-                                              // (one 16-wave workgroup per CU, 128 VGPRs, 104 B scratch) 45.1 against 38.5;
-                                              // workgroups of 2/3/4 waves at 3 per SIMD are equal, larger ones slower
-#endif
-#ifndef CSPM_VIEW_MINW
-#define CSPM_VIEW_MINW CSPM_ROW_MINW
-#endif
-#ifndef CSPM_INIT_MINW
-#define CSPM_INIT_MINW CSPM_ROW_MINW
-#endif
-#ifndef CSPM_ROW_EXIT
-#define CSPM_ROW_EXIT 1   // early exit tested after every window row (0: at level ends only)
-#endif
-#ifndef CSPM_CELL_BUMP
-#define CSPM_CELL_BUMP 1   // table rows with an immediate pitch: likewise (cell_row_taps)
-#endif
-#ifndef CSPM_ROW_BUMP
-#define CSPM_ROW_BUMP 1    // general rows: the groups of seven step their LDS bases by hand (row_taps)
-#endif
-#ifndef CSPM_EDGE_ALLV
-#define CSPM_EDGE_ALLV 1   // waves at the image's left / right border: all-valid taps (with the column mask) on the rows that allow it
-#endif
-#ifndef CSPM_TABLE_DMA
-#define CSPM_TABLE_DMA 1   // cell tables filled by LDS-DMA from the level's device-cell volume when the cost object carries one (0: always computed)
-#endif
-#ifndef CSPM_TABLE_CLUSTERS
-#define CSPM_TABLE_CLUSTERS 1     // ... and with the rows of TWO disparity clusters when a wave's lanes lie on two surfaces
-#endif
-#ifndef CSPM_TABLE_DMA_SINGLE
-#define CSPM_TABLE_DMA_SINGLE 1   // ... also with ONE table buffer where two do not fit (0: compute the table then)
-#endif
-#ifndef CSPM_PREFER_WTAB
-#define CSPM_PREFER_WTAB 0   // DMA-filled range tables: 1 = the per-row guide-weight table wherever it fits; 0 = per-tap weights for waves of <= CSPM_WTAB_MAXC centres whose window is inside the image (building the table costs more than it saves once the cells are not computed: measured)
-#endif
-#ifndef CSPM_WTAB_MAXC
-#define CSPM_WTAB_MAXC 64
-#endif
-#ifndef CSPM_CELL_SUB
-#define CSPM_CELL_SUB 4  // table rows: taps of a group of seven whose LDS round trips are overlapped (4 + 3)
-#endif
-#ifndef CSPM_OWN_SINGLE
-#define CSPM_OWN_SINGLE 1  // own-view gradient reads of a tap batch as volatile single reads off one base (0: through laundered copies of the base)
-#endif
-#ifndef CSPM_CELL_PITCH_IMM
-#define CSPM_CELL_PITCH_IMM 1  // DMA-filled tables: the usual pitches as instruction immediates (cell_row_taps); 0: always CellRow::stride
-#endif
-#ifndef CSPM_CELL_PAD
-#define CSPM_CELL_PAD 1    // cell tables with a pitch of a multiple of 256 bytes when they fit (no bank conflicts between table rows)
-#endif
-#ifndef CSPM_RANGE_MODE
-#define CSPM_RANGE_MODE 1  // cell mode with range-restricted tables on the levels whose full tables do not fit (0: general taps there)
-#endif
-#ifndef CSPM_CELL_MODE
-#define CSPM_CELL_MODE 1  // coarse levels of the fused GRD cost: per-row cell and weight tables (cell mode below); 0 = always the general taps
-#endif
+constexpr int kRowWaves = 4;     // waves per workgroup (they share the two lookup tables); 2 and 3 measured equal, larger workgroups lost
+constexpr int kRowMinWaves = 3;  // waves per SIMD the register allocator must leave room for (168 VGPRs), in every kernel of this file; 2, 4, 5 and
+                                 // 6 lost, and so did bounds of their own for the init and view kernels (DESIGN.md section 5.6 has every figure)
+constexpr int kRowSub = 2;       // general rows: taps of a group of seven whose memory round trips are overlapped (register pressure vs latency
+                                 // hiding; the other splits lost)
+constexpr int kCellSub = 4;      // table rows: taps of a group of seven whose LDS round trips are overlapped (4 + 3; the other splits lost)
 constexpr int kRowBlock = kRowWaves * kWave;
 #ifdef CSPM_ROW_STATS
 // debug (tools/row_stats.py): per phase slot (0 init, 1 view, 2+step refinement), pyramid level and bucket, the number of staged
@@ -216,12 +160,8 @@ __device__ __forceinline__ uint4 rd_own(int adr_g, int adr_p, int j) {
     const uint32_t pix = lds_ld<uint32_t>(adr_p + j * 4);
     uint2 g{0u, 0u};
     if constexpr (SRC == kSrcGrd || SRC == kSrcImg) {
-#if CSPM_OWN_SINGLE
       const u32x2 v = *(volatile __attribute__((address_space(3))) const u32x2 *)(uintptr_t)(unsigned)(adr_g + j * 8);  // never ds_read2_b64 (lds_ld_single)
       g = uint2{v[0], v[1]};
-#else
-      g = lds_ld<uint2>(adr_g + j * 8);
-#endif
     }
     return uint4{g.x, g.y, pix, 0u};
   }
@@ -289,7 +229,8 @@ struct RowSrc {
   // staged: LDS addresses (lds_addr) of window column 0 of the lane: other strip at f = 0 (biased one slot down for the left
   // view, see rd_cells); own strip gradient / colour arrays
   int adr_o, adr_g, adr_p;
-  int adr_g2, adr_g3;  // == adr_g, but opaque to the compiler (see tap_batch stage 1)
+  int adr_g2, adr_g3;  // == adr_g, laundered; UNREAD since round 4 (tap_batch reads adr_g only).  Still here because level_rows' two asm
+                       // statements and the per-row stepping are real instructions: removing them changes every row kernel's code
   int adr_og, adr_gg;  // kSrcCenGrd: the gradient arrays of the two strips, addressed like adr_o / adr_g at half the stride
   // unstaged: image rows in global memory and the byte offset of the lane's window column 0
   const char *own_row, *oth_row;
@@ -306,13 +247,10 @@ struct RowSrc {
 //   VIEW   : 0 = left view (other view read at x-f, x-f-1), 1 = right view (x+f, x+f+1)
 //   EDGE   : some lane's window leaves the image in x -> per-tap mask (e_rel = g0 - e_lo per lane, e_span)
 //   STAGED : operands come from the two LDS strips, else from global memory
-#ifndef CSPM_ROW_SUB
-#define CSPM_ROW_SUB 2  // taps whose memory round trips are overlapped (sub-batch of a group of 7): register pressure vs latency hiding
-#endif
 //   ALLV   : every tap of this window row is known to take the interpolation branch in every lane (level_rows decides that per
 //            row from the two end columns): no clamp, no validity test, no select -- 4 instructions per tap less
 template <int SRC, int VIEW, bool EDGE, bool STAGED, bool ALLV, int J0, int J1>
-__device__ __forceinline__ void tap_batch(const RowLevel &A, const Luts &lut, const RowSrc &R, int g0, int adr_o, int adr_g, int adr_g2, int adr_g3, int adr_p, int off_g,
+__device__ __forceinline__ void tap_batch(const RowLevel &A, const Luts &lut, const RowSrc &R, int g0, int adr_o, int adr_g, int adr_p, int off_g,
                                           uint32_t Ip, double pa, double Gg, double qxg_d, int e_rel, int e_span, int qy, int cx_lane,
                                           double S[kRowMod]) {
   constexpr int E = elem_size<SRC>();
@@ -327,8 +265,8 @@ __device__ __forceinline__ void tap_batch(const RowLevel &A, const Luts &lut, co
   bool valid[N], in_img[N];
   [[maybe_unused]] double Pg[N], og0[N], og1[N];  // kSrcCenGrd: the gradients of P, o0, o1 (8-byte reads beside the 16-byte ones)
   // stage 1: own elements.  (Two 8-byte reads off the same register would be merged into one ds_read2_b64, which runs at half the
-  // rate of ds_read_b64: the gradient reads are volatile -- until round 4 they went through laundered copies of the base.)
-  if constexpr (STAGED && CSPM_OWN_SINGLE && (SRC == kSrcGrd || SRC == kSrcImg)) {
+  // rate of ds_read_b64: the gradient reads are volatile single reads off one base -- until round 4 they went through laundered copies of the base, which lost.)
+  if constexpr (STAGED && (SRC == kSrcGrd || SRC == kSrcImg)) {
     // colours first (they may pair up into ds_read2_b32, same rate), then the gradients as single 8-byte reads
 #pragma unroll
     for (int k = 0; k < N; ++k) P[k].z = lds_ld<uint32_t>(adr_p + (J0 + k) * 4);
@@ -340,7 +278,7 @@ __device__ __forceinline__ void tap_batch(const RowLevel &A, const Luts &lut, co
   } else {
 #pragma unroll
     for (int k = 0; k < N; ++k)
-      P[k] = STAGED ? rd_own<SRC>(CSPM_OWN_SINGLE || k == 0 ? adr_g : k == 1 ? adr_g2 : adr_g3, adr_p, J0 + k) : ld_elem<SRC>(R.own_row, off_g + (J0 + k) * E);
+      P[k] = STAGED ? rd_own<SRC>(adr_g, adr_p, J0 + k) : ld_elem<SRC>(R.own_row, off_g + (J0 + k) * E);
     if constexpr (SRC == kSrcCenGrd) {
 #pragma unroll
       for (int k = 0; k < N; ++k) Pg[k] = STAGED ? lds_ld_single(R.adr_gg + (g0 + J0 + k) * 8) : ld_grad(R.own_grow, (off_g + (J0 + k) * E) >> 1);
@@ -433,20 +371,19 @@ template <int SRC, int VIEW, bool EDGE, bool STAGED, bool ALLV, int CNT>
 __device__ __forceinline__ void tap_group(const RowLevel &A, const Luts &lut, const RowSrc &R, int g0, int ga, uint32_t Ip, double pa, double rowterm,
                                           double &qxg_d, int e_rel, int e_span, int qy, int cx_lane, double S[kRowMod]) {
   constexpr int E = elem_size<SRC>();
-  constexpr int SUB = CSPM_ROW_SUB;
+  constexpr int SUB = kRowSub;
   const double Gg = group_disp(pa, qxg_d, rowterm);  // the group's disparity base (device order, cspm_tap.h)
   const double qxg = qxg_d;
   qxg_d += (double)kRowMod;                          // exact: small integers
   // ga: the group's first window column as far as the addresses go (g0, or 0 when row_taps steps the bases itself)
   const int adr_o = R.adr_o + ga * 16, adr_g = R.adr_g + ga * (census_elem<SRC>() ? 16 : 8), adr_p = R.adr_p + ga * 4, off_g = R.lane_off + ga * E;
-  const int adr_g2 = R.adr_g2 + ga * (census_elem<SRC>() ? 16 : 8), adr_g3 = R.adr_g3 + ga * (census_elem<SRC>() ? 16 : 8);
-  tap_batch<SRC, VIEW, EDGE, STAGED, ALLV, 0, (CNT < SUB ? CNT : SUB)>(A, lut, R, g0, adr_o, adr_g, adr_g2, adr_g3, adr_p, off_g, Ip, pa, Gg, qxg, e_rel, e_span, qy,
+  tap_batch<SRC, VIEW, EDGE, STAGED, ALLV, 0, (CNT < SUB ? CNT : SUB)>(A, lut, R, g0, adr_o, adr_g, adr_p, off_g, Ip, pa, Gg, qxg, e_rel, e_span, qy,
                                                                   cx_lane, S);
   if constexpr (CNT > SUB)
-    tap_batch<SRC, VIEW, EDGE, STAGED, ALLV, SUB, (CNT < 2 * SUB ? CNT : 2 * SUB)>(A, lut, R, g0, adr_o, adr_g, adr_g2, adr_g3, adr_p, off_g, Ip, pa, Gg, qxg, e_rel,
+    tap_batch<SRC, VIEW, EDGE, STAGED, ALLV, SUB, (CNT < 2 * SUB ? CNT : 2 * SUB)>(A, lut, R, g0, adr_o, adr_g, adr_p, off_g, Ip, pa, Gg, qxg, e_rel,
                                                                               e_span, qy, cx_lane, S);
   if constexpr (CNT > 2 * SUB)
-    tap_batch<SRC, VIEW, EDGE, STAGED, ALLV, 2 * SUB, CNT>(A, lut, R, g0, adr_o, adr_g, adr_g2, adr_g3, adr_p, off_g, Ip, pa, Gg, qxg, e_rel, e_span, qy, cx_lane, S);
+    tap_batch<SRC, VIEW, EDGE, STAGED, ALLV, 2 * SUB, CNT>(A, lut, R, g0, adr_o, adr_g, adr_p, off_g, Ip, pa, Gg, qxg, e_rel, e_span, qy, cx_lane, S);
 }
 
 // One window row of one level for all 64 lanes -> row total R (ROWTREE7: seven interleaved partial sums, combined left to right)
@@ -459,9 +396,9 @@ __device__ __forceinline__ double row_taps(const RowLevel &A, const Luts &lut, c
   double qx_d = qx0_d;
   const int full = A.n / kRowMod * kRowMod;
   int g0 = 0;
-  if constexpr (CSPM_ROW_BUMP && STAGED && SRC == kSrcGrd) {
+  if constexpr (STAGED && SRC == kSrcGrd) {
     // The three LDS bases are stepped by hand and laundered: left to itself the loop optimiser keeps bases WITHOUT the row's buffer offset
-    // and re-adds it in every group (seven address additions per group instead of three).
+    // and re-adds it in every group (seven address additions per group instead of three; the plain loop lost).
     RowSrc Rg = R;
     for (; g0 < full; g0 += kRowMod) {
       tap_group<SRC, VIEW, EDGE, STAGED, ALLV, kRowMod>(A, lut, Rg, g0, 0, Ip, pa, rowterm, qx_d, g0 - e_lo, e_span, qy, cx_lane, S);
@@ -557,11 +494,11 @@ __device__ __forceinline__ void cell_group(const RowLevel &A, const Luts &lut, c
   const double Gg = group_disp(pa, qxg_d, rowterm);
   qxg_d += (double)kRowMod;
   const int g8 = g0 * 8, adr_c = C.adr_c + g8, adr_c1 = C.adr_c + C.stride + g8, adr_w = C.adr_w + g8, adr_p = C.adr_p + g0 * 4;
-  constexpr int SUB = CSPM_CELL_SUB;
+  constexpr int SUB = kCellSub;
   cell_batch<ALLV, WTAB, 0, (CNT < SUB ? CNT : SUB), STRIDE>(A, lut, C, adr_c, adr_c1, adr_w, adr_p, g8, pa, Gg, S);
   if constexpr (CNT > SUB) cell_batch<ALLV, WTAB, SUB, CNT, STRIDE>(A, lut, C, adr_c, adr_c1, adr_w, adr_p, g8, pa, Gg, S);
 }
-// PITCH_IMM: the pitches level_rows chooses for a 35 x 35 window on 64-pixel segments (level 0 padded / unpadded, level 1 padded /
+// PITCH_IMM (DMA-filled tables; CellRow::stride everywhere lost): the pitches level_rows chooses for a 35 x 35 window on 64-pixel segments (level 0 padded / unpadded, level 1 padded /
 // unpadded, levels 2, 3, 4) run the groups of seven with the pitch as an immediate; anything else (other window sizes, ragged
 // segments, computed tables) with CellRow::stride.
 template <bool ALLV, bool WTAB, bool PITCH_IMM = false>
@@ -573,11 +510,11 @@ __device__ __forceinline__ double cell_row_taps(const RowLevel &A, const Luts &l
   const int full = A.n / kRowMod * kRowMod;
   int g0 = 0;
   bool done = false;
-  if constexpr (PITCH_IMM && CSPM_CELL_PITCH_IMM) {
+  if constexpr (PITCH_IMM) {
     done = true;
     switch (C.stride) {
-#if CSPM_CELL_BUMP
-      // (the table and weight / colour bases stepped by hand and laundered, as in row_taps: two address additions per group instead of four)
+      // (the table and weight / colour bases stepped by hand and laundered, as in row_taps: two address additions per group instead of four;
+      // the plain loop over g0 lost)
 #define CSPM_PITCH(P)                                                                    \
   case P * 8: {                                                                          \
     CellRow Cg = C;                                                                      \
@@ -588,9 +525,6 @@ __device__ __forceinline__ double cell_row_taps(const RowLevel &A, const Luts &l
       else { Cg.adr_p += kRowMod * 4; asm("" : "+v"(Cg.adr_c), "+v"(Cg.adr_p)); }       \
     }                                                                                    \
   } break;
-#else
-#define CSPM_PITCH(P) case P * 8: for (; g0 < full; g0 += kRowMod) cell_group<ALLV, WTAB, kRowMod, P * 8>(A, lut, C, g0, pa, rowterm, qx_d, S); break;
-#endif
       CSPM_PITCH(128) CSPM_PITCH(100) CSPM_PITCH(80) CSPM_PITCH(68) CSPM_PITCH(52) CSPM_PITCH(44) CSPM_PITCH(40)
 #undef CSPM_PITCH
       default: done = false; break;
@@ -640,12 +574,9 @@ __device__ __forceinline__ RowCtx make_row_ctx(unsigned char *smem, int y, int c
 // One level of eval_rows for a wave: centres cx (per lane) in row cy (uniform), plane (a, b, c per lane) -> level sum.
 // (Outlining it -- noinline, to make the caller park its long-lived state once per level -- was measured: 2.8x slower,
 // the LDS pointers degrade to flat pointers and the Cost block to scratch memory across the call.)
-#ifndef CSPM_LEVEL_INLINE
-#define CSPM_LEVEL_INLINE __forceinline__
-#endif
 template <int SRC, int VIEW>
-__device__ CSPM_LEVEL_INLINE double level_rows(const Cost &cd, const Luts &lut, const RowCtx &ctx, int s, int cx, int cy, double a, double b,
-                                             double c, bool exit_on, double need, bool dead_in) {
+__device__ __forceinline__ double level_rows(const Cost &cd, const Luts &lut, const RowCtx &ctx, int s, int cx, int cy, double a, double b,
+                                           double c, bool exit_on, double need, bool dead_in) {
   constexpr int E = elem_size<SRC>();
   const int lane = ctx.lane;
 #ifdef CSPM_ROW_STATS
@@ -708,16 +639,12 @@ __device__ CSPM_LEVEL_INLINE double level_rows(const Cost &cd, const Luts &lut, 
   // Row-granular early exit (result-preserving, only with the early-exit licence): `need` is what the level sum must reach for
   // the lane's total to be >= its threshold, with a 2^-40 margin over every rounding on the way (eval_rows_view).  Row totals
   // are >= 0, so a running sum of completed rows that has reached it proves the rejection; once that holds in all 64 lanes the
-  // wave abandons the level -- a rejected candidate's cost is never stored.  Returns +inf then.
+  // wave abandons the level -- a rejected candidate's cost is never stored.  Returns +inf then.  (The test at level ends only lost.)
   double partial = 0.0;
   auto all_rejected = [&](double Rsum) -> bool {
-#if CSPM_ROW_EXIT
     if (!exit_on) return false;
     partial = partial + Rsum;
     return __builtin_amdgcn_ballot_w64(!(dead_in | (partial >= need))) == 0ull;
-#else
-    return false;
-#endif
   };
   if constexpr (SRC == kSrcGrd) {
     // Cell mode: the wave builds per window row a table of the cells it can touch (and, where it fits, of the guide weights) in
@@ -727,7 +654,8 @@ __device__ CSPM_LEVEL_INLINE double level_rows(const Cost &cd, const Luts &lut, 
     //           [1 + 2^-20, D - 2^-20]: the disparity is linear over the window up to two roundings of < 2^-43 each) and the wave's
     //           integer disparities span few values [f_lo, f_hi]: a table of just those ND = f_hi - f_lo + 1 disparities, strips
     //           of just the columns they need, the weight table when it still fits and per-tap weights when not.
-    // Same grd_cell(), same terms, same order: identical results whichever path a level takes.
+    // Same grd_cell(), same terms, same order: identical results whichever path a level takes.  (General taps on the levels that can
+    // take either kind of table lost, and so did tables that are always computed where the cost object carries the level's cell volume.)
     const int ncent = cmax - cmin + 1, NQ = o_len;
     const int lds_room = wave_lds_bytes(ctx.cap, ctx.ocap) - 64;
     const int own_bytes = (NQ * 8 + 15) / 16 * 16 + (NQ * 4 + 15) / 16 * 16, wtab_bytes = ncent * A.n * 8 + ncent * 4;
@@ -737,7 +665,7 @@ __device__ CSPM_LEVEL_INLINE double level_rows(const Cost &cd, const Luts &lut, 
     // disparities (unpadded -- 98 entries, two bank pairs further per row -- a lane one disparity up collides with the lane two
     // columns on).  With ~32 centres (level 1) two lanes share each column and may differ in disparity: the rows must NOT line up;
     // a pitch = 16 mod 32 gives the 16 columns of a half-wave two disjoint halves of the banks for rows r and r+1.  Coarser levels
-    // (few columns per half-wave) are conflict-free as they are.  Padded when the LDS has the room.
+    // (few columns per half-wave) are conflict-free as they are.  Padded when the LDS has the room (unpadded tables everywhere lost).
     const int NQP = ncent >= 48 ? (NQ + 31) / 32 * 32 : ncent >= 24 ? (NQ + 15) / 32 * 32 + 16 : NQ;
     int d_base = 1, ND = D, pitch = NQ;
     bool cells_on = false, wtab = true, allv_level = false, tdma = false;
@@ -746,15 +674,15 @@ __device__ CSPM_LEVEL_INLINE double level_rows(const Cost &cd, const Luts &lut, 
     bool lane_b = false;
     int tbuf = 2;  // DMA-filled tables: 2 = the next row's table lands while this row's taps run; 1 = it is fetched after them
     const int p2 = (NQ * 4 + 15) / 16 * 16;  // a run of own colours, in 16-byte DMA pieces
-    if (CSPM_CELL_MODE && staged && D >= 2) {
+    if (staged && D >= 2) {
       const bool full_fits = (NQ + D) * 16 + own_bytes + NQ * D * 8 + wtab_bytes <= lds_room;
       // DMA-filled tables (Level::cvol): the device cells of this level are in memory, a table row is a run of a volume row
-      const bool have_cvol = CSPM_TABLE_DMA && L.cvol[VIEW] != nullptr;
+      const bool have_cvol = L.cvol[VIEW] != nullptr;
       // the range test, where it can matter: the full table does not fit, or the tables could be DMA-filled (two of them must fit)
       bool range_ok = false;
       int f_lo = 1, f_hi = 1;
       int fl_lane = 1, fh_lane = 1;  // the lane's own interval of integer disparities (valid when range_ok)
-      if ((!full_fits || have_cvol) && CSPM_RANGE_MODE && D < 512 && dy_lo <= dy_hi) {
+      if ((!full_fits || have_cvol) && D < 512 && dy_lo <= dy_hi) {
         const int jl = (A.n - 1) % kRowMod;
         const double rt0 = b * (double)(cy - A.half + dy_lo) + c, rt1 = b * (double)(cy - A.half + dy_hi) + c;  // q_disp_y of the first / last row
         const double q00 = tap_disp(a, 0.0, group_disp(a, qx0_d, rt0)), q01 = tap_disp(a, (double)jl, group_disp(a, qx0_d + (double)(A.n - 1 - jl), rt0));
@@ -777,30 +705,34 @@ __device__ CSPM_LEVEL_INLINE double level_rows(const Cost &cd, const Luts &lut, 
         // that for 64 slabs, and a small window's table may hold more)
         auto span32 = [&](int n_) { return (unsigned long long)n_ * (unsigned long long)L.H * (unsigned long long)L.cvW * 8ull < (1ull << 32); };
         auto fits = [&](int nb, int n_, int pit, bool wt) { return nb * n_ * pit * 8 + 2 * p2 + (wt ? wtab_bytes : 0) <= lds_room && n_ * (pit / 2) <= 12 * kWave && span32(n_); };
-        // in order of preference: two tables before one (with one, the fetch of the next row's table waits for this row's taps: its
-        // latency is hidden by the other waves of the SIMD only), padded pitch before unpadded, the weight table before per-tap weights
+        // In order of preference: two tables before one (with one, the fetch of the next row's table waits for this row's taps: its
+        // latency is hidden by the other waves of the SIMD only; computing the table instead lost).  Range tables: a wave of at most
+        // kWave centres whose window is inside the image takes per-tap weights, padded pitch before unpadded (building the weight table
+        // costs more than it saves once the cells are not computed: the weight table wherever it fits lost);
+        // every other wave padded pitch before unpadded (a pitch of a multiple of 256 bytes: no bank conflicts between table rows)
+        // and, at each pitch, the weight table before per-tap weights.  Full tables: the weight table always, padded before unpadded.
+        // (Per-tap weights need the window inside the image; ncent <= kWave is not shown for every caller's centres, so it is tested.)
         for (int nb = 2; nb >= 1 && !tdma; --nb) {
           if (range_ok) {
-            if (!CSPM_PREFER_WTAB && CSPM_CELL_PAD && !edge && ncent <= CSPM_WTAB_MAXC && fits(nb, nd, NQD, false)) { tdma = true; pitch = NQD; wtab = false; }
-            else if (!CSPM_PREFER_WTAB && !edge && ncent <= CSPM_WTAB_MAXC && fits(nb, nd, NQE, false)) { tdma = true; pitch = NQE; wtab = false; }
-            else if (CSPM_CELL_PAD && fits(nb, nd, NQD, true)) { tdma = true; pitch = NQD; }
-            else if (CSPM_CELL_PAD && !edge && fits(nb, nd, NQD, false)) { tdma = true; pitch = NQD; wtab = false; }
+            if (!edge && ncent <= kWave && fits(nb, nd, NQD, false)) { tdma = true; pitch = NQD; wtab = false; }
+            else if (!edge && ncent <= kWave && fits(nb, nd, NQE, false)) { tdma = true; pitch = NQE; wtab = false; }
+            else if (fits(nb, nd, NQD, true)) { tdma = true; pitch = NQD; }
+            else if (!edge && fits(nb, nd, NQD, false)) { tdma = true; pitch = NQD; wtab = false; }
             else if (fits(nb, nd, NQE, true)) { tdma = true; pitch = NQE; }
             else if (!edge && fits(nb, nd, NQE, false)) { tdma = true; pitch = NQE; wtab = false; }
             if (tdma) { cells_on = true; d_base = f_lo; ND = nd; allv_level = true; tbuf = nb; }
           }
           if (!tdma && full_fits) {  // every disparity of a coarse level
-            if (CSPM_CELL_PAD && fits(nb, D, NQD, true)) { tdma = true; pitch = NQD; }
+            if (fits(nb, D, NQD, true)) { tdma = true; pitch = NQD; }
             else if (fits(nb, D, NQE, true)) { tdma = true; pitch = NQE; }
             if (tdma) { cells_on = true; tbuf = nb; }
           }
-          if (!CSPM_TABLE_DMA_SINGLE) break;
         }
         // Two surfaces in one wave (a depth discontinuity: 20-35 % of the level passes at levels 0-1 once the planes have settled):
         // the lanes' disparity intervals fall into two narrow clusters far apart.  Cut at the middle of the wave's span; when
         // no lane's interval straddles the cut, the table holds the rows of cluster A and then those of cluster B, and a lane
-        // addresses the rows of its own cluster.
-        if (CSPM_TABLE_CLUSTERS && !tdma && range_ok && nd > 2) {
+        // addresses the rows of its own cluster (without it these passes fall to computed tables or general taps: lost).
+        if (!tdma && range_ok && nd > 2) {
           const int cut = (f_lo + f_hi + 1) / 2;
           const bool in_a = fh_lane < cut, in_b = fl_lane >= cut;
           if (__builtin_amdgcn_ballot_w64(!(in_a | in_b)) == 0ull) {
@@ -810,13 +742,13 @@ __device__ CSPM_LEVEL_INLINE double level_rows(const Cost &cd, const Luts &lut, 
             const int na = a_hi - f_lo + 1, nb_ = f_hi - bl + 1, nt = na + nb_;
             const bool span_ok = span32(f_hi - f_lo + 1);  // 32-bit DMA offsets: cluster B's rows are addressed from cluster A's first slab
             if (nt < nd && span_ok) {
+              // in order of preference: two tables before one, padded pitch before unpadded, the weight table before per-tap weights
               for (int nb = 2; nb >= 1 && !tdma; --nb) {
-                if (CSPM_CELL_PAD && fits(nb, nt, NQD, true)) { tdma = true; pitch = NQD; }
-                else if (CSPM_CELL_PAD && !edge && fits(nb, nt, NQD, false)) { tdma = true; pitch = NQD; wtab = false; }
+                if (fits(nb, nt, NQD, true)) { tdma = true; pitch = NQD; }
+                else if (!edge && fits(nb, nt, NQD, false)) { tdma = true; pitch = NQD; wtab = false; }
                 else if (fits(nb, nt, NQE, true)) { tdma = true; pitch = NQE; }
                 else if (!edge && fits(nb, nt, NQE, false)) { tdma = true; pitch = NQE; wtab = false; }
                 if (tdma) { cells_on = true; d_base = f_lo; ND = nt; allv_level = true; tbuf = nb; nd_a = na; b_lo = bl; lane_b = in_b; }
-                if (!CSPM_TABLE_DMA_SINGLE) break;
               }
             }
           }
@@ -825,12 +757,12 @@ __device__ CSPM_LEVEL_INLINE double level_rows(const Cost &cd, const Luts &lut, 
       if (!tdma) {
         if (full_fits) {
           cells_on = true;
-          if (CSPM_CELL_PAD && (NQ + D) * 16 + own_bytes + NQP * D * 8 + wtab_bytes <= lds_room) pitch = NQP;
+          if ((NQ + D) * 16 + own_bytes + NQP * D * 8 + wtab_bytes <= lds_room) pitch = NQP;
         } else if (range_ok && (NQ + nd) <= kStripRegs * kWave) {
           const int strip_bytes = (NQ + nd) * 16 + own_bytes;
           // in order of preference: padded pitch with the weight table, padded without, unpadded with, unpadded without
-          if (CSPM_CELL_PAD && strip_bytes + NQP * nd * 8 + wtab_bytes <= lds_room) { cells_on = true; pitch = NQP; }
-          else if (CSPM_CELL_PAD && !edge && strip_bytes + p2 + NQP * nd * 8 <= lds_room) { cells_on = true; wtab = false; pitch = NQP; }
+          if (strip_bytes + NQP * nd * 8 + wtab_bytes <= lds_room) { cells_on = true; pitch = NQP; }
+          else if (!edge && strip_bytes + p2 + NQP * nd * 8 <= lds_room) { cells_on = true; wtab = false; pitch = NQP; }
           else if (strip_bytes + NQ * nd * 8 + wtab_bytes <= lds_room) { cells_on = true; }
           else if (!edge && strip_bytes + p2 + NQ * nd * 8 <= lds_room) { cells_on = true; wtab = false; }
           if (cells_on) { d_base = f_lo; ND = nd; allv_level = true; }
@@ -1138,8 +1070,9 @@ __device__ CSPM_LEVEL_INLINE double level_rows(const Cost &cd, const Luts &lut, 
           Rsum = allv ? row_taps<SRC, VIEW, false, true, true>(A, lut, Rr, Ip, a, rowterm, qx0_d, e_lo, e_span, qy, cx)
                       : row_taps<SRC, VIEW, false, true>(A, lut, Rr, Ip, a, rowterm, qx0_d, e_lo, e_span, qy, cx);
         } else {
-          Rsum = (CSPM_EDGE_ALLV && allv) ? row_taps<SRC, VIEW, true, true, true>(A, lut, Rr, Ip, a, rowterm, qx0_d, e_lo, e_span, qy, cx)
-                                          : row_taps<SRC, VIEW, true, true>(A, lut, Rr, Ip, a, rowterm, qx0_d, e_lo, e_span, qy, cx);
+          // waves at the image's left / right border take the all-valid taps too, with the column mask (general taps on every such row lost)
+          Rsum = allv ? row_taps<SRC, VIEW, true, true, true>(A, lut, Rr, Ip, a, rowterm, qx0_d, e_lo, e_span, qy, cx)
+                      : row_taps<SRC, VIEW, true, true>(A, lut, Rr, Ip, a, rowterm, qx0_d, e_lo, e_span, qy, cx);
         }
         tree.push(dy, Rsum);
 #ifdef CSPM_ROW_STATS
@@ -1356,11 +1289,8 @@ __device__ __forceinline__ double eval_rows(const Cost &cd, const Luts &lut, con
 //    image rows (both views stacked) are cut into blocks of kRowBand rows, XCD k works through blocks k, k+8, k+16, ... and a
 //    workgroup takes x-adjacent segments of one row: every XCD and every CU gets the same mix of image top, middle, bottom and
 //    border columns (border rows have clipped windows and are cheaper, border columns carry the column mask and are dearer;
-//    contiguous eighths of the image left half of the XCDs idle at the end -- measured, CSPM_ROW_BAND).
-#ifndef CSPM_ROW_BAND
-#define CSPM_ROW_BAND 4
-#endif
-constexpr int kRowBand = CSPM_ROW_BAND;
+//    contiguous eighths of the image left half of the XCDs idle at the end -- measured; other block heights than kRowBand lost).
+constexpr int kRowBand = 4;
 struct RowItem {
   int v, y, x0;
 };
@@ -1446,7 +1376,7 @@ __device__ __forceinline__ RowPlane init_plane(const Pm &pm, int v, int x, int y
 }
 
 template <bool CS, int SRC>
-__global__ __launch_bounds__(kRowBlock, CSPM_INIT_MINW) void k_init(Cost cd, Pm pm, RowQueue rq, int cap, int ocap) {
+__global__ __launch_bounds__(kRowBlock, kRowMinWaves) void k_init(Cost cd, Pm pm, RowQueue rq, int cap, int ocap) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   LutMem &s_lut = *reinterpret_cast<LutMem *>(smem);
   const Luts lut = load_luts(cd, s_lut);
@@ -1479,7 +1409,7 @@ __device__ __forceinline__ RowPlane stored_plane(const Pm &pm, int v, int x, int
 }
 
 template <bool CS, int SRC>
-__global__ __launch_bounds__(kRowBlock, CSPM_INIT_MINW) void k_rescore(Cost cd, Pm pm, RowQueue rq, int cap, int ocap) {
+__global__ __launch_bounds__(kRowBlock, kRowMinWaves) void k_rescore(Cost cd, Pm pm, RowQueue rq, int cap, int ocap) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   LutMem &s_lut = *reinterpret_cast<LutMem *>(smem);
   const Luts lut = load_luts(cd, s_lut);
@@ -1520,7 +1450,7 @@ __device__ __forceinline__ RowPlane refine_plane(const Pm &pm, int v, int x, int
 }
 
 template <bool CS, int SRC>
-__global__ __launch_bounds__(kRowBlock, CSPM_ROW_MINW) void k_refine(Cost cd, Pm pm, RowQueue rq, int iter, int first_step, int nsteps, double z_iter, double n_iter, int cap, int ocap) {
+__global__ __launch_bounds__(kRowBlock, kRowMinWaves) void k_refine(Cost cd, Pm pm, RowQueue rq, int iter, int first_step, int nsteps, double z_iter, double n_iter, int cap, int ocap) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   LutMem &s_lut = *reinterpret_cast<LutMem *>(smem);
   const Luts lut = load_luts(cd, s_lut);
@@ -1640,7 +1570,7 @@ __global__ __launch_bounds__(256) void k_view_sort(Pm pm, int v, ViewCand vc) {
 }
 
 template <bool CS, int SRC>
-__global__ __launch_bounds__(kRowBlock, CSPM_VIEW_MINW) void k_view_eval(Cost cd, Pm pm, RowQueue rq, int v, ViewCand vc, int cap, int ocap) {
+__global__ __launch_bounds__(kRowBlock, kRowMinWaves) void k_view_eval(Cost cd, Pm pm, RowQueue rq, int v, ViewCand vc, int cap, int ocap) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   LutMem &s_lut = *reinterpret_cast<LutMem *>(smem);
   const Luts lut = load_luts(cd, s_lut);
@@ -1696,7 +1626,7 @@ __device__ __forceinline__ RowPlane snap_plane(const SnapField &s, int W, int x,
 }
 
 template <bool CS, int SRC>
-__global__ __launch_bounds__(kRowBlock, CSPM_ROW_MINW) void k_spatial_diffuse(Cost cd, Pm pm, RowQueue rq, Diffuse df, int cap, int ocap) {
+__global__ __launch_bounds__(kRowBlock, kRowMinWaves) void k_spatial_diffuse(Cost cd, Pm pm, RowQueue rq, Diffuse df, int cap, int ocap) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   LutMem &s_lut = *reinterpret_cast<LutMem *>(smem);
   const Luts lut = load_luts(cd, s_lut);
@@ -1784,11 +1714,11 @@ __device__ __forceinline__ void merge_rows(const Cost &cd, const Pm &pm, const R
 }
 
 template <bool CS, int SRC>
-__global__ __launch_bounds__(kRowBlock, CSPM_INIT_MINW) void k_merge(Cost cd, Pm pm, RowQueue rq, CandField cand, int view0, int views, int cap, int ocap) {
+__global__ __launch_bounds__(kRowBlock, kRowMinWaves) void k_merge(Cost cd, Pm pm, RowQueue rq, CandField cand, int view0, int views, int cap, int ocap) {
   merge_rows<CS, SRC>(cd, pm, rq, cand, view0, views, cap, ocap);
 }
 template <bool CS, int SRC>
-__global__ __launch_bounds__(kRowBlock, CSPM_INIT_MINW) void k_merge_keep(Cost cd, Pm pm, RowQueue rq, CandInit cand, int view0, int views, int cap, int ocap) {
+__global__ __launch_bounds__(kRowBlock, kRowMinWaves) void k_merge_keep(Cost cd, Pm pm, RowQueue rq, CandInit cand, int view0, int views, int cap, int ocap) {
   merge_rows<CS, SRC>(cd, pm, rq, cand, view0, views, cap, ocap);
 }
 

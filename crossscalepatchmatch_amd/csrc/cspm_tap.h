@@ -138,14 +138,11 @@ __device__ __forceinline__ T lds_ld(int adr) {
 // in one register (v_sad_u8 / v_sad_hi_u8: <= 765 each, 16 bits apart), ONE packed minimum against kClrSat, and the LDS addresses of the two
 // table entries with one instruction each (v_mad_u32_u16: a 16-bit half * 8 + table) -- five instructions where two grd_cell() take six.
 // The same table entries, the same arithmetic after them: the bits of grd_cell().  `lut_a` MUST point into LDS (Luts::a of load_luts():
-// every kernel of the two tap engines; the volume builders, whose table is in global memory, call grd_cell()).
-#ifndef CSPM_PAIR_SAD
-#define CSPM_PAIR_SAD 1
-#endif
+// every kernel of the two tap engines; the volume builders, whose table is in global memory, call grd_cell()).  Two cell_of() per tap lost.
 typedef unsigned short u16x2_t __attribute__((ext_vector_type(2)));
 template <int SRC>
 __device__ __forceinline__ void cell_pair_of(const double *lut_a, const uint4 &own, const uint4 &o0, const uint4 &o1, double &c0, double &c1) {
-  if constexpr (SRC == kSrcCen || !CSPM_PAIR_SAD) {
+  if constexpr (SRC == kSrcCen) {
     c0 = cell_of<SRC>(lut_a, own, o0);
     c1 = cell_of<SRC>(lut_a, own, o1);
   } else {
