@@ -52,6 +52,7 @@ SYMBOLS = [
     "cspm_aggregate_cv_host", "cspm_local_stereo", "cspm_rescore_planes", "cspm_patchmatch_warm", "cspm_upsample_planes",
     "cspm_merge_planes", "cspm_merge_planes_host", "cspm_pm_init_keep",
     "cspm_set_pp_speckle", "cspm_get_pp_speckle", "cspm_filter_speckles_host",
+    "cspm_fit_default_params", "cspm_fit_planes_host", "cspm_fit_planes",
 ]
 
 
@@ -63,6 +64,11 @@ class PmParams(C.Structure):
     """struct cspm_pm_params"""
     _fields_ = [("seed", C.c_uint64), ("schedule", C.c_int), ("rb_rounds", C.c_int), ("rb_neighbours", C.c_int),
                 ("rng_mode", C.c_int), ("early_exit", C.c_int)]
+
+
+class FitParams(C.Structure):
+    """struct cspm_fit_params"""
+    _fields_ = [("radius", C.c_int), ("max_diff", C.c_double), ("min_support", C.c_int), ("use_guide", C.c_int)]
 
 
 def library_path():
@@ -92,6 +98,7 @@ def load_library():
     vp, dp, ip, u8p = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_uint8)
     llp = C.POINTER(C.c_longlong)
     pp = C.POINTER(PmParams)
+    fp = C.POINTER(FitParams)
     sig = {
         "cspm_device_count": (C.c_int, []),
         "cspm_create": (C.c_int, [C.POINTER(vp), C.c_int]),
@@ -155,6 +162,9 @@ def load_library():
         "cspm_set_pp_speckle": (C.c_int, [vp, C.c_int, C.c_double]),
         "cspm_get_pp_speckle": (C.c_int, [vp, ip, dp]),
         "cspm_filter_speckles_host": (C.c_int, [C.c_int, dp, u8p, C.c_int, C.c_int, C.c_int, C.c_double, u8p, C.POINTER(C.c_int32)]),
+        "cspm_fit_default_params": (C.c_int, [fp]),
+        "cspm_fit_planes_host": (C.c_int, [C.c_int, dp, u8p, u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, fp, dp, u8p]),
+        "cspm_fit_planes": (C.c_int, [vp, fp, C.c_int]),
     }
     assert sorted(sig) == sorted(SYMBOLS)
     for name, (res, args) in sig.items():
@@ -374,9 +384,23 @@ class StereoContext:
             assert m.shape == (self.h, self.w), m.shape
         self._chk(self.L.cspm_merge_planes_host(self.p, view, _dp(f), _u8(m) if m is not None else None))
 
-    def merge_disparity(self, view, disp):
-        """a disparity map (h, w) offered as the fronto-parallel planes (0, 0, 1, 0, 0, d); a non-finite d is no candidate"""
-        self.merge_planes(view, disparity_planes(disp))
+    def merge_disparity(self, view, disp, fit=None):
+        """a disparity map (h, w) offered as the fronto-parallel planes (0, 0, 1, 0, 0, d); a non-finite d is no candidate.
+        fit: a dict of plane-fit parameters ({} = the defaults): the map is offered as the slanted planes fit_planes_host fits to it
+        with the view's level-0 image as guide, under the `fitted` mask."""
+        if fit is None:
+            self.merge_planes(view, disparity_planes(disp))
+            return
+        guide = self.level_image(view, 0)
+        planes, fitted = fit_planes_host(disp, None, guide, max_dis=self.level_dims(0)[2], **dict(fit))
+        self.merge_planes(view, planes, fitted)
+
+    def fit_planes(self, merge=False, **params):
+        """slanted planes fitted to the stored field's own disparity maps, both views (cspm_fit_planes; asynchronous).  merge=False:
+        every pixel's plane is replaced and min_cost is stale (patchmatch_warm re-scores); merge=True: the fitted planes are
+        candidates that win only where they cost less.  params: radius, max_diff, min_support, use_guide."""
+        p = fit_params(**params)
+        self._chk(self.L.cspm_fit_planes(self.p, C.byref(p), int(bool(merge))))
 
     def pm_init_keep(self, **kw):
         """the random init as a challenger: a pixel takes its InitRandomPlane plane only where it costs less than the stored one"""
@@ -499,6 +523,44 @@ def filter_speckles(device, disp, valid, max_size, max_diff):
     if rc != 0:
         raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
     return out, sizes
+
+
+def fit_params(**params):
+    """struct cspm_fit_params: cspm_fit_default_params with the given fields replaced"""
+    p = FitParams()
+    rc = load_library().cspm_fit_default_params(C.byref(p))
+    assert rc == 0
+    for k, v in params.items():
+        if k not in ("radius", "max_diff", "min_support", "use_guide"):
+            raise TypeError(f"unknown plane-fit parameter {k!r}")
+        setattr(p, k, float(v) if k == "max_diff" else int(v))
+    return p
+
+
+def fit_planes_host(disp, valid=None, guide=None, max_dis=0, device=0, **params):
+    """slanted planes fitted to a host disparity map (cspm_fit_planes_host): disp (h, w) f64, valid (h, w) or
+    None (every pixel), guide (h, w, 3) uint8 BGR or None (no guide weights).  Returns ((h, w, 6) planes in the layout of get_planes,
+    (h, w) uint8 fitted); a pixel that is masked out or not finite gets six NaNs and fitted = 0."""
+    L = load_library()
+    d = np.ascontiguousarray(disp, dtype=np.float64)
+    assert d.ndim == 2
+    h, w = d.shape
+    m = None
+    if valid is not None:
+        m = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+        assert m.shape == d.shape, m.shape
+    g = None
+    if guide is not None:
+        g = np.ascontiguousarray(guide, dtype=np.uint8)
+        assert g.shape == (h, w, 3), g.shape
+    p = fit_params(**params)
+    planes = np.zeros((h, w, 6))
+    fitted = np.zeros((h, w), np.uint8)
+    rc = L.cspm_fit_planes_host(device, _dp(d), _u8(m) if m is not None else None, _u8(g) if g is not None else None, w * 3, w, h, int(max_dis),
+                                C.byref(p), _dp(planes), _u8(fitted))
+    if rc != 0:
+        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    return planes, fitted
 
 
 def disparity_planes(disp):

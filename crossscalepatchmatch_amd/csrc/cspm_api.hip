@@ -13,6 +13,7 @@
 #include "cspm_kernels.h"
 #include "cspm_pp.h"
 #include "cspm_speckle.h"
+#include "cspm_fit.h"
 #include "cspm_ca.h"
 
 using namespace cspm;
@@ -192,6 +193,7 @@ struct cspm_ctx {
   Repeat repeat;                      // when a run is repeated after a sweep timeout
   double *warm_snap = nullptr;        // the starting field of the last warm run (both views, 7 arrays each), kept with the field
   double *cand_mem = nullptr;         // cspm_merge_planes_host: one view's candidate planes (6 arrays) and, behind them, its mask bytes; allocated by the first such call and kept with the field
+  double *fit_mem = nullptr;          // cspm_fit_planes: both views' disparity snapshots (2 arrays) and, behind them, the exp(-k/10) table; allocated by the first such call and kept with the field
   double *diffuse_snap = nullptr;     // CSPM_SCHED_DIFFUSE: the round's snapshot (both views, the 6 plane arrays each), allocated by the first such propagation and kept with the field
   long long sweep_fallbacks = 0;      // how often that happened (cspm_get_option)
   // CSPatchMatch over a foreign IPlaneCost (cspm_fpm_*): candidate buffers and what the pending batch was
@@ -349,6 +351,7 @@ void free_field(cspm_ctx *c) {
   dfree(c->warm_snap);
   dfree(c->diffuse_snap);
   dfree(c->cand_mem);
+  dfree(c->fit_mem);
   dfree(c->vc.cost);
   dfree(c->vc.c);
   dfree(c->vc.cx);
@@ -1244,6 +1247,35 @@ void speckle_launch(hipStream_t stream, const T *const *d, uint8_t *const *valid
                      vs.v[1].valid, n, max_size, removed, size_out);
 }
 
+// plane fitting (cspm_fit.h)
+const char *fit_params_error(const cspm_fit_params *p) {
+  if (p->radius < 1 || p->radius > kFitMaxRadius) return "plane fit: radius must be 1 .. 17";
+  if (p->min_support < 3) return "plane fit: min_support must be at least 3";
+  if (!(p->max_diff >= 0.0)) return "plane fit: max_diff must be >= 0 (it may be +infinity)";
+  return nullptr;
+}
+const cspm_fit_params kFitDefaults = {5, 1.5, 6, 1};
+// lookup_exp_ once more (the cost object owns its own copy): exp(-k/10) by the host's libm
+const double *fit_lut() {
+  static double lut[kFitLut];
+  static const bool filled = [] {
+    for (int i = 0; i < kFitLut; ++i) lut[i] = std::exp(-i * 1.0 / 10.0);
+    return true;
+  }();
+  (void)filled;
+  return lut;
+}
+// one view: in.pix == nullptr means no guide
+void fit_launch(hipStream_t stream, FitIn in, const FitOut &out, int w, int h, const cspm_fit_params *p, int max_dis) {
+  const dim3 grid((unsigned)((w + kFitTileW - 1) / kFitTileW), (unsigned)((h + kFitTileH - 1) / kFitTileH));
+  const size_t lds = fit_lds_bytes(p->radius);
+  if (p->use_guide && in.pix)
+    hipLaunchKernelGGL(k_fit_planes<true>, grid, dim3(kFitBlock), lds, stream, in, out, w, h, p->radius, p->max_diff, p->min_support, (double)max_dis);
+  else
+    hipLaunchKernelGGL(k_fit_planes<false>, grid, dim3(kFitBlock), lds, stream, in, out, w, h, p->radius, p->max_diff, p->min_support, (double)max_dis);
+}
+constexpr int kFitMaxRows = 65535 * kFitTileH;  // gridDim.y
+
 // PostProcessing's speckle filter on c->d_valid, between LeftRightCheck and FillInvalid; nothing at all when off
 template <class T>
 int speckle_enqueue(cspm_ctx *c, const T *d0, const T *d1, double thr) {
@@ -2065,6 +2097,49 @@ int cspm_filter_speckles_host(int device, const double *disp, const uint8_t *val
   return S.done(CSPM_OK);
 }
 
+// the plane fit alone on caller maps: the launch cspm_fit_planes enqueues, on one view
+int cspm_fit_default_params(cspm_fit_params *p) {
+  if (!p) return CSPM_ERR_ARG;
+  *p = kFitDefaults;
+  return CSPM_OK;
+}
+
+int cspm_fit_planes_host(int device, const double *disp, const uint8_t *valid, const uint8_t *guide_bgr, size_t guide_stride, int w, int h, int max_dis,
+                         const cspm_fit_params *p, double *np_out, uint8_t *fitted_out) {
+  if (!p) p = &kFitDefaults;
+  if (const char *msg = fit_params_error(p)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (!disp || !np_out || w < 1 || h < 1 || h > kFitMaxRows || max_dis < 0 || (guide_bgr && guide_stride < (size_t)w * 3))
+    return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
+  Scratch S;
+  int rc = cspm_create(&S.c, device);
+  if (rc) return rc;
+  cspm_ctx *c = S.c;
+  const size_t n = (size_t)w * h;
+  const bool guided = guide_bgr && p->use_guide;
+  double *dd = nullptr, *dout = nullptr, *dlut = nullptr;
+  uint8_t *dv = nullptr, *dfit = nullptr, *dbgr = nullptr;
+  uint32_t *dpix = nullptr;
+  if ((rc = dalloc(c, &dd, n, &S.tmp)) || (rc = dalloc(c, &dout, 6 * n, &S.tmp)) || (rc = dalloc(c, &dfit, n, &S.tmp)) ||
+      (valid && (rc = dalloc(c, &dv, n, &S.tmp))) ||
+      (guided && ((rc = dalloc(c, &dbgr, 3 * n, &S.tmp)) || (rc = dalloc(c, &dpix, n, &S.tmp)) || (rc = dalloc(c, &dlut, (size_t)kFitLut, &S.tmp)))))
+    return S.done(rc);
+  if (hipMemcpyAsync(dd, disp, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      (valid && hipMemcpyAsync(dv, valid, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+      (guided && (hipMemcpy2DAsync(dbgr, (size_t)w * 3, guide_bgr, guide_stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                  hipMemcpyAsync(dlut, fit_lut(), sizeof(double) * kFitLut, hipMemcpyHostToDevice, c->stream) != hipSuccess)))
+    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  if (guided) hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, dbgr, (size_t)w * 3, w, h, w, 0, dpix);
+  fit_launch(c->stream, FitIn{dd, dv, dpix, dlut}, FitOut{dout, dout + n, dout + 2 * n, dout + 3 * n, dout + 4 * n, dout + 5 * n, dfit, 0}, w, h, p, max_dis);
+  std::vector<double> hst(6 * n);
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hst.data(), dout, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      (fitted_out && hipMemcpyAsync(fitted_out, dfit, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, "plane fit kernel failed"));
+  for (size_t i = 0; i < n; ++i)
+    for (int k = 0; k < 6; ++k) np_out[6 * i + k] = hst[k * n + i];
+  return S.done(CSPM_OK);
+}
+
 // local stereo over the ctx's cost object (cspm.h): asynchronous on the ctx stream like cspm_patchmatch
 int cspm_local_stereo(cspm_ctx *c, int method) {
   if (!c) return CSPM_ERR_ARG;
@@ -2256,6 +2331,53 @@ int cspm_merge_planes_host(cspm_ctx *c, int view, const double *np, const uint8_
   cf.mask[view] = mask ? d_mask : nullptr;
   c->repeat.taint_unchecked_run();
   return do_merge(c, &cf, &kDefaultParams, view, 1, evals);
+}
+
+// slanted planes fitted to the stored field's own disparity maps (cspm.h "plane fitting"); asynchronous on the ctx stream
+int cspm_fit_planes(cspm_ctx *c, const cspm_fit_params *p, int merge) {
+  if (!c) return CSPM_ERR_ARG;
+  if (!p) p = &kFitDefaults;
+  if (const char *msg = fit_params_error(p)) return fail(c, CSPM_ERR_ARG, msg);
+  if (!c->img0[0]) return fail(c, CSPM_ERR_STATE, "cspm_set_images first");
+  int rc;
+  if ((rc = need_field(c, "no plane field to fit (cspm_local_stereo, cspm_set_planes, cspm_pm_init or an earlier run)"))) return rc;
+  if (merge && (rc = need_cost(c))) return rc;
+  if (c->max_dis < 1) return fail(c, CSPM_ERR_STATE, "no max_dis known: build a cost object (or cspm_fpm_begin) first");
+  if (c->H > kFitMaxRows) return fail(c, CSPM_ERR_ARG, "image too high for the plane fit");
+  ON_DEVICE(c);
+  const size_t n = (size_t)c->W * c->H;
+  if (!c->fit_mem) {
+    if ((rc = dalloc(c, &c->fit_mem, 2 * n + kFitLut, nullptr))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->fit_mem + 2 * n, fit_lut(), sizeof(double) * kFitLut, hipMemcpyHostToDevice, c->stream));
+  }
+  if (merge) {
+    if (!c->cand_mem && (rc = dalloc(c, &c->cand_mem, 6 * n + (n + 7) / 8, nullptr))) return rc;  // the buffer of cspm_merge_planes_host
+    if ((rc = ensure_consistent(c))) return rc;
+  } else {
+    c->field_consistent = false;  // min_cost still belongs to the planes that were replaced
+  }
+  c->repeat.taint_unchecked_run();  // it can no longer be repeated over these planes
+  const Pm pm = field_pm(c);
+  for (int v = 0; v < 2; ++v) {
+    double *d = c->fit_mem + (size_t)v * n;
+    double *b = merge ? c->cand_mem : nullptr;
+    uint8_t *d_mask = merge ? reinterpret_cast<uint8_t *>(c->cand_mem + 6 * n) : nullptr;
+    const Field &f = c->f[v];
+    const FitOut out = merge ? FitOut{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, d_mask, 0} : FitOut{f.nx, f.ny, f.nz, f.a, f.b, f.c, nullptr, 1};
+    {
+      Timed t(c, CSPM_K_MISC, (long long)n);
+      hipLaunchKernelGGL(k_plane_to_disp_f64, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, pm, v, d);
+      fit_launch(c->stream, FitIn{d, nullptr, c->img0[v], c->fit_mem + 2 * n}, out, c->W, c->H, p, c->max_dis);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (merge) {
+      CandField cf{};
+      cf.s[v] = SnapField{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n};
+      cf.mask[v] = d_mask;
+      if ((rc = do_merge(c, &cf, &kDefaultParams, v, 1, (long long)n))) return rc;
+    }
+  }
+  return CSPM_OK;
 }
 
 int cspm_pm_init_keep(cspm_ctx *c, const cspm_pm_params *p) {

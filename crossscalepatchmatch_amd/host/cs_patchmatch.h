@@ -1,5 +1,6 @@
 // cs_patchmatch.h -- class CSPatchMatch with the reference's public interface (CSPM/cs_patchmatch.h:17-68).
 #pragma once
+#include "../../include/cspm.h"
 #include "commfunc.h"
 #include "plane.h"
 #include "plane_cost/i_plane_cost.h"
@@ -26,6 +27,12 @@ class CSPatchMatch {
   // cspm_local_stereo); dis(), planes(), disparity() and use_pp as after PatchMatch.  Begin / End as above (End = PatchMatchEnd).
   void LocalStereo(const int &ca_method, const IPlaneCost *plane_cost, const bool &use_pp);
   void LocalStereoBegin(const int &ca_method, const IPlaneCost *plane_cost, const bool &use_pp);
+  // slanted planes fitted to the disparity maps of the plane field in the device context of plane_cost (an addition; include/cspm.h
+  // cspm_fit_planes) -- after LocalStereo(Begin), whose field is fronto-parallel, or any run.  merge = false: every plane is replaced
+  // (PatchMatchFrom re-scores); merge = true: a fitted plane wins only where it costs less.  Enqueued on the cost object's stream: it
+  // may follow a ...Begin on the same cost object and be followed by PatchMatchFromBegin / PatchMatchKeepBegin.  One of this
+  // library's device costs only: a foreign IPlaneCost throws.
+  void FitPlanes(const IPlaneCost *plane_cost, const cspm_fit_params &params, const bool &merge);
   // warm start (an addition): iter_num PatchMatch iterations from the plane field already in the device context of plane_cost --
   // after LocalStereo, a previous pair's run, or the planes given to SetPlanes -- instead of InitRandomPlane.  The field is re-scored
   // under plane_cost first (include/cspm.h cspm_patchmatch_warm).  Begin may follow a LocalStereoBegin on the same cost object
@@ -41,6 +48,10 @@ class CSPatchMatch {
   // candidate.  Any number per view; kept here until the next PatchMatchSeeded / PatchMatchKeep, which merges them in this order.
   void AddCandidates(const RefView &view, const std::vector<Plane> &planes);
   void AddCandidateDisparity(const RefView &view, const Mat &disp);
+  // the same map offered as SLANTED planes (an addition; include/cspm.h "plane fitting"): a weighted least-squares plane is fitted
+  // around every value with this object's image of the view as guide (cspm_fit_planes_host; non-finite and negative values are no
+  // nodes) and merged under the fit's `fitted` mask.  Throws for parameters the C ABI refuses.
+  void AddCandidateDisparity(const RefView &view, const Mat &disp, const cspm_fit_params &params);
   // PatchMatchSeeded: InitRandomPlane, then the candidates merged, then iter_num iterations (cspm_pm_init, cspm_merge_planes_host,
   // cspm_patchmatch_warm).  PatchMatchKeep: the field already in the device context of plane_cost (LocalStereo, the previous frame's
   // run, SetPlanes) stays wherever InitRandomPlane's plane costs no less (cspm_pm_init_keep), then the candidates, then the iterations.

@@ -467,6 +467,35 @@ void CSPatchMatch::AddCandidateDisparity(const RefView &view, const Mat &disp) {
   candidates_[view].push_back(c);
 }
 
+void CSPatchMatch::AddCandidateDisparity(const RefView &view, const Mat &disp, const cspm_fit_params &params) {
+  if (disp.cols != wid_ || disp.rows != hei_ || (disp.type() != CV_32FC1 && disp.type() != CV_64FC1))
+    throw std::runtime_error("CSPatchMatch::AddCandidateDisparity: a CV_32FC1 or CV_64FC1 map of the image size expected");
+  const size_t n = (size_t)wid_ * hei_;
+  std::vector<double> d(n);
+  std::vector<uint8_t> valid(n);
+  for (int y = 0; y < hei_; ++y)
+    for (int x = 0; x < wid_; ++x) {
+      const size_t i = (size_t)y * wid_ + x;
+      d[i] = disp.type() == CV_32FC1 ? (double)disp.at<float>(y, x) : disp.at<double>(y, x);
+      valid[i] = std::isfinite(d[i]) && d[i] >= 0.0;  // what the fronto-parallel overload takes as a candidate
+    }
+  Candidates c;
+  c.norm_param.resize(6 * n);
+  c.mask.resize(n);
+  const Mat &g = img_[view];
+  check(cspm_fit_planes_host(DevicePlaneCost::device, d.data(), valid.data(), g.data, g.step, wid_, hei_, max_dis_, &params, c.norm_param.data(),
+                             c.mask.data()), NULL, "cspm_fit_planes_host");
+  candidates_[view].push_back(c);
+}
+
+void CSPatchMatch::FitPlanes(const IPlaneCost *plane_cost, const cspm_fit_params &params, const bool &merge) {
+  const IDevicePlaneCost *dev = dynamic_cast<const IDevicePlaneCost *>(plane_cost);
+  if (!dev) throw std::runtime_error("CSPatchMatch::FitPlanes needs one of this library's device costs");
+  cspm_ctx *ctx = dev->device_ctx();
+  if (pending_ctx_ && pending_ctx_ != ctx) throw std::runtime_error("CSPatchMatch::FitPlanes: the previous run has not been ended");
+  check(cspm_fit_planes(ctx, &params, merge ? 1 : 0), ctx, "cspm_fit_planes");  // asynchronous: enqueued on the context's stream
+}
+
 void CSPatchMatch::SeededBegin(bool keep, int iter_num, const IPlaneCost *plane_cost, bool use_pp) {
   const IDevicePlaneCost *dev = dynamic_cast<const IDevicePlaneCost *>(plane_cost);
   if (!dev) throw std::runtime_error("CSPatchMatch::PatchMatchSeeded / PatchMatchKeep need one of this library's device costs (a foreign IPlaneCost runs cold only: PatchMatch)");

@@ -2,7 +2,8 @@
 // (main.cc:57-139): read the pair, construct the plane cost (timed), run PatchMatch, print "Total Time", write the
 // two 8-bit maps.  Runs on the GPU through the host layer.  Extra flags: --seed --schedule --neighbours --device --iters --ca_name (local stereo)
 // --warm_ca (local stereo, then --iters warm PatchMatch iterations) --l_seed_pfm --r_seed_pfm (disparity maps offered to the random start
-// field as candidates) --seed_ca (local stereo, kept wherever the random start plane costs no less, then --iters iterations).
+// field as candidates) --seed_ca (local stereo, kept wherever the random start plane costs no less, then --iters iterations)
+// --fit_radius --fit_max_diff --fit_merge (slanted planes fitted to the local-stereo field or to the seed maps before what follows).
 #include "../../include/cspm.h"
 #include "commfunc.h"
 #include "cs_patchmatch.h"
@@ -45,6 +46,12 @@ DEFINE_string(l_seed_pfm, "", "a float32 PFM disparity map of the left view offe
                               "keep-init of --seed_ca) a pixel takes the fronto-parallel plane of its value where that costs less; non-finite "
                               "or negative values are no candidates.  Not with --ca_name, --warm_ca or --batch_list");
 DEFINE_string(r_seed_pfm, "", "the same for the right view (see --l_seed_pfm)");
+DEFINE_int32(fit_radius, 0, "fit slanted planes (weighted least squares over a window of this half-width, 1 .. 17; include/cspm.h \"plane "
+                           "fitting\") to the local-stereo field of --warm_ca / --seed_ca / --ca_name before what follows, and to the maps of "
+                           "--l_seed_pfm / --r_seed_pfm instead of offering them as fronto-parallel planes; 0 = off.  An error without one of those");
+DEFINE_double(fit_max_diff, 1.5, "with --fit_radius: a window pixel takes part in a fit when its disparity is within this of the centre's");
+DEFINE_bool(fit_merge, false, "with --fit_radius and a local-stereo field: a fitted plane replaces the stored one only where it costs less "
+                              "(default: every plane is replaced)");
 DEFINE_bool(use_cs, false, "cross-scale aggregation over a 5-level pyramid (PreCSPC) instead of PreSSPC");
 DEFINE_bool(use_pp, false, "left-right check, hole filling and weighted median afterwards");
 DEFINE_double(reg_lambda, 0.0, "cross-scale regularisation weight");
@@ -136,6 +143,11 @@ void begin(PairRun &p, CCMethod *cost_fn) {
     p.matcher->SetSpeckleFilter(FLAGS_pp_speckle_size, FLAGS_pp_speckle_diff);
     if (FLAGS_schedule == "diffuse") p.matcher->set_schedule(CSPM_SCHED_DIFFUSE, 1, FLAGS_neighbours);
     else p.matcher->set_schedule(FLAGS_schedule == "redblack" ? 1 : 0);
+    cspm_fit_params fit;
+    cspm_fit_default_params(&fit);
+    fit.radius = FLAGS_fit_radius;
+    fit.max_diff = FLAGS_fit_max_diff;
+    const bool use_fit = FLAGS_fit_radius != 0;
     const string *seed_pfm[kViewNum] = {&FLAGS_l_seed_pfm, &FLAGS_r_seed_pfm};
     for (int v = 0; v < kViewNum; ++v) {
       if (seed_pfm[v]->empty()) continue;
@@ -145,20 +157,24 @@ void begin(PairRun &p, CCMethod *cost_fn) {
         throw std::runtime_error("can not read " + *seed_pfm[v] + " as a single-channel PFM of the image size");
       Mat m(h, w, CV_64FC1);
       for (int y = 0; y < h; ++y) std::copy(d.begin() + (size_t)y * w, d.begin() + (size_t)(y + 1) * w, m.ptr<double>(y));
-      p.matcher->AddCandidateDisparity(v == 0 ? kLeft : kRight, m);
+      if (use_fit) p.matcher->AddCandidateDisparity(v == 0 ? kLeft : kRight, m, fit);
+      else p.matcher->AddCandidateDisparity(v == 0 ? kLeft : kRight, m);
     }
     if (!FLAGS_seed_ca.empty()) {  // keep-init and the iterations are enqueued behind the local stereo on the cost object's stream
       p.matcher->LocalStereoBegin(ca_method(FLAGS_seed_ca), p.cost.get(), FLAGS_use_pp);
+      if (use_fit) p.matcher->FitPlanes(p.cost.get(), fit, FLAGS_fit_merge);
       p.matcher->PatchMatchKeepBegin(FLAGS_iters, p.cost.get(), FLAGS_use_pp);
     } else if (!FLAGS_l_seed_pfm.empty() || !FLAGS_r_seed_pfm.empty()) {
       p.matcher->PatchMatchSeededBegin(FLAGS_iters, p.cost.get(), FLAGS_use_pp);
     } else if (!FLAGS_warm_ca.empty()) {  // the warm run is enqueued behind the local stereo on the cost object's stream
       p.matcher->LocalStereoBegin(ca_method(FLAGS_warm_ca), p.cost.get(), FLAGS_use_pp);
+      if (use_fit) p.matcher->FitPlanes(p.cost.get(), fit, FLAGS_fit_merge);
       p.matcher->PatchMatchFromBegin(FLAGS_iters, p.cost.get(), FLAGS_use_pp);
     } else if (FLAGS_ca_name.empty()) {
       p.matcher->PatchMatchBegin(FLAGS_iters, p.cost.get(), FLAGS_use_pp);
     } else {
       p.matcher->LocalStereoBegin(ca_method(FLAGS_ca_name), p.cost.get(), FLAGS_use_pp);
+      if (use_fit) p.matcher->FitPlanes(p.cost.get(), fit, FLAGS_fit_merge);
     }
   } catch (const std::exception &e) {  // a bad pair must not take the batch down
     p.log << "Error: " << e.what() << "\n";
@@ -360,6 +376,19 @@ int run() {
   }
   if (seed_pfm && !FLAGS_batch_list.empty()) {
     cout << "Error: --l_seed_pfm / --r_seed_pfm belong to one pair: not with --batch_list\n";
+    return EXIT_FAILURE;
+  }
+  if (FLAGS_fit_radius != 0 && (FLAGS_fit_radius < 1 || FLAGS_fit_radius > 17 || !(FLAGS_fit_max_diff >= 0.0))) {
+    cout << "Error: --fit_radius must be 1 .. 17 (0 = off) and --fit_max_diff >= 0\n";
+    return EXIT_FAILURE;
+  }
+  if (FLAGS_fit_radius != 0 && !seed_pfm && FLAGS_warm_ca.empty() && FLAGS_seed_ca.empty() && FLAGS_ca_name.empty()) {
+    cout << "Error: --fit_radius fits planes to a local-stereo field or to seed maps: it needs --warm_ca, --seed_ca, --ca_name, --l_seed_pfm or "
+            "--r_seed_pfm\n";
+    return EXIT_FAILURE;
+  }
+  if (FLAGS_fit_merge && FLAGS_fit_radius == 0) {
+    cout << "Error: --fit_merge needs --fit_radius\n";
     return EXIT_FAILURE;
   }
   if ((seed_pfm || !FLAGS_seed_ca.empty()) && FLAGS_pc_name != "PRE" && FLAGS_pc_name != "IMG") {

@@ -317,6 +317,53 @@ int cspm_merge_planes_host(cspm_ctx *ctx, int view, const double *norm_param, co
 /* keep-init over both views.  Without a plane field it is cspm_pm_init (nothing is there to keep); CSPM_ERR_STATE without a cost
  * object; params as for cspm_pm_init. */
 int cspm_pm_init_keep(cspm_ctx *ctx, const cspm_pm_params *p);
+/* ---- plane fitting (an addition): slanted planes from a disparity map --------------------------------------------
+ * F(D, V, I, radius r, max_diff t, min_support m, use_guide, max_dis) -> (planes, fitted) on one view: D a w x h f64 map, V w x h bytes
+ * (NULL = all 1), I an 8-bit BGR guide (absent: use_guide = 0).  A pixel is a NODE when V = 1 and D is finite.  For a node p = (x, y) the
+ * window is visited j = -r .. r outer, i = -r .. r inner, q = (x+i, y+j); a tap CONTRIBUTES when q is inside the image, q is a node and
+ * fabs(D[q] - D[p]) <= t (false for a NaN; t may be +infinity); the centre always contributes.  Per contributing tap:
+ *     wq = LUT[|dB| + |dG| + |dR|], LUT[k] = exp(-k/10) computed on the host with libm (1.0 when use_guide = 0);
+ *     e = D[q] - D[p];  u = (double)i;  v = (double)j;
+ *     S = S + wq * t for the nine sums Sw, Su, Sv, Suu, Suv, Svv, Se, Sue, Sve with t = 1, u, v, u*u, u*v, v*v, e, u*e, v*e
+ * -- every product and every sum one IEEE f64 operation, nothing contracted, serial in the visiting order; n = contributing taps.  Then
+ *     C00 = Svv*Sw - Sv*Sv   C01 = Suv*Sw - Sv*Su   C02 = Suv*Sv - Svv*Su
+ *     C11 = Suu*Sw - Su*Su   C12 = Suu*Sv - Suv*Su  C22 = Suu*Svv - Suv*Suv
+ *     det = (Suu*C00 - Suv*C01) + Su*C02
+ * The fit is DEGENERATE when n < m or !(det > 1e-6 * ((Suu*Svv)*Sw)) (Hadamard: 0 <= det <= Suu*Svv*Sw, so the ratio is a scale-free
+ * measure of collinearity; 1e-6 is a stated condition, not a tuned value): then a = b = c0 = 0.  Otherwise, with three true divisions,
+ *     a  = ((C00*Sue - C01*Sve) + C02*Se) / det
+ *     b  = ((C11*Sve - C01*Sue) - C12*Se) / det
+ *     c0 = ((C02*Sue - C12*Sve) + C22*Se) / det
+ * Output: t = D[p] + c0;  z = t > 0 ? t : 0;  z = z < max_dis ? z : max_dis;  normal = (-a, -b, 1) * (1 / max(len, 1e-8)) with
+ * len = sqrt((a*a + b*b) + 1) summed in that order (InitRandomPlane's normalisation);  plane = Plane(normal, (x, y, z)): the stored a, b, c
+ * are derived from the normal like every other plane of a field;  fitted[p] = 1.  A non-node gets six NaNs and fitted = 0: exactly "no
+ * candidate" for cspm_merge_planes_host.
+ * Defaults (chosen, not tuned): radius 5, max_diff 1.5, min_support 6, use_guide 1.  Every entry returns CSPM_ERR_ARG for a radius outside
+ * 1 .. 17, min_support < 3 or a negative or NaN max_diff.  params == NULL: the defaults. */
+typedef struct cspm_fit_params {
+  int radius;       /* window half-width, 1 .. 17 */
+  double max_diff;  /* t: a tap contributes when its disparity is within t of the centre's; +infinity = every node */
+  int min_support;  /* m >= 3: fewer contributing taps give the fronto-parallel plane */
+  int use_guide;    /* 1: taps are weighted by colour similarity to the centre */
+} cspm_fit_params;
+int cspm_fit_default_params(cspm_fit_params *p);
+/* the fit alone on caller maps, no context needed (like cspm_filter_speckles_host): disp w*h doubles, valid w*h bytes or NULL, guide_bgr
+ * packed 8UC3 BGR rows of guide_stride bytes (>= 3*w) or NULL (implies use_guide = 0); norm_param_out w*h*6 doubles in the layout of
+ * cspm_get_planes, fitted_out w*h bytes or NULL.  Synchronous.  CSPM_ERR_ARG also for max_dis < 0 or h > 262140. */
+int cspm_fit_planes_host(int device, const double *disp, const uint8_t *valid, const uint8_t *guide_bgr, size_t guide_stride, int w, int h,
+                         int max_dis, const cspm_fit_params *p, double *norm_param_out, uint8_t *fitted_out);
+/* both views of the context's plane field: D = the stored field's a*x+b*y+c (what cspm_get_disparity_f64 returns), computed into scratch
+ * first so that the fit reads a snapshot and never its own output; V all 1; I the view's level-0 image; max_dis the context's (that of
+ * its last cost constructor or cspm_fpm_begin).
+ * merge = 0: every fitted pixel's plane is replaced; min_cost is left stale and the field is not consistent (as after cspm_local_stereo
+ * or cspm_upsample_planes: cspm_patchmatch_warm re-scores).
+ * merge = 1: the fitted planes go into the candidate buffer of cspm_merge_planes_host with `fitted` as the mask and are merged by that
+ * entry's rule, one view after the other; a field that is not consistent is re-scored first, and the field is left consistent.
+ * Asynchronous on the ctx stream.  Timed under CSPM_K_MISC: one bracket per view around the snapshot and the fit, w*h evaluations each;
+ * the merge launches under CSPM_K_INIT as in cspm_merge_planes_host.  A whole run in front of it that has not been checked can no longer be
+ * repeated (as with cspm_local_stereo).  Scratch: two doubles per pixel and the table, allocated by the first call and kept with the
+ * plane field.  CSPM_ERR_STATE without images, a plane field or a known max_dis, and with merge = 1 without a cost object. */
+int cspm_fit_planes(cspm_ctx *ctx, const cspm_fit_params *p, int merge);
 /* PlaneToDisp + dis() (cs_patchmatch.cc:590-601, 111-113): saturate_u8(Round2Int(d*dis_scale)) */
 int cspm_get_disparity_u8(cspm_ctx *ctx, int view, int dis_scale, uint8_t *out, size_t stride);
 int cspm_get_disparity_f64(cspm_ctx *ctx, int view, double *out); /* unquantised a*x+b*y+c */
