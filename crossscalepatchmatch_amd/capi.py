@@ -35,6 +35,7 @@ OPT_FAULT_VOLUME_ALLOC = 16  # write only, TEST HOOK: the n-th optional-volume a
 OPT_CENGRD_FUSED = 19        # set before build_cost_cengrd: 1 = no volumes, the cells are computed inside the PatchMatch kernels (default 0; identical planes)
 OPT_CENGRD_FUSED_ACTIVE = 20 # read only: the current cost object is a fused CENGRD one
 OPT_PP_SPECKLE_REMOVED = 21  # read only, synchronises: pixels the speckle filter removed from both masks in the last post-processing
+MEDIAN_MAX_RADIUS = 7  # CSPM_MEDIAN_MAX_RADIUS: the median filter's window is at most 15 x 15
 CA_BOX, CA_GF, CA_BF = 0, 1, 2  # cost aggregation: BoxCA, GFCA, BFCA (ca_filter/)
 CENGRD_KAPPA, CENGRD_TAU = 0.0625, 32.0  # CSPM_CENGRD_KAPPA / CSPM_CENGRD_TAU: cell = fma(KAPPA, min(H, TAU), G)
 
@@ -52,6 +53,7 @@ SYMBOLS = [
     "cspm_aggregate_cv_host", "cspm_local_stereo", "cspm_rescore_planes", "cspm_patchmatch_warm", "cspm_upsample_planes",
     "cspm_merge_planes", "cspm_merge_planes_host", "cspm_pm_init_keep",
     "cspm_set_pp_speckle", "cspm_get_pp_speckle", "cspm_filter_speckles_host",
+    "cspm_median_filter_u8_host", "cspm_median_filter_f64_host", "cspm_set_pp_median", "cspm_get_pp_median",
     "cspm_fit_default_params", "cspm_fit_planes_host", "cspm_fit_planes",
 ]
 
@@ -162,6 +164,10 @@ def load_library():
         "cspm_set_pp_speckle": (C.c_int, [vp, C.c_int, C.c_double]),
         "cspm_get_pp_speckle": (C.c_int, [vp, ip, dp]),
         "cspm_filter_speckles_host": (C.c_int, [C.c_int, dp, u8p, C.c_int, C.c_int, C.c_int, C.c_double, u8p, C.POINTER(C.c_int32)]),
+        "cspm_median_filter_u8_host": (C.c_int, [C.c_int, u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, u8p, C.c_size_t]),
+        "cspm_median_filter_f64_host": (C.c_int, [C.c_int, dp, C.c_int, C.c_int, C.c_int, dp]),
+        "cspm_set_pp_median": (C.c_int, [vp, C.c_int]),
+        "cspm_get_pp_median": (C.c_int, [vp, ip]),
         "cspm_fit_default_params": (C.c_int, [fp]),
         "cspm_fit_planes_host": (C.c_int, [C.c_int, dp, u8p, u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, fp, dp, u8p]),
         "cspm_fit_planes": (C.c_int, [vp, fp, C.c_int]),
@@ -466,6 +472,17 @@ class StereoContext:
         self._chk(self.L.cspm_get_pp_speckle(self.p, C.byref(n), C.byref(x)))
         return n.value, x.value
 
+    def set_pp_median(self, r):
+        """median filter of every post-processing entry: as the last step, after the weighted median, every
+        pixel of both maps becomes the median of its (2r+1)^2 window with the border replicated -- M8 on the 8-bit maps, M64 (NaN taps
+        do not vote, the lower median, a tap's own bits) on the f64 maps.  r = 0 (the default) = no filter; at most MEDIAN_MAX_RADIUS."""
+        self._chk(self.L.cspm_set_pp_median(self.p, int(r)))
+
+    def get_pp_median(self):
+        r = C.c_int()
+        self._chk(self.L.cspm_get_pp_median(self.p, C.byref(r)))
+        return r.value
+
     def postprocess_f64_device(self, d_l_ptr, d_r_ptr):
         """the same with device-resident outputs (packed h*w f64 each; asynchronous on the context's stream)"""
         self._chk(self.L.cspm_postprocess_f64_device(self.p, C.c_void_p(d_l_ptr), C.c_void_p(d_r_ptr)))
@@ -561,6 +578,30 @@ def fit_planes_host(disp, valid=None, guide=None, max_dis=0, device=0, **params)
     if rc != 0:
         raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
     return planes, fitted
+
+
+def median_filter(device, img, r):
+    """the median filter alone on a host image: uint8 (h, w) or (h, w, 1 .. 4) -> M8 per channel, float64 (h, w)
+    -> M64.  Returns a new array of the input's shape and dtype."""
+    L = load_library()
+    a = np.asarray(img)
+    if a.dtype == np.uint8:
+        assert a.ndim in (2, 3), a.shape
+        src = np.ascontiguousarray(a)
+        h, w = src.shape[:2]
+        cn = src.shape[2] if src.ndim == 3 else 1
+        out = np.zeros_like(src)
+        rc = L.cspm_median_filter_u8_host(device, _u8(src), w * cn, w, h, cn, int(r), _u8(out), w * cn)
+    elif a.dtype == np.float64:
+        assert a.ndim == 2, a.shape
+        src = np.ascontiguousarray(a)
+        out = np.zeros_like(src)
+        rc = L.cspm_median_filter_f64_host(device, _dp(src), src.shape[1], src.shape[0], int(r), _dp(out))
+    else:
+        raise TypeError(f"median_filter takes uint8 or float64 images, not {a.dtype}")
+    if rc != 0:
+        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    return out
 
 
 def disparity_planes(disp):

@@ -13,6 +13,7 @@
 #include "cspm_kernels.h"
 #include "cspm_pp.h"
 #include "cspm_speckle.h"
+#include "cspm_median.h"
 #include "cspm_fit.h"
 #include "cspm_ca.h"
 
@@ -180,6 +181,9 @@ struct cspm_ctx {
   int pp_speckle_size = 0;                   // cspm_set_pp_speckle: 0 = no speckle filter (no launch, no scratch)
   double pp_speckle_diff = 1.0;
   int *d_speckle = nullptr;                  // speckle filter: per view n parents, then per view n counts, then the removed-pixel counter; allocated by the first filtered call and kept
+  int pp_median = 0;                         // cspm_set_pp_median: radius of the final median filter, 0 = none (no launch, no second buffer)
+  uint8_t *d_med8[2] = {nullptr, nullptr};   // median filter: the second 8-bit buffer per view; swapped with d_dis by every filtered call.  Allocated by the first one and kept
+  double *d_med64 = nullptr;                 // median filter: the second pair of f64 maps (one allocation, like d_pp); swapped with d_pp[0]
   bool speckle_ran = false;                  // the last post-processing enqueued ran the filter (CSPM_OPT_PP_SPECKLE_REMOVED reads its counter)
   // persistent raster sweep (k_spatial_sweep)
   unsigned int *d_sweep_ctrl = nullptr, *d_sweep_start = nullptr;
@@ -363,6 +367,9 @@ void free_field(cspm_ctx *c) {
   dfree(c->d_todo);
   dfree(c->d_speckle);
   c->speckle_ran = false;
+  dfree(c->d_med8[0]);
+  dfree(c->d_med8[1]);
+  dfree(c->d_med64);
   dfree(c->d_pp[0]);  // one allocation holds both maps
   c->d_pp[1] = nullptr;
   dfree(c->d_rowq);
@@ -1294,8 +1301,8 @@ int speckle_enqueue(cspm_ctx *c, const T *d0, const T *d1, double thr) {
   return CSPM_OK;
 }
 
-// PlaneToDisp + PostProcessing (cs_patchmatch.cc:103-107, 508-588) enqueued on the ctx stream; results in c->d_dis[v]
-int postprocess_enqueue(cspm_ctx *c, int dis_scale) {
+// the reference's steps of postprocess_enqueue, timed as one CSPM_K_POST bracket
+int postprocess_steps(cspm_ctx *c, int dis_scale) {
   const Pm pm = field_pm(c);
   const long long n = (long long)c->W * c->H;
   const Level &L0 = c->cost.lv[0];
@@ -1319,6 +1326,66 @@ int postprocess_enqueue(cspm_ctx *c, int dis_scale) {
   return CSPM_OK;
 }
 
+// The median filter's one launch (cspm_median.h) for `views` views (1 or 2) of w x h, 1 <= r <= CSPM_MEDIAN_MAX_RADIUS: radii 1 .. 3 have
+// kernels of their own, the rest share the one that takes the radius as an argument.
+inline unsigned median_tiles(int w, int h) { return (unsigned)(((w + kMedTileW - 1) / kMedTileW) * (long long)((h + kMedTileH - 1) / kMedTileH)); }
+void median_launch_u8(hipStream_t stream, const uint8_t *const *src, uint8_t *const *dst, int views, size_t sstride, size_t dstride, int w, int h, int cn,
+                      int r) {
+  const dim3 grid(median_tiles(w, h), (unsigned)cn, (unsigned)views), block(kMedBlock);
+  const int u = views - 1;
+#define CSPM_MEDIAN_U8(RT) hipLaunchKernelGGL(k_median_u8<RT>, grid, block, 0, stream, src[0], src[u], dst[0], dst[u], sstride, dstride, w, h, cn, r)
+  if (r == 1) CSPM_MEDIAN_U8(1);
+  else if (r == 2) CSPM_MEDIAN_U8(2);
+  else if (r == 3) CSPM_MEDIAN_U8(3);
+  else CSPM_MEDIAN_U8(0);
+#undef CSPM_MEDIAN_U8
+}
+void median_launch_f64(hipStream_t stream, const double *const *src, double *const *dst, int views, int w, int h, int r) {
+  const dim3 grid(median_tiles(w, h), (unsigned)views), block(kMedBlock);
+  const int u = views - 1;
+  typedef unsigned long long Bits;
+#define CSPM_MEDIAN_F64(RT) \
+  hipLaunchKernelGGL(k_median_f64<RT>, grid, block, 0, stream, (const Bits *)src[0], (const Bits *)src[u], (Bits *)dst[0], (Bits *)dst[u], w, h, r)
+  if (r == 1) CSPM_MEDIAN_F64(1);
+  else if (r == 2) CSPM_MEDIAN_F64(2);
+  else if (r == 3) CSPM_MEDIAN_F64(3);
+  else CSPM_MEDIAN_F64(0);
+#undef CSPM_MEDIAN_F64
+}
+
+// PostProcessing's last step: M8 of c->d_dis into the second buffers, which then are the maps; nothing at all when off
+int median_u8_enqueue(cspm_ctx *c) {
+  if (c->pp_median == 0) return CSPM_OK;
+  for (int v = 0; v < 2; ++v)
+    if (!c->d_med8[v])
+      if (int rc = dalloc(c, &c->d_med8[v], (size_t)c->W * c->H, nullptr)) return rc;
+  Timed t(c, CSPM_K_POST, 0);
+  median_launch_u8(c->stream, c->d_dis, c->d_med8, 2, (size_t)c->W, (size_t)c->W, c->W, c->H, 1, c->pp_median);
+  HIPCHK(c, hipGetLastError());
+  for (int v = 0; v < 2; ++v) std::swap(c->d_dis[v], c->d_med8[v]);
+  return CSPM_OK;
+}
+// the same on the sub-pixel maps: M64 of c->d_pp into the second pair
+int median_f64_enqueue(cspm_ctx *c) {
+  if (c->pp_median == 0) return CSPM_OK;
+  const size_t n = (size_t)c->W * c->H;
+  if (!c->d_med64)
+    if (int rc = dalloc(c, &c->d_med64, 2 * n, nullptr)) return rc;
+  double *dst[2] = {c->d_med64, c->d_med64 + n};
+  Timed t(c, CSPM_K_POST, 0);
+  median_launch_f64(c->stream, c->d_pp, dst, 2, c->W, c->H, c->pp_median);
+  HIPCHK(c, hipGetLastError());
+  std::swap(c->d_pp[0], c->d_med64);
+  c->d_pp[1] = c->d_pp[0] + n;
+  return CSPM_OK;
+}
+
+// PlaneToDisp + PostProcessing (cs_patchmatch.cc:103-107, 508-588) enqueued on the ctx stream; results in c->d_dis[v]
+int postprocess_enqueue(cspm_ctx *c, int dis_scale) {
+  if (int rc = postprocess_steps(c, dis_scale)) return rc;
+  return median_u8_enqueue(c);
+}
+
 // PlaneToDisp of one view into a device buffer (u8, packed W*H), enqueued on the ctx stream
 int enqueue_disp_u8(cspm_ctx *c, int view, int dis_scale, void *d_out) {
   const Pm pm = field_pm(c);
@@ -1333,7 +1400,7 @@ int enqueue_disp_u8(cspm_ctx *c, int view, int dis_scale, void *d_out) {
 
 // sub-pixel PostProcessing (cspm_pp.h) enqueued on the ctx stream; maps in c->d_pp[v], flags in c->d_valid[v].
 // The 8-bit path's maps (c->d_dis) are not touched; the flags and the work list are scratch of whichever path runs.
-int postprocess_f64_enqueue(cspm_ctx *c) {
+int postprocess_f64_steps(cspm_ctx *c) {
   const long long n = (long long)c->W * c->H;
   if (!c->d_pp[0]) {
     int rc = dalloc(c, &c->d_pp[0], 2 * (size_t)n, nullptr);
@@ -1356,6 +1423,10 @@ int postprocess_f64_enqueue(cspm_ctx *c) {
                      c->W, c->H, c->d_valid[0], c->d_valid[1], c->d_lut, c->d_pp[0], c->d_pp[1], c->d_todo, todo_cnt);
   HIPCHK(c, hipGetLastError());
   return CSPM_OK;
+}
+int postprocess_f64_enqueue(cspm_ctx *c) {
+  if (int rc = postprocess_f64_steps(c)) return rc;
+  return median_f64_enqueue(c);
 }
 
 // An asynchronous output, enqueued on the ctx stream: the map of one view, or both post-processed maps copied to the caller's buffers.
@@ -1757,6 +1828,17 @@ int cspm_set_pp_speckle(cspm_ctx *c, int max_size, double max_diff) {
   c->pp_speckle_diff = max_diff;
   return CSPM_OK;
 }
+int cspm_set_pp_median(cspm_ctx *c, int r) {
+  if (!c) return CSPM_ERR_ARG;
+  if (r < 0 || r > CSPM_MEDIAN_MAX_RADIUS) return fail(c, CSPM_ERR_ARG, "median filter: radius 0 (off) .. CSPM_MEDIAN_MAX_RADIUS");
+  c->pp_median = r;
+  return CSPM_OK;
+}
+int cspm_get_pp_median(cspm_ctx *c, int *r) {
+  if (!c || !r) return CSPM_ERR_ARG;
+  *r = c->pp_median;
+  return CSPM_OK;
+}
 int cspm_get_pp_speckle(cspm_ctx *c, int *max_size, double *max_diff) {
   if (!c) return CSPM_ERR_ARG;
   if (max_size) *max_size = c->pp_speckle_size;
@@ -2137,6 +2219,48 @@ int cspm_fit_planes_host(int device, const double *disp, const uint8_t *valid, c
     return S.done(fail(c, CSPM_ERR_HIP, "plane fit kernel failed"));
   for (size_t i = 0; i < n; ++i)
     for (int k = 0; k < 6; ++k) np_out[6 * i + k] = hst[k * n + i];
+  return S.done(CSPM_OK);
+}
+
+// the median filter alone on caller memory: the launch PostProcessing enqueues, on one image
+int cspm_median_filter_u8_host(int device, const uint8_t *src, size_t src_stride, int w, int h, int channels, int r, uint8_t *dst, size_t dst_stride) {
+  if (!src || !dst || src == dst || w < 1 || h < 1 || channels < 1 || channels > 4 || r < 1 || r > CSPM_MEDIAN_MAX_RADIUS)
+    return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
+  const size_t row = (size_t)w * channels;
+  if (src_stride < row || dst_stride < row) return fail(nullptr, CSPM_ERR_ARG, "a stride is below w * channels");
+  Scratch S;
+  int rc = cspm_create(&S.c, device);
+  if (rc) return rc;
+  cspm_ctx *c = S.c;
+  uint8_t *ds = nullptr, *dd = nullptr;  // packed rows on the device
+  if ((rc = dalloc(c, &ds, row * h, &S.tmp)) || (rc = dalloc(c, &dd, row * h, &S.tmp))) return S.done(rc);
+  if (hipMemcpy2DAsync(ds, row, src, src_stride, row, (size_t)h, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  const uint8_t *s1[1] = {ds};
+  uint8_t *d1[1] = {dd};
+  median_launch_u8(c->stream, s1, d1, 1, row, row, w, h, channels, r);
+  if (hipGetLastError() != hipSuccess || hipMemcpy2DAsync(dst, dst_stride, dd, row, row, (size_t)h, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, "median filter kernel failed"));
+  return S.done(CSPM_OK);
+}
+
+int cspm_median_filter_f64_host(int device, const double *src, int w, int h, int r, double *dst) {
+  if (!src || !dst || src == dst || w < 1 || h < 1 || r < 1 || r > CSPM_MEDIAN_MAX_RADIUS) return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
+  Scratch S;
+  int rc = cspm_create(&S.c, device);
+  if (rc) return rc;
+  cspm_ctx *c = S.c;
+  const size_t n = (size_t)w * h;
+  double *ds = nullptr, *dd = nullptr;
+  if ((rc = dalloc(c, &ds, n, &S.tmp)) || (rc = dalloc(c, &dd, n, &S.tmp))) return S.done(rc);
+  if (hipMemcpyAsync(ds, src, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  const double *s1[1] = {ds};
+  double *d1[1] = {dd};
+  median_launch_f64(c->stream, s1, d1, 1, w, h, r);
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(dst, dd, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, "median filter kernel failed"));
   return S.done(CSPM_OK);
 }
 

@@ -25,5 +25,10 @@ inline int Round2Int(double d) {
   std::memcpy(&lo, &d, sizeof lo);
   return lo;
 }
+// commfunc.cc:11-25, `MedianFilter(in, out, r)` on a Mat of depth 8U with 1 .. 4 channels, in place or not: the median of the
+// (2r+1) x (2r+1) window with the border replicated (include/cspm.h M8), computed on the calling thread's device; r in 1 .. 7.
+// Throws std::runtime_error for another depth, an empty image or a radius outside the range.  Defined in host_impl.cc.
+void MedianFilter(const Mat &src, Mat &dst, int r);
+
 // commfunc.h:129-145: a single wrap-around
 inline int HandleBorder(const int &loc, const int &size) { return loc < 0 ? loc + size : (loc >= size ? loc - size : loc); }

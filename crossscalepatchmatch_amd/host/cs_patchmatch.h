@@ -85,6 +85,11 @@ class CSPatchMatch {
   // here and written into the cost object's context by every post-processing of this object.  Throws for max_size < 0 and for a
   // max_diff that is negative or not finite.
   void SetSpeckleFilter(int max_size, double max_diff);
+  // median filter of PostProcessing (an addition; include/cspm.h cspm_set_pp_median): the call the reference keeps commented out at the
+  // end of PostProcessing (cs_patchmatch.cc:573-575), as the last step after the weighted median, on every pixel of both views -- M8 on
+  // use_pp's 8-bit maps, M64 on PostProcessedDisparity's.  r == 0 (the default) = no filter.  Kept here and written into the cost
+  // object's context by every post-processing of this object.  Throws for r outside 0 .. CSPM_MEDIAN_MAX_RADIUS.
+  void SetMedianFilter(int r);
 
  private:
   Mat img_[kViewNum], dis_[kViewNum];
@@ -97,7 +102,8 @@ class CSPatchMatch {
   bool pending_pp_;
   int speckle_size_;
   double speckle_diff_;
-  void ApplySpeckleFilter(cspm_ctx *ctx) const;
+  int median_r_;
+  void ApplyPostFilters(cspm_ctx *ctx) const;
   std::vector<Plane> start_planes_[kViewNum];  // SetPlanes, not yet written into a context
   struct Candidates {  // AddCandidates / AddCandidateDisparity, not yet merged: 6 doubles per pixel and a mask (empty: every pixel)
     std::vector<double> norm_param;

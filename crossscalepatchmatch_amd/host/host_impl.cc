@@ -273,7 +273,7 @@ double DevicePlaneCost::GetPlaneCost(const int &ref_x, const int &ref_y, const P
 
 // ---------------------------------------------------------------- CSPatchMatch (cs_patchmatch.cc:3-109)
 CSPatchMatch::CSPatchMatch(const Mat &l_img, const Mat &r_img, const int &max_dis, const int &dis_scale)
-    : max_dis_(max_dis), dis_scale_(dis_scale), seed_(12345), schedule_(CSPM_SCHED_RASTER), rb_rounds_(1), rb_neighbours_(4), last_ctx_(NULL), own_ctx_(NULL), pending_ctx_(NULL), pending_pp_(false), speckle_size_(0), speckle_diff_(1.0) {
+    : max_dis_(max_dis), dis_scale_(dis_scale), seed_(12345), schedule_(CSPM_SCHED_RASTER), rb_rounds_(1), rb_neighbours_(4), last_ctx_(NULL), own_ctx_(NULL), pending_ctx_(NULL), pending_pp_(false), speckle_size_(0), speckle_diff_(1.0), median_r_(0) {
   CV_Assert(l_img.type() == CV_8UC3 && r_img.type() == CV_8UC3);  // cs_patchmatch.cc:8
   img_[kLeft] = l_img.clone();
   img_[kRight] = r_img.clone();
@@ -329,7 +329,7 @@ void CSPatchMatch::PatchMatchForeign(int iter_num, const IPlaneCost *plane_cost,
   }
   if (use_pp) {  // PostProcessing reads the level-0 images of a cost object: the cheapest one provides them
     check(cspm_build_cost_img(ctx, max_dis_, 35, 0, 0.0), ctx, "cspm_build_cost_img");
-    ApplySpeckleFilter(ctx);
+    ApplyPostFilters(ctx);
     check(cspm_postprocess(ctx, dis_scale_, dis_[kLeft].data, dis_[kRight].data, dis_[kLeft].step), ctx, "cspm_postprocess");
   } else {
     for (int v = 0; v < kViewNum; ++v)
@@ -370,7 +370,7 @@ void CSPatchMatch::PatchMatchEnd() {
   pending_ctx_ = NULL;
   if (!DevicePlaneCost::is_live(ctx)) throw std::runtime_error("CSPatchMatch::PatchMatchEnd: the plane cost the run was started on has been deleted");
   if (pending_pp_) {  // PostProcessing (cs_patchmatch.cc:105-107)
-    ApplySpeckleFilter(ctx);
+    ApplyPostFilters(ctx);
     check(cspm_postprocess(ctx, dis_scale_, dis_[kLeft].data, dis_[kRight].data, dis_[kLeft].step), ctx, "cspm_postprocess");
   } else {            // PlaneToDisp (cs_patchmatch.cc:103)
     for (int v = 0; v < kViewNum; ++v)
@@ -564,7 +564,7 @@ void CSPatchMatch::PostProcessedDisparity(std::vector<double> *l_out, std::vecto
   std::vector<double> unwanted;  // the library post-processes both views in one call
   std::vector<double> *outs[kViewNum] = {l_out ? l_out : &unwanted, r_out ? r_out : &unwanted};
   for (int v = 0; v < kViewNum; ++v) outs[v]->resize((size_t)wid_ * hei_);
-  ApplySpeckleFilter(last_ctx_);
+  ApplyPostFilters(last_ctx_);
   check(cspm_postprocess_f64(last_ctx_, outs[kLeft]->data(), outs[kRight]->data(), NULL, NULL), last_ctx_, "cspm_postprocess_f64");
 }
 
@@ -576,8 +576,23 @@ void CSPatchMatch::SetSpeckleFilter(int max_size, double max_diff) {
 }
 
 // a context serves one cost object after the other (and, parked, one pair after the other): every post-processing sets what it wants
-void CSPatchMatch::ApplySpeckleFilter(cspm_ctx *ctx) const {
+void CSPatchMatch::ApplyPostFilters(cspm_ctx *ctx) const {
   check(cspm_set_pp_speckle(ctx, speckle_size_, speckle_diff_), ctx, "cspm_set_pp_speckle");
+  check(cspm_set_pp_median(ctx, median_r_), ctx, "cspm_set_pp_median");
+}
+
+void CSPatchMatch::SetMedianFilter(int r) {
+  if (r < 0 || r > CSPM_MEDIAN_MAX_RADIUS) throw std::runtime_error("CSPatchMatch::SetMedianFilter: a radius of 0 (off) .. 7 expected");
+  median_r_ = r;
+}
+
+// commfunc.cc:11-25 over the device filter (include/cspm.h M8).  src and dst may be the same Mat, as in the reference's own call.
+void MedianFilter(const Mat &src, Mat &dst, int r) {
+  CV_Assert(src.depth() == CV_8U);
+  Mat tmp(src.rows, src.cols, src.type());
+  check(cspm_median_filter_u8_host(DeviceSlot::current().device(), src.data, src.step, src.cols, src.rows, src.channels(), r, tmp.data, tmp.step), NULL,
+        "MedianFilter");
+  dst = tmp;
 }
 
 void CSPatchMatch::planes(const RefView &view, std::vector<Plane> *out, std::vector<double> *min_cost) const {

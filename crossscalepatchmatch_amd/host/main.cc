@@ -72,6 +72,9 @@ DEFINE_int32(pp_speckle_size, 0, "with --use_pp: speckle filter between the left
                                  "8-bit maps and, with --pp_pfm, to the PFM maps");
 DEFINE_double(pp_speckle_diff, 1.0, "with --pp_speckle_size: two neighbouring pixels belong to one component when their disparities differ by at "
                                     "most this much (in disparity units, before --dis_scale)");
+DEFINE_int32(pp_median, 0, "with --use_pp: radius of a median filter as the last post-processing step, on every pixel of both views (a "
+                           "(2R+1) x (2R+1) window, border replicated); 0 = no filter, at most 7.  Applies to the 8-bit maps and, with "
+                           "--pp_pfm, to the PFM maps");
 DEFINE_string(batch_list, "", "text file, one stereo pair per line: l_img r_img l_dis r_dis [l_pfm r_pfm]; all pairs run with the "
                               "matching flags of this command line on one device context (buffers are reused between pairs). A pair "
                               "that fails is reported and the batch goes on; the exit code is non-zero if any pair failed");
@@ -141,6 +144,7 @@ void begin(PairRun &p, CCMethod *cost_fn) {
     p.matcher.reset(new CSPatchMatch(p.left, p.right, FLAGS_max_dis, FLAGS_dis_scale));
     p.matcher->set_seed(static_cast<uint64_t>(FLAGS_seed));
     p.matcher->SetSpeckleFilter(FLAGS_pp_speckle_size, FLAGS_pp_speckle_diff);
+    p.matcher->SetMedianFilter(FLAGS_pp_median);
     if (FLAGS_schedule == "diffuse") p.matcher->set_schedule(CSPM_SCHED_DIFFUSE, 1, FLAGS_neighbours);
     else p.matcher->set_schedule(FLAGS_schedule == "redblack" ? 1 : 0);
     cspm_fit_params fit;
@@ -343,6 +347,14 @@ int run() {
   }
   if (FLAGS_pp_speckle_size < 0 || !(FLAGS_pp_speckle_diff >= 0.0) || !std::isfinite(FLAGS_pp_speckle_diff)) {
     cout << "Error: --pp_speckle_size must be >= 0 and --pp_speckle_diff finite and >= 0\n";
+    return EXIT_FAILURE;
+  }
+  if (FLAGS_pp_median != 0 && !FLAGS_use_pp) {
+    cout << "Error: --pp_median filters the post-processed maps and needs --use_pp\n";
+    return EXIT_FAILURE;
+  }
+  if (FLAGS_pp_median < 0 || FLAGS_pp_median > CSPM_MEDIAN_MAX_RADIUS) {
+    cout << "Error: --pp_median must be 0 .. " << CSPM_MEDIAN_MAX_RADIUS << " (got " << FLAGS_pp_median << ")\n";
     return EXIT_FAILURE;
   }
   if (!FLAGS_ca_name.empty() && ca_method(FLAGS_ca_name) < 0) {  // checked before anything opens a device

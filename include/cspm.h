@@ -409,6 +409,30 @@ int cspm_get_pp_speckle(cspm_ctx *ctx, int *max_size, double *max_diff);
 int cspm_filter_speckles_host(int device, const double *disp, const uint8_t *valid, int w, int h, int max_size, double max_diff,
                               uint8_t *valid_out, int32_t *size_out);
 
+/* median filter (an addition): the reference's MedianFilter (commfunc.cc:11-25; the call PostProcessing keeps
+ * commented out, cs_patchmatch.cc:573-575), restated from its behaviour.  Window of radius r: the (2r+1)^2 taps
+ * D[clamp(y+j, 0, h-1)][clamp(x+i, 0, w-1)], i, j in -r .. r (the border is replicated), defined for every w, h >= 1.
+ *   M8(D, r), 8-bit, cn interleaved channels: out[y][x][c] = the tap of 0-based rank 2r^2 + 2r among the window's values of channel c.
+ *   M64(D, r), f64: a NaN tap does not vote; a NaN centre stays as it is (the same bits); otherwise, with n >= 1 voting taps, the tap
+ *     of 0-based rank (n - 1) / 2 (integer division: the lower median) in the total order of the order-preserving 64-bit key of the
+ *     bit pattern (-inf < finite < +inf, -0.0 < +0.0).  The output is a tap's own bits: nothing is averaged or rounded.  Without
+ *     NaNs the rank is 2r^2 + 2r, and M64 of integer-valued data equals M8.
+ * Both read a snapshot, never their own output. */
+#define CSPM_MEDIAN_MAX_RADIUS 7
+/* M8 / M64 alone on caller memory, no context needed, synchronous.  u8: channels 1 .. 4, strides in bytes and >= w * channels; f64:
+ * packed w*h maps.  r in 1 .. CSPM_MEDIAN_MAX_RADIUS.  CSPM_ERR_ARG for a radius or channels outside the range, a NULL buffer, a
+ * stride below w * channels, w or h < 1, or src == dst. */
+int cspm_median_filter_u8_host(int device, const uint8_t *src, size_t src_stride, int w, int h, int channels, int r, uint8_t *dst,
+                               size_t dst_stride);
+int cspm_median_filter_f64_host(int device, const double *src, int w, int h, int r, double *dst);
+/* the filter as the LAST step of all four post-processing entries above, after the weighted median, on every pixel of both views:
+ * cspm_postprocess and cspm_postprocess_device run M8 (one channel) on the 8-bit maps, the two f64 entries M64 on the f64 maps; the
+ * consistency masks cspm_postprocess_f64 returns are not changed.  r = 0 (the default) = off: no launch, no memory, today's bytes.
+ * The filter writes into a second buffer per view, which then is the map; it is allocated by the first filtered call and kept with the
+ * plane field.  Timed under CSPM_K_POST as a bracket of its own.  CSPM_ERR_ARG for r outside 0 .. CSPM_MEDIAN_MAX_RADIUS or a NULL r. */
+int cspm_set_pp_median(cspm_ctx *ctx, int r);
+int cspm_get_pp_median(cspm_ctx *ctx, int *r);
+
 /* ---- CSPatchMatch::PatchMatch over a FOREIGN IPlaneCost (plane_cost/i_plane_cost.h:28-33) ------------------------------
  * Any object with a GetPlaneCost(x, y, plane, view) that is not one of this library's device costs: the reference drives it
  * through the virtual call (call sites cs_patchmatch.cc:144,181,191,200,208,269,334).  Here the device keeps the plane field,
