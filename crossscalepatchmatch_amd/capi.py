@@ -37,6 +37,7 @@ OPT_CENGRD_FUSED_ACTIVE = 20 # read only: the current cost object is a fused CEN
 OPT_PP_SPECKLE_REMOVED = 21  # read only, synchronises: pixels the speckle filter removed from both masks in the last post-processing
 MEDIAN_MAX_RADIUS = 7  # CSPM_MEDIAN_MAX_RADIUS: the median filter's window is at most 15 x 15
 CA_BOX, CA_GF, CA_BF = 0, 1, 2  # cost aggregation: BoxCA, GFCA, BFCA (ca_filter/)
+GEOM_RAW, GEOM_PP = 0, 1  # cspm_reproject's source: the stored field's a*x+b*y+c, or the sub-pixel post-processed map
 CENGRD_KAPPA, CENGRD_TAU = 0.0625, 32.0  # CSPM_CENGRD_KAPPA / CSPM_CENGRD_TAU: cell = fma(KAPPA, min(H, TAU), G)
 
 # every symbol include/cspm.h declares
@@ -55,6 +56,7 @@ SYMBOLS = [
     "cspm_set_pp_speckle", "cspm_get_pp_speckle", "cspm_filter_speckles_host",
     "cspm_median_filter_u8_host", "cspm_median_filter_f64_host", "cspm_set_pp_median", "cspm_get_pp_median",
     "cspm_fit_default_params", "cspm_fit_planes_host", "cspm_fit_planes",
+    "cspm_geom_default_params", "cspm_reproject_host", "cspm_reproject", "cspm_reproject_device",
 ]
 
 
@@ -71,6 +73,22 @@ class PmParams(C.Structure):
 class FitParams(C.Structure):
     """struct cspm_fit_params"""
     _fields_ = [("radius", C.c_int), ("max_diff", C.c_double), ("min_support", C.c_int), ("use_guide", C.c_int)]
+
+
+class Calib(C.Structure):
+    """struct cspm_calib: a rectified pair (focal length in pixels, principal point of view 0, baseline, doffs = cx1 - cx0)"""
+    _fields_ = [("f", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("baseline", C.c_double), ("doffs", C.c_double)]
+
+
+class GeomParams(C.Structure):
+    """struct cspm_geom_params"""
+    _fields_ = [("z_near", C.c_double), ("z_far", C.c_double), ("min_cos", C.c_double), ("left_frame", C.c_int), ("consistent_only", C.c_int)]
+
+
+# struct cspm_point: one 32-byte cloud record
+Point = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
+                  ("b", "u1"), ("g", "u1"), ("r", "u1"), ("a", "u1"), ("pixel", "<u4")])
+assert Point.itemsize == 32
 
 
 def library_path():
@@ -101,6 +119,7 @@ def load_library():
     llp = C.POINTER(C.c_longlong)
     pp = C.POINTER(PmParams)
     fp = C.POINTER(FitParams)
+    kp, gp, up = C.POINTER(Calib), C.POINTER(GeomParams), C.POINTER(C.c_uint)
     sig = {
         "cspm_device_count": (C.c_int, []),
         "cspm_create": (C.c_int, [C.POINTER(vp), C.c_int]),
@@ -171,6 +190,10 @@ def load_library():
         "cspm_fit_default_params": (C.c_int, [fp]),
         "cspm_fit_planes_host": (C.c_int, [C.c_int, dp, u8p, u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, fp, dp, u8p]),
         "cspm_fit_planes": (C.c_int, [vp, fp, C.c_int]),
+        "cspm_geom_default_params": (C.c_int, [gp]),
+        "cspm_reproject_host": (C.c_int, [C.c_int, kp, gp, C.c_int, dp, u8p, dp, dp, u8p, C.c_size_t, C.c_int, C.c_int, dp, dp, dp, u8p, vp, C.c_size_t, up]),
+        "cspm_reproject": (C.c_int, [vp, C.c_int, C.c_int, kp, gp, fp, dp, dp, dp, u8p, vp, C.c_size_t, up]),
+        "cspm_reproject_device": (C.c_int, [vp, C.c_int, C.c_int, kp, gp, fp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
     }
     assert sorted(sig) == sorted(SYMBOLS)
     for name, (res, args) in sig.items():
@@ -487,6 +510,42 @@ class StereoContext:
         """the same with device-resident outputs (packed h*w f64 each; asynchronous on the context's stream)"""
         self._chk(self.L.cspm_postprocess_f64_device(self.p, C.c_void_p(d_l_ptr), C.c_void_p(d_r_ptr)))
 
+    # ---- reprojection (DESIGN.md section 19) ----
+    def reproject(self, view, calib, source=GEOM_RAW, fit=None, dense=True, cloud=True, cloud_cap=None, **params):
+        """metric geometry of one view of the stored plane field (cspm_reproject): calib a Calib or (f, cx, cy, baseline, doffs);
+        source GEOM_RAW (the field's own disparities) or GEOM_PP (the sub-pixel post-processed map); fit: None = the field's slopes, a
+        dict of plane-fit parameters ({} = the defaults) = slopes fitted to the map; params: z_near, z_far, min_cos, left_frame,
+        consistent_only.  Returns a dict: count always; with dense depth (h, w), xyz (3, h, w), normal (3, h, w), keep (h, w) uint8;
+        with cloud the Point records of the kept pixels in raster order (at most cloud_cap of them; None = all)."""
+        k, g = calib_struct(calib), geom_params(**params)
+        f = fit_params(**dict(fit)) if fit is not None else None
+        n = self.w * self.h
+        out = {}
+        if dense:
+            out.update(depth=np.zeros((self.h, self.w)), xyz=np.zeros((3, self.h, self.w)), normal=np.zeros((3, self.h, self.w)),
+                       keep=np.zeros((self.h, self.w), np.uint8))
+        cap = n if cloud_cap is None else int(cloud_cap)
+        pts = np.zeros(cap, Point) if cloud else None
+        count = C.c_uint(0)
+        self._chk(self.L.cspm_reproject(self.p, int(view), int(source), C.byref(k), C.byref(g), C.byref(f) if f is not None else None,
+                                        _dp(out["depth"]) if dense else None, _dp(out["xyz"]) if dense else None,
+                                        _dp(out["normal"]) if dense else None, _u8(out["keep"]) if dense else None,
+                                        C.c_void_p(pts.ctypes.data) if cloud else None, cap if cloud else 0, C.byref(count)))
+        out["count"] = count.value
+        if cloud:
+            out["cloud"] = pts[:min(count.value, cap)]
+        return out
+
+    def reproject_device(self, view, calib, source=GEOM_RAW, fit=None, d_depth=0, d_xyz=0, d_normal=0, d_keep=0, d_cloud=0, cloud_cap=0, d_count=0,
+                         **params):
+        """the same with device pointers (integers; 0 = not requested) for every output and a device unsigned int for the count;
+        asynchronous on the context's stream (cspm_reproject_device)"""
+        k, g = calib_struct(calib), geom_params(**params)
+        f = fit_params(**dict(fit)) if fit is not None else None
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._chk(self.L.cspm_reproject_device(self.p, int(view), int(source), C.byref(k), C.byref(g), C.byref(f) if f is not None else None,
+                                               vp(d_depth), vp(d_xyz), vp(d_normal), vp(d_keep), vp(d_cloud), int(cloud_cap), vp(d_count)))
+
     # ---- measurement ----
     def enable_timing(self, on=True):
         self._chk(self.L.cspm_enable_timing(self.p, int(on)))
@@ -578,6 +637,71 @@ def fit_planes_host(disp, valid=None, guide=None, max_dis=0, device=0, **params)
     if rc != 0:
         raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
     return planes, fitted
+
+
+def calib_struct(calib):
+    """a Calib from a Calib or a sequence (f, cx, cy, baseline, doffs)"""
+    if isinstance(calib, Calib):
+        return calib
+    f, cx, cy, baseline, doffs = (float(t) for t in calib)
+    return Calib(f, cx, cy, baseline, doffs)
+
+
+def geom_params(**params):
+    """struct cspm_geom_params: cspm_geom_default_params with the given fields replaced"""
+    p = GeomParams()
+    rc = load_library().cspm_geom_default_params(C.byref(p))
+    assert rc == 0
+    for k, v in params.items():
+        if k not in ("z_near", "z_far", "min_cos", "left_frame", "consistent_only"):
+            raise TypeError(f"unknown reprojection parameter {k!r}")
+        setattr(p, k, int(v) if k in ("left_frame", "consistent_only") else float(v))
+    return p
+
+
+def reproject_host(calib, view, disp, valid=None, slope_a=None, slope_b=None, bgr=None, dense=("depth", "xyz", "normal", "keep"), cloud=True,
+                   cloud_cap=None, count=True, device=0, out=None, **params):
+    """G alone on host maps (cspm_reproject_host): disp (h, w) f64, valid (h, w) or None, slopes (h, w) f64 or None,
+    bgr (h, w, 3) uint8 or None.  dense: the dense outputs to compute (normal is dropped without slopes); cloud / cloud_cap / count as
+    for StereoContext.reproject.  out: a dict of preallocated arrays to write into instead of fresh ones (tests poison them).
+    Returns a dict with the requested arrays, `count` and `cloud`."""
+    L = load_library()
+    d = np.ascontiguousarray(disp, dtype=np.float64)
+    assert d.ndim == 2
+    h, w = d.shape
+    m = None if valid is None else np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+    a = None if slope_a is None else np.ascontiguousarray(slope_a, dtype=np.float64)
+    b = None if slope_b is None else np.ascontiguousarray(slope_b, dtype=np.float64)
+    img = None if bgr is None else np.ascontiguousarray(bgr, dtype=np.uint8)
+    assert (m is None or m.shape == d.shape) and (a is None or a.shape == d.shape) and (b is None or b.shape == d.shape)
+    assert img is None or img.shape == (h, w, 3)
+    k, g = calib_struct(calib), geom_params(**params)
+    res = dict(out or {})
+    shapes = {"depth": (h, w), "xyz": (3, h, w), "normal": (3, h, w), "keep": (h, w)}
+    for name in dense:
+        if name == "normal" and a is None and (out is None or "normal" not in out):
+            continue
+        if name not in res:
+            res[name] = np.zeros(shapes[name], np.uint8 if name == "keep" else np.float64)
+    cap = w * h if cloud_cap is None else int(cloud_cap)
+    pts = None
+    if cloud:
+        pts = res.get("cloud_buffer")
+        if pts is None:
+            pts = np.zeros(cap, Point)
+    cnt = C.c_uint(0)
+    ptr = lambda name, f: f(res[name]) if name in res and name in dense else None
+    rc = L.cspm_reproject_host(device, C.byref(k), C.byref(g), int(view), _dp(d), _u8(m) if m is not None else None,
+                               _dp(a) if a is not None else None, _dp(b) if b is not None else None, _u8(img) if img is not None else None, w * 3, w, h,
+                               ptr("depth", _dp), ptr("xyz", _dp), ptr("normal", _dp), ptr("keep", _u8),
+                               C.c_void_p(pts.ctypes.data) if pts is not None else None, cap if pts is not None else 0, C.byref(cnt) if count else None)
+    if rc != 0:
+        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    if count:
+        res["count"] = cnt.value
+    if pts is not None:
+        res["cloud"] = pts[:min(cnt.value, cap)] if count else pts
+    return res
 
 
 def median_filter(device, img, r):

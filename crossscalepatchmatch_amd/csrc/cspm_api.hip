@@ -15,6 +15,7 @@
 #include "cspm_speckle.h"
 #include "cspm_median.h"
 #include "cspm_fit.h"
+#include "cspm_geom.h"
 #include "cspm_ca.h"
 
 using namespace cspm;
@@ -198,6 +199,9 @@ struct cspm_ctx {
   double *warm_snap = nullptr;        // the starting field of the last warm run (both views, 7 arrays each), kept with the field
   double *cand_mem = nullptr;         // cspm_merge_planes_host: one view's candidate planes (6 arrays) and, behind them, its mask bytes; allocated by the first such call and kept with the field
   double *fit_mem = nullptr;          // cspm_fit_planes: both views' disparity snapshots (2 arrays) and, behind them, the exp(-k/10) table; allocated by the first such call and kept with the field
+  double *geom_disp = nullptr;        // cspm_reproject: the CSPM_GEOM_RAW disparity map (1 array); allocated by the first such call and kept with the field
+  double *geom_fit = nullptr;         // cspm_reproject with a fit: the fitted planes (6 arrays) and, behind them, the exp(-k/10) table
+  unsigned int *geom_counts = nullptr;  // cspm_reproject: the kept pixels per workgroup, then the total
   double *diffuse_snap = nullptr;     // CSPM_SCHED_DIFFUSE: the round's snapshot (both views, the 6 plane arrays each), allocated by the first such propagation and kept with the field
   long long sweep_fallbacks = 0;      // how often that happened (cspm_get_option)
   // CSPatchMatch over a foreign IPlaneCost (cspm_fpm_*): candidate buffers and what the pending batch was
@@ -356,6 +360,9 @@ void free_field(cspm_ctx *c) {
   dfree(c->diffuse_snap);
   dfree(c->cand_mem);
   dfree(c->fit_mem);
+  dfree(c->geom_disp);
+  dfree(c->geom_fit);
+  dfree(c->geom_counts);
   dfree(c->vc.cost);
   dfree(c->vc.c);
   dfree(c->vc.cx);
@@ -1508,6 +1515,106 @@ int with_source(cspm_ctx *dst, cspm_ctx *src, const char *entry, Body body) {
   return rc;
 }
 
+// ---- reprojection (cspm_geom.h) ---------------------------------------------------------------------------
+const cspm_geom_params kGeomDefaults = {0.0, HUGE_VAL, 0.0, 0, 0};
+const char *geom_args_error(const cspm_calib *k, const cspm_geom_params *g, int view) {
+  if (!k) return "reprojection: no calibration";
+  if (!std::isfinite(k->f) || !std::isfinite(k->cx) || !std::isfinite(k->cy) || !std::isfinite(k->baseline) || !std::isfinite(k->doffs))
+    return "reprojection: the calibration must be finite";
+  if (!(k->f > 0.0) || !(k->baseline > 0.0)) return "reprojection: f and baseline must be positive";
+  if (!(g->z_near >= 0.0)) return "reprojection: z_near must be >= 0";
+  if (!(g->z_far >= g->z_near)) return "reprojection: z_far must be >= z_near (it may be +infinity)";
+  if (!(g->min_cos >= 0.0 && g->min_cos <= 1.0)) return "reprojection: min_cos must be in [0, 1]";
+  if (view < 0 || view > 1) return "reprojection: view must be 0 or 1";
+  return nullptr;
+}
+GeomCam geom_cam(const cspm_calib *k, const cspm_geom_params *g, int view) {
+  GeomCam m{};
+  m.f = k->f; m.cy = k->cy; m.baseline = k->baseline; m.doffs = k->doffs;
+  m.cxv = k->cx + (double)view * k->doffs;
+  m.fB = k->f * k->baseline;
+  m.z_near = g->z_near; m.z_far = g->z_far; m.min_cos = g->min_cos;
+  m.add_baseline = (g->left_frame && view == 1) ? 1 : 0;
+  return m;
+}
+inline unsigned geom_blocks(long long n) { return (unsigned)((n + kGeomBlock - 1) / kGeomBlock); }
+// the passes of G on one view: dense planes and keep; then, when a cloud or a count is wanted, the scan and the records.
+// counts: geom_blocks(n) + 1 unsigned ints (the last one receives the total unless d_total names another place)
+void geom_launch(hipStream_t stream, const GeomCam &cam, const GeomIn &in, const GeomOut &out, int w, int h, uint4 *cloud, size_t cap, bool want_count,
+                 unsigned int *counts, unsigned int *d_total) {
+  const long long n = (long long)w * h;
+  const unsigned nb = geom_blocks(n);
+  const bool slopes = in.a != nullptr;
+  const bool compact = cloud != nullptr || want_count;
+  unsigned int *cnt = compact ? counts : nullptr;
+  if (slopes) hipLaunchKernelGGL(k_geom_dense<true>, dim3(nb), dim3(kGeomBlock), 0, stream, cam, in, out, w, n, cnt);
+  else hipLaunchKernelGGL(k_geom_dense<false>, dim3(nb), dim3(kGeomBlock), 0, stream, cam, in, out, w, n, cnt);
+  if (!compact) return;
+  hipLaunchKernelGGL(k_geom_scan, dim3(1), dim3(kGeomScanBlock), 0, stream, counts, (int)nb, d_total ? d_total : counts + nb);
+  const unsigned int cap32 = (unsigned int)std::min<size_t>(cap, (size_t)n);
+  if (!cloud || cap32 == 0) return;
+  if (slopes) hipLaunchKernelGGL(k_geom_cloud<true>, dim3(nb), dim3(kGeomBlock), 0, stream, cam, in, w, n, (const unsigned int *)counts, cloud, cap32);
+  else hipLaunchKernelGGL(k_geom_cloud<false>, dim3(nb), dim3(kGeomBlock), 0, stream, cam, in, w, n, (const unsigned int *)counts, cloud, cap32);
+}
+
+// cspm_reproject / cspm_reproject_device after their argument checks: the pending-run check, the inputs of the chosen source, the
+// passes.  Every output is a device pointer; d_total == nullptr: the total goes behind the context's counts.
+int reproject_enqueue(cspm_ctx *c, int view, int source, const cspm_calib *calib, const cspm_geom_params *g, const cspm_fit_params *fit, const GeomOut &out,
+                      uint4 *cloud, size_t cap, bool want_count, unsigned int *d_total) {
+  int rc = check_sweep(c);  // BEFORE the field is read: a run repeated after a sweep timeout must be the one the geometry comes from
+  if (rc) return rc;
+  const size_t n = (size_t)c->W * c->H;
+  const unsigned nb = geom_blocks((long long)n);
+  if (!c->geom_counts && (rc = dalloc(c, &c->geom_counts, (size_t)nb + 1, nullptr))) return rc;
+  if (source == CSPM_GEOM_RAW && !c->geom_disp && (rc = dalloc(c, &c->geom_disp, n, nullptr))) return rc;
+  if (fit && !c->geom_fit) {
+    if ((rc = dalloc(c, &c->geom_fit, 6 * n + kFitLut, nullptr))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->geom_fit + 6 * n, fit_lut(), sizeof(double) * kFitLut, hipMemcpyHostToDevice, c->stream));
+  }
+  if (source == CSPM_GEOM_PP && (rc = postprocess_f64_enqueue(c))) return rc;
+  const Field &f = c->f[view];
+  GeomIn in{};
+  in.pix = c->img0[view];
+  {
+    Timed t(c, CSPM_K_MISC, (long long)n);
+    if (source == CSPM_GEOM_RAW) {
+      hipLaunchKernelGGL(k_plane_to_disp_f64, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, field_pm(c), view, c->geom_disp);
+      in.disp = c->geom_disp;
+      in.a = f.a; in.b = f.b;
+    } else {
+      in.disp = c->d_pp[view];
+      in.valid = g->consistent_only ? c->d_valid[view] : nullptr;
+      in.a = f.a; in.b = f.b;
+      in.slope_mask = c->d_valid[view];
+    }
+    if (fit) {
+      double *b = c->geom_fit;
+      fit_launch(c->stream, FitIn{in.disp, in.valid, c->img0[view], c->geom_fit + 6 * n}, FitOut{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, nullptr, 0},
+                 c->W, c->H, fit, c->max_dis);
+      in.a = b + 3 * n; in.b = b + 4 * n;
+      in.slope_mask = nullptr;
+    }
+    geom_launch(c->stream, geom_cam(calib, g, view), in, out, c->W, c->H, cloud, cap, want_count, c->geom_counts, d_total);
+  }
+  HIPCHK(c, hipGetLastError());
+  return CSPM_OK;
+}
+// the checks cspm_reproject and cspm_reproject_device share; g and fit are defaulted / validated
+int reproject_check(cspm_ctx *c, int view, int source, const cspm_calib *calib, const cspm_geom_params **g, const cspm_fit_params *fit) {
+  if (!*g) *g = &kGeomDefaults;
+  if (const char *msg = geom_args_error(calib, *g, view)) return fail(c, CSPM_ERR_ARG, msg);
+  if (source != CSPM_GEOM_RAW && source != CSPM_GEOM_PP) return fail(c, CSPM_ERR_ARG, "reprojection: source must be CSPM_GEOM_RAW or CSPM_GEOM_PP");
+  if (fit)
+    if (const char *msg = fit_params_error(fit)) return fail(c, CSPM_ERR_ARG, msg);
+  if (!c->img0[0]) return fail(c, CSPM_ERR_STATE, "cspm_set_images first");
+  if (int rc = need_field(c, "no plane field to reproject (cspm_patchmatch, cspm_local_stereo, cspm_set_planes, ...)")) return rc;
+  if ((source == CSPM_GEOM_PP || fit) && (!c->cost_alloc || !c->cost_ready || c->max_dis < 1))
+    return fail(c, CSPM_ERR_STATE, "reprojection of the post-processed map or with a plane fit needs a cost object (its max_dis)");
+  if ((long long)c->W * c->H >= (1LL << 31)) return fail(c, CSPM_ERR_ARG, "w * h must be below 2^31: cloud records hold 32-bit pixel indices");
+  if (fit && c->H > kFitMaxRows) return fail(c, CSPM_ERR_ARG, "image too high for the plane fit");
+  return CSPM_OK;
+}
+
 // ---- cost aggregation (cspm_ca.h) ----------------------------------------------------------------------------------------------
 constexpr int kCaRadiusBox = 3, kCaRadiusGf = 9;  // BoxCA.cpp:11, GuidedFilter.h:24
 inline int ca_min_size(int method) { return method == CSPM_CA_BOX ? 2 * kCaRadiusBox + 1 : (method == CSPM_CA_GF ? 2 * kCaRadiusGf + 1 : 17); }
@@ -2502,6 +2609,114 @@ int cspm_fit_planes(cspm_ctx *c, const cspm_fit_params *p, int merge) {
     }
   }
   return CSPM_OK;
+}
+
+// G alone on caller maps: the launches cspm_reproject enqueues, on one view.  Arguments first, then the device.
+int cspm_geom_default_params(cspm_geom_params *p) {
+  if (!p) return CSPM_ERR_ARG;
+  *p = kGeomDefaults;
+  return CSPM_OK;
+}
+
+int cspm_reproject_host(int device, const cspm_calib *calib, const cspm_geom_params *g, int view, const double *disp, const uint8_t *valid, const double *slope_a,
+                        const double *slope_b, const uint8_t *bgr, size_t bgr_stride, int w, int h, double *depth_out, double *xyz_out, double *normal_out,
+                        uint8_t *keep_out, cspm_point *cloud_out, size_t cloud_cap, unsigned int *count_out) {
+  if (!g) g = &kGeomDefaults;
+  if (const char *msg = geom_args_error(calib, g, view)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (!disp || w < 1 || h < 1) return fail(nullptr, CSPM_ERR_ARG, "reprojection: no disparity map or an empty one");
+  if ((long long)w * h >= (1LL << 31)) return fail(nullptr, CSPM_ERR_ARG, "w * h must be below 2^31: cloud records hold 32-bit pixel indices");
+  if ((slope_a == nullptr) != (slope_b == nullptr)) return fail(nullptr, CSPM_ERR_ARG, "reprojection: the two slope maps come together or not at all");
+  if (normal_out && !slope_a) return fail(nullptr, CSPM_ERR_ARG, "reprojection: normals need the slope maps");
+  if (bgr && bgr_stride < (size_t)w * 3) return fail(nullptr, CSPM_ERR_ARG, "reprojection: bgr_stride is below 3 * w");
+  Scratch S;
+  int rc = cspm_create(&S.c, device);
+  if (rc) return rc;
+  cspm_ctx *c = S.c;
+  const size_t n = (size_t)w * h;
+  const unsigned nb = geom_blocks((long long)n);
+  const size_t cap = std::min(cloud_out ? cloud_cap : (size_t)0, n);
+  double *dd = nullptr, *da = nullptr, *db = nullptr, *ddepth = nullptr, *dxyz = nullptr, *dnormal = nullptr;
+  uint8_t *dv = nullptr, *dbgr = nullptr, *dkeep = nullptr;
+  uint32_t *dpix = nullptr;
+  unsigned int *dcounts = nullptr;
+  uint4 *dcloud = nullptr;
+  if ((rc = dalloc(c, &dd, n, &S.tmp)) || (rc = dalloc(c, &dcounts, (size_t)nb + 1, &S.tmp)) || (valid && (rc = dalloc(c, &dv, n, &S.tmp))) ||
+      (slope_a && ((rc = dalloc(c, &da, n, &S.tmp)) || (rc = dalloc(c, &db, n, &S.tmp)))) ||
+      (bgr && ((rc = dalloc(c, &dbgr, 3 * n, &S.tmp)) || (rc = dalloc(c, &dpix, n, &S.tmp)))) || (depth_out && (rc = dalloc(c, &ddepth, n, &S.tmp))) ||
+      (xyz_out && (rc = dalloc(c, &dxyz, 3 * n, &S.tmp))) || (normal_out && (rc = dalloc(c, &dnormal, 3 * n, &S.tmp))) ||
+      (keep_out && (rc = dalloc(c, &dkeep, n, &S.tmp))) || (cap && (rc = dalloc(c, &dcloud, 2 * cap, &S.tmp))))
+    return S.done(rc);
+  if (hipMemcpyAsync(dd, disp, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      (valid && hipMemcpyAsync(dv, valid, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+      (slope_a && (hipMemcpyAsync(da, slope_a, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                   hipMemcpyAsync(db, slope_b, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess)) ||
+      (bgr && hipMemcpy2DAsync(dbgr, (size_t)w * 3, bgr, bgr_stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->stream) != hipSuccess))
+    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  if (bgr) hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, dbgr, (size_t)w * 3, w, h, w, 0, dpix);
+  const bool want_count = count_out != nullptr || cloud_out != nullptr;
+  geom_launch(c->stream, geom_cam(calib, g, view), GeomIn{dd, dv, da, db, nullptr, dpix}, GeomOut{ddepth, dxyz, dnormal, dkeep}, w, h, dcloud, cap, want_count,
+              dcounts, nullptr);
+  unsigned int total = 0;
+  if (hipGetLastError() != hipSuccess || (depth_out && hipMemcpyAsync(depth_out, ddepth, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      (xyz_out && hipMemcpyAsync(xyz_out, dxyz, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      (normal_out && hipMemcpyAsync(normal_out, dnormal, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      (keep_out && hipMemcpyAsync(keep_out, dkeep, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      (want_count && hipMemcpyAsync(&total, dcounts + nb, sizeof total, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, "reprojection kernels failed"));
+  const size_t wrote = std::min((size_t)total, cap);
+  if (wrote && hipMemcpy(cloud_out, dcloud, sizeof(cspm_point) * wrote, hipMemcpyDeviceToHost) != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, "cloud download failed"));
+  if (count_out) *count_out = total;
+  return S.done(CSPM_OK);
+}
+
+// G on one view of the stored field (cspm.h "reprojection"): synchronous, host outputs
+int cspm_reproject(cspm_ctx *c, int view, int source, const cspm_calib *calib, const cspm_geom_params *g, const cspm_fit_params *fit, double *depth_out,
+                   double *xyz_out, double *normal_out, uint8_t *keep_out, cspm_point *cloud_out, size_t cloud_cap, unsigned int *count_out) {
+  if (!c) return CSPM_ERR_ARG;
+  int rc = reproject_check(c, view, source, calib, &g, fit);
+  if (rc) return rc;
+  ON_DEVICE(c);
+  const size_t n = (size_t)c->W * c->H;
+  const unsigned nb = geom_blocks((long long)n);
+  const size_t cap = std::min(cloud_out ? cloud_cap : (size_t)0, n);
+  std::vector<void *> tmp;
+  struct Free {
+    std::vector<void *> &t;
+    ~Free() { for (void *p : t) (void)hipFree(p); }
+  } free_tmp{tmp};
+  double *ddepth = nullptr, *dxyz = nullptr, *dnormal = nullptr;
+  uint8_t *dkeep = nullptr;
+  uint4 *dcloud = nullptr;
+  if ((depth_out && (rc = dalloc(c, &ddepth, n, &tmp))) || (xyz_out && (rc = dalloc(c, &dxyz, 3 * n, &tmp))) ||
+      (normal_out && (rc = dalloc(c, &dnormal, 3 * n, &tmp))) || (keep_out && (rc = dalloc(c, &dkeep, n, &tmp))) || (cap && (rc = dalloc(c, &dcloud, 2 * cap, &tmp))))
+    return rc;
+  const bool want_count = count_out != nullptr || cloud_out != nullptr;
+  if ((rc = reproject_enqueue(c, view, source, calib, g, fit, GeomOut{ddepth, dxyz, dnormal, dkeep}, dcloud, cap, want_count, nullptr))) return rc;
+  unsigned int total = 0;
+  if (depth_out) HIPCHK(c, hipMemcpyAsync(depth_out, ddepth, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  if (xyz_out) HIPCHK(c, hipMemcpyAsync(xyz_out, dxyz, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, c->stream));
+  if (normal_out) HIPCHK(c, hipMemcpyAsync(normal_out, dnormal, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, c->stream));
+  if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, dkeep, n, hipMemcpyDeviceToHost, c->stream));
+  if (want_count) HIPCHK(c, hipMemcpyAsync(&total, c->geom_counts + nb, sizeof total, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t wrote = std::min((size_t)total, cap);
+  if (wrote) HIPCHK(c, hipMemcpy(cloud_out, dcloud, sizeof(cspm_point) * wrote, hipMemcpyDeviceToHost));
+  if (count_out) *count_out = total;
+  return CSPM_OK;
+}
+
+// the same with device-resident outputs: asynchronous on the ctx stream behind the pending-run check; not replayed (cspm.h)
+int cspm_reproject_device(cspm_ctx *c, int view, int source, const cspm_calib *calib, const cspm_geom_params *g, const cspm_fit_params *fit, void *d_depth_out,
+                          void *d_xyz_out, void *d_normal_out, void *d_keep_out, void *d_cloud_out, size_t cloud_cap, void *d_count_out) {
+  if (!c) return CSPM_ERR_ARG;
+  int rc = reproject_check(c, view, source, calib, &g, fit);
+  if (rc) return rc;
+  if (d_cloud_out && ((uintptr_t)d_cloud_out & 15u)) return fail(c, CSPM_ERR_ARG, "reprojection: the cloud buffer must be 16-byte aligned");
+  ON_DEVICE(c);
+  return reproject_enqueue(c, view, source, calib, g, fit, GeomOut{(double *)d_depth_out, (double *)d_xyz_out, (double *)d_normal_out, (uint8_t *)d_keep_out},
+                           (uint4 *)d_cloud_out, d_cloud_out ? cloud_cap : 0, d_count_out != nullptr || d_cloud_out != nullptr, (unsigned int *)d_count_out);
 }
 
 int cspm_pm_init_keep(cspm_ctx *c, const cspm_pm_params *p) {

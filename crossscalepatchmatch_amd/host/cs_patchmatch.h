@@ -90,6 +90,14 @@ class CSPatchMatch {
   // use_pp's 8-bit maps, M64 on PostProcessedDisparity's.  r == 0 (the default) = no filter.  Kept here and written into the cost
   // object's context by every post-processing of this object.  Throws for r outside 0 .. CSPM_MEDIAN_MAX_RADIUS.
   void SetMedianFilter(int r);
+  // metric geometry of a view's final plane field (an addition; include/cspm.h "reprojection", cspm_reproject): source CSPM_GEOM_RAW (the
+  // field's own disparities) or CSPM_GEOM_PP (the sub-pixel post-processed map, with this object's speckle and median settings); fit ==
+  // NULL: the field's slopes, else slopes fitted to the map.  depth / keep: wid x hei row-major; xyz / normal: three planes of wid x hei;
+  // cloud: the kept pixels' records in raster order.  Every output may be NULL.  Returns the number of kept pixels.  Reads the device
+  // context of the plane cost the last run used, like disparity(); throws for what the C ABI refuses.
+  size_t Reproject(const RefView &view, const cspm_calib &calib, const cspm_geom_params &params, int source, const cspm_fit_params *fit,
+                   std::vector<double> *depth, std::vector<double> *xyz, std::vector<double> *normal, std::vector<uint8_t> *keep,
+                   std::vector<cspm_point> *cloud) const;
 
  private:
   Mat img_[kViewNum], dis_[kViewNum];

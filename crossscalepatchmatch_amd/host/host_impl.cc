@@ -568,6 +568,26 @@ void CSPatchMatch::PostProcessedDisparity(std::vector<double> *l_out, std::vecto
   check(cspm_postprocess_f64(last_ctx_, outs[kLeft]->data(), outs[kRight]->data(), NULL, NULL), last_ctx_, "cspm_postprocess_f64");
 }
 
+size_t CSPatchMatch::Reproject(const RefView &view, const cspm_calib &calib, const cspm_geom_params &params, int source, const cspm_fit_params *fit,
+                               std::vector<double> *depth, std::vector<double> *xyz, std::vector<double> *normal, std::vector<uint8_t> *keep,
+                               std::vector<cspm_point> *cloud) const {
+  if (!last_ctx_) throw std::runtime_error("CSPatchMatch::Reproject before PatchMatch");
+  if (!DevicePlaneCost::is_live(last_ctx_)) throw std::runtime_error("CSPatchMatch::Reproject: the plane cost PatchMatch ran on has been deleted");
+  const size_t n = (size_t)wid_ * hei_;
+  if (depth) depth->resize(n);
+  if (xyz) xyz->resize(3 * n);
+  if (normal) normal->resize(3 * n);
+  if (keep) keep->resize(n);
+  if (cloud) cloud->resize(n);
+  if (source == CSPM_GEOM_PP) ApplyPostFilters(last_ctx_);
+  unsigned int count = 0;
+  check(cspm_reproject(last_ctx_, view, source, &calib, &params, fit, depth ? depth->data() : NULL, xyz ? xyz->data() : NULL,
+                       normal ? normal->data() : NULL, keep ? keep->data() : NULL, cloud ? cloud->data() : NULL, cloud ? n : 0, &count),
+        last_ctx_, "cspm_reproject");
+  if (cloud) cloud->resize(count);
+  return count;
+}
+
 void CSPatchMatch::SetSpeckleFilter(int max_size, double max_diff) {
   if (max_size < 0 || !(max_diff >= 0.0) || !std::isfinite(max_diff))
     throw std::runtime_error("CSPatchMatch::SetSpeckleFilter: max_size >= 0 and a finite max_diff >= 0 expected");

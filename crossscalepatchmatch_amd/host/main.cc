@@ -3,7 +3,9 @@
 // two 8-bit maps.  Runs on the GPU through the host layer.  Extra flags: --seed --schedule --neighbours --device --iters --ca_name (local stereo)
 // --warm_ca (local stereo, then --iters warm PatchMatch iterations) --l_seed_pfm --r_seed_pfm (disparity maps offered to the random start
 // field as candidates) --seed_ca (local stereo, kept wherever the random start plane costs no less, then --iters iterations)
-// --fit_radius --fit_max_diff --fit_merge (slanted planes fitted to the local-stereo field or to the seed maps before what follows).
+// --fit_radius --fit_max_diff --fit_merge (slanted planes fitted to the local-stereo field or to the seed maps before what follows)
+// --calib --l_ply --r_ply --l_depth_pfm --r_depth_pfm --geom_min_cos --geom_z_far --geom_left_frame --geom_fit_radius (metric depth maps and
+// point clouds of the final plane field; include/cspm.h "reprojection").
 #include "../../include/cspm.h"
 #include "commfunc.h"
 #include "cs_patchmatch.h"
@@ -12,7 +14,9 @@
 #include "plane_cost/grd_pc.h"
 #include "plane_cost/pre_cs_pc.h"
 #include "plane_cost/pre_ss_pc.h"
+#include "calib_io.h"
 #include "pfm_io.h"
+#include "ply_io.h"
 
 #include <atomic>
 #include <cmath>
@@ -75,6 +79,18 @@ DEFINE_double(pp_speckle_diff, 1.0, "with --pp_speckle_size: two neighbouring pi
 DEFINE_int32(pp_median, 0, "with --use_pp: radius of a median filter as the last post-processing step, on every pixel of both views (a "
                            "(2R+1) x (2R+1) window, border replicated); 0 = no filter, at most 7.  Applies to the 8-bit maps and, with "
                            "--pp_pfm, to the PFM maps");
+DEFINE_string(calib, "", "a Middlebury-2014 calib.txt (cam0, cam1, doffs, baseline, width, height) of the pair: needed by the point-cloud and depth "
+                         "outputs below.  When its width differs from the image width, f, cx, cy and doffs are scaled by image width / width");
+DEFINE_string(l_ply, "", "write the left view's point cloud (binary little-endian PLY: x y z nx ny nz, red green blue; the baseline's unit) from the "
+                         "final plane field: the raw plane disparities, or with --use_pp the sub-pixel post-processed map.  Needs --calib; not with --batch_list");
+DEFINE_string(r_ply, "", "the same for the right view, in its own camera frame unless --geom_left_frame");
+DEFINE_string(l_depth_pfm, "", "write the left view's metric depth Z as float32 PFM, NaN where there is none (see --l_ply)");
+DEFINE_string(r_depth_pfm, "", "the same for the right view");
+DEFINE_double(geom_min_cos, 0.0, "point clouds: drop a pixel whose surface normal makes a smaller cosine than this with its view ray (0 .. 1; 0 = keep all)");
+DEFINE_double(geom_z_far, 0.0, "point clouds and depth maps: no point beyond this depth (0 = no limit)");
+DEFINE_bool(geom_left_frame, false, "the right view's points are given in the left camera's frame (X + baseline)");
+DEFINE_int32(geom_fit_radius, 0, "normals from planes fitted to the disparity map over a window of this half-width (1 .. 17) instead of the plane "
+                                "field's own slopes; 0 = the field's slopes");
 DEFINE_string(batch_list, "", "text file, one stereo pair per line: l_img r_img l_dis r_dis [l_pfm r_pfm]; all pairs run with the "
                               "matching flags of this command line on one device context (buffers are reused between pairs). A pair "
                               "that fails is reported and the batch goes on; the exit code is non-zero if any pair failed");
@@ -105,6 +121,9 @@ struct PairRun {
   std::unique_ptr<IPlaneCost> cost;
   std::unique_ptr<CSPatchMatch> matcher;
   std::vector<double> pfm[kViewNum];
+  std::vector<double> depth[kViewNum];      // --l_depth_pfm / --r_depth_pfm
+  std::vector<cspm_point> cloud[kViewNum];  // --l_ply / --r_ply
+  cspm_calib calib;
   double t0;
   int rc;
   std::ostringstream log;
@@ -204,6 +223,25 @@ void finish(PairRun &p) {
         for (int v = 0; v < kViewNum; ++v)
           if (!pfm[v]->empty()) p.matcher->disparity(v == 0 ? kLeft : kRight, &p.pfm[v]);  // reads the cost object's context: before it goes
       }
+      const string *ply[kViewNum] = {&FLAGS_l_ply, &FLAGS_r_ply}, *dpfm[kViewNum] = {&FLAGS_l_depth_pfm, &FLAGS_r_depth_pfm};
+      for (int v = 0; v < kViewNum; ++v) {  // reads the cost object's context: before it goes
+        if (ply[v]->empty() && dpfm[v]->empty()) continue;
+        cspm_geom_params g;
+        cspm_geom_default_params(&g);
+        g.min_cos = FLAGS_geom_min_cos;
+        if (FLAGS_geom_z_far > 0.0) g.z_far = FLAGS_geom_z_far;
+        g.left_frame = FLAGS_geom_left_frame ? 1 : 0;
+        cspm_fit_params fit;
+        cspm_fit_default_params(&fit);
+        fit.radius = FLAGS_geom_fit_radius;
+        const double g0 = static_cast<double>(getTickCount());
+        const size_t count = p.matcher->Reproject(v == 0 ? kLeft : kRight, p.calib, g, FLAGS_use_pp ? CSPM_GEOM_PP : CSPM_GEOM_RAW,
+                                                  FLAGS_geom_fit_radius != 0 ? &fit : NULL, dpfm[v]->empty() ? NULL : &p.depth[v], NULL, NULL, NULL,
+                                                  ply[v]->empty() ? NULL : &p.cloud[v]);
+        if (!FLAGS_quiet)
+          p.log << "Reprojection, view " << v << ": " << count << " points, " << (static_cast<double>(getTickCount()) - g0) / getTickFrequency() * 1e3
+                << " ms\n";
+      }
     } catch (const std::exception &e) {
       p.log << "Error: " << e.what() << "\n";
       p.rc = EXIT_FAILURE;
@@ -218,6 +256,11 @@ void write(PairRun &p) {
   const string *pfm[kViewNum] = {&p.files.l_pfm, &p.files.r_pfm};
   for (int v = 0; v < kViewNum && written; ++v)
     if (!pfm[v]->empty()) written = WritePFM(*pfm[v], p.pfm[v].data(), p.left.cols, p.left.rows);
+  const string *ply[kViewNum] = {&FLAGS_l_ply, &FLAGS_r_ply}, *dpfm[kViewNum] = {&FLAGS_l_depth_pfm, &FLAGS_r_depth_pfm};
+  for (int v = 0; v < kViewNum && written; ++v) {
+    if (!dpfm[v]->empty()) written = WritePFM(*dpfm[v], p.depth[v].data(), p.left.cols, p.left.rows);
+    if (written && !ply[v]->empty()) written = WritePLY(*ply[v], p.cloud[v].data(), p.cloud[v].size());
+  }
   if (!written) {
     p.log << "Error: can not write disparity maps\n";
     p.rc = EXIT_FAILURE;
@@ -411,6 +454,28 @@ int run() {
     cout << "Error: --ca_name aggregates cost volumes; --pc_name=IMG (GrdPC / CSPC) has none\n";
     return EXIT_FAILURE;
   }
+  const bool geom_out = !FLAGS_l_ply.empty() || !FLAGS_r_ply.empty() || !FLAGS_l_depth_pfm.empty() || !FLAGS_r_depth_pfm.empty();
+  if (geom_out && FLAGS_calib.empty()) {  // checked before anything opens a device
+    cout << "Error: --l_ply / --r_ply / --l_depth_pfm / --r_depth_pfm need --calib\n";
+    return EXIT_FAILURE;
+  }
+  if ((geom_out || !FLAGS_calib.empty()) && !FLAGS_batch_list.empty()) {
+    cout << "Error: --calib and the point-cloud and depth outputs belong to one pair: not with --batch_list\n";
+    return EXIT_FAILURE;
+  }
+  if (!(FLAGS_geom_min_cos >= 0.0 && FLAGS_geom_min_cos <= 1.0) || !(FLAGS_geom_z_far >= 0.0) || FLAGS_geom_fit_radius < 0 || FLAGS_geom_fit_radius > 17) {
+    cout << "Error: --geom_min_cos must be 0 .. 1, --geom_z_far >= 0 (0 = no limit) and --geom_fit_radius 0 .. 17\n";
+    return EXIT_FAILURE;
+  }
+  if (geom_out && FLAGS_pc_name != "PRE" && FLAGS_pc_name != "IMG") {
+    cout << "Error: the point-cloud and depth outputs need one of this library's plane costs (--pc_name=PRE or IMG), not " << FLAGS_pc_name << "\n";
+    return EXIT_FAILURE;
+  }
+  CalibFile calib_file;
+  if (!FLAGS_calib.empty() && !ReadCalibFile(FLAGS_calib, &calib_file)) {
+    cout << "Error: can not read " << FLAGS_calib << " as a Middlebury calib.txt (cam0, cam1, doffs, baseline, width, height)\n";
+    return EXIT_FAILURE;
+  }
   DevicePlaneCost::device = FLAGS_device;
   if (FLAGS_use_pp && !FLAGS_pp_pfm && !(FLAGS_l_disp_pfm.empty() && FLAGS_r_disp_pfm.empty()) && !FLAGS_quiet)
     cout << "Note: the PFM maps hold the plane disparities before post-processing (--pp_pfm writes the post-processed ones)\n";
@@ -420,6 +485,7 @@ int run() {
     if (!FLAGS_quiet) cout << "Load Image: " << FLAGS_l_img_file << " " << FLAGS_r_img_file << "\n";
     PairRun p(PairFiles{FLAGS_l_img_file, FLAGS_r_img_file, FLAGS_l_dis_file, FLAGS_r_dis_file, FLAGS_l_disp_pfm, FLAGS_r_disp_pfm}, 0);
     load(p);
+    if (!FLAGS_calib.empty() && p.rc == EXIT_SUCCESS) p.calib = ScaledCalib(calib_file, p.left.cols);
     begin(p, cost_fn.get());
     finish(p);
     write(p);

@@ -1,0 +1,45 @@
+// ply_io.h -- a point cloud of cspm_point records (include/cspm.h "reprojection") as a binary little-endian PLY: per vertex
+// x y z nx ny nz as float and red green blue as uchar, 27 bytes.  A normal with a NaN component is written as 0 0 0 (viewers take a zero
+// normal for "none"; a NaN makes several of them drop the file).
+#pragma once
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/cspm.h"
+
+static_assert(sizeof(cspm_point) == 32, "cspm_point is one 32-byte record");
+
+inline bool WritePLY(const std::string &path, const cspm_point *pts, size_t n) {
+  FILE *fp = std::fopen(path.c_str(), "wb");
+  if (!fp) return false;
+  std::fprintf(fp,
+               "ply\nformat binary_little_endian 1.0\nelement vertex %zu\nproperty float x\nproperty float y\nproperty float z\n"
+               "property float nx\nproperty float ny\nproperty float nz\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n",
+               n);
+  const uint16_t one = 1;
+  const bool host_little = *reinterpret_cast<const unsigned char *>(&one) == 1;
+  constexpr size_t kRec = 27, kChunk = 4096;
+  std::vector<unsigned char> buf(kRec * kChunk);
+  bool ok = true;
+  for (size_t i0 = 0; i0 < n && ok; i0 += kChunk) {
+    const size_t m = n - i0 < kChunk ? n - i0 : kChunk;
+    for (size_t j = 0; j < m; ++j) {
+      const cspm_point &p = pts[i0 + j];
+      float v[6] = {p.x, p.y, p.z, p.nx, p.ny, p.nz};
+      if (v[3] != v[3] || v[4] != v[4] || v[5] != v[5]) v[3] = v[4] = v[5] = 0.0f;
+      unsigned char *o = buf.data() + kRec * j;
+      for (int k = 0; k < 6; ++k) {
+        unsigned char b[4];
+        std::memcpy(b, &v[k], 4);
+        if (!host_little) { const unsigned char t0 = b[0], t1 = b[1]; b[0] = b[3]; b[1] = b[2]; b[2] = t1; b[3] = t0; }
+        std::memcpy(o + 4 * k, b, 4);
+      }
+      o[24] = p.r; o[25] = p.g; o[26] = p.b;
+    }
+    ok = std::fwrite(buf.data(), kRec, m, fp) == m;
+  }
+  return std::fclose(fp) == 0 && ok;
+}

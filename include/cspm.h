@@ -433,6 +433,86 @@ int cspm_median_filter_f64_host(int device, const double *src, int w, int h, int
 int cspm_set_pp_median(cspm_ctx *ctx, int r);
 int cspm_get_pp_median(cspm_ctx *ctx, int *r);
 
+/* ---- reprojection (an addition): metric depth, camera-space points, unit normals, a point cloud ---------------------
+ * A plane in disparity space is a plane in 3-D: with x = f X/Z + cx, y = f Y/Z + cy, d + doffs = f B/Z the disparity plane d = a x + b y + c
+ * is  a f X + b f Y + (a cx + b cy + c + doffs) Z = f B  -- exact, no finite differences.
+ * G(calib, params, view v, D, V, A, Bs, I) on one view: D a w x h f64 disparity map, V w x h bytes (NULL = all 1), slopes A, Bs w x h f64
+ * (NULL = no normals), I an 8-bit BGR image (NULL = no colour).  Every product, sum, quotient and square root is one IEEE f64 operation in
+ * the association written here, nothing contracted, no reciprocal.  The host computes once cxv = cx + (double)v * doffs and fB = f * baseline.
+ * Per pixel (x, y):
+ *     t  = D + doffs
+ *     ok = V != 0 && isfinite(D) && t > 0.0
+ *     Z  = fB / t
+ *     u  = (double)x - cxv          wv = (double)y - cy
+ *     X  = (u * Z) / f              Y  = (wv * Z) / f
+ *     if (left_frame && v == 1) X = X + baseline
+ *     ok = ok && Z >= z_near && Z <= z_far
+ * and with slopes
+ *     n0  = A * f    n1 = Bs * f    n2 = (t - A*u) - Bs*wv
+ *     len = sqrt((n0*n0 + n1*n1) + n2*n2)
+ *     N   = (-n0/len, -n1/len, -n2/len)                       the unit normal facing the camera, three divisions
+ *     cos = (f * t) / (len * sqrt((u*u + wv*wv) + f*f))       the cosine between the normal and the view ray
+ * n . (u, wv, f) = f t, so cos > 0 whenever t > 0: a plane is never seen from behind.  A non-finite A or Bs gives NaN normals and a NaN
+ * cos without a branch.  keep = ok && (no slopes || min_cos == 0.0 || cos >= min_cos); a NaN cos fails the test.
+ * Dense outputs, each optional (NULL) and untouched when not requested: depth = Z where ok, NaN elsewhere; xyz = three w x h planes X, Y, Z,
+ * NaN where !ok; normal = three planes, NaN where !ok (without slopes: CSPM_ERR_ARG); keep = w x h bytes.
+ * Cloud: the kept pixels in raster order (y outer, x inner), one 32-byte cspm_point each: the six floats are (float) of the f64 values, round
+ * to nearest (NaN stays NaN; without slopes the normal is NaN); pixel = y*w + x; b, g, r from the image and a = 255, without an image all
+ * four bytes 0.  *count = the number of kept pixels whatever the capacity; when count > cloud_cap the first cloud_cap records in raster
+ * order are written and the rest of the buffer is untouched; a NULL cloud asks for the count only; count_out may be NULL.  w*h < 2^31.
+ * Calibration: valid when all five values are finite, f > 0 and baseline > 0.  Parameters (NULL = the defaults 0, +infinity, 0, 0, 0):
+ * CSPM_ERR_ARG for a NaN or negative z_near, a z_far that is NaN or below z_near, a min_cos outside [0, 1]. */
+typedef struct cspm_calib {
+  double f;        /* focal length in pixels */
+  double cx, cy;   /* principal point of view 0 */
+  double baseline; /* any length unit: the outputs are in that unit */
+  double doffs;    /* cx1 - cx0 */
+} cspm_calib;
+typedef struct cspm_geom_params {
+  double z_near, z_far; /* ok only for z_near <= Z <= z_far (both inclusive) */
+  double min_cos;       /* keep only pixels whose normal makes at least this cosine with the view ray; 0 = every ok pixel */
+  int left_frame;       /* 1: view 1's points are moved into view 0's camera frame (X + baseline) */
+  int consistent_only;  /* cspm_reproject(_device), CSPM_GEOM_PP: V = the left-right consistency mask instead of all 1 */
+} cspm_geom_params;
+typedef struct cspm_point {
+  float x, y, z, nx, ny, nz;
+  uint8_t b, g, r, a;
+  uint32_t pixel;
+} cspm_point;
+int cspm_geom_default_params(cspm_geom_params *p);
+/* G alone on caller memory, no context needed (like cspm_fit_planes_host), synchronous.  slope_a and slope_b come together or not at all;
+ * bgr: packed 8UC3 rows of bgr_stride bytes (>= 3*w) or NULL.  Arguments are checked before a device is opened: CSPM_ERR_ARG for a bad
+ * calibration, parameters or view, a NULL disp, w or h < 1, w*h >= 2^31, one slope map without the other, normal_out without slopes, or
+ * a bgr_stride below 3*w. */
+int cspm_reproject_host(int device, const cspm_calib *calib, const cspm_geom_params *params, int view, const double *disp, const uint8_t *valid,
+                        const double *slope_a, const double *slope_b, const uint8_t *bgr, size_t bgr_stride, int w, int h, double *depth_out,
+                        double *xyz_out, double *normal_out, uint8_t *keep_out, cspm_point *cloud_out, size_t cloud_cap, unsigned int *count_out);
+/* G on one view of the context's stored plane field; I = the view's level-0 image.  source:
+ *   CSPM_GEOM_RAW  D = the field's a*x+b*y+c (what cspm_get_disparity_f64 returns) written into scratch; V all 1; slopes = the field's a, b.
+ *   CSPM_GEOM_PP   D = the view's map of the sub-pixel post-processing (cspm_postprocess_f64, with the context's speckle and median
+ *                  settings), which this call runs itself, by the path that entry takes, so that the map always belongs to the stored field;
+ *                  V all 1, or the consistency mask that entry returns when consistent_only; slopes = the field's a, b where the pixel
+ *                  passed the check (that mask) and NaN elsewhere: a filled pixel has a disparity but no plane of its own.
+ * fit != NULL replaces the slopes of EVERY pixel by those of the plane fit F (cspm_fit_planes_host) applied to (D, V) with the level-0 image
+ * as guide and the context's max_dis, computed into scratch; an unfitted pixel gets NaN slopes.
+ * Like cspm_get_disparity_f64 the entry first checks a pending run, so it never reads planes of an aborted sweep.  Synchronous; host outputs.
+ * Timed as one CSPM_K_MISC bracket per call with w*h evaluations (CSPM_GEOM_PP: behind the post-processing's own CSPM_K_POST brackets).
+ * Scratch (a map, six fit planes and the counts) is allocated on first use and freed with the plane field.
+ * CSPM_ERR_ARG for a bad view, source, calibration, parameters or fit parameters; CSPM_ERR_STATE without images
+ * or a plane field, and without a cost object when source is CSPM_GEOM_PP or fit is given (these need max_dis). */
+#define CSPM_GEOM_RAW 0
+#define CSPM_GEOM_PP 1
+int cspm_reproject(cspm_ctx *ctx, int view, int source, const cspm_calib *calib, const cspm_geom_params *params, const cspm_fit_params *fit,
+                   double *depth_out, double *xyz_out, double *normal_out, uint8_t *keep_out, cspm_point *cloud_out, size_t cloud_cap,
+                   unsigned int *count_out);
+/* the same with device pointers for every output (d_cloud_out 16-byte aligned) and a device unsigned int for the count.  Makes the same
+ * pending-run check on entry, then enqueues on the ctx stream and returns.  Deliberately NOT part of the deferred-output replay of the
+ * asynchronous outputs above: a run enqueued BEHIND this call that times out and is repeated does not rewrite these buffers -- they hold
+ * the geometry of the field as it was checked on entry, which is what was asked for. */
+int cspm_reproject_device(cspm_ctx *ctx, int view, int source, const cspm_calib *calib, const cspm_geom_params *params,
+                          const cspm_fit_params *fit, void *d_depth_out, void *d_xyz_out, void *d_normal_out, void *d_keep_out, void *d_cloud_out,
+                          size_t cloud_cap, void *d_count_out);
+
 /* ---- CSPatchMatch::PatchMatch over a FOREIGN IPlaneCost (plane_cost/i_plane_cost.h:28-33) ------------------------------
  * Any object with a GetPlaneCost(x, y, plane, view) that is not one of this library's device costs: the reference drives it
  * through the virtual call (call sites cs_patchmatch.cc:144,181,191,200,208,269,334).  Here the device keeps the plane field,
