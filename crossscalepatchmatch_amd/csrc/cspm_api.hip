@@ -3053,6 +3053,13 @@ int cspm_debug_rangestats(unsigned long long *out1024, int reset) {
   if (reset && hipMemcpyToSymbol(HIP_SYMBOL(cspm::g_rangestat), z, sizeof z) != hipSuccess) return CSPM_ERR_HIP;
   return CSPM_OK;
 }
+// tools/row_paths.py: which leaf of level_rows' decision the level passes took, [2 views][16 slots][8 levels][128 leaves] (cspm_rows.h g_pathstat)
+int cspm_debug_pathstats(unsigned long long *out32768, int reset) {
+  static unsigned long long z[2 * 16 * 8 * cspm::kPathLeaves];
+  if (hipMemcpyFromSymbol(out32768, HIP_SYMBOL(cspm::g_pathstat), sizeof z) != hipSuccess) return CSPM_ERR_HIP;
+  if (reset && hipMemcpyToSymbol(HIP_SYMBOL(cspm::g_pathstat), z, sizeof z) != hipSuccess) return CSPM_ERR_HIP;
+  return CSPM_OK;
+}
 int cspm_debug_rowstats(unsigned long long *out1024, int reset) {
   static unsigned long long z[16 * 8 * 8];
   if (hipMemcpyFromSymbol(out1024, HIP_SYMBOL(cspm::g_rowstat), sizeof z) != hipSuccess) return CSPM_ERR_HIP;

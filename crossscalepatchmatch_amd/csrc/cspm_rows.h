@@ -50,6 +50,14 @@ __device__ unsigned long long g_rowtime[8 * 8];
 // level passes that fail the range test only by the SPAN of their disparities, by the size of the UNION of the lanes' intervals:
 // [level][0] <= 8, [1] <= 11, [2] <= 16, [3] <= 24, [4] more
 __device__ unsigned long long g_unionstat[8 * 8];
+// which leaf of level_rows' decision a level pass of a wave took (fused GRD cost) (tools/row_paths.py,
+// tests/rows_path_ref.py restates the decision; DESIGN.md section 5.1 has the table), [view][slot][level][leaf].  Slots as above, and 13 = k_rescore,
+// 14 = k_merge / k_merge_keep.  leaf = kind | two table buffers << 3 | the padded pitch (NQD / NQP) was taken << 4 | weight table << 5
+// | edge << 6;  kind: 0 unstaged or D < 2, 1 general taps (the range test failed), 2 general taps (too many disparities),
+// 3 full table computed, 4 full table DMA-filled, 5 range table computed, 6 range table DMA-filled, 7 two-cluster table (DMA-filled).
+// The buffer, pitch and weight-table bits are 0 for the kinds 0 - 2.
+constexpr int kPathLeaves = 128;
+__device__ unsigned long long g_pathstat[2 * 16 * 8 * kPathLeaves];
 #define ROWTIME_NOW() __builtin_readcyclecounter()
 #define ROWTIME_ADD(slot, v) do { rowtime_acc[(slot) & 3] += (unsigned long long)(v); rowtime_base = (slot) & 4; } while (0)
 #define ROWTIME_FLUSH() do { if (lane == 0 && rowtime_acc[3]) for (int k_ = 0; k_ < 4; ++k_) atomicAdd(&g_rowtime[s * 8 + rowtime_base + k_], rowtime_acc[k_]); } while (0)
@@ -674,6 +682,10 @@ __device__ __forceinline__ double level_rows(const Cost &cd, const Luts &lut, co
     bool lane_b = false;
     int tbuf = 2;  // DMA-filled tables: 2 = the next row's table lands while this row's taps run; 1 = it is fetched after them
     const int p2 = (NQ * 4 + 15) / 16 * 16;  // a run of own colours, in 16-byte DMA pieces
+#ifdef CSPM_ROW_STATS
+    // leaf kind 0 (counted here, ahead of the wave-uniform branch: a lane-0 branch that joins where the decision's variables merge would make them per-lane values)
+    if (!(staged && D >= 2) && lane == 0) atomicAdd(&g_pathstat[((VIEW * 16 + ctx.stat_slot) * 8 + s) * kPathLeaves + (edge ? 64 : 0)], 1ull);
+#endif
     if (staged && D >= 2) {
       const bool full_fits = (NQ + D) * 16 + own_bytes + NQ * D * 8 + wtab_bytes <= lds_room;
       // DMA-filled tables (Level::cvol): the device cells of this level are in memory, a table row is a run of a volume row
@@ -786,6 +798,12 @@ __device__ __forceinline__ double level_rows(const Cost &cd, const Luts &lut, co
           else if (cells_on) { atomicAdd(&g[wtab ? 2 : 3], 1ull); atomicAdd(&g[5], (unsigned long long)nd); }
           else { atomicAdd(&g[4], 1ull); atomicAdd(&g[6], (unsigned long long)nd); }
         }
+        // the leaf (g_pathstat above)
+        const int NQE_ = (NQ + 3) & ~3, NQD_ = NQP > NQE_ ? NQP : NQE_;
+        int leaf = !cells_on ? (range_ok ? 2 : 1) : tdma ? (nd_a > 0 ? 7 : allv_level ? 6 : 4) : (allv_level ? 5 : 3);
+        if (cells_on) leaf |= ((tdma && tbuf == 2) ? 8 : 0) | (pitch == (tdma ? NQD_ : NQP) ? 16 : 0) | (wtab ? 32 : 0);
+        leaf |= edge ? 64 : 0;
+        atomicAdd(&g_pathstat[((VIEW * 16 + ctx.stat_slot) * 8 + s) * kPathLeaves + leaf], 1ull);
       }
 #endif
     }
@@ -1419,6 +1437,9 @@ __global__ __launch_bounds__(kRowBlock, kRowMinWaves) void k_rescore(Cost cd, Pm
   RowCtx ctx = make_row_ctx(smem, it.y, cap, ocap);
   const bool live = it.x0 + lane < pm.W;
   const int x = live ? it.x0 + lane : pm.W - 1;  // tail lanes shadow the last pixel
+#ifdef CSPM_ROW_STATS
+  ctx.stat_slot = 13;
+#endif
   auto gen = [&](int xs) { return stored_plane(pm, it.v, xs, it.y); };
   const double cost = eval_rows<CS, SRC>(cd, lut, ctx, it.v, x, gen, kDoubleMax, false);
   if (live) pm.f[it.v].cost[(long long)it.y * pm.W + x] = cost;
@@ -1701,6 +1722,9 @@ __device__ __forceinline__ void merge_rows(const Cost &cd, const Pm &pm, const R
   const long long i = (long long)it.y * pm.W + x;
   const Field &f = pm.f[v];
   const double cur_min = f.cost[i];
+#ifdef CSPM_ROW_STATS
+  ctx.stat_slot = 14;
+#endif
   const bool use_thresh = pm.use_thresh != 0 && *cd.early_ok != 0;
   auto gen = [&](int xs) {
     RowPlane p;

@@ -1,5 +1,6 @@
 """debug (needs `make -C crossscalepatchmatch_amd/csrc ../libcspm_rowstats.so`): per phase and pyramid level, how the level passes of the
-row engine's waves split between full cell mode, range-restricted cell mode (with / without the weight table) and the general taps."""
+row engine's waves split between full cell mode, range-restricted cell mode (with / without the weight table) and the general taps.
+tools/row_paths.py counts the same decision leaf by leaf (buffers, pitch, weights, edge) on fields built to take every leaf."""
 import ctypes as C
 import os
 import sys
