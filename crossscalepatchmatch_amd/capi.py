@@ -37,6 +37,7 @@ OPT_CENGRD_FUSED_ACTIVE = 20 # read only: the current cost object is a fused CEN
 OPT_PP_SPECKLE_REMOVED = 21  # read only, synchronises: pixels the speckle filter removed from both masks in the last post-processing
 MEDIAN_MAX_RADIUS = 7  # CSPM_MEDIAN_MAX_RADIUS: the median filter's window is at most 15 x 15
 CA_BOX, CA_GF, CA_BF = 0, 1, 2  # cost aggregation: BoxCA, GFCA, BFCA (ca_filter/)
+SYNTH_MAX_WIDTH = 6784  # CSPM_SYNTH_MAX_WIDTH: the widest image cspm_synthesize* takes (a target row lives in one workgroup's LDS)
 GEOM_RAW, GEOM_PP = 0, 1  # cspm_reproject's source: the stored field's a*x+b*y+c, or the sub-pixel post-processed map
 CENGRD_KAPPA, CENGRD_TAU = 0.0625, 32.0  # CSPM_CENGRD_KAPPA / CSPM_CENGRD_TAU: cell = fma(KAPPA, min(H, TAU), G)
 
@@ -57,6 +58,7 @@ SYMBOLS = [
     "cspm_median_filter_u8_host", "cspm_median_filter_f64_host", "cspm_set_pp_median", "cspm_get_pp_median",
     "cspm_fit_default_params", "cspm_fit_planes_host", "cspm_fit_planes",
     "cspm_geom_default_params", "cspm_reproject_host", "cspm_reproject", "cspm_reproject_device",
+    "cspm_synth_default_params", "cspm_synthesize_host", "cspm_synthesize", "cspm_synthesize_device",
 ]
 
 
@@ -83,6 +85,17 @@ class Calib(C.Structure):
 class GeomParams(C.Structure):
     """struct cspm_geom_params"""
     _fields_ = [("z_near", C.c_double), ("z_far", C.c_double), ("min_cos", C.c_double), ("left_frame", C.c_int), ("consistent_only", C.c_int)]
+
+
+class SynthParams(C.Structure):
+    """struct cspm_synth_params"""
+    _fields_ = [("views", C.c_int), ("fill", C.c_int), ("max_stretch", C.c_double), ("merge_diff", C.c_double)]
+
+
+class SynthView(C.Structure):
+    """struct cspm_synth_view: one source view of cspm_synthesize_host"""
+    _fields_ = [("disp", C.POINTER(C.c_double)), ("valid", C.POINTER(C.c_uint8)), ("slope_a", C.POINTER(C.c_double)),
+                ("bgr", C.POINTER(C.c_uint8)), ("stride", C.c_size_t)]
 
 
 # struct cspm_point: one 32-byte cloud record
@@ -120,6 +133,7 @@ def load_library():
     pp = C.POINTER(PmParams)
     fp = C.POINTER(FitParams)
     kp, gp, up = C.POINTER(Calib), C.POINTER(GeomParams), C.POINTER(C.c_uint)
+    sp, svp = C.POINTER(SynthParams), C.POINTER(SynthView)
     sig = {
         "cspm_device_count": (C.c_int, []),
         "cspm_create": (C.c_int, [C.POINTER(vp), C.c_int]),
@@ -194,6 +208,10 @@ def load_library():
         "cspm_reproject_host": (C.c_int, [C.c_int, kp, gp, C.c_int, dp, u8p, dp, dp, u8p, C.c_size_t, C.c_int, C.c_int, dp, dp, dp, u8p, vp, C.c_size_t, up]),
         "cspm_reproject": (C.c_int, [vp, C.c_int, C.c_int, kp, gp, fp, dp, dp, dp, u8p, vp, C.c_size_t, up]),
         "cspm_reproject_device": (C.c_int, [vp, C.c_int, C.c_int, kp, gp, fp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+        "cspm_synth_default_params": (C.c_int, [sp]),
+        "cspm_synthesize_host": (C.c_int, [C.c_int, sp, C.c_double, svp, svp, C.c_int, C.c_int, u8p, C.c_size_t, dp, u8p]),
+        "cspm_synthesize": (C.c_int, [vp, C.c_int, sp, C.c_double, u8p, C.c_size_t, dp, u8p]),
+        "cspm_synthesize_device": (C.c_int, [vp, C.c_int, sp, C.c_double, vp, C.c_size_t, vp, vp]),
     }
     assert sorted(sig) == sorted(SYMBOLS)
     for name, (res, args) in sig.items():
@@ -546,6 +564,28 @@ class StereoContext:
         self._chk(self.L.cspm_reproject_device(self.p, int(view), int(source), C.byref(k), C.byref(g), C.byref(f) if f is not None else None,
                                                vp(d_depth), vp(d_xyz), vp(d_normal), vp(d_keep), vp(d_cloud), int(cloud_cap), vp(d_count)))
 
+    # ---- view synthesis ----
+    def synthesize(self, t, source=GEOM_RAW, outputs=("bgr", "disp", "mask"), out=None, **params):
+        """the scene from the camera at fraction t of the baseline (0 = view 0, 1 = view 1), rendered from the stored plane field and the
+        level-0 images (cspm_synthesize): source GEOM_RAW or GEOM_PP; params: views, max_stretch, merge_diff, fill.  outputs: which of
+        bgr (h, w, 3) uint8, disp (h, w) f64 (NaN in holes), mask (h, w) uint8 (0 hole, 1 / 2 one view, 3 both, 4 filled) to compute.
+        out: a dict of preallocated arrays to write into (bgr may have padded rows).  Returns a dict of the requested arrays."""
+        p = synth_params(**params)
+        res = _synth_outputs(self.h, self.w, outputs, out)
+        b = res.get("bgr")
+        self._chk(self.L.cspm_synthesize(self.p, int(source), C.byref(p), float(t), _u8(b) if b is not None else None,
+                                         b.strides[0] if b is not None else 0, _dp(res["disp"]) if "disp" in res else None,
+                                         _u8(res["mask"]) if "mask" in res else None))
+        return res
+
+    def synthesize_device(self, t, source=GEOM_RAW, d_bgr=0, out_stride=0, d_disp=0, d_mask=0, **params):
+        """the same with device pointers (integers; 0 = not requested): d_bgr rows of out_stride bytes (0 = 3 * w), d_disp h*w f64, d_mask
+        h*w bytes; asynchronous on the context's stream (cspm_synthesize_device)"""
+        p = synth_params(**params)
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._chk(self.L.cspm_synthesize_device(self.p, int(source), C.byref(p), float(t), vp(d_bgr), int(out_stride) or 3 * self.w, vp(d_disp),
+                                                vp(d_mask)))
+
     # ---- measurement ----
     def enable_timing(self, on=True):
         self._chk(self.L.cspm_enable_timing(self.p, int(on)))
@@ -701,6 +741,70 @@ def reproject_host(calib, view, disp, valid=None, slope_a=None, slope_b=None, bg
         res["count"] = cnt.value
     if pts is not None:
         res["cloud"] = pts[:min(cnt.value, cap)] if count else pts
+    return res
+
+
+def synth_params(**params):
+    """struct cspm_synth_params: cspm_synth_default_params with the given fields replaced"""
+    p = SynthParams()
+    rc = load_library().cspm_synth_default_params(C.byref(p))
+    assert rc == 0
+    for k, v in params.items():
+        if k not in ("views", "fill", "max_stretch", "merge_diff"):
+            raise TypeError(f"unknown view-synthesis parameter {k!r}")
+        setattr(p, k, int(v) if k in ("views", "fill") else float(v))
+    return p
+
+
+def _synth_outputs(h, w, outputs, out):
+    res = dict(out or {})
+    for name in outputs:
+        if name not in ("bgr", "disp", "mask"):
+            raise TypeError(f"unknown view-synthesis output {name!r}")
+        if name not in res:
+            res[name] = np.zeros({"bgr": (h, w, 3), "disp": (h, w), "mask": (h, w)}[name], np.float64 if name == "disp" else np.uint8)
+    res = {k: v for k, v in res.items() if k in outputs}
+    if "bgr" in res:
+        b = res["bgr"]
+        assert b.dtype == np.uint8 and b.shape == (h, w, 3) and b.strides[1:] == (3, 1), "bgr: uint8 (h, w, 3) with packed pixels"
+    assert "disp" not in res or (res["disp"].dtype == np.float64 and res["disp"].shape == (h, w) and res["disp"].flags.c_contiguous)
+    assert "mask" not in res or (res["mask"].dtype == np.uint8 and res["mask"].shape == (h, w) and res["mask"].flags.c_contiguous)
+    return res
+
+
+def synthesize_host(t, disp, bgr, valid=(None, None), slope_a=(None, None), outputs=("bgr", "disp", "mask"), out=None, device=0, **params):
+    """N alone on host maps (cspm_synthesize_host).  disp, bgr, valid, slope_a: pairs (view 0, view 1); disp (h, w)
+    f64, bgr (h, w, 3) uint8 (rows may be padded), valid (h, w) or None, slope_a (h, w) f64 or None; both entries of a view that `views`
+    does not name may be None.  outputs / out / params and the result as for StereoContext.synthesize."""
+    L = load_library()
+    p = synth_params(**params)
+    keep, views, shape = [], [], None
+    for v in range(2):
+        if disp[v] is None or bgr[v] is None:
+            views.append(None)
+            continue
+        d = np.ascontiguousarray(disp[v], dtype=np.float64)
+        assert d.ndim == 2 and (shape is None or d.shape == shape), d.shape
+        shape = d.shape
+        img = np.asarray(bgr[v])
+        if img.dtype != np.uint8 or img.strides[1:] != (3, 1):
+            img = np.ascontiguousarray(img, dtype=np.uint8)
+        assert img.shape == d.shape + (3,), img.shape
+        m = None if valid[v] is None else np.ascontiguousarray(np.asarray(valid[v]) != 0, dtype=np.uint8)
+        a = None if slope_a[v] is None else np.ascontiguousarray(slope_a[v], dtype=np.float64)
+        assert (m is None or m.shape == shape) and (a is None or a.shape == shape)
+        keep += [d, img, m, a]
+        views.append(SynthView(_dp(d), _u8(m) if m is not None else None, _dp(a) if a is not None else None, _u8(img), img.strides[0]))
+    assert shape is not None, "no source view"
+    h, w = shape
+    res = _synth_outputs(h, w, outputs, out)
+    b = res.get("bgr")
+    rc = L.cspm_synthesize_host(device, C.byref(p), float(t), C.byref(views[0]) if views[0] is not None else None,
+                                C.byref(views[1]) if views[1] is not None else None, w, h, _u8(b) if b is not None else None,
+                                b.strides[0] if b is not None else 0, _dp(res["disp"]) if "disp" in res else None,
+                                _u8(res["mask"]) if "mask" in res else None)
+    if rc != 0:
+        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
     return res
 
 

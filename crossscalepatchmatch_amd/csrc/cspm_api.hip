@@ -16,6 +16,7 @@
 #include "cspm_median.h"
 #include "cspm_fit.h"
 #include "cspm_geom.h"
+#include "cspm_synth.h"
 #include "cspm_ca.h"
 
 using namespace cspm;
@@ -202,6 +203,7 @@ struct cspm_ctx {
   double *geom_disp = nullptr;        // cspm_reproject: the CSPM_GEOM_RAW disparity map (1 array); allocated by the first such call and kept with the field
   double *geom_fit = nullptr;         // cspm_reproject with a fit: the fitted planes (6 arrays) and, behind them, the exp(-k/10) table
   unsigned int *geom_counts = nullptr;  // cspm_reproject: the kept pixels per workgroup, then the total
+  double *synth_disp = nullptr;       // cspm_synthesize: both views' CSPM_GEOM_RAW disparity maps (2 arrays); allocated by the first such call and kept with the field
   double *diffuse_snap = nullptr;     // CSPM_SCHED_DIFFUSE: the round's snapshot (both views, the 6 plane arrays each), allocated by the first such propagation and kept with the field
   long long sweep_fallbacks = 0;      // how often that happened (cspm_get_option)
   // CSPatchMatch over a foreign IPlaneCost (cspm_fpm_*): candidate buffers and what the pending batch was
@@ -363,6 +365,7 @@ void free_field(cspm_ctx *c) {
   dfree(c->geom_disp);
   dfree(c->geom_fit);
   dfree(c->geom_counts);
+  dfree(c->synth_disp);
   dfree(c->vc.cost);
   dfree(c->vc.c);
   dfree(c->vc.cx);
@@ -1615,6 +1618,73 @@ int reproject_check(cspm_ctx *c, int view, int source, const cspm_calib *calib, 
   return CSPM_OK;
 }
 
+// ---- view synthesis (cspm_synth.h) ------------------------------------------------------------------------
+static_assert(kSynthMaxWidth == CSPM_SYNTH_MAX_WIDTH, "cspm.h states the widest row of the synthesis kernel");
+const cspm_synth_params kSynthDefaults = {3, 1, 4.0, 1.0};
+const char *synth_args_error(const cspm_synth_params *p, double t, int w, int h, bool want_bgr, size_t out_stride) {
+  if (!(t >= 0.0 && t <= 1.0)) return "view synthesis: t must be in [0, 1]";
+  if (p->views < 1 || p->views > 3) return "view synthesis: views must be 1, 2 or 3";
+  if (!(p->max_stretch >= 1.0)) return "view synthesis: max_stretch must be >= 1";
+  if (!(p->merge_diff >= 0.0)) return "view synthesis: merge_diff must be >= 0";
+  if (w < 1 || h < 1) return "view synthesis: an empty image";
+  if ((long long)w * h >= (1LL << 31)) return "view synthesis: w * h must be below 2^31";
+  if (w > kSynthMaxWidth) return "view synthesis: the image is wider than CSPM_SYNTH_MAX_WIDTH";
+  if (want_bgr && out_stride < (size_t)w * 3) return "view synthesis: out_stride is below 3 * w";
+  return nullptr;
+}
+void synth_launch(hipStream_t stream, const SynthView &v0, const SynthView &v1, const cspm_synth_params *p, double t, const SynthOut &out, int w, int h) {
+  SynthParams k{};
+  k.sigma[0] = -t;
+  k.sigma[1] = 1.0 - t;
+  k.w0 = 1.0 - t;
+  k.w1 = t;
+  k.max_stretch = p->max_stretch;
+  k.merge_diff = p->merge_diff;
+  k.views = p->views;
+  k.fill = p->fill ? 1 : 0;
+  const size_t shmem = synth_lds_bytes(w);
+  allow_lds(k_synth_row, shmem);
+  hipLaunchKernelGGL(k_synth_row, dim3((unsigned)h), dim3(kSynthBlock), shmem, stream, v0, v1, k, out, w);
+}
+// the checks cspm_synthesize and cspm_synthesize_device share; p is defaulted / validated
+int synthesize_check(cspm_ctx *c, int source, const cspm_synth_params **p, double t, bool want_bgr, size_t out_stride) {
+  if (!*p) *p = &kSynthDefaults;
+  if (source != CSPM_GEOM_RAW && source != CSPM_GEOM_PP) return fail(c, CSPM_ERR_ARG, "view synthesis: source must be CSPM_GEOM_RAW or CSPM_GEOM_PP");
+  if (const char *msg = synth_args_error(*p, t, 1, 1, false, 0)) return fail(c, CSPM_ERR_ARG, msg);  // t and the parameters, before the state
+  if (!c->img0[0]) return fail(c, CSPM_ERR_STATE, "cspm_set_images first");
+  if (int rc = need_field(c, "no plane field to synthesise a view from (cspm_patchmatch, cspm_local_stereo, cspm_set_planes, ...)")) return rc;
+  if (const char *msg = synth_args_error(*p, t, c->W, c->H, want_bgr, out_stride)) return fail(c, CSPM_ERR_ARG, msg);
+  if (source == CSPM_GEOM_PP && (!c->cost_alloc || !c->cost_ready || c->max_dis < 1))
+    return fail(c, CSPM_ERR_STATE, "view synthesis from the post-processed maps needs a cost object (its max_dis)");
+  return CSPM_OK;
+}
+// after the checks: the pending-run check, the inputs of the chosen source, the launch.  Every output is a device pointer.
+int synthesize_enqueue(cspm_ctx *c, int source, const cspm_synth_params *p, double t, const SynthOut &out) {
+  int rc = check_sweep(c);  // BEFORE the field is read, as in reproject_enqueue
+  if (rc) return rc;
+  const size_t n = (size_t)c->W * c->H;
+  if (source == CSPM_GEOM_RAW && !c->synth_disp && (rc = dalloc(c, &c->synth_disp, 2 * n, nullptr))) return rc;
+  if (source == CSPM_GEOM_PP && (rc = postprocess_f64_enqueue(c))) return rc;
+  {
+    Timed tm(c, CSPM_K_MISC, (long long)n);
+    SynthView sv[2];
+    for (int v = 0; v < 2; ++v) {
+      sv[v] = SynthView{nullptr, nullptr, c->f[v].a, nullptr, c->img0[v]};
+      if (source == CSPM_GEOM_RAW) {
+        if (p->views >> v & 1)
+          hipLaunchKernelGGL(k_plane_to_disp_f64, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, field_pm(c), v, c->synth_disp + (size_t)v * n);
+        sv[v].disp = c->synth_disp + (size_t)v * n;
+      } else {
+        sv[v].disp = c->d_pp[v];
+        sv[v].a_mask = c->d_valid[v];
+      }
+    }
+    synth_launch(c->stream, sv[0], sv[1], p, t, out, c->W, c->H);
+  }
+  HIPCHK(c, hipGetLastError());
+  return CSPM_OK;
+}
+
 // ---- cost aggregation (cspm_ca.h) ----------------------------------------------------------------------------------------------
 constexpr int kCaRadiusBox = 3, kCaRadiusGf = 9;  // BoxCA.cpp:11, GuidedFilter.h:24
 inline int ca_min_size(int method) { return method == CSPM_CA_BOX ? 2 * kCaRadiusBox + 1 : (method == CSPM_CA_GF ? 2 * kCaRadiusGf + 1 : 17); }
@@ -2717,6 +2787,91 @@ int cspm_reproject_device(cspm_ctx *c, int view, int source, const cspm_calib *c
   ON_DEVICE(c);
   return reproject_enqueue(c, view, source, calib, g, fit, GeomOut{(double *)d_depth_out, (double *)d_xyz_out, (double *)d_normal_out, (uint8_t *)d_keep_out},
                            (uint4 *)d_cloud_out, d_cloud_out ? cloud_cap : 0, d_count_out != nullptr || d_cloud_out != nullptr, (unsigned int *)d_count_out);
+}
+
+// N alone on caller maps: the launch cspm_synthesize enqueues.  Arguments first, then the device.
+int cspm_synth_default_params(cspm_synth_params *p) {
+  if (!p) return CSPM_ERR_ARG;
+  *p = kSynthDefaults;
+  return CSPM_OK;
+}
+
+int cspm_synthesize_host(int device, const cspm_synth_params *p, double t, const cspm_synth_view *view0, const cspm_synth_view *view1, int w, int h,
+                         uint8_t *bgr_out, size_t out_stride, double *disp_out, uint8_t *mask_out) {
+  if (!p) p = &kSynthDefaults;
+  if (const char *msg = synth_args_error(p, t, w, h, bgr_out != nullptr, out_stride)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  const cspm_synth_view *in[2] = {view0, view1};
+  for (int v = 0; v < 2; ++v) {
+    if (!(p->views >> v & 1)) continue;
+    if (!in[v] || !in[v]->disp || !in[v]->bgr) return fail(nullptr, CSPM_ERR_ARG, "view synthesis: a view that `views` names has no disparity map or no image");
+    if (in[v]->stride < (size_t)w * 3) return fail(nullptr, CSPM_ERR_ARG, "view synthesis: an image stride is below 3 * w");
+  }
+  Scratch S;
+  int rc = cspm_create(&S.c, device);
+  if (rc) return rc;
+  cspm_ctx *c = S.c;
+  const size_t n = (size_t)w * h;
+  SynthView sv[2] = {};
+  for (int v = 0; v < 2; ++v) {
+    if (!(p->views >> v & 1)) continue;
+    double *dd = nullptr, *da = nullptr;
+    uint8_t *dv = nullptr, *dbgr = nullptr;
+    uint32_t *dpix = nullptr;
+    if ((rc = dalloc(c, &dd, n, &S.tmp)) || (in[v]->valid && (rc = dalloc(c, &dv, n, &S.tmp))) || (in[v]->slope_a && (rc = dalloc(c, &da, n, &S.tmp))) ||
+        (rc = dalloc(c, &dbgr, 3 * n, &S.tmp)) || (rc = dalloc(c, &dpix, n, &S.tmp)))
+      return S.done(rc);
+    if (hipMemcpyAsync(dd, in[v]->disp, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+        (dv && hipMemcpyAsync(dv, in[v]->valid, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+        (da && hipMemcpyAsync(da, in[v]->slope_a, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+        hipMemcpy2DAsync(dbgr, (size_t)w * 3, in[v]->bgr, in[v]->stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+      return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+    hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, dbgr, (size_t)w * 3, w, h, w, 0, dpix);
+    sv[v] = SynthView{dd, dv, da, nullptr, dpix};
+  }
+  uint8_t *dout = nullptr, *dmask = nullptr;
+  double *ddisp = nullptr;
+  if ((bgr_out && (rc = dalloc(c, &dout, 3 * n, &S.tmp))) || (disp_out && (rc = dalloc(c, &ddisp, n, &S.tmp))) || (mask_out && (rc = dalloc(c, &dmask, n, &S.tmp))))
+    return S.done(rc);
+  synth_launch(c->stream, sv[0], sv[1], p, t, SynthOut{dout, (size_t)w * 3, ddisp, dmask}, w, h);
+  if (hipGetLastError() != hipSuccess ||
+      (bgr_out && hipMemcpy2DAsync(bgr_out, out_stride, dout, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      (disp_out && hipMemcpyAsync(disp_out, ddisp, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      (mask_out && hipMemcpyAsync(mask_out, dmask, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) || hipStreamSynchronize(c->stream) != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, "view synthesis kernel failed"));
+  return S.done(CSPM_OK);
+}
+
+// N on the stored field (cspm.h "view synthesis"): synchronous, host outputs
+int cspm_synthesize(cspm_ctx *c, int source, const cspm_synth_params *p, double t, uint8_t *bgr_out, size_t out_stride, double *disp_out, uint8_t *mask_out) {
+  if (!c) return CSPM_ERR_ARG;
+  int rc = synthesize_check(c, source, &p, t, bgr_out != nullptr, out_stride);
+  if (rc) return rc;
+  ON_DEVICE(c);
+  const size_t n = (size_t)c->W * c->H, row = (size_t)c->W * 3;
+  std::vector<void *> tmp;
+  struct Free {
+    std::vector<void *> &t;
+    ~Free() { for (void *q : t) (void)hipFree(q); }
+  } free_tmp{tmp};
+  uint8_t *dout = nullptr, *dmask = nullptr;
+  double *ddisp = nullptr;
+  if ((bgr_out && (rc = dalloc(c, &dout, 3 * n, &tmp))) || (disp_out && (rc = dalloc(c, &ddisp, n, &tmp))) || (mask_out && (rc = dalloc(c, &dmask, n, &tmp)))) return rc;
+  if ((rc = synthesize_enqueue(c, source, p, t, SynthOut{dout, row, ddisp, dmask}))) return rc;
+  if (bgr_out) HIPCHK(c, hipMemcpy2DAsync(bgr_out, out_stride, dout, row, row, c->H, hipMemcpyDeviceToHost, c->stream));
+  if (disp_out) HIPCHK(c, hipMemcpyAsync(disp_out, ddisp, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+  if (mask_out) HIPCHK(c, hipMemcpyAsync(mask_out, dmask, n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return CSPM_OK;
+}
+
+// the same with device-resident outputs: asynchronous on the ctx stream behind the pending-run check; not replayed (cspm.h)
+int cspm_synthesize_device(cspm_ctx *c, int source, const cspm_synth_params *p, double t, void *d_bgr_out, size_t out_stride, void *d_disp_out,
+                           void *d_mask_out) {
+  if (!c) return CSPM_ERR_ARG;
+  int rc = synthesize_check(c, source, &p, t, d_bgr_out != nullptr, out_stride);
+  if (rc) return rc;
+  ON_DEVICE(c);
+  return synthesize_enqueue(c, source, p, t, SynthOut{(uint8_t *)d_bgr_out, out_stride, (double *)d_disp_out, (uint8_t *)d_mask_out});
 }
 
 int cspm_pm_init_keep(cspm_ctx *c, const cspm_pm_params *p) {

@@ -98,6 +98,11 @@ class CSPatchMatch {
   size_t Reproject(const RefView &view, const cspm_calib &calib, const cspm_geom_params &params, int source, const cspm_fit_params *fit,
                    std::vector<double> *depth, std::vector<double> *xyz, std::vector<double> *normal, std::vector<uint8_t> *keep,
                    std::vector<cspm_point> *cloud) const;
+  // view synthesis (cspm.h "view synthesis"): the scene from the camera at fraction t of the baseline (0 = the left
+  // view, 1 = the right one), rendered from the stored plane field and the two images.  source as for Reproject.  bgr: a wid x hei 8UC3
+  // image; disp: wid x hei row-major, NaN in holes; mask: wid x hei bytes, 0 hole, 1 / 2 one view, 3 both, 4 filled.  Every output may be
+  // NULL.  Throws for what the C ABI refuses.
+  void Synthesize(double t, const cspm_synth_params &params, int source, Mat *bgr, std::vector<double> *disp, std::vector<uint8_t> *mask) const;
 
  private:
   Mat img_[kViewNum], dis_[kViewNum];

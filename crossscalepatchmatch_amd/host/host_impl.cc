@@ -588,6 +588,19 @@ size_t CSPatchMatch::Reproject(const RefView &view, const cspm_calib &calib, con
   return count;
 }
 
+void CSPatchMatch::Synthesize(double t, const cspm_synth_params &params, int source, Mat *bgr, std::vector<double> *disp, std::vector<uint8_t> *mask) const {
+  if (!last_ctx_) throw std::runtime_error("CSPatchMatch::Synthesize before PatchMatch");
+  if (!DevicePlaneCost::is_live(last_ctx_)) throw std::runtime_error("CSPatchMatch::Synthesize: the plane cost PatchMatch ran on has been deleted");
+  const size_t n = (size_t)wid_ * hei_;
+  if (bgr) bgr->create(hei_, wid_, CV_8UC3);
+  if (disp) disp->resize(n);
+  if (mask) mask->resize(n);
+  if (source == CSPM_GEOM_PP) ApplyPostFilters(last_ctx_);
+  check(cspm_synthesize(last_ctx_, source, &params, t, bgr ? bgr->ptr<unsigned char>(0) : NULL, bgr ? bgr->step : 0, disp ? disp->data() : NULL,
+                        mask ? mask->data() : NULL),
+        last_ctx_, "cspm_synthesize");
+}
+
 void CSPatchMatch::SetSpeckleFilter(int max_size, double max_diff) {
   if (max_size < 0 || !(max_diff >= 0.0) || !std::isfinite(max_diff))
     throw std::runtime_error("CSPatchMatch::SetSpeckleFilter: max_size >= 0 and a finite max_diff >= 0 expected");

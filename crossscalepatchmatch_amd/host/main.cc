@@ -5,7 +5,8 @@
 // field as candidates) --seed_ca (local stereo, kept wherever the random start plane costs no less, then --iters iterations)
 // --fit_radius --fit_max_diff --fit_merge (slanted planes fitted to the local-stereo field or to the seed maps before what follows)
 // --calib --l_ply --r_ply --l_depth_pfm --r_depth_pfm --geom_min_cos --geom_z_far --geom_left_frame --geom_fit_radius (metric depth maps and
-// point clouds of the final plane field; include/cspm.h "reprojection").
+// point clouds of the final plane field; include/cspm.h "reprojection") --synth_t --synth_png --synth_dis_pfm --synth_views --synth_max_stretch
+// --synth_merge_diff --synth_fill (the scene rendered from a camera between the two views; include/cspm.h "view synthesis").
 #include "../../include/cspm.h"
 #include "commfunc.h"
 #include "cs_patchmatch.h"
@@ -91,7 +92,18 @@ DEFINE_double(geom_z_far, 0.0, "point clouds and depth maps: no point beyond thi
 DEFINE_bool(geom_left_frame, false, "the right view's points are given in the left camera's frame (X + baseline)");
 DEFINE_int32(geom_fit_radius, 0, "normals from planes fitted to the disparity map over a window of this half-width (1 .. 17) instead of the plane "
                                 "field's own slopes; 0 = the field's slopes");
-DEFINE_string(batch_list, "", "text file, one stereo pair per line: l_img r_img l_dis r_dis [l_pfm r_pfm]; all pairs run with the "
+DEFINE_double(synth_t, -1.0, "render the scene from the camera at this fraction of the baseline, 0 (the left view) .. 1 (the right view), from the "
+                             "final plane field and the two images: the raw plane disparities, or with --use_pp the sub-pixel post-processed maps "
+                             "(include/cspm.h \"view synthesis\").  Needs --synth_png or --synth_dis_pfm (with --batch_list: the list's columns); "
+                             "negative = off");
+DEFINE_string(synth_png, "", "with --synth_t: write the rendered view as an 8-bit colour PNG / PPM.  Not with --batch_list, whose lines name it");
+DEFINE_string(synth_dis_pfm, "", "with --synth_t: write the rendered view's disparity map as float32 PFM, NaN in holes.  Not with --batch_list");
+DEFINE_int32(synth_views, 3, "with --synth_t: the source views used, 1 = left, 2 = right, 3 = both");
+DEFINE_double(synth_max_stretch, 4.0, "with --synth_t: a source pixel is dropped when its plane stretches it over more target pixels than this (>= 1)");
+DEFINE_double(synth_merge_diff, 1.0, "with --synth_t: the two views are blended where their disparities differ by at most this (>= 0)");
+DEFINE_bool(synth_fill, true, "with --synth_t: holes take the nearest pixel of their row on the background side");
+DEFINE_string(batch_list, "", "text file, one stereo pair per line: l_img r_img l_dis r_dis [l_pfm r_pfm [synth_png [synth_pfm]]] (the last two with "
+                              "--synth_t, and then `-` skips an optional column); all pairs run with the "
                               "matching flags of this command line on one device context (buffers are reused between pairs). A pair "
                               "that fails is reported and the batch goes on; the exit code is non-zero if any pair failed");
 DEFINE_int32(in_flight, 2, "with --batch_list: stereo pairs in flight per GPU (2 measured best on MI355X, 3 and 4 within 1.5 %).  Each is a worker thread with its own device context (one HIP stream): "
@@ -107,7 +119,7 @@ const int kWindow = 35;  // main.cc:94
 const int kScales = 5;   // main.cc:100
 
 struct PairFiles {
-  string l_img, r_img, l_dis, r_dis, l_pfm, r_pfm;
+  string l_img, r_img, l_dis, r_dis, l_pfm, r_pfm, synth_png, synth_pfm;
 };
 
 // One stereo pair on its way through the flow of main.cc:57-139, cut into the four stages a batch worker overlaps: load (decode the
@@ -123,6 +135,8 @@ struct PairRun {
   std::vector<double> pfm[kViewNum];
   std::vector<double> depth[kViewNum];      // --l_depth_pfm / --r_depth_pfm
   std::vector<cspm_point> cloud[kViewNum];  // --l_ply / --r_ply
+  Mat synth;                      // --synth_png
+  std::vector<double> synth_dis;  // --synth_dis_pfm
   cspm_calib calib;
   double t0;
   int rc;
@@ -242,6 +256,19 @@ void finish(PairRun &p) {
           p.log << "Reprojection, view " << v << ": " << count << " points, " << (static_cast<double>(getTickCount()) - g0) / getTickFrequency() * 1e3
                 << " ms\n";
       }
+      if (FLAGS_synth_t >= 0.0 && (!p.files.synth_png.empty() || !p.files.synth_pfm.empty())) {  // reads the cost object's context: before it goes
+        cspm_synth_params sp;
+        cspm_synth_default_params(&sp);
+        sp.views = FLAGS_synth_views;
+        sp.max_stretch = FLAGS_synth_max_stretch;
+        sp.merge_diff = FLAGS_synth_merge_diff;
+        sp.fill = FLAGS_synth_fill ? 1 : 0;
+        const double s0 = static_cast<double>(getTickCount());
+        p.matcher->Synthesize(FLAGS_synth_t, sp, FLAGS_use_pp ? CSPM_GEOM_PP : CSPM_GEOM_RAW, p.files.synth_png.empty() ? NULL : &p.synth,
+                              p.files.synth_pfm.empty() ? NULL : &p.synth_dis, NULL);
+        if (!FLAGS_quiet)
+          p.log << "View synthesis, t = " << FLAGS_synth_t << ": " << (static_cast<double>(getTickCount()) - s0) / getTickFrequency() * 1e3 << " ms\n";
+      }
     } catch (const std::exception &e) {
       p.log << "Error: " << e.what() << "\n";
       p.rc = EXIT_FAILURE;
@@ -261,6 +288,8 @@ void write(PairRun &p) {
     if (!dpfm[v]->empty()) written = WritePFM(*dpfm[v], p.depth[v].data(), p.left.cols, p.left.rows);
     if (written && !ply[v]->empty()) written = WritePLY(*ply[v], p.cloud[v].data(), p.cloud[v].size());
   }
+  if (written && !p.synth.empty()) written = imwrite(p.files.synth_png, p.synth);
+  if (written && !p.synth_dis.empty()) written = WritePFM(p.files.synth_pfm, p.synth_dis.data(), p.left.cols, p.left.rows);
   if (!written) {
     p.log << "Error: can not write disparity maps\n";
     p.rc = EXIT_FAILURE;
@@ -471,6 +500,25 @@ int run() {
     cout << "Error: the point-cloud and depth outputs need one of this library's plane costs (--pc_name=PRE or IMG), not " << FLAGS_pc_name << "\n";
     return EXIT_FAILURE;
   }
+  const bool synth_flags = !FLAGS_synth_png.empty() || !FLAGS_synth_dis_pfm.empty();
+  if (FLAGS_synth_t < 0.0 && synth_flags) {  // checked before anything opens a device
+    cout << "Error: --synth_png / --synth_dis_pfm need --synth_t\n";
+    return EXIT_FAILURE;
+  }
+  if (FLAGS_synth_t >= 0.0 || std::isnan(FLAGS_synth_t)) {
+    if (!(FLAGS_synth_t <= 1.0) || FLAGS_synth_views < 1 || FLAGS_synth_views > 3 || !(FLAGS_synth_max_stretch >= 1.0) || !(FLAGS_synth_merge_diff >= 0.0)) {
+      cout << "Error: --synth_t must be 0 .. 1, --synth_views 1 .. 3, --synth_max_stretch >= 1 and --synth_merge_diff >= 0\n";
+      return EXIT_FAILURE;
+    }
+    if (FLAGS_batch_list.empty() ? !synth_flags : synth_flags) {
+      cout << "Error: --synth_t writes to --synth_png / --synth_dis_pfm for one pair, and to the list's columns 7 and 8 with --batch_list\n";
+      return EXIT_FAILURE;
+    }
+    if (FLAGS_pc_name != "PRE" && FLAGS_pc_name != "IMG") {
+      cout << "Error: view synthesis needs one of this library's plane costs (--pc_name=PRE or IMG), not " << FLAGS_pc_name << "\n";
+      return EXIT_FAILURE;
+    }
+  }
   CalibFile calib_file;
   if (!FLAGS_calib.empty() && !ReadCalibFile(FLAGS_calib, &calib_file)) {
     cout << "Error: can not read " << FLAGS_calib << " as a Middlebury calib.txt (cam0, cam1, doffs, baseline, width, height)\n";
@@ -483,7 +531,9 @@ int run() {
     const std::unique_ptr<CCMethod> cost_fn(GetCCType(FLAGS_cc_name));  // NULL for unknown names, rejected by the cost constructors
     if (CenGrdCC *cg = dynamic_cast<CenGrdCC *>(cost_fn.get())) cg->set_fused(FLAGS_cc_fused);
     if (!FLAGS_quiet) cout << "Load Image: " << FLAGS_l_img_file << " " << FLAGS_r_img_file << "\n";
-    PairRun p(PairFiles{FLAGS_l_img_file, FLAGS_r_img_file, FLAGS_l_dis_file, FLAGS_r_dis_file, FLAGS_l_disp_pfm, FLAGS_r_disp_pfm}, 0);
+    PairRun p(PairFiles{FLAGS_l_img_file, FLAGS_r_img_file, FLAGS_l_dis_file, FLAGS_r_dis_file, FLAGS_l_disp_pfm, FLAGS_r_disp_pfm, FLAGS_synth_png,
+                        FLAGS_synth_dis_pfm},
+              0);
     load(p);
     if (!FLAGS_calib.empty() && p.rc == EXIT_SUCCESS) p.calib = ScaledCalib(calib_file, p.left.cols);
     begin(p, cost_fn.get());
@@ -511,7 +561,15 @@ int run() {
       ++bad_lines;
       continue;
     }
-    is >> f.l_pfm >> f.r_pfm;
+    is >> f.l_pfm >> f.r_pfm >> f.synth_png >> f.synth_pfm;
+    if (FLAGS_synth_t >= 0.0) {  // a list that names view-synthesis outputs may skip an earlier optional column with "-"
+      string *opt[4] = {&f.l_pfm, &f.r_pfm, &f.synth_png, &f.synth_pfm};
+      for (int k = 0; k < 4; ++k)
+        if (*opt[k] == "-") opt[k]->clear();
+    } else {
+      f.synth_png.clear();
+      f.synth_pfm.clear();
+    }
     if (FLAGS_batch_skip_existing && std::ifstream(f.l_dis.c_str()).good() && std::ifstream(f.r_dis.c_str()).good()) {
       ++skipped;
       continue;

@@ -513,6 +513,78 @@ int cspm_reproject_device(cspm_ctx *ctx, int view, int source, const cspm_calib 
                           const cspm_fit_params *fit, void *d_depth_out, void *d_xyz_out, void *d_normal_out, void *d_keep_out, void *d_cloud_out,
                           size_t cloud_cap, void *d_count_out);
 
+/* ---- view synthesis (an addition): the scene rendered from a camera between (or at) the two views ----------------------
+ * A rectified warp never leaves its image row, and a slanted plane says how one source pixel stretches or compresses in the target view,
+ * so a surface is rasterised exactly, without cracks, instead of splatting rounded disparities.
+ * N(t, params, per view v in {0, 1}: D_v, V_v, A_v, I_v): D a w x h f64 disparity map, V w x h bytes (NULL = all 1), A the w x h f64 x-slope
+ * of the pixel's plane (NULL = all 0; the y-slope is not needed: D is already the plane at the pixel and the warp stays in the row), I a
+ * packed 8-bit BGR image.  t in [0, 1] is the fraction of the baseline from view 0 to view 1.  Every product, sum and quotient is one IEEE
+ * f64 operation in the association written here, nothing contracted, no reciprocal.  The host computes once
+ *     sigma_0 = -t        sigma_1 = 1.0 - t        w0 = 1.0 - t        w1 = t
+ * Step 1, footprints.  For view v (sigma = sigma_v) and source pixel (x, y):
+ *     usable = V != 0 && isfinite(D) && D >= 0.0
+ *     a    = isfinite(A) ? A : 0.0
+ *     g    = 1.0 + sigma * a                   target pixels one source pixel covers
+ *     u    = (double)x + sigma * D
+ *     half = 0.5 * g        lo = u - half        hi = u + half
+ *     used = usable && g > 0.0 && g <= max_stretch
+ *   A non-positive g is a surface seen from behind, a g above the cap one stretched beyond what its colours can fill.  A used pixel
+ *   covers every integer x' with lo <= (double)x' < hi and 0 <= x' < w (half-open; lo and hi are the rounded values above), and there
+ *     xs = (double)x + ((double)x' - u) / g    the source position
+ *     d' = D + a * (xs - (double)x)            the plane's disparity there
+ * Step 2, visibility.  Per view and target pixel the candidate with the greatest d' wins, in the total order of the order-preserving
+ *   64-bit key of the bit pattern (as M64 above: -0.0 < +0.0; a candidate is never NaN); among bit-equal d' the smallest source x wins.
+ *   In exact arithmetic two pixels of one view cannot tie; the rule makes the result independent of the execution order.  The result is
+ *   Z_v(x') = d' and xs_v(x') of the winner, or a hole.
+ * Step 3, colour.  fl = floor(xs), f = xs - fl, ia = clamp(fl, 0, w-1), ib = clamp(fl + 1, 0, w-1), and per channel
+ *     C_v = (1.0 - f) * (double)I[y][ia] + f * (double)I[y][ib]
+ * Step 4, merge.  Both views present and fabs(Z_0 - Z_1) <= merge_diff: C = w0 * C_0 + w1 * C_1 per channel, Z = w0 * Z_0 + w1 * Z_1,
+ *   mask 3.  Both present otherwise: view 0 alone when Z_0 >= Z_1 (mask 1), else view 1 alone (mask 2).  One present: that view, mask 1 or
+ *   2.  None: a hole, mask 0.
+ * Step 5, fill, when `fill`.  A hole takes the nearest non-hole pixel of its row on either side; with both sides present the right one
+ *   when its Z is smaller (Z_R < Z_L: the background, the reference's choice in FillInvalid, cs_patchmatch.cc:399-411) and the left one
+ *   otherwise.  Colour and disparity are copied, the mask is 4.  A row without any non-hole pixel stays a hole.
+ * Outputs, each optional (NULL) and untouched when not requested: a BGR 8-bit image with rows of out_stride bytes (bytes beyond 3*w of a
+ * row are untouched), each channel the Round2Int (round half to even) of the f64 colour saturated to 0 .. 255, holes 0; an f64 disparity
+ * map, NaN in holes; a u8 mask, 0 .. 4.
+ * Parameters (NULL = the defaults).  The defaults are documented choices, not tuned values: no quality figure was optimised over them. */
+#define CSPM_SYNTH_MAX_WIDTH 6784 /* a target row lives in one workgroup's LDS (24 bytes per pixel of 160 KiB); wider: CSPM_ERR_ARG */
+typedef struct cspm_synth_params {
+  int views;          /* bit mask of the source views used: 1 = view 0, 2 = view 1, 3 = both (the default) */
+  int fill;           /* step 5 on (the default, 1) or off (0) */
+  double max_stretch; /* a source pixel is used only when 0 < g <= max_stretch; >= 1, may be +infinity; default 4.0 */
+  double merge_diff;  /* the views are blended where their disparities differ by at most this; >= 0, may be +infinity; default 1.0 */
+} cspm_synth_params;
+typedef struct cspm_synth_view {
+  const double *disp;    /* D: w*h, packed rows */
+  const uint8_t *valid;  /* V: w*h bytes or NULL */
+  const double *slope_a; /* A: w*h or NULL */
+  const uint8_t *bgr;    /* I: 8UC3 rows of `stride` bytes */
+  size_t stride;         /* >= 3*w */
+} cspm_synth_view;
+int cspm_synth_default_params(cspm_synth_params *p);
+/* N alone on caller memory, no context needed, synchronous.  view0 / view1 may be NULL when `views` does not name the view.  Arguments are
+ * checked before a device is opened: CSPM_ERR_ARG for a t that is NaN or outside [0, 1], views outside 1 .. 3, a max_stretch that is NaN or
+ * < 1, a merge_diff that is NaN or negative, a missing map or image of a view that `views` names, w or h < 1, w*h >= 2^31,
+ * w > CSPM_SYNTH_MAX_WIDTH, an input stride of a named view below 3*w, or (with bgr_out) an out_stride below 3*w. */
+int cspm_synthesize_host(int device, const cspm_synth_params *params, double t, const cspm_synth_view *view0, const cspm_synth_view *view1,
+                         int w, int h, uint8_t *bgr_out, size_t out_stride, double *disp_out, uint8_t *mask_out);
+/* N on the context's stored plane field; I = the level-0 images.  source as for cspm_reproject:
+ *   CSPM_GEOM_RAW  D = the field's a*x+b*y+c of either view written into scratch, A = the field's a, V all 1.
+ *   CSPM_GEOM_PP   D = the maps of the sub-pixel post-processing (cspm_postprocess_f64, with the context's speckle and median settings),
+ *                  which this call runs itself; A = the field's a where the pixel passed the left-right check (the masks that entry
+ *                  returns) and 0 elsewhere; V all 1.
+ * Makes the same pending-run check on entry as cspm_reproject.  Synchronous; host outputs.  Timed as one CSPM_K_MISC bracket per call with
+ * w*h evaluations (CSPM_GEOM_PP: behind the post-processing's own CSPM_K_POST brackets).  Scratch (two maps, CSPM_GEOM_RAW only) is
+ * allocated on first use and freed with the plane field.  CSPM_ERR_ARG as above and for a bad source; CSPM_ERR_STATE without images or a
+ * plane field, and without a cost object when source is CSPM_GEOM_PP. */
+int cspm_synthesize(cspm_ctx *ctx, int source, const cspm_synth_params *params, double t, uint8_t *bgr_out, size_t out_stride,
+                    double *disp_out, uint8_t *mask_out);
+/* the same with device pointers for every output; enqueued on the ctx stream behind the pending-run check.  Like cspm_reproject_device it is
+ * NOT part of the deferred-output replay. */
+int cspm_synthesize_device(cspm_ctx *ctx, int source, const cspm_synth_params *params, double t, void *d_bgr_out, size_t out_stride,
+                           void *d_disp_out, void *d_mask_out);
+
 /* ---- CSPatchMatch::PatchMatch over a FOREIGN IPlaneCost (plane_cost/i_plane_cost.h:28-33) ------------------------------
  * Any object with a GetPlaneCost(x, y, plane, view) that is not one of this library's device costs: the reference drives it
  * through the virtual call (call sites cs_patchmatch.cc:144,181,191,200,208,269,334).  Here the device keeps the plane field,
