@@ -56,6 +56,7 @@ SYMBOLS = [
     "cspm_merge_planes", "cspm_merge_planes_host", "cspm_pm_init_keep",
     "cspm_set_pp_speckle", "cspm_get_pp_speckle", "cspm_filter_speckles_host",
     "cspm_median_filter_u8_host", "cspm_median_filter_f64_host", "cspm_set_pp_median", "cspm_get_pp_median",
+    "cspm_smooth_default_params", "cspm_smooth_disparity_host", "cspm_set_pp_smooth", "cspm_get_pp_smooth",
     "cspm_fit_default_params", "cspm_fit_planes_host", "cspm_fit_planes",
     "cspm_geom_default_params", "cspm_reproject_host", "cspm_reproject", "cspm_reproject_device",
     "cspm_synth_default_params", "cspm_synthesize_host", "cspm_synthesize", "cspm_synthesize_device",
@@ -75,6 +76,11 @@ class PmParams(C.Structure):
 class FitParams(C.Structure):
     """struct cspm_fit_params"""
     _fields_ = [("radius", C.c_int), ("max_diff", C.c_double), ("min_support", C.c_int), ("use_guide", C.c_int)]
+
+
+class SmoothParams(C.Structure):
+    """struct cspm_smooth_params"""
+    _fields_ = [("lambda_", C.c_double), ("sigma_color", C.c_double), ("iterations", C.c_int), ("fill_conf", C.c_double)]
 
 
 class Calib(C.Structure):
@@ -132,6 +138,7 @@ def load_library():
     llp = C.POINTER(C.c_longlong)
     pp = C.POINTER(PmParams)
     fp = C.POINTER(FitParams)
+    mp = C.POINTER(SmoothParams)
     kp, gp, up = C.POINTER(Calib), C.POINTER(GeomParams), C.POINTER(C.c_uint)
     sp, svp = C.POINTER(SynthParams), C.POINTER(SynthView)
     sig = {
@@ -201,6 +208,10 @@ def load_library():
         "cspm_median_filter_f64_host": (C.c_int, [C.c_int, dp, C.c_int, C.c_int, C.c_int, dp]),
         "cspm_set_pp_median": (C.c_int, [vp, C.c_int]),
         "cspm_get_pp_median": (C.c_int, [vp, ip]),
+        "cspm_smooth_default_params": (C.c_int, [mp]),
+        "cspm_smooth_disparity_host": (C.c_int, [C.c_int, dp, dp, u8p, C.c_int, C.c_int, mp, C.c_int, dp]),
+        "cspm_set_pp_smooth": (C.c_int, [vp, mp]),
+        "cspm_get_pp_smooth": (C.c_int, [vp, mp, ip]),
         "cspm_fit_default_params": (C.c_int, [fp]),
         "cspm_fit_planes_host": (C.c_int, [C.c_int, dp, u8p, u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, fp, dp, u8p]),
         "cspm_fit_planes": (C.c_int, [vp, fp, C.c_int]),
@@ -524,6 +535,20 @@ class StereoContext:
         self._chk(self.L.cspm_get_pp_median(self.p, C.byref(r)))
         return r.value
 
+    def set_pp_smooth(self, **params):
+        """edge-aware global smoothing of the sub-pixel post-processing: as the last step of postprocess_f64 and
+        postprocess_f64_device, after the weighted median and the median filter, both maps are smoothed along their level-0 images with
+        confidence 1 where the pixel passed the left-right check and fill_conf elsewhere.  params: lam, sigma_color, iterations,
+        fill_conf (the rest keep the defaults 100, 20, 3, 0.25); lam=0 (the context's default) = off.  The 8-bit entries are not affected."""
+        p = smooth_params(**params)
+        self._chk(self.L.cspm_set_pp_smooth(self.p, C.byref(p)))
+
+    def get_pp_smooth(self):
+        """the smoothing parameters as a dict (lam, sigma_color, iterations, fill_conf) and on (bool)"""
+        p, on = SmoothParams(), C.c_int()
+        self._chk(self.L.cspm_get_pp_smooth(self.p, C.byref(p), C.byref(on)))
+        return {"lam": p.lambda_, "sigma_color": p.sigma_color, "iterations": p.iterations, "fill_conf": p.fill_conf, "on": bool(on.value)}
+
     def postprocess_f64_device(self, d_l_ptr, d_r_ptr):
         """the same with device-resident outputs (packed h*w f64 each; asynchronous on the context's stream)"""
         self._chk(self.L.cspm_postprocess_f64_device(self.p, C.c_void_p(d_l_ptr), C.c_void_p(d_r_ptr)))
@@ -806,6 +831,44 @@ def synthesize_host(t, disp, bgr, valid=(None, None), slope_a=(None, None), outp
     if rc != 0:
         raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
     return res
+
+
+def smooth_params(**params):
+    """struct cspm_smooth_params: cspm_smooth_default_params with the given fields replaced.  `lambda` is a Python keyword: the field
+    is given as lam (or as "lambda" through a dict)."""
+    p = SmoothParams()
+    rc = load_library().cspm_smooth_default_params(C.byref(p))
+    assert rc == 0
+    for k, v in params.items():
+        if k in ("lam", "lambda", "lambda_"):
+            p.lambda_ = float(v)
+        elif k in ("sigma_color", "fill_conf"):
+            setattr(p, k, float(v))
+        elif k == "iterations":
+            p.iterations = int(v)
+        else:
+            raise TypeError(f"unknown smoothing parameter {k!r}")
+    return p
+
+
+def smooth_disparity(device, disp, conf=None, guide=None, max_dis=0, **params):
+    """the edge-aware global smoother alone (cspm_smooth_disparity_host) on a host map: disp (h, w) f64 (a
+    non-finite pixel is a hole), conf (h, w) f64 in [0, 1] or None (all 1), guide (h, w, 3) uint8 BGR or None (every weight 1);
+    params: lam, sigma_color, iterations; max_dis > 0 clamps the smoothed values to [0, max_dis].  Returns a new (h, w) f64 map."""
+    L = load_library()
+    p = smooth_params(**params)
+    d = np.ascontiguousarray(disp, dtype=np.float64)
+    assert d.ndim == 2, d.shape
+    h, w = d.shape
+    c = None if conf is None else np.ascontiguousarray(conf, dtype=np.float64)
+    g = None if guide is None else np.ascontiguousarray(guide, dtype=np.uint8)
+    assert (c is None or c.shape == (h, w)) and (g is None or g.shape == (h, w, 3))
+    out = np.zeros_like(d)
+    rc = L.cspm_smooth_disparity_host(device, _dp(d), _dp(c) if c is not None else None, _u8(g) if g is not None else None, w, h, C.byref(p),
+                                      int(max_dis), _dp(out))
+    if rc != 0:
+        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    return out
 
 
 def median_filter(device, img, r):

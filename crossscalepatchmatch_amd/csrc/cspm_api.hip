@@ -14,6 +14,7 @@
 #include "cspm_pp.h"
 #include "cspm_speckle.h"
 #include "cspm_median.h"
+#include "cspm_smooth.h"
 #include "cspm_fit.h"
 #include "cspm_geom.h"
 #include "cspm_synth.h"
@@ -186,6 +187,10 @@ struct cspm_ctx {
   int pp_median = 0;                         // cspm_set_pp_median: radius of the final median filter, 0 = none (no launch, no second buffer)
   uint8_t *d_med8[2] = {nullptr, nullptr};   // median filter: the second 8-bit buffer per view; swapped with d_dis by every filtered call.  Allocated by the first one and kept
   double *d_med64 = nullptr;                 // median filter: the second pair of f64 maps (one allocation, like d_pp); swapped with d_pp[0]
+  cspm_smooth_params pp_smooth = {0.0, 20.0, 3, 0.25};  // cspm_set_pp_smooth: lambda == 0 = no smoothing (no launch, no scratch)
+  double *d_smooth = nullptr;                // smoothing: N, M and ct of both views (one allocation of 6 maps), then the table; allocated by the first smoothed call and kept
+  std::vector<double> smooth_lut;            // the host's copy of the uploaded exp(-k / sigma) table
+  double smooth_lut_sigma = 0.0;             // ... and the sigma it was computed for (0 = none yet)
   bool speckle_ran = false;                  // the last post-processing enqueued ran the filter (CSPM_OPT_PP_SPECKLE_REMOVED reads its counter)
   // persistent raster sweep (k_spatial_sweep)
   unsigned int *d_sweep_ctrl = nullptr, *d_sweep_start = nullptr;
@@ -380,6 +385,8 @@ void free_field(cspm_ctx *c) {
   dfree(c->d_med8[0]);
   dfree(c->d_med8[1]);
   dfree(c->d_med64);
+  dfree(c->d_smooth);
+  c->smooth_lut_sigma = 0.0;
   dfree(c->d_pp[0]);  // one allocation holds both maps
   c->d_pp[1] = nullptr;
   dfree(c->d_rowq);
@@ -1390,6 +1397,78 @@ int median_f64_enqueue(cspm_ctx *c) {
   return CSPM_OK;
 }
 
+// Edge-aware global smoothing (cspm_smooth.h).  Defaults chosen, not tuned.
+const cspm_smooth_params kSmoothDefaults = {100.0, 20.0, 3, 0.25};
+const char *smooth_params_error(const cspm_smooth_params *p, bool with_fill_conf) {
+  if (!(p->lambda >= 0.0) || !std::isfinite(p->lambda)) return "smoothing: lambda must be finite and >= 0";
+  if (!(p->sigma_color > 0.0) || !std::isfinite(p->sigma_color)) return "smoothing: sigma_color must be finite and > 0";
+  if (p->iterations < 1 || p->iterations > kSmMaxIters) return "smoothing: iterations 1 .. 8";
+  if (with_fill_conf && !(p->fill_conf >= 0.0 && p->fill_conf <= 1.0)) return "smoothing: fill_conf must lie in [0, 1]";
+  return nullptr;
+}
+// LUT[k] = exp(-k / sigma) by the host's libm, like the fit's table
+void smooth_lut_fill(double sigma, double *lut) {
+  for (int k = 0; k < kSmLut; ++k) lut[k] = std::exp(-(double)k / sigma);
+}
+// S on `views` views (1 or 2) of w x h in place on d: init, T rounds of a horizontal and a vertical pass, finish.  lut == nullptr: no guide.
+void smooth_launch(hipStream_t stream, double *const *d, const SmoothConf &cf, const SmoothPair &s, int views, int w, int h, const cspm_smooth_params *p,
+                   double max_dis, const double *lut) {
+  const long long n = (long long)w * h;
+  const int u = views - 1, T = p->iterations;
+  hipLaunchKernelGGL(k_smooth_init, dim3(ew_grid(n * views)), dim3(256), 0, stream, d[0], d[u], cf, s, n, views);
+  double pow_T = 1.0;  // 4^T, exact
+  for (int i = 0; i < T; ++i) pow_T *= 4.0;
+  const dim3 rows((unsigned)((h + kSmRows - 1) / kSmRows), (unsigned)views), cols((unsigned)((w + kWave - 1) / kWave), (unsigned)views);
+  for (int t = 1; t <= T; ++t) {
+    double pow_t = 1.0;  // 4^(T - t)
+    for (int i = 0; i < T - t; ++i) pow_t *= 4.0;
+    const double lam = ((1.5 * pow_t) / (pow_T - 1.0)) * p->lambda;
+    if (lut) {
+      hipLaunchKernelGGL(k_smooth_rows<true>, rows, dim3(kWave), 0, stream, s, w, h, lam, lut);
+      hipLaunchKernelGGL(k_smooth_cols<true>, cols, dim3(kWave), 0, stream, s, w, h, lam, lut);
+    } else {
+      hipLaunchKernelGGL(k_smooth_rows<false>, rows, dim3(kWave), 0, stream, s, w, h, lam, lut);
+      hipLaunchKernelGGL(k_smooth_cols<false>, cols, dim3(kWave), 0, stream, s, w, h, lam, lut);
+    }
+  }
+  hipLaunchKernelGGL(k_smooth_finish, dim3(ew_grid(n * views)), dim3(256), 0, stream, d[0], d[u], s, n, views, max_dis);
+}
+
+// the last step of the sub-pixel PostProcessing: S in place on c->d_pp, C from the final consistency masks; nothing at all when off
+int smooth_f64_enqueue(cspm_ctx *c) {
+  const cspm_smooth_params &p = c->pp_smooth;
+  if (p.lambda == 0.0) return CSPM_OK;
+  const size_t n = (size_t)c->W * c->H;
+  if (!c->d_smooth) {
+    if (int rc = dalloc(c, &c->d_smooth, 6 * n + kSmLut, nullptr)) return rc;
+    c->smooth_lut_sigma = 0.0;
+  }
+  double *d_lut = c->d_smooth + 6 * n;
+  if (c->smooth_lut_sigma != p.sigma_color) {  // a new table: the stream is drained so that no earlier launch still reads the old one
+    c->smooth_lut.resize(kSmLut);
+    smooth_lut_fill(p.sigma_color, c->smooth_lut.data());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_lut, c->smooth_lut.data(), sizeof(double) * kSmLut, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->smooth_lut_sigma = p.sigma_color;
+  }
+  const Level &L0 = c->cost.lv[0];
+  SmoothPair s;
+  SmoothConf cf;
+  for (int v = 0; v < 2; ++v) {
+    s.v[v] = SmoothView{c->d_smooth + v * n, c->d_smooth + (2 + v) * n, c->d_smooth + (4 + v) * n, L0.pix[v]};
+    cf.conf[v] = nullptr;
+    cf.ok[v] = c->d_valid[v];
+  }
+  s.Wp = L0.Wp;
+  s.pad = L0.pad;
+  cf.fill_conf = p.fill_conf;
+  Timed t(c, CSPM_K_POST, 0);
+  smooth_launch(c->stream, c->d_pp, cf, s, 2, c->W, c->H, &p, (double)c->max_dis, d_lut);
+  HIPCHK(c, hipGetLastError());
+  return CSPM_OK;
+}
+
 // PlaneToDisp + PostProcessing (cs_patchmatch.cc:103-107, 508-588) enqueued on the ctx stream; results in c->d_dis[v]
 int postprocess_enqueue(cspm_ctx *c, int dis_scale) {
   if (int rc = postprocess_steps(c, dis_scale)) return rc;
@@ -1436,7 +1515,8 @@ int postprocess_f64_steps(cspm_ctx *c) {
 }
 int postprocess_f64_enqueue(cspm_ctx *c) {
   if (int rc = postprocess_f64_steps(c)) return rc;
-  return median_f64_enqueue(c);
+  if (int rc = median_f64_enqueue(c)) return rc;
+  return smooth_f64_enqueue(c);
 }
 
 // An asynchronous output, enqueued on the ctx stream: the map of one view, or both post-processed maps copied to the caller's buffers.
@@ -2016,6 +2096,27 @@ int cspm_get_pp_median(cspm_ctx *c, int *r) {
   *r = c->pp_median;
   return CSPM_OK;
 }
+int cspm_smooth_default_params(cspm_smooth_params *p) {
+  if (!p) return CSPM_ERR_ARG;
+  *p = kSmoothDefaults;
+  return CSPM_OK;
+}
+int cspm_set_pp_smooth(cspm_ctx *c, const cspm_smooth_params *p) {
+  if (!c) return CSPM_ERR_ARG;
+  if (!p || p->lambda == 0.0) {  // off: the other values stay as they were
+    c->pp_smooth.lambda = 0.0;
+    return CSPM_OK;
+  }
+  if (const char *msg = smooth_params_error(p, true)) return fail(c, CSPM_ERR_ARG, msg);
+  c->pp_smooth = *p;
+  return CSPM_OK;
+}
+int cspm_get_pp_smooth(cspm_ctx *c, cspm_smooth_params *p, int *on) {
+  if (!c) return CSPM_ERR_ARG;
+  if (p) *p = c->pp_smooth;
+  if (on) *on = c->pp_smooth.lambda != 0.0;
+  return CSPM_OK;
+}
 int cspm_get_pp_speckle(cspm_ctx *c, int *max_size, double *max_diff) {
   if (!c) return CSPM_ERR_ARG;
   if (max_size) *max_size = c->pp_speckle_size;
@@ -2438,6 +2539,47 @@ int cspm_median_filter_f64_host(int device, const double *src, int w, int h, int
   if (hipGetLastError() != hipSuccess || hipMemcpyAsync(dst, dd, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
       hipStreamSynchronize(c->stream) != hipSuccess)
     return S.done(fail(c, CSPM_ERR_HIP, "median filter kernel failed"));
+  return S.done(CSPM_OK);
+}
+
+// the smoother alone on caller memory: the launches PostProcessing enqueues, on one view
+int cspm_smooth_disparity_host(int device, const double *disp, const double *conf, const uint8_t *guide_bgr, int w, int h, const cspm_smooth_params *p,
+                               int max_dis, double *out) {
+  if (!p) p = &kSmoothDefaults;
+  if (const char *msg = smooth_params_error(p, false)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (!disp || !out || out == disp || w < 1 || h < 1 || max_dis < 0) return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
+  const size_t n = (size_t)w * h;
+  if (conf)
+    for (size_t i = 0; i < n; ++i)
+      if (!(conf[i] >= 0.0 && conf[i] <= 1.0)) return fail(nullptr, CSPM_ERR_ARG, "smoothing: a confidence outside [0, 1] or a NaN");
+  Scratch S;
+  int rc = cspm_create(&S.c, device);
+  if (rc) return rc;
+  cspm_ctx *c = S.c;
+  double *dd = nullptr, *work = nullptr, *dconf = nullptr, *dlut = nullptr;
+  uint8_t *dbgr = nullptr;
+  uint32_t *dpix = nullptr;
+  if ((rc = dalloc(c, &dd, n, &S.tmp)) || (rc = dalloc(c, &work, 3 * n, &S.tmp)) || (conf && (rc = dalloc(c, &dconf, n, &S.tmp))) ||
+      (guide_bgr && ((rc = dalloc(c, &dbgr, 3 * n, &S.tmp)) || (rc = dalloc(c, &dpix, n, &S.tmp)) || (rc = dalloc(c, &dlut, (size_t)kSmLut, &S.tmp)))))
+    return S.done(rc);
+  std::vector<double> lut(kSmLut);
+  smooth_lut_fill(p->sigma_color, lut.data());
+  if (hipMemcpyAsync(dd, disp, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      (conf && hipMemcpyAsync(dconf, conf, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+      (guide_bgr && (hipMemcpyAsync(dbgr, guide_bgr, 3 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                     hipMemcpyAsync(dlut, lut.data(), sizeof(double) * kSmLut, hipMemcpyHostToDevice, c->stream) != hipSuccess)))
+    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  if (guide_bgr) hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, dbgr, (size_t)w * 3, w, h, w, 0, dpix);
+  SmoothPair s;
+  s.v[0] = s.v[1] = SmoothView{work, work + n, work + 2 * n, dpix};
+  s.Wp = w;
+  s.pad = 0;
+  const SmoothConf cf{{dconf, dconf}, {nullptr, nullptr}, 0.0};
+  double *d1[1] = {dd};
+  smooth_launch(c->stream, d1, cf, s, 1, w, h, p, (double)max_dis, dlut);
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out, dd, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, "smoothing kernels failed"));
   return S.done(CSPM_OK);
 }
 

@@ -29,6 +29,12 @@ inline int Round2Int(double d) {
 // (2r+1) x (2r+1) window with the border replicated (include/cspm.h M8), computed on the calling thread's device; r in 1 .. 7.
 // Throws std::runtime_error for another depth, an empty image or a radius outside the range.  Defined in host_impl.cc.
 void MedianFilter(const Mat &src, Mat &dst, int r);
+// an addition (include/cspm.h "smoothing", cspm_smooth_disparity_host): the edge-aware global smoother on a CV_64FC1 disparity map,
+// computed on the calling thread's device.  conf: a CV_64FC1 map of confidences in [0, 1] or NULL (all 1); guide: a CV_8UC3 image or
+// NULL (every weight 1); params NULL = the defaults (fill_conf is not used); max_dis > 0 clamps the smoothed values.  dst may be src.
+// Throws std::runtime_error for another type, differing sizes and for what the C ABI refuses.  Defined in host_impl.cc.
+struct cspm_smooth_params;
+void SmoothDisparity(const Mat &src, const Mat *conf, const Mat *guide, const cspm_smooth_params *params, int max_dis, Mat &dst);
 
 // commfunc.h:129-145: a single wrap-around
 inline int HandleBorder(const int &loc, const int &size) { return loc < 0 ? loc + size : (loc >= size ? loc - size : loc); }

@@ -90,6 +90,11 @@ class CSPatchMatch {
   // use_pp's 8-bit maps, M64 on PostProcessedDisparity's.  r == 0 (the default) = no filter.  Kept here and written into the cost
   // object's context by every post-processing of this object.  Throws for r outside 0 .. CSPM_MEDIAN_MAX_RADIUS.
   void SetMedianFilter(int r);
+  // edge-aware global smoothing of the sub-pixel PostProcessing (an addition; include/cspm.h cspm_set_pp_smooth): the last step of
+  // PostProcessedDisparity and of the CSPM_GEOM_PP sources of Reproject and Synthesize, after the median filter, on both views.  use_pp's
+  // 8-bit maps are not affected.  NULL or lambda == 0 (the default) = off.  Kept here and written into the cost object's context by
+  // every post-processing of this object.  Throws for what cspm_set_pp_smooth refuses.
+  void SetSmoothing(const cspm_smooth_params *params);
   // metric geometry of a view's final plane field (an addition; include/cspm.h "reprojection", cspm_reproject): source CSPM_GEOM_RAW (the
   // field's own disparities) or CSPM_GEOM_PP (the sub-pixel post-processed map, with this object's speckle and median settings); fit ==
   // NULL: the field's slopes, else slopes fitted to the map.  depth / keep: wid x hei row-major; xyz / normal: three planes of wid x hei;
@@ -116,6 +121,7 @@ class CSPatchMatch {
   int speckle_size_;
   double speckle_diff_;
   int median_r_;
+  cspm_smooth_params smooth_;  // lambda == 0: off
   void ApplyPostFilters(cspm_ctx *ctx) const;
   std::vector<Plane> start_planes_[kViewNum];  // SetPlanes, not yet written into a context
   struct Candidates {  // AddCandidates / AddCandidateDisparity, not yet merged: 6 doubles per pixel and a mask (empty: every pixel)

@@ -273,7 +273,7 @@ double DevicePlaneCost::GetPlaneCost(const int &ref_x, const int &ref_y, const P
 
 // ---------------------------------------------------------------- CSPatchMatch (cs_patchmatch.cc:3-109)
 CSPatchMatch::CSPatchMatch(const Mat &l_img, const Mat &r_img, const int &max_dis, const int &dis_scale)
-    : max_dis_(max_dis), dis_scale_(dis_scale), seed_(12345), schedule_(CSPM_SCHED_RASTER), rb_rounds_(1), rb_neighbours_(4), last_ctx_(NULL), own_ctx_(NULL), pending_ctx_(NULL), pending_pp_(false), speckle_size_(0), speckle_diff_(1.0), median_r_(0) {
+    : max_dis_(max_dis), dis_scale_(dis_scale), seed_(12345), schedule_(CSPM_SCHED_RASTER), rb_rounds_(1), rb_neighbours_(4), last_ctx_(NULL), own_ctx_(NULL), pending_ctx_(NULL), pending_pp_(false), speckle_size_(0), speckle_diff_(1.0), median_r_(0), smooth_() {
   CV_Assert(l_img.type() == CV_8UC3 && r_img.type() == CV_8UC3);  // cs_patchmatch.cc:8
   img_[kLeft] = l_img.clone();
   img_[kRight] = r_img.clone();
@@ -612,6 +612,34 @@ void CSPatchMatch::SetSpeckleFilter(int max_size, double max_diff) {
 void CSPatchMatch::ApplyPostFilters(cspm_ctx *ctx) const {
   check(cspm_set_pp_speckle(ctx, speckle_size_, speckle_diff_), ctx, "cspm_set_pp_speckle");
   check(cspm_set_pp_median(ctx, median_r_), ctx, "cspm_set_pp_median");
+  check(cspm_set_pp_smooth(ctx, &smooth_), ctx, "cspm_set_pp_smooth");
+}
+
+void CSPatchMatch::SetSmoothing(const cspm_smooth_params *params) {
+  if (!params || params->lambda == 0.0) {
+    smooth_.lambda = 0.0;
+    return;
+  }
+  const cspm_smooth_params &p = *params;
+  if (!(p.lambda >= 0.0) || !std::isfinite(p.lambda) || !(p.sigma_color > 0.0) || !std::isfinite(p.sigma_color) || p.iterations < 1 || p.iterations > 8 ||
+      !(p.fill_conf >= 0.0 && p.fill_conf <= 1.0))
+    throw std::runtime_error("CSPatchMatch::SetSmoothing: lambda >= 0, sigma_color > 0 (both finite), iterations 1 .. 8 and fill_conf in [0, 1] expected");
+  smooth_ = p;
+}
+
+// include/cspm.h S over the device smoother: the Mats' rows are packed first (clone), dst may be src
+void SmoothDisparity(const Mat &src, const Mat *conf, const Mat *guide, const cspm_smooth_params *params, int max_dis, Mat &dst) {
+  if (src.empty() || src.type() != CV_64FC1) throw std::runtime_error("SmoothDisparity: a CV_64FC1 disparity map expected");
+  if (conf && (conf->type() != CV_64FC1 || conf->rows != src.rows || conf->cols != src.cols))
+    throw std::runtime_error("SmoothDisparity: the confidences must be a CV_64FC1 map of the disparity map's size");
+  if (guide && (guide->type() != CV_8UC3 || guide->rows != src.rows || guide->cols != src.cols))
+    throw std::runtime_error("SmoothDisparity: the guide must be a CV_8UC3 image of the disparity map's size");
+  const Mat d = src.clone(), c = conf ? conf->clone() : Mat(), g = guide ? guide->clone() : Mat();
+  Mat tmp(src.rows, src.cols, CV_64FC1);
+  check(cspm_smooth_disparity_host(DeviceSlot::current().device(), d.ptr<double>(0), conf ? c.ptr<double>(0) : NULL, guide ? g.ptr<unsigned char>(0) : NULL,
+                                   src.cols, src.rows, params, max_dis, tmp.ptr<double>(0)),
+        NULL, "SmoothDisparity");
+  dst = tmp;
 }
 
 void CSPatchMatch::SetMedianFilter(int r) {

@@ -80,6 +80,12 @@ DEFINE_double(pp_speckle_diff, 1.0, "with --pp_speckle_size: two neighbouring pi
 DEFINE_int32(pp_median, 0, "with --use_pp: radius of a median filter as the last post-processing step, on every pixel of both views (a "
                            "(2R+1) x (2R+1) window, border replicated); 0 = no filter, at most 7.  Applies to the 8-bit maps and, with "
                            "--pp_pfm, to the PFM maps");
+DEFINE_double(pp_smooth_lambda, 0.0, "with --use_pp --pp_pfm: edge-aware global smoothing (the fast global smoother) as the last step of the sub-pixel "
+                                     "post-processing, along the view's image, with confidence 1 where the pixel passed the left-right check; the "
+                                     "smoothing strength, 0 = no smoothing.  Applies to the PFM maps only");
+DEFINE_double(pp_smooth_sigma, 20.0, "with --pp_smooth_lambda: the colour scale of the guide weights exp(-(|dB|+|dG|+|dR|) / sigma)");
+DEFINE_int32(pp_smooth_iters, 3, "with --pp_smooth_lambda: rounds of a horizontal and a vertical pass, 1 .. 8");
+DEFINE_double(pp_smooth_fill_conf, 0.25, "with --pp_smooth_lambda: the confidence of a pixel that failed the left-right check, 0 .. 1");
 DEFINE_string(calib, "", "a Middlebury-2014 calib.txt (cam0, cam1, doffs, baseline, width, height) of the pair: needed by the point-cloud and depth "
                          "outputs below.  When its width differs from the image width, f, cx, cy and doffs are scaled by image width / width");
 DEFINE_string(l_ply, "", "write the left view's point cloud (binary little-endian PLY: x y z nx ny nz, red green blue; the baseline's unit) from the "
@@ -178,6 +184,8 @@ void begin(PairRun &p, CCMethod *cost_fn) {
     p.matcher->set_seed(static_cast<uint64_t>(FLAGS_seed));
     p.matcher->SetSpeckleFilter(FLAGS_pp_speckle_size, FLAGS_pp_speckle_diff);
     p.matcher->SetMedianFilter(FLAGS_pp_median);
+    const cspm_smooth_params smooth = {FLAGS_pp_smooth_lambda, FLAGS_pp_smooth_sigma, FLAGS_pp_smooth_iters, FLAGS_pp_smooth_fill_conf};
+    p.matcher->SetSmoothing(&smooth);
     if (FLAGS_schedule == "diffuse") p.matcher->set_schedule(CSPM_SCHED_DIFFUSE, 1, FLAGS_neighbours);
     else p.matcher->set_schedule(FLAGS_schedule == "redblack" ? 1 : 0);
     cspm_fit_params fit;
@@ -427,6 +435,16 @@ int run() {
   }
   if (FLAGS_pp_median < 0 || FLAGS_pp_median > CSPM_MEDIAN_MAX_RADIUS) {
     cout << "Error: --pp_median must be 0 .. " << CSPM_MEDIAN_MAX_RADIUS << " (got " << FLAGS_pp_median << ")\n";
+    return EXIT_FAILURE;
+  }
+  if (FLAGS_pp_smooth_lambda != 0.0 && !(FLAGS_use_pp && FLAGS_pp_pfm)) {
+    cout << "Error: --pp_smooth_lambda smooths the sub-pixel post-processed PFM maps and needs --use_pp --pp_pfm\n";
+    return EXIT_FAILURE;
+  }
+  if (!(FLAGS_pp_smooth_lambda >= 0.0) || !std::isfinite(FLAGS_pp_smooth_lambda) || !(FLAGS_pp_smooth_sigma > 0.0) || !std::isfinite(FLAGS_pp_smooth_sigma) ||
+      FLAGS_pp_smooth_iters < 1 || FLAGS_pp_smooth_iters > 8 || !(FLAGS_pp_smooth_fill_conf >= 0.0 && FLAGS_pp_smooth_fill_conf <= 1.0)) {
+    cout << "Error: --pp_smooth_lambda must be finite and >= 0, --pp_smooth_sigma finite and > 0, --pp_smooth_iters 1 .. 8 and "
+            "--pp_smooth_fill_conf 0 .. 1\n";
     return EXIT_FAILURE;
   }
   if (!FLAGS_ca_name.empty() && ca_method(FLAGS_ca_name) < 0) {  // checked before anything opens a device

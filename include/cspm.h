@@ -433,6 +433,46 @@ int cspm_median_filter_f64_host(int device, const double *src, int w, int h, int
 int cspm_set_pp_median(cspm_ctx *ctx, int r);
 int cspm_get_pp_median(cspm_ctx *ctx, int *r);
 
+/* edge-aware global smoothing (an addition): the fast global smoother on an f64 disparity map,
+ * S(D, C, I, lambda, sigma, T, max_dis) -> O on one view.  D: w x h f64; C: w x h f64 confidences in [0, 1] (absent: all 1); I: an 8-bit BGR
+ * guide (absent: every weight is 1.0).  A pixel is a node when D is finite; c[p] = C[p] at a node and 0.0 elsewhere; N[p] = c[p] * D[p] at a
+ * node and 0.0 elsewhere; M[p] = c[p].
+ * Weights: LUT[k] = exp(-k / sigma), k = 0 .. 765, by the host's libm; between horizontal neighbours (x, y) and (x+1, y) the weight is
+ * LUT[|dB| + |dG| + |dR|], between vertical neighbours likewise.
+ * Schedule: for t = 1 .. T, lambda_t = ((1.5 * 4^(T-t)) / (4^T - 1)) * lambda (exact powers, one division, one multiplication, on the host),
+ * then a horizontal pass over every row and a vertical pass over every column.
+ * A pass replaces N and M on each line of length n by the solution of one tridiagonal system with the two right-hand sides.  Per element i, with
+ * wl the weight to i-1 and wr the weight to i+1:  a = -(lambda_t * wl), or 0.0 at i = 0;  cc = -(lambda_t * wr), or 0.0 at i = n-1;
+ * b = (1.0 - a) - cc.  Forward, serial in i:  r = 1.0 / b, ct[0] = cc * r, ft[0] = F[0] * r;  for i >= 1  r = 1.0 / (b - ct[i-1] * a),
+ * ct[i] = cc * r, ft[i] = (F[i] - ft[i-1] * a) * r.  Backward:  U[n-1] = ft[n-1], U[i] = ft[i] - ct[i] * U[i+1].  F is N for one right-hand side
+ * and M for the other; ct and r are shared.  One true division per element; every product, sum and difference is one IEEE f64 operation,
+ * nothing contracted; the serial order is part of the definition.  The system is strictly diagonally dominant: no pivoting, no singular case.
+ * Output: O[p] = N[p] / M[p] where M[p] > 0 (false for a NaN), elsewhere D[p]'s own bits; where max_dis > 0 a quotient t is clamped as the
+ * plane fit clamps: z = t > 0 ? t : 0; z = z < max_dis ? z : max_dis.  A non-node with a confident pixel in reach is filled: intended.
+ * Defaults (chosen, not tuned): lambda 100, sigma_color 20, iterations 3, fill_conf 0.25. */
+typedef struct cspm_smooth_params {
+  double lambda;      /* >= 0 and finite; 0 switches cspm_set_pp_smooth off */
+  double sigma_color; /* > 0 and finite */
+  int iterations;     /* T, 1 .. 8 */
+  double fill_conf;   /* cspm_set_pp_smooth only: the confidence of a pixel that failed the left-right check, in [0, 1] */
+} cspm_smooth_params;
+int cspm_smooth_default_params(cspm_smooth_params *p);
+/* S alone on caller memory, no context needed (like cspm_filter_speckles_host), synchronous.  disp, out: packed w*h doubles; conf: w*h doubles
+ * or NULL; guide_bgr: packed 8UC3 rows of 3*w bytes or NULL; params NULL = the defaults, fill_conf is ignored; max_dis 0 = no clamp.
+ * CSPM_ERR_ARG, before a device is opened, for lambda < 0, NaN or infinite, sigma_color <= 0 or not finite, iterations outside 1 .. 8, a
+ * confidence outside [0, 1] or NaN (the host scans the map), a NULL disp or out, w or h < 1, max_dis < 0, or out == disp. */
+int cspm_smooth_disparity_host(int device, const double *disp, const double *conf, const uint8_t *guide_bgr, int w, int h,
+                               const cspm_smooth_params *params, int max_dis, double *out);
+/* S as the LAST step of cspm_postprocess_f64 and cspm_postprocess_f64_device, after the weighted median and after the median filter when
+ * that is on, on both views: C = 1.0 where the view's final consistency mask (after the speckle filter) is 1 and fill_conf elsewhere, I = the
+ * view's level-0 image, max_dis the context's.  The masks the entries return are not changed, and the CSPM_GEOM_PP / PP sources of
+ * cspm_reproject* and cspm_synthesize* read the smoothed maps.  The 8-bit entries cspm_postprocess and cspm_postprocess_device are NOT
+ * affected.  params NULL or lambda == 0 = off (the default): no launch, no memory, today's bytes.  Scratch (three maps per view and the
+ * table) is allocated by the first smoothed call and kept with the plane field.  Timed under CSPM_K_POST as a bracket of its own.
+ * CSPM_ERR_ARG as above, and for a fill_conf outside [0, 1].  The getter's outputs may be NULL; *on = 1 while smoothing is switched on. */
+int cspm_set_pp_smooth(cspm_ctx *ctx, const cspm_smooth_params *params);
+int cspm_get_pp_smooth(cspm_ctx *ctx, cspm_smooth_params *params, int *on);
+
 /* ---- reprojection (an addition): metric depth, camera-space points, unit normals, a point cloud ---------------------
  * A plane in disparity space is a plane in 3-D: with x = f X/Z + cx, y = f Y/Z + cy, d + doffs = f B/Z the disparity plane d = a x + b y + c
  * is  a f X + b f Y + (a cx + b cy + c + doffs) Z = f B  -- exact, no finite differences.
