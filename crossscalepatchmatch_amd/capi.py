@@ -58,6 +58,7 @@ SYMBOLS = [
     "cspm_median_filter_u8_host", "cspm_median_filter_f64_host", "cspm_set_pp_median", "cspm_get_pp_median",
     "cspm_smooth_default_params", "cspm_smooth_disparity_host", "cspm_set_pp_smooth", "cspm_get_pp_smooth",
     "cspm_fit_default_params", "cspm_fit_planes_host", "cspm_fit_planes",
+    "cspm_seg_default_params", "cspm_segment_count", "cspm_segment_host", "cspm_segment_planes_host", "cspm_segment_planes", "cspm_get_segments",
     "cspm_geom_default_params", "cspm_reproject_host", "cspm_reproject", "cspm_reproject_device",
     "cspm_synth_default_params", "cspm_synthesize_host", "cspm_synthesize", "cspm_synthesize_device",
 ]
@@ -76,6 +77,11 @@ class PmParams(C.Structure):
 class FitParams(C.Structure):
     """struct cspm_fit_params"""
     _fields_ = [("radius", C.c_int), ("max_diff", C.c_double), ("min_support", C.c_int), ("use_guide", C.c_int)]
+
+
+class SegParams(C.Structure):
+    """struct cspm_seg_params"""
+    _fields_ = [("step", C.c_int), ("compactness", C.c_int), ("iters", C.c_int), ("tau", C.c_double), ("rounds", C.c_int), ("min_support", C.c_int)]
 
 
 class SmoothParams(C.Structure):
@@ -139,6 +145,7 @@ def load_library():
     pp = C.POINTER(PmParams)
     fp = C.POINTER(FitParams)
     mp = C.POINTER(SmoothParams)
+    qp, i32p = C.POINTER(SegParams), C.POINTER(C.c_int32)
     kp, gp, up = C.POINTER(Calib), C.POINTER(GeomParams), C.POINTER(C.c_uint)
     sp, svp = C.POINTER(SynthParams), C.POINTER(SynthView)
     sig = {
@@ -215,6 +222,12 @@ def load_library():
         "cspm_fit_default_params": (C.c_int, [fp]),
         "cspm_fit_planes_host": (C.c_int, [C.c_int, dp, u8p, u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, fp, dp, u8p]),
         "cspm_fit_planes": (C.c_int, [vp, fp, C.c_int]),
+        "cspm_seg_default_params": (C.c_int, [qp]),
+        "cspm_segment_count": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+        "cspm_segment_host": (C.c_int, [C.c_int, u8p, C.c_size_t, C.c_int, C.c_int, qp, i32p, i32p, i32p]),
+        "cspm_segment_planes_host": (C.c_int, [C.c_int, dp, u8p, i32p, C.c_int, C.c_int, C.c_int, qp, dp, i32p, dp, u8p]),
+        "cspm_segment_planes": (C.c_int, [vp, qp, C.c_int]),
+        "cspm_get_segments": (C.c_int, [vp, C.c_int, i32p]),
         "cspm_geom_default_params": (C.c_int, [gp]),
         "cspm_reproject_host": (C.c_int, [C.c_int, kp, gp, C.c_int, dp, u8p, dp, dp, u8p, C.c_size_t, C.c_int, C.c_int, dp, dp, dp, u8p, vp, C.c_size_t, up]),
         "cspm_reproject": (C.c_int, [vp, C.c_int, C.c_int, kp, gp, fp, dp, dp, dp, u8p, vp, C.c_size_t, up]),
@@ -238,6 +251,10 @@ def _dp(a):
 
 def _u8(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def _i32(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
 class StereoContext:
@@ -459,6 +476,20 @@ class StereoContext:
         candidates that win only where they cost less.  params: radius, max_diff, min_support, use_guide."""
         p = fit_params(**params)
         self._chk(self.L.cspm_fit_planes(self.p, C.byref(p), int(bool(merge))))
+
+    def segment_planes(self, merge=False, **params):
+        """one robustly fitted plane per superpixel of the stored field's own disparity maps, both views (cspm_segment_planes;
+        asynchronous).  merge=False: the planes of fitted segments replace the stored ones and min_cost is stale
+        (patchmatch_warm re-scores); merge=True: they are candidates that win only where they cost less.  params: step, compactness,
+        iters, tau, rounds, min_support."""
+        p = seg_params(**params)
+        self._chk(self.L.cspm_segment_planes(self.p, C.byref(p), int(bool(merge))))
+
+    def segments(self, view):
+        """the (h, w) int32 labels of the last segment_planes call (cspm_get_segments)"""
+        labels = np.zeros((self.h, self.w), np.int32)
+        self._chk(self.L.cspm_get_segments(self.p, view, _i32(labels)))
+        return labels
 
     def pm_init_keep(self, **kw):
         """the random init as a challenger: a pixel takes its InitRandomPlane plane only where it costs less than the stored one"""
@@ -702,6 +733,72 @@ def fit_planes_host(disp, valid=None, guide=None, max_dis=0, device=0, **params)
     if rc != 0:
         raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
     return planes, fitted
+
+
+def seg_params(**params):
+    """struct cspm_seg_params: cspm_seg_default_params with the given fields replaced"""
+    p = SegParams()
+    rc = load_library().cspm_seg_default_params(C.byref(p))
+    assert rc == 0
+    for k, v in params.items():
+        if k not in ("step", "compactness", "iters", "tau", "rounds", "min_support"):
+            raise TypeError(f"unknown segment-plane parameter {k!r}")
+        setattr(p, k, float(v) if k == "tau" else int(v))
+    return p
+
+
+def segment_count(w, h, step):
+    """K = ceil(w / step) * ceil(h / step) (cspm_segment_count)"""
+    k = load_library().cspm_segment_count(int(w), int(h), int(step))
+    if k < 0:
+        raise CspmError(f"cspm error {k}: bad size or step")
+    return k
+
+
+def segment_host(bgr, device=0, **params):
+    """the superpixel segmentation of a host image (cspm_segment_host): bgr (h, w, 3) uint8.  Returns
+    (labels (h, w) int32, centres (K, 5) int32 in 1/16 units (cx, cy, cb, cg, cr), counts (K,) int32).  params: step, compactness, iters."""
+    L = load_library()
+    g = np.ascontiguousarray(bgr, dtype=np.uint8)
+    assert g.ndim == 3 and g.shape[2] == 3, g.shape
+    h, w = g.shape[:2]
+    p = seg_params(**params)
+    K = segment_count(w, h, p.step)
+    labels = np.zeros((h, w), np.int32)
+    centres = np.zeros((K, 5), np.int32)
+    counts = np.zeros(K, np.int32)
+    rc = L.cspm_segment_host(device, _u8(g), w * 3, w, h, C.byref(p), _i32(labels), _i32(centres), _i32(counts))
+    if rc != 0:
+        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    return labels, centres, counts
+
+
+def segment_planes_host(disp, valid, labels, max_dis=0, device=0, **params):
+    """one robust plane per segment of a host disparity map (cspm_segment_planes_host): disp (h, w) f64, valid
+    (h, w) or None (every pixel), labels (h, w) int32 for the grid of `step`.  Returns (seg_planes (K, 3) f64 (a, b, c), inliers (K,)
+    int32, planes (h, w, 6) in the layout of get_planes, fitted (h, w) uint8); an unfitted segment has NaNs, 0 inliers, and its pixels six
+    NaNs and fitted = 0.  params: step, tau, rounds, min_support."""
+    L = load_library()
+    d = np.ascontiguousarray(disp, dtype=np.float64)
+    assert d.ndim == 2
+    h, w = d.shape
+    m = None
+    if valid is not None:
+        m = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+        assert m.shape == d.shape, m.shape
+    lab = np.ascontiguousarray(labels, dtype=np.int32)
+    assert lab.shape == d.shape, lab.shape
+    p = seg_params(**params)
+    K = segment_count(w, h, p.step)
+    seg = np.zeros((K, 3))
+    inl = np.zeros(K, np.int32)
+    planes = np.zeros((h, w, 6))
+    fitted = np.zeros((h, w), np.uint8)
+    rc = L.cspm_segment_planes_host(device, _dp(d), _u8(m) if m is not None else None, _i32(lab), w, h, int(max_dis), C.byref(p), _dp(seg), _i32(inl),
+                                    _dp(planes), _u8(fitted))
+    if rc != 0:
+        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    return seg, inl, planes, fitted
 
 
 def calib_struct(calib):

@@ -16,6 +16,7 @@
 #include "cspm_median.h"
 #include "cspm_smooth.h"
 #include "cspm_fit.h"
+#include "cspm_seg.h"
 #include "cspm_geom.h"
 #include "cspm_synth.h"
 #include "cspm_ca.h"
@@ -205,6 +206,8 @@ struct cspm_ctx {
   double *warm_snap = nullptr;        // the starting field of the last warm run (both views, 7 arrays each), kept with the field
   double *cand_mem = nullptr;         // cspm_merge_planes_host: one view's candidate planes (6 arrays) and, behind them, its mask bytes; allocated by the first such call and kept with the field
   double *fit_mem = nullptr;          // cspm_fit_planes: both views' disparity snapshots (2 arrays) and, behind them, the exp(-k/10) table; allocated by the first such call and kept with the field
+  char *seg_mem = nullptr;            // cspm_segment_planes: both views' disparity snapshots and labels, then centres, counts and segment planes for the finest grid (step 4); allocated by the first such call and kept with the field
+  bool seg_ran = false;               // cspm_get_segments: seg_mem holds the labels of a call
   double *geom_disp = nullptr;        // cspm_reproject: the CSPM_GEOM_RAW disparity map (1 array); allocated by the first such call and kept with the field
   double *geom_fit = nullptr;         // cspm_reproject with a fit: the fitted planes (6 arrays) and, behind them, the exp(-k/10) table
   unsigned int *geom_counts = nullptr;  // cspm_reproject: the kept pixels per workgroup, then the total
@@ -367,6 +370,8 @@ void free_field(cspm_ctx *c) {
   dfree(c->diffuse_snap);
   dfree(c->cand_mem);
   dfree(c->fit_mem);
+  dfree(c->seg_mem);
+  c->seg_ran = false;
   dfree(c->geom_disp);
   dfree(c->geom_fit);
   dfree(c->geom_counts);
@@ -1299,6 +1304,49 @@ void fit_launch(hipStream_t stream, FitIn in, const FitOut &out, int w, int h, c
     hipLaunchKernelGGL(k_fit_planes<false>, grid, dim3(kFitBlock), lds, stream, in, out, w, h, p->radius, p->max_diff, p->min_support, (double)max_dis);
 }
 constexpr int kFitMaxRows = 65535 * kFitTileH;  // gridDim.y
+
+// segment planes (cspm_seg.h)
+const char *seg_params_error(const cspm_seg_params *p) {
+  if (p->step < kSegMinStep || p->step > kSegMaxStep) return "segment planes: step must be 4 .. 64";
+  if (p->compactness < 0 || p->compactness > 255) return "segment planes: compactness must be 0 .. 255";
+  if (p->iters < 1 || p->iters > 16) return "segment planes: iters must be 1 .. 16";
+  if (p->rounds < 0 || p->rounds > 8) return "segment planes: rounds must be 0 .. 8";
+  if (p->min_support < 3) return "segment planes: min_support must be at least 3";
+  if (!(p->tau >= 0.0)) return "segment planes: tau must be >= 0 (it may be +infinity)";
+  return nullptr;
+}
+const cspm_seg_params kSegDefaults = {16, 20, 5, 1.0, 3, 6};
+constexpr int kSegMaxRows = 65535 * kSegTileH;  // gridDim.y of k_seg_assign
+inline SegGrid seg_grid(int w, int h, int s) { return SegGrid{w, h, s, (w + s - 1) / s, (h + s - 1) / s}; }
+// the device records of a grid of K segments behind one another: centres (5 ints), counts (1 int), inliers (1 int), planes (4 doubles)
+struct SegMem {
+  int *cen, *counts, *inliers;
+  double *planes;
+  static size_t bytes(size_t K) { return K * (4 * sizeof(double) + 7 * sizeof(int)); }
+  SegMem(void *base, size_t K) {
+    planes = static_cast<double *>(base);  // the doubles first: aligned whatever K is
+    cen = reinterpret_cast<int *>(planes + 4 * K);
+    counts = cen + 5 * K;
+    inliers = counts + K;
+  }
+};
+// S on one view: T times ASSIGN then UPDATE
+void seg_segment_launch(hipStream_t stream, const SegGrid &g, const uint32_t *pix, const cspm_seg_params *p, int *labels, const SegMem &m) {
+  const int K = g.nx * g.ny, per = seg_per_block(g.s);
+  const dim3 tiles((unsigned)((g.W + kSegTileW - 1) / kSegTileW), (unsigned)((g.H + kSegTileH - 1) / kSegTileH));
+  hipLaunchKernelGGL(k_seg_init, dim3(ew_grid(K)), dim3(256), 0, stream, g, pix, m.cen);
+  for (int t = 0; t < p->iters; ++t) {
+    hipLaunchKernelGGL(k_seg_assign, tiles, dim3(kSegBlock), 0, stream, g, pix, m.cen, p->compactness, labels);
+    hipLaunchKernelGGL(k_seg_update, dim3((unsigned)((K + per - 1) / per)), dim3(kSegBlock), 0, stream, g, pix, labels, m.cen, m.counts, per);
+  }
+}
+// P on one view: the rounds of every segment, then the planes of every pixel
+void seg_fit_launch(hipStream_t stream, const SegGrid &g, const SegFitIn &in, const cspm_seg_params *p, int max_dis, const SegMem &m, const FitOut &out) {
+  const int K = g.nx * g.ny, per = seg_per_block(g.s);
+  hipLaunchKernelGGL(k_seg_fit, dim3((unsigned)((K + per - 1) / per)), dim3(kSegBlock), 0, stream, g, in, p->tau, p->rounds, p->min_support, m.planes,
+                     m.inliers, per);
+  hipLaunchKernelGGL(k_seg_scatter, dim3(ew_grid((long long)g.W * g.H)), dim3(256), 0, stream, g, in.labels, m.planes, m.inliers, (double)max_dis, out);
+}
 
 // PostProcessing's speckle filter on c->d_valid, between LeftRightCheck and FillInvalid; nothing at all when off
 template <class T>
@@ -2500,6 +2548,98 @@ int cspm_fit_planes_host(int device, const double *disp, const uint8_t *valid, c
   return S.done(CSPM_OK);
 }
 
+// the segmentation and the segment fit alone on caller memory: the launches cspm_segment_planes enqueues, on one view
+int cspm_seg_default_params(cspm_seg_params *p) {
+  if (!p) return CSPM_ERR_ARG;
+  *p = kSegDefaults;
+  return CSPM_OK;
+}
+
+int cspm_segment_count(int w, int h, int step) {
+  if (w < 1 || h < 1 || step < kSegMinStep || step > kSegMaxStep) return CSPM_ERR_ARG;
+  const long long K = (long long)((w + step - 1) / step) * ((h + step - 1) / step);
+  return K < (1LL << 31) ? (int)K : CSPM_ERR_ARG;
+}
+
+int cspm_segment_host(int device, const uint8_t *bgr, size_t stride, int w, int h, const cspm_seg_params *p, int32_t *labels_out, int32_t *centres_out,
+                      int32_t *counts_out) {
+  if (!p) p = &kSegDefaults;
+  if (const char *msg = seg_params_error(p)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (!bgr || !labels_out || w < 1 || h < 1 || h > kSegMaxRows || stride < (size_t)w * 3 || (long long)w * h >= (1LL << 31))
+    return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
+  Scratch S;
+  int rc = cspm_create(&S.c, device);
+  if (rc) return rc;
+  cspm_ctx *c = S.c;
+  const size_t n = (size_t)w * h;
+  const SegGrid g = seg_grid(w, h, p->step);
+  const size_t K = (size_t)g.nx * g.ny;
+  uint8_t *dbgr = nullptr, *dseg = nullptr;
+  uint32_t *dpix = nullptr;
+  int *dlab = nullptr;
+  if ((rc = dalloc(c, &dbgr, 3 * n, &S.tmp)) || (rc = dalloc(c, &dpix, n, &S.tmp)) || (rc = dalloc(c, &dlab, n, &S.tmp)) ||
+      (rc = dalloc(c, &dseg, SegMem::bytes(K), &S.tmp)))
+    return S.done(rc);
+  const SegMem m(dseg, K);
+  if (hipMemcpy2DAsync(dbgr, (size_t)w * 3, bgr, stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, dbgr, (size_t)w * 3, w, h, w, 0, dpix);
+  seg_segment_launch(c->stream, g, dpix, p, dlab, m);
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(labels_out, dlab, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      (centres_out && hipMemcpyAsync(centres_out, m.cen, sizeof(int) * 5 * K, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      (counts_out && hipMemcpyAsync(counts_out, m.counts, sizeof(int) * K, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, "segmentation kernels failed"));
+  return S.done(CSPM_OK);
+}
+
+int cspm_segment_planes_host(int device, const double *disp, const uint8_t *valid, const int32_t *labels, int w, int h, int max_dis, const cspm_seg_params *p,
+                             double *seg_planes_out, int32_t *inliers_out, double *np_out, uint8_t *fitted_out) {
+  if (!p) p = &kSegDefaults;
+  if (const char *msg = seg_params_error(p)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (!disp || !labels || !np_out || w < 1 || h < 1 || max_dis < 0 || (long long)w * h >= (1LL << 31)) return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
+  const SegGrid g = seg_grid(w, h, p->step);
+  const size_t n = (size_t)w * h, K = (size_t)g.nx * g.ny;
+  for (int y = 0; y < h; ++y)  // the 3 x 3 property: what makes the owners' window scans complete
+    for (int x = 0; x < w; ++x) {
+      const int32_t k = labels[(size_t)y * w + x];
+      if (k < 0 || (size_t)k >= K || std::abs(k % g.nx - x / g.s) > 1 || std::abs(k / g.nx - y / g.s) > 1)
+        return fail(nullptr, CSPM_ERR_ARG, "segment planes: a label is no segment of the 3 x 3 cells around its pixel");
+    }
+  Scratch S;
+  int rc = cspm_create(&S.c, device);
+  if (rc) return rc;
+  cspm_ctx *c = S.c;
+  double *dd = nullptr, *dout = nullptr;
+  uint8_t *dv = nullptr, *dfit = nullptr, *dseg = nullptr;
+  int *dlab = nullptr;
+  if ((rc = dalloc(c, &dd, n, &S.tmp)) || (rc = dalloc(c, &dout, 6 * n, &S.tmp)) || (rc = dalloc(c, &dfit, n, &S.tmp)) || (rc = dalloc(c, &dlab, n, &S.tmp)) ||
+      (valid && (rc = dalloc(c, &dv, n, &S.tmp))) || (rc = dalloc(c, &dseg, SegMem::bytes(K), &S.tmp)))
+    return S.done(rc);
+  const SegMem m(dseg, K);
+  if (hipMemcpyAsync(dd, disp, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemcpyAsync(dlab, labels, sizeof(int) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      (valid && hipMemcpyAsync(dv, valid, n, hipMemcpyHostToDevice, c->stream) != hipSuccess))
+    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  seg_fit_launch(c->stream, g, SegFitIn{dd, dv, dlab}, p, max_dis, m, FitOut{dout, dout + n, dout + 2 * n, dout + 3 * n, dout + 4 * n, dout + 5 * n, dfit, 0});
+  std::vector<double> hst(6 * n), hseg(4 * K);
+  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hst.data(), dout, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipMemcpyAsync(hseg.data(), m.planes, sizeof(double) * 4 * K, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      (inliers_out && hipMemcpyAsync(inliers_out, m.inliers, sizeof(int) * K, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      (fitted_out && hipMemcpyAsync(fitted_out, dfit, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, "segment fit kernels failed"));
+  for (size_t i = 0; i < n; ++i)
+    for (int k = 0; k < 6; ++k) np_out[6 * i + k] = hst[k * n + i];
+  if (seg_planes_out)
+    for (size_t k = 0; k < K; ++k) {
+      seg_planes_out[3 * k] = hseg[4 * k];
+      seg_planes_out[3 * k + 1] = hseg[4 * k + 1];
+      seg_planes_out[3 * k + 2] = hseg[4 * k + 3];
+    }
+  return S.done(CSPM_OK);
+}
+
 // the median filter alone on caller memory: the launch PostProcessing enqueues, on one image
 int cspm_median_filter_u8_host(int device, const uint8_t *src, size_t src_stride, int w, int h, int channels, int r, uint8_t *dst, size_t dst_stride) {
   if (!src || !dst || src == dst || w < 1 || h < 1 || channels < 1 || channels > 4 || r < 1 || r > CSPM_MEDIAN_MAX_RADIUS)
@@ -2820,6 +2960,69 @@ int cspm_fit_planes(cspm_ctx *c, const cspm_fit_params *p, int merge) {
       if ((rc = do_merge(c, &cf, &kDefaultParams, v, 1, (long long)n))) return rc;
     }
   }
+  return CSPM_OK;
+}
+
+// one robustly fitted plane per superpixel of the stored field's own disparity maps (cspm.h "segment planes"); asynchronous on the ctx stream
+int cspm_segment_planes(cspm_ctx *c, const cspm_seg_params *p, int merge) {
+  if (!c) return CSPM_ERR_ARG;
+  if (!p) p = &kSegDefaults;
+  if (const char *msg = seg_params_error(p)) return fail(c, CSPM_ERR_ARG, msg);
+  if (!c->img0[0]) return fail(c, CSPM_ERR_STATE, "cspm_set_images first");
+  int rc;
+  if ((rc = need_field(c, "no plane field to fit (cspm_local_stereo, cspm_set_planes, cspm_pm_init or an earlier run)"))) return rc;
+  if (merge && (rc = need_cost(c))) return rc;
+  if (c->max_dis < 1) return fail(c, CSPM_ERR_STATE, "no max_dis known: build a cost object (or cspm_fpm_begin) first");
+  if (c->H > kSegMaxRows) return fail(c, CSPM_ERR_ARG, "image too high for the segmentation");
+  ON_DEVICE(c);
+  const size_t n = (size_t)c->W * c->H;
+  const SegGrid finest = seg_grid(c->W, c->H, kSegMinStep), g = seg_grid(c->W, c->H, p->step);
+  const size_t Kmax = (size_t)finest.nx * finest.ny, K = (size_t)g.nx * g.ny;
+  if (!c->seg_mem && (rc = dalloc(c, &c->seg_mem, 2 * n * (sizeof(double) + sizeof(int)) + SegMem::bytes(Kmax), nullptr))) return rc;
+  double *snap = reinterpret_cast<double *>(c->seg_mem);
+  int *labels = reinterpret_cast<int *>(snap + 2 * n);
+  const SegMem m(labels + 2 * n, K);  // 8-byte aligned: 2n ints behind 2n doubles
+  if (merge) {
+    if (!c->cand_mem && (rc = dalloc(c, &c->cand_mem, 6 * n + (n + 7) / 8, nullptr))) return rc;  // the buffer of cspm_merge_planes_host
+    if ((rc = ensure_consistent(c))) return rc;
+  } else {
+    c->field_consistent = false;  // min_cost still belongs to the planes that were replaced
+  }
+  c->repeat.taint_unchecked_run();  // it can no longer be repeated over these planes
+  c->seg_ran = true;
+  const Pm pm = field_pm(c);
+  for (int v = 0; v < 2; ++v) {
+    double *d = snap + (size_t)v * n;
+    int *lab = labels + (size_t)v * n;
+    double *b = merge ? c->cand_mem : nullptr;
+    uint8_t *d_mask = merge ? reinterpret_cast<uint8_t *>(c->cand_mem + 6 * n) : nullptr;
+    const Field &f = c->f[v];
+    const FitOut out = merge ? FitOut{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, d_mask, 0} : FitOut{f.nx, f.ny, f.nz, f.a, f.b, f.c, nullptr, 1};
+    {
+      Timed t(c, CSPM_K_MISC, (long long)n);
+      hipLaunchKernelGGL(k_plane_to_disp_f64, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, pm, v, d);
+      seg_segment_launch(c->stream, g, c->img0[v], p, lab, m);
+      seg_fit_launch(c->stream, g, SegFitIn{d, nullptr, lab}, p, c->max_dis, m, out);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (merge) {
+      CandField cf{};
+      cf.s[v] = SnapField{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n};
+      cf.mask[v] = d_mask;
+      if ((rc = do_merge(c, &cf, &kDefaultParams, v, 1, (long long)n))) return rc;
+    }
+  }
+  return CSPM_OK;
+}
+
+int cspm_get_segments(cspm_ctx *c, int view, int32_t *labels_out) {
+  if (!c || view < 0 || view > 1 || !labels_out) return CSPM_ERR_ARG;
+  if (!c->seg_mem || !c->seg_ran) return fail(c, CSPM_ERR_STATE, "no segmentation yet (cspm_segment_planes)");
+  ON_DEVICE(c);
+  const size_t n = (size_t)c->W * c->H;
+  const int *labels = reinterpret_cast<const int *>(reinterpret_cast<const double *>(c->seg_mem) + 2 * n) + (size_t)view * n;
+  HIPCHK(c, hipMemcpyAsync(labels_out, labels, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return CSPM_OK;
 }
 

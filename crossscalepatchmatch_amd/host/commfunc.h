@@ -35,6 +35,17 @@ void MedianFilter(const Mat &src, Mat &dst, int r);
 // Throws std::runtime_error for another type, differing sizes and for what the C ABI refuses.  Defined in host_impl.cc.
 struct cspm_smooth_params;
 void SmoothDisparity(const Mat &src, const Mat *conf, const Mat *guide, const cspm_smooth_params *params, int max_dis, Mat &dst);
+// additions (include/cspm.h "segment planes", cspm_segment_host / cspm_segment_planes_host), computed on the calling thread's device;
+// params NULL = the defaults.  SegmentImage: the superpixel labels (CV_32SC1) of a CV_8UC3 image.  SegmentPlanes: one robustly fitted
+// plane per segment of a CV_64FC1 disparity map under a CV_32SC1 label map of the same size for the grid of params->step; valid: a
+// CV_8UC1 mask or NULL (every pixel).  planes: rows x cols Planes, row-major, those of unfitted segments with NaN entries; fitted:
+// CV_8UC1 or NULL; seg_abc: three doubles (a, b, c) per segment or NULL.  Both throw std::runtime_error for another type, differing
+// sizes and for what the C ABI refuses (labels outside the 3 x 3 cells of their pixel among it).  Defined in host_impl.cc.
+struct cspm_seg_params;
+class Plane;
+void SegmentImage(const Mat &img, Mat &labels, const cspm_seg_params *params);
+void SegmentPlanes(const Mat &disp, const Mat *valid, const Mat &labels, const cspm_seg_params *params, int max_dis, std::vector<Plane> *planes, Mat *fitted,
+                   std::vector<double> *seg_abc);
 
 // commfunc.h:129-145: a single wrap-around
 inline int HandleBorder(const int &loc, const int &size) { return loc < 0 ? loc + size : (loc >= size ? loc - size : loc); }

@@ -33,6 +33,12 @@ class CSPatchMatch {
   // may follow a ...Begin on the same cost object and be followed by PatchMatchFromBegin / PatchMatchKeepBegin.  One of this
   // library's device costs only: a foreign IPlaneCost throws.
   void FitPlanes(const IPlaneCost *plane_cost, const cspm_fit_params &params, const bool &merge);
+  // one robustly fitted plane per superpixel of the plane field in the device context of plane_cost (an addition; include/cspm.h
+  // cspm_segment_planes), offered to every pixel of the segment.  merge = false: the planes of fitted segments replace the stored ones
+  // (PatchMatchFrom re-scores); merge = true: a segment's plane wins only where it costs less.  Enqueued on the cost object's stream
+  // like FitPlanes: it may follow any ...Begin on the same cost object and be followed by PatchMatchFromBegin.  One of this library's
+  // device costs only: a foreign IPlaneCost throws.
+  void SegmentPlanes(const IPlaneCost *plane_cost, const cspm_seg_params &params, const bool &merge);
   // warm start (an addition): iter_num PatchMatch iterations from the plane field already in the device context of plane_cost --
   // after LocalStereo, a previous pair's run, or the planes given to SetPlanes -- instead of InitRandomPlane.  The field is re-scored
   // under plane_cost first (include/cspm.h cspm_patchmatch_warm).  Begin may follow a LocalStereoBegin on the same cost object

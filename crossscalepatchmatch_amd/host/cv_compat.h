@@ -21,10 +21,11 @@
 namespace cv {
 
 typedef unsigned char uchar;
-enum { CV_8U = 0, CV_32F = 5, CV_64F = 6 };
+enum { CV_8U = 0, CV_32S = 4, CV_32F = 5, CV_64F = 6 };
 #define CV_MAKETYPE(depth, cn) ((depth) + (((cn)-1) << 3))
 #define CV_8UC1 CV_MAKETYPE(cv::CV_8U, 1)
 #define CV_8UC3 CV_MAKETYPE(cv::CV_8U, 3)
+#define CV_32SC1 CV_MAKETYPE(cv::CV_32S, 1)
 #define CV_32FC1 CV_MAKETYPE(cv::CV_32F, 1)
 #define CV_64FC1 CV_MAKETYPE(cv::CV_64F, 1)
 #define CV_64FC3 CV_MAKETYPE(cv::CV_64F, 3)
@@ -60,7 +61,7 @@ class Mat {
   int type() const { return type_; }
   int depth() const { return type_ & 7; }
   int channels() const { return (type_ >> 3) + 1; }
-  size_t elemSize() const { return (size_t)channels() * (depth() == CV_8U ? 1 : depth() == CV_32F ? 4 : 8); }
+  size_t elemSize() const { return (size_t)channels() * (depth() == CV_8U ? 1 : (depth() == CV_32F || depth() == CV_32S) ? 4 : 8); }
   Size size() const { return Size(cols, rows); }
   bool empty() const { return data == nullptr || rows == 0 || cols == 0; }
   Mat clone() const {

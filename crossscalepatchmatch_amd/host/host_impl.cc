@@ -496,6 +496,14 @@ void CSPatchMatch::FitPlanes(const IPlaneCost *plane_cost, const cspm_fit_params
   check(cspm_fit_planes(ctx, &params, merge ? 1 : 0), ctx, "cspm_fit_planes");  // asynchronous: enqueued on the context's stream
 }
 
+void CSPatchMatch::SegmentPlanes(const IPlaneCost *plane_cost, const cspm_seg_params &params, const bool &merge) {
+  const IDevicePlaneCost *dev = dynamic_cast<const IDevicePlaneCost *>(plane_cost);
+  if (!dev) throw std::runtime_error("CSPatchMatch::SegmentPlanes needs one of this library's device costs");
+  cspm_ctx *ctx = dev->device_ctx();
+  if (pending_ctx_ && pending_ctx_ != ctx) throw std::runtime_error("CSPatchMatch::SegmentPlanes: the previous run has not been ended");
+  check(cspm_segment_planes(ctx, &params, merge ? 1 : 0), ctx, "cspm_segment_planes");  // asynchronous: enqueued on the context's stream
+}
+
 void CSPatchMatch::SeededBegin(bool keep, int iter_num, const IPlaneCost *plane_cost, bool use_pp) {
   const IDevicePlaneCost *dev = dynamic_cast<const IDevicePlaneCost *>(plane_cost);
   if (!dev) throw std::runtime_error("CSPatchMatch::PatchMatchSeeded / PatchMatchKeep need one of this library's device costs (a foreign IPlaneCost runs cold only: PatchMatch)");
@@ -640,6 +648,45 @@ void SmoothDisparity(const Mat &src, const Mat *conf, const Mat *guide, const cs
                                    src.cols, src.rows, params, max_dis, tmp.ptr<double>(0)),
         NULL, "SmoothDisparity");
   dst = tmp;
+}
+
+void SegmentImage(const Mat &img, Mat &labels, const cspm_seg_params *params) {
+  if (img.empty() || img.type() != CV_8UC3) throw std::runtime_error("SegmentImage: a CV_8UC3 image expected");
+  Mat tmp(img.rows, img.cols, CV_32SC1);
+  check(cspm_segment_host(DeviceSlot::current().device(), img.data, img.step, img.cols, img.rows, params, tmp.ptr<int32_t>(0), NULL, NULL), NULL,
+        "SegmentImage");
+  labels = tmp;
+}
+
+void SegmentPlanes(const Mat &disp, const Mat *valid, const Mat &labels, const cspm_seg_params *params, int max_dis, std::vector<Plane> *planes, Mat *fitted,
+                   std::vector<double> *seg_abc) {
+  if (disp.empty() || disp.type() != CV_64FC1) throw std::runtime_error("SegmentPlanes: a CV_64FC1 disparity map expected");
+  if (labels.type() != CV_32SC1 || labels.rows != disp.rows || labels.cols != disp.cols)
+    throw std::runtime_error("SegmentPlanes: the labels must be a CV_32SC1 map of the disparity map's size");
+  if (valid && (valid->type() != CV_8UC1 || valid->rows != disp.rows || valid->cols != disp.cols))
+    throw std::runtime_error("SegmentPlanes: the mask must be a CV_8UC1 map of the disparity map's size");
+  const Mat d = disp.clone(), l = labels.clone(), v = valid ? valid->clone() : Mat();  // packed rows
+  const size_t n = (size_t)disp.rows * disp.cols;
+  cspm_seg_params p;
+  cspm_seg_default_params(&p);
+  if (params) p = *params;
+  const int K = cspm_segment_count(disp.cols, disp.rows, p.step);
+  std::vector<double> np(6 * n), abc(K > 0 ? 3 * (size_t)K : 0);
+  Mat fit(disp.rows, disp.cols, CV_8UC1);
+  check(cspm_segment_planes_host(DeviceSlot::current().device(), d.ptr<double>(0), valid ? v.ptr<unsigned char>(0) : NULL, l.ptr<int32_t>(0), disp.cols,
+                                 disp.rows, max_dis, &p, K > 0 ? abc.data() : NULL, NULL, np.data(), fit.ptr<unsigned char>(0)),
+        NULL, "SegmentPlanes");
+  if (planes) {
+    planes->resize(n);
+    for (size_t i = 0; i < n; ++i) {
+      Plane pl;
+      pl.set_norm(Point3d(np[6 * i], np[6 * i + 1], np[6 * i + 2]));
+      pl.set_param(Vec3d(np[6 * i + 3], np[6 * i + 4], np[6 * i + 5]));
+      (*planes)[i] = pl;
+    }
+  }
+  if (fitted) *fitted = fit;
+  if (seg_abc) seg_abc->swap(abc);
 }
 
 void CSPatchMatch::SetMedianFilter(int r) {

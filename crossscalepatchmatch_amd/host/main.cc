@@ -4,6 +4,8 @@
 // --warm_ca (local stereo, then --iters warm PatchMatch iterations) --l_seed_pfm --r_seed_pfm (disparity maps offered to the random start
 // field as candidates) --seed_ca (local stereo, kept wherever the random start plane costs no less, then --iters iterations)
 // --fit_radius --fit_max_diff --fit_merge (slanted planes fitted to the local-stereo field or to the seed maps before what follows)
+// --seg_step --seg_compactness --seg_iters --seg_tau --seg_rounds --seg_warm_iters (one robust plane per superpixel of the field after the
+// --iters iterations, merged where it costs less, then warm iterations; include/cspm.h "segment planes")
 // --calib --l_ply --r_ply --l_depth_pfm --r_depth_pfm --geom_min_cos --geom_z_far --geom_left_frame --geom_fit_radius (metric depth maps and
 // point clouds of the final plane field; include/cspm.h "reprojection") --synth_t --synth_png --synth_dis_pfm --synth_views --synth_max_stretch
 // --synth_merge_diff --synth_fill (the scene rendered from a camera between the two views; include/cspm.h "view synthesis").
@@ -57,6 +59,15 @@ DEFINE_int32(fit_radius, 0, "fit slanted planes (weighted least squares over a w
 DEFINE_double(fit_max_diff, 1.5, "with --fit_radius: a window pixel takes part in a fit when its disparity is within this of the centre's");
 DEFINE_bool(fit_merge, false, "with --fit_radius and a local-stereo field: a fitted plane replaces the stored one only where it costs less "
                               "(default: every plane is replaced)");
+DEFINE_int32(seg_step, 0, "segment planes (include/cspm.h \"segment planes\"): after the --iters PatchMatch iterations of any start, superpixels of "
+                         "about this many pixels across (4 .. 64) each get one robustly fitted plane, offered to every pixel of the segment where "
+                         "it costs less; --seg_warm_iters warm iterations follow, before post-processing and every output; 0 = off.  Not with "
+                         "--ca_name; needs --pc_name=PRE or IMG");
+DEFINE_int32(seg_compactness, 20, "with --seg_step: the weight of position against colour in the superpixel distance, 0 .. 255");
+DEFINE_int32(seg_iters, 5, "with --seg_step: assignment + update rounds of the segmentation, 1 .. 16");
+DEFINE_double(seg_tau, 1.0, "with --seg_step: the inlier threshold of the last re-fit, in disparities (it halves towards it round by round)");
+DEFINE_int32(seg_rounds, 3, "with --seg_step: re-fits on the inliers, 0 .. 8 (0 = plain least squares)");
+DEFINE_int32(seg_warm_iters, 1, "with --seg_step: warm PatchMatch iterations after the merge, 0 .. 15");
 DEFINE_bool(use_cs, false, "cross-scale aggregation over a 5-level pyramid (PreCSPC) instead of PreSSPC");
 DEFINE_bool(use_pp, false, "left-right check, hole filling and weighted median afterwards");
 DEFINE_double(reg_lambda, 0.0, "cross-scale regularisation weight");
@@ -220,6 +231,17 @@ void begin(PairRun &p, CCMethod *cost_fn) {
     } else {
       p.matcher->LocalStereoBegin(ca_method(FLAGS_ca_name), p.cost.get(), FLAGS_use_pp);
       if (use_fit) p.matcher->FitPlanes(p.cost.get(), fit, FLAGS_fit_merge);
+    }
+    if (FLAGS_seg_step != 0) {  // enqueued behind the run on the cost object's stream; the merge leaves the field consistent
+      cspm_seg_params seg;
+      cspm_seg_default_params(&seg);
+      seg.step = FLAGS_seg_step;
+      seg.compactness = FLAGS_seg_compactness;
+      seg.iters = FLAGS_seg_iters;
+      seg.tau = FLAGS_seg_tau;
+      seg.rounds = FLAGS_seg_rounds;
+      p.matcher->SegmentPlanes(p.cost.get(), seg, true);
+      if (FLAGS_seg_warm_iters > 0) p.matcher->PatchMatchFromBegin(FLAGS_seg_warm_iters, p.cost.get(), FLAGS_use_pp);
     }
   } catch (const std::exception &e) {  // a bad pair must not take the batch down
     p.log << "Error: " << e.what() << "\n";
@@ -492,6 +514,22 @@ int run() {
   if (FLAGS_fit_merge && FLAGS_fit_radius == 0) {
     cout << "Error: --fit_merge needs --fit_radius\n";
     return EXIT_FAILURE;
+  }
+  if (FLAGS_seg_step != 0) {
+    if (FLAGS_seg_step < 4 || FLAGS_seg_step > 64 || FLAGS_seg_compactness < 0 || FLAGS_seg_compactness > 255 || FLAGS_seg_iters < 1 || FLAGS_seg_iters > 16 ||
+        !(FLAGS_seg_tau >= 0.0) || FLAGS_seg_rounds < 0 || FLAGS_seg_rounds > 8 || FLAGS_seg_warm_iters < 0 || FLAGS_seg_warm_iters > 15) {
+      cout << "Error: --seg_step must be 4 .. 64 (0 = off), --seg_compactness 0 .. 255, --seg_iters 1 .. 16, --seg_tau >= 0, --seg_rounds 0 .. 8 and "
+              "--seg_warm_iters 0 .. 15\n";
+      return EXIT_FAILURE;
+    }
+    if (!FLAGS_ca_name.empty()) {
+      cout << "Error: --seg_step merges segment planes into a PatchMatch field under its plane cost: not with --ca_name (use --warm_ca or --seed_ca)\n";
+      return EXIT_FAILURE;
+    }
+    if (FLAGS_pc_name != "PRE" && FLAGS_pc_name != "IMG") {
+      cout << "Error: --seg_step needs one of this library's plane costs (--pc_name=PRE or IMG), not " << FLAGS_pc_name << "\n";
+      return EXIT_FAILURE;
+    }
   }
   if ((seed_pfm || !FLAGS_seed_ca.empty()) && FLAGS_pc_name != "PRE" && FLAGS_pc_name != "IMG") {
     cout << "Error: seeded starts need one of this library's plane costs (--pc_name=PRE or IMG), not " << FLAGS_pc_name << "\n";

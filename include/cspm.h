@@ -364,6 +364,81 @@ int cspm_fit_planes_host(int device, const double *disp, const uint8_t *valid, c
  * repeated (as with cspm_local_stereo).  Scratch: two doubles per pixel and the table, allocated by the first call and kept with the
  * plane field.  CSPM_ERR_STATE without images, a plane field or a known max_dis, and with merge = 1 without a cost object. */
 int cspm_fit_planes(cspm_ctx *ctx, const cspm_fit_params *p, int merge);
+/* ---- segment planes (an addition): one robustly fitted plane per superpixel ----------------------------------------
+ * Everything whose result could depend on the order of a sum is done in integers, so a device may reduce in any order and still give
+ * exactly these results.
+ *
+ * SEGMENTATION S(I, step s, compactness m, iters T) -> labels: I an 8-bit BGR w x h image.  Grid nx = ceil(w/s), ny = ceil(h/s), K = nx*ny
+ * segments; segment k = gy*nx + gx has HOME CELL (gx, gy).  A centre is five integers (cx, cy, cb, cg, cr) in 1/16 units; it starts as 16 *
+ * the coordinates and colour of the pixel (min(w-1, gx*s + s/2), min(h-1, gy*s + s/2)).  T times ASSIGN, then UPDATE:
+ *   ASSIGN: pixel (x, y) has home cell (min(nx-1, x/s), min(ny-1, y/s)); its candidates are the up-to-nine segments of the 3 x 3 cells around
+ *     it that exist, visited gy outer, gx inner, ascending.  Dist = dc*s*s + ds*m*m in 64-bit integers with
+ *     dc = (16B-cb)^2 + (16G-cg)^2 + (16R-cr)^2 and ds = (16x-cx)^2 + (16y-cy)^2; the label is the first candidate with the strictly smallest Dist.
+ *   UPDATE: for every segment with n > 0 member pixels every centre component becomes (2*Sum + n) / (2*n) by integer division, Sum = the sum
+ *     of 16 * the members' value (a mean rounded half up); a segment with n = 0 keeps its centre.
+ * Outputs: labels, a w x h int32 map, from the last ASSIGN; the centres and member counts of the UPDATE after it.  Connectivity is NOT enforced:
+ * a segment is a label set inside the 3 x 3 cells around its home cell (the 3 x 3 PROPERTY), possibly in several pieces, possibly empty.
+ * Magnitudes: a member lies within 2s of its segment's home-cell origin and so does the centre, a pixel and a candidate's centre are less than
+ * 3s <= 192 pixels apart: ds < 2 * (16*192)^2 < 2^25, ds*m*m < 2^41; dc <= 3 * (16*255)^2 < 2^26, dc*s*s < 2^38: Dist < 2^42.  A centre
+ * component is at most 16 * max(w, h, 255) and is stored as an int32.
+ *
+ * SEGMENT FIT P(D, V, labels, s, max_dis, tau, rounds R, min_support) -> (segment planes, inliers, per-pixel planes, fitted): D a w x h f64
+ * map, V w x h bytes (NULL = all 1), labels any map with the 3 x 3 property.  A pixel is a NODE when V != 0 and fabs(D) <= 32768 (false for NaN
+ * and inf).  For segment k with home-cell origin (ox, oy) = (gx*s, gy*s) a member node has u = x - ox, v = y - oy (-s <= u, v < 2s) and
+ * q = llrint(D * 65536.0).  The nine sums over the SELECTED member nodes are exact 64-bit integer sums
+ *     Sw = n, Su, Sv, Suu, Suv, Svv, Se = sum q, Sue = sum u*q, Sve = sum v*q
+ * (at most 9*64^2 < 2^16 nodes, |u|, |v| <= 2^7, |q| <= 2^31: every sum stays below 2^54, far below 2^63), each converted to double once.
+ * Then the cofactors C00 .. C22, det and the degeneracy test of "plane fitting" above, verbatim -- degenerate when n < min_support or
+ * !(det > 1e-6 * ((Suu*Svv)*Sw)) -- and, with three true divisions followed by an exact scaling by 2^-16,
+ *     a  = (((C00*Sue - C01*Sve) + C02*Se) / det) * 2^-16   b = (((C11*Sve - C01*Sue) - C12*Se) / det) * 2^-16
+ *     c0 = (((C02*Sue - C12*Sve) + C22*Se) / det) * 2^-16
+ * Round 0 selects every member node.  Round r = 1 .. R selects the member nodes with fabs(D - ((a*u + b*v) + c0)) <= tau * 2^(R-r) under
+ * the previous round's plane (u, v as doubles; every operation one IEEE f64 operation, nothing contracted; the threshold shrinks 4 tau, 2 tau,
+ * tau at the defaults).  A degenerate round 0 leaves the segment UNFITTED; a degenerate later round ends the rounds and keeps the previous
+ * plane.  inliers = the n of the last round that produced the plane (0 for an unfitted segment).
+ * Per segment: (a, b, c) with c = (c0 - a*ox) - b*oy, so that d(x, y) = a*x + b*y + c; three NaNs when unfitted.
+ * Per pixel of a fitted segment, node or not (a hole receives its segment's plane): t = (a*u + b*v) + c0;  z = t > 0 ? t : 0;
+ * z = z < max_dis ? z : max_dis;  normal and Plane(normal, (x, y, z)) exactly as "plane fitting" builds them;  fitted = 1.  A pixel of an
+ * unfitted segment gets six NaNs and fitted = 0: exactly "no candidate" for cspm_merge_planes_host.
+ * Defaults (chosen, not tuned): step 16, compactness 20, iters 5, tau 1.0, rounds 3, min_support 6.  Every entry returns CSPM_ERR_ARG for a
+ * step outside 4 .. 64, a compactness outside 0 .. 255, iters outside 1 .. 16, rounds outside 0 .. 8, min_support < 3 or a negative or NaN tau
+ * (+infinity is allowed).  params == NULL: the defaults. */
+typedef struct cspm_seg_params {
+  int step;         /* s: the grid spacing in pixels, 4 .. 64 */
+  int compactness;  /* m: the weight of position against colour, 0 .. 255 */
+  int iters;        /* T: ASSIGN + UPDATE repetitions, 1 .. 16 */
+  double tau;       /* the last round's inlier threshold in disparities; +infinity = every round is plain least squares */
+  int rounds;       /* R: re-fits on the inliers, 0 .. 8; 0 = plain least squares */
+  int min_support;  /* >= 3: a round with fewer selected nodes is degenerate */
+} cspm_seg_params;
+int cspm_seg_default_params(cspm_seg_params *p);
+/* K = ceil(w/step) * ceil(h/step); CSPM_ERR_ARG for w or h < 1 or a step outside 4 .. 64 */
+int cspm_segment_count(int w, int h, int step);
+/* S alone on caller memory, no context needed, synchronous: bgr packed 8UC3 rows of `stride` bytes (>= 3*w); labels_out w*h int32;
+ * centres_out K*5 int32 (cx, cy, cb, cg, cr per segment) or NULL; counts_out K int32 or NULL.  Only step, compactness and iters are used
+ * (all six are validated).  CSPM_ERR_ARG also for h > 262140 or w*h >= 2^31. */
+int cspm_segment_host(int device, const uint8_t *bgr, size_t stride, int w, int h, const cspm_seg_params *p, int32_t *labels_out,
+                      int32_t *centres_out, int32_t *counts_out);
+/* P alone on caller memory, synchronous: disp w*h doubles, valid w*h bytes or NULL, labels w*h int32 for the grid of p->step.  The labels are
+ * checked on the host first: CSPM_ERR_ARG unless every label has the 3 x 3 property (the device scans only those cells).  seg_planes_out
+ * K*3 doubles (a, b, c) or NULL, inliers_out K int32 or NULL, norm_param_out w*h*6 doubles in the layout of cspm_get_planes, fitted_out w*h
+ * bytes or NULL.  CSPM_ERR_ARG also for max_dis < 0. */
+int cspm_segment_planes_host(int device, const double *disp, const uint8_t *valid, const int32_t *labels, int w, int h, int max_dis,
+                             const cspm_seg_params *p, double *seg_planes_out, int32_t *inliers_out, double *norm_param_out, uint8_t *fitted_out);
+/* both views of the context's plane field: I = the view's level-0 image, D = a snapshot of the stored field's a*x+b*y+c (what
+ * cspm_get_disparity_f64 returns), V all 1, max_dis the context's.
+ * merge = 0: the planes of fitted segments replace the stored ones (a pixel of an unfitted segment keeps its plane); min_cost is left stale
+ * and the field is not consistent (cspm_patchmatch_warm re-scores).
+ * merge = 1: the planes go into the candidate buffer of cspm_merge_planes_host with `fitted` as the mask and are merged by that entry's
+ * rule, one view after the other; a field that is not consistent is re-scored first, and the field is left consistent.
+ * Asynchronous on the ctx stream.  Timed under CSPM_K_MISC: one bracket per view around the snapshot, S and P, w*h evaluations each; the
+ * merge launches under CSPM_K_INIT as in cspm_merge_planes_host.  A whole run in front of it that has not been checked can no longer be
+ * repeated (as with cspm_fit_planes).  Scratch: 12 bytes per pixel and view (snapshot and labels) and 60 bytes per segment of the finest
+ * grid, allocated by the first call and kept with the plane field.  The state rules are those of cspm_fit_planes: CSPM_ERR_STATE without
+ * images, a plane field or a known max_dis, and with merge = 1 without a cost object. */
+int cspm_segment_planes(cspm_ctx *ctx, const cspm_seg_params *p, int merge);
+/* the labels (w*h int32) of the last cspm_segment_planes call for one view; synchronising.  CSPM_ERR_STATE if there was none. */
+int cspm_get_segments(cspm_ctx *ctx, int view, int32_t *labels_out);
 /* PlaneToDisp + dis() (cs_patchmatch.cc:590-601, 111-113): saturate_u8(Round2Int(d*dis_scale)) */
 int cspm_get_disparity_u8(cspm_ctx *ctx, int view, int dis_scale, uint8_t *out, size_t stride);
 int cspm_get_disparity_f64(cspm_ctx *ctx, int view, double *out); /* unquantised a*x+b*y+c */
