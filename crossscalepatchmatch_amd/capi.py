@@ -61,6 +61,8 @@ SYMBOLS = [
     "cspm_seg_default_params", "cspm_segment_count", "cspm_segment_host", "cspm_segment_planes_host", "cspm_segment_planes", "cspm_get_segments",
     "cspm_geom_default_params", "cspm_reproject_host", "cspm_reproject", "cspm_reproject_device",
     "cspm_synth_default_params", "cspm_synthesize_host", "cspm_synthesize", "cspm_synthesize_device",
+    "cspm_rect_default_params", "cspm_rectify_compute", "cspm_rectify_host", "cspm_set_rectification", "cspm_get_rect_map",
+    "cspm_set_images_raw", "cspm_set_images_raw_device",
 ]
 
 
@@ -110,6 +112,27 @@ class SynthView(C.Structure):
                 ("bgr", C.POINTER(C.c_uint8)), ("stride", C.c_size_t)]
 
 
+class Camera(C.Structure):
+    """struct cspm_camera: K = [fx skew cx; 0 fy cy; 0 0 1] and Brown-Conrady distortion"""
+    _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "skew", "k1", "k2", "p1", "p2", "k3")]
+
+
+class Rig(C.Structure):
+    """struct cspm_rig: two cameras, X1 = R*X0 + T (row-major R), the raw image size"""
+    _fields_ = [("cam", Camera * 2), ("R", C.c_double * 9), ("T", C.c_double * 3), ("raw_w", C.c_int), ("raw_h", C.c_int)]
+
+
+class RectParams(C.Structure):
+    """struct cspm_rect_params: f <= 0, NaN cx / cy, w / h <= 0 = automatic"""
+    _fields_ = [("f", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("w", C.c_int), ("h", C.c_int)]
+
+
+class Rectification(C.Structure):
+    """struct cspm_rectification: X_rect = Rv * X_camv, the common projection, the rectified size"""
+    _fields_ = [("R0", C.c_double * 9), ("R1", C.c_double * 9), ("f", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("baseline", C.c_double), ("w", C.c_int), ("h", C.c_int)]
+
+
 # struct cspm_point: one 32-byte cloud record
 Point = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
                   ("b", "u1"), ("g", "u1"), ("r", "u1"), ("a", "u1"), ("pixel", "<u4")])
@@ -148,6 +171,7 @@ def load_library():
     qp, i32p = C.POINTER(SegParams), C.POINTER(C.c_int32)
     kp, gp, up = C.POINTER(Calib), C.POINTER(GeomParams), C.POINTER(C.c_uint)
     sp, svp = C.POINTER(SynthParams), C.POINTER(SynthView)
+    rgp, rpp, rcp = C.POINTER(Rig), C.POINTER(RectParams), C.POINTER(Rectification)
     sig = {
         "cspm_device_count": (C.c_int, []),
         "cspm_create": (C.c_int, [C.POINTER(vp), C.c_int]),
@@ -236,6 +260,13 @@ def load_library():
         "cspm_synthesize_host": (C.c_int, [C.c_int, sp, C.c_double, svp, svp, C.c_int, C.c_int, u8p, C.c_size_t, dp, u8p]),
         "cspm_synthesize": (C.c_int, [vp, C.c_int, sp, C.c_double, u8p, C.c_size_t, dp, u8p]),
         "cspm_synthesize_device": (C.c_int, [vp, C.c_int, sp, C.c_double, vp, C.c_size_t, vp, vp]),
+        "cspm_rect_default_params": (C.c_int, [rpp]),
+        "cspm_rectify_compute": (C.c_int, [rgp, rpp, rcp, kp]),
+        "cspm_rectify_host": (C.c_int, [C.c_int, rgp, rcp, C.c_int, u8p, C.c_size_t, u8p, C.c_size_t, dp, u8p]),
+        "cspm_set_rectification": (C.c_int, [vp, rgp, rcp]),
+        "cspm_get_rect_map": (C.c_int, [vp, C.c_int, dp, u8p]),
+        "cspm_set_images_raw": (C.c_int, [vp, u8p, u8p, C.c_size_t]),
+        "cspm_set_images_raw_device": (C.c_int, [vp, vp, vp, C.c_size_t]),
     }
     assert sorted(sig) == sorted(SYMBOLS)
     for name, (res, args) in sig.items():
@@ -267,6 +298,7 @@ class StereoContext:
         if rc != 0:
             raise CspmError(f"cspm_create failed ({rc}): {self.L.cspm_last_error(None).decode()}")
         self.w = self.h = 0
+        self._rect = None  # (raw_w, raw_h, w, h) of the stored rectification
 
     def close(self):
         if getattr(self, "p", None) and self.p:
@@ -294,6 +326,53 @@ class StereoContext:
     def set_images_device(self, d_l_ptr, d_r_ptr, w, h, stride=None):
         self.h, self.w = h, w
         self._chk(self.L.cspm_set_images_device(self.p, C.c_void_p(d_l_ptr), C.c_void_p(d_r_ptr), w, h, stride or w * 3))
+
+    # ---- rectification ----
+    def set_rectification(self, rig, rect=None, **params):
+        """build and keep both views' sampling maps (cspm_set_rectification).  rig: a Rig (see make_rig) or None to drop the stored
+        rectification; rect: a Rectification, or None to derive it from the rig with rectify_compute(rig, **params).  Returns
+        (rect, calib): the rectification in use and the cspm_calib of the rectified pair."""
+        if rig is None:
+            self._chk(self.L.cspm_set_rectification(self.p, None, None))
+            self._rect = None
+            return None
+        calib = None
+        if rect is None:
+            rect, calib = rectify_compute(rig, **params)
+        elif params:
+            raise TypeError("give a Rectification or the parameters to derive one, not both")
+        self._chk(self.L.cspm_set_rectification(self.p, C.byref(rig), C.byref(rect)))
+        self._rect = (rig.raw_w, rig.raw_h, rect.w, rect.h)
+        return rect, calib if calib is not None else Calib(rect.f, rect.cx, rect.cy, rect.baseline, 0.0)
+
+    def _raw_dims(self):
+        if self._rect is None:
+            self._chk(self.L.cspm_set_images_raw(self.p, None, None, 0))  # CSPM_ERR_STATE with the library's message
+        return self._rect
+
+    def set_images_raw(self, l_raw, r_raw):
+        """a RAW pair of the rig's size, remapped on the device into the level-0 images (cspm_set_images_raw)"""
+        l = np.ascontiguousarray(l_raw, dtype=np.uint8)
+        r = np.ascontiguousarray(r_raw, dtype=np.uint8)
+        rw, rh, w, h = self._raw_dims()
+        if l.shape != (rh, rw, 3) or r.shape != (rh, rw, 3):
+            raise CspmError(f"cspm error -1: raw images of the rig's size {rw} x {rh} x 3 expected, got {l.shape} and {r.shape}")
+        self._chk(self.L.cspm_set_images_raw(self.p, _u8(l), _u8(r), rw * 3))
+        self.h, self.w = h, w
+
+    def set_images_raw_device(self, d_l_ptr, d_r_ptr, stride=None):
+        rw, rh, w, h = self._raw_dims()
+        self._chk(self.L.cspm_set_images_raw_device(self.p, C.c_void_p(d_l_ptr), C.c_void_p(d_r_ptr), stride or rw * 3))
+        self.h, self.w = h, w
+
+    def rect_map(self, view):
+        """the stored map of one view: (sx, sy) as (h, w) f64 arrays and the valid bytes (h, w) u8 (cspm_get_rect_map)"""
+        if self._rect is None:
+            self._chk(self.L.cspm_get_rect_map(self.p, int(view), None, None))
+        _, _, w, h = self._rect
+        xy, valid = np.empty((2, h, w), np.float64), np.empty((h, w), np.uint8)
+        self._chk(self.L.cspm_get_rect_map(self.p, int(view), _dp(xy), _u8(valid)))
+        return xy[0], xy[1], valid
 
     def set_stream(self, stream_ptr):
         self._chk(self.L.cspm_set_stream(self.p, C.c_void_p(stream_ptr)))
@@ -863,6 +942,67 @@ def reproject_host(calib, view, disp, valid=None, slope_a=None, slope_b=None, bg
         res["count"] = cnt.value
     if pts is not None:
         res["cloud"] = pts[:min(cnt.value, cap)] if count else pts
+    return res
+
+
+def make_rig(cam0, cam1, R, T, raw_w, raw_h):
+    """a Rig from two cameras (Camera, or a sequence fx, fy, cx, cy[, skew, k1, k2, p1, p2, k3]), R (3 x 3, X1 = R X0 + T), T and the raw size"""
+    rig = Rig()
+    for v, cam in enumerate((cam0, cam1)):
+        if not isinstance(cam, Camera):
+            vals = [float(x) for x in cam]
+            cam = Camera(*(vals + [0.0] * (10 - len(vals))))
+        rig.cam[v] = cam
+    rig.R[:] = [float(x) for x in np.asarray(R, np.float64).reshape(9)]
+    rig.T[:] = [float(x) for x in np.asarray(T, np.float64).reshape(3)]
+    rig.raw_w, rig.raw_h = int(raw_w), int(raw_h)
+    return rig
+
+
+def rect_params(**params):
+    """a RectParams from keywords f, cx, cy, w, h over the library's defaults (everything automatic)"""
+    p = RectParams()
+    load_library().cspm_rect_default_params(C.byref(p))
+    for k, v in params.items():
+        if k not in ("f", "cx", "cy", "w", "h"):
+            raise TypeError(f"unknown rectification parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def rectify_compute(rig, **params):
+    """the rectifying rotations, the common projection and the cspm_calib of the rectified pair (cspm_rectify_compute): pure host logic,
+    answers without a GPU.  Returns (Rectification, Calib)."""
+    L = load_library()
+    p, rect, calib = rect_params(**params), Rectification(), Calib()
+    rc = L.cspm_rectify_compute(C.byref(rig), C.byref(p), C.byref(rect), C.byref(calib))
+    if rc != 0:
+        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    return rect, calib
+
+
+def rectify_host(rig, rect, view, raw=None, outputs=("bgr", "map", "valid"), raw_stride=None, out_stride=None, device=0):
+    """R alone on host memory (cspm_rectify_host): raw (raw_h, raw_w, 3) u8, or a 2-D u8 array of padded rows with
+    raw_stride = its row length; returns a dict with the requested outputs: bgr (h, w, 3) u8, map (2, h, w) f64 (sx, sy), valid (h, w) u8.
+    out_stride: the image is written into rows of that many bytes, returned as bgr_rows (h, out_stride) with the padding at 0xA5."""
+    L = load_library()
+    w, h = rect.w, rect.h
+    res = {}
+    if "bgr" in outputs:
+        res["bgr_rows"] = np.full((h, out_stride if out_stride is not None else w * 3), 0xA5, np.uint8)
+    if "map" in outputs:
+        res["map"] = np.empty((2, h, w), np.float64)
+    if "valid" in outputs:
+        res["valid"] = np.empty((h, w), np.uint8)
+    r = np.ascontiguousarray(raw, dtype=np.uint8) if raw is not None else None
+    stride = raw_stride if raw_stride is not None else rig.raw_w * 3
+    rc = L.cspm_rectify_host(device, C.byref(rig), C.byref(rect), int(view), _u8(r) if r is not None else None, stride,
+                             _u8(res["bgr_rows"]) if "bgr_rows" in res else None, out_stride if out_stride is not None else w * 3,
+                             _dp(res["map"]) if "map" in res else None, _u8(res["valid"]) if "valid" in res else None)
+    if rc != 0:
+        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    if "bgr_rows" in res:
+        res["bgr"] = np.ascontiguousarray(res["bgr_rows"][:, :w * 3]).reshape(h, w, 3)
     return res
 
 

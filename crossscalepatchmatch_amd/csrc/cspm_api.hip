@@ -19,6 +19,7 @@
 #include "cspm_seg.h"
 #include "cspm_geom.h"
 #include "cspm_synth.h"
+#include "cspm_rect.h"
 #include "cspm_ca.h"
 
 using namespace cspm;
@@ -212,6 +213,15 @@ struct cspm_ctx {
   double *geom_fit = nullptr;         // cspm_reproject with a fit: the fitted planes (6 arrays) and, behind them, the exp(-k/10) table
   unsigned int *geom_counts = nullptr;  // cspm_reproject: the kept pixels per workgroup, then the total
   double *synth_disp = nullptr;       // cspm_synthesize: both views' CSPM_GEOM_RAW disparity maps (2 arrays); allocated by the first such call and kept with the field
+  // rectification (cspm_set_rectification): kept until the context goes or the rectification is dropped
+  bool rect_on = false;
+  cspm_rig rect_rig{};
+  cspm_rectification rect{};
+  double *rect_map[2] = {nullptr, nullptr};     // per view: the planes sx, sy (2 * w*h doubles) ...
+  uint8_t *rect_valid[2] = {nullptr, nullptr};  // ... and the valid bytes
+  uint8_t *rect_stage = nullptr;                // cspm_set_images_raw: the raw pair's bytes (host sources only), allocated by the first such call
+  uint32_t *rect_rawpix = nullptr;              // cspm_set_images_raw(_device): the raw pair as packed words (k_pack_bgr)
+  uint8_t *rect_out = nullptr;                  // ... and the rectified 8UC3 pair cspm_set_images_device's path consumes
   double *diffuse_snap = nullptr;     // CSPM_SCHED_DIFFUSE: the round's snapshot (both views, the 6 plane arrays each), allocated by the first such propagation and kept with the field
   long long sweep_fallbacks = 0;      // how often that happened (cspm_get_option)
   // CSPatchMatch over a foreign IPlaneCost (cspm_fpm_*): candidate buffers and what the pending batch was
@@ -408,6 +418,16 @@ void free_field(cspm_ctx *c) {
   dfree(c->d_sweep_qctl);
   dfree(c->d_sweep_queue);
   c->field_alloc = false;
+}
+void free_rect(cspm_ctx *c) {
+  for (int v = 0; v < 2; ++v) {
+    dfree(c->rect_map[v]);
+    dfree(c->rect_valid[v]);
+  }
+  dfree(c->rect_stage);
+  dfree(c->rect_rawpix);
+  dfree(c->rect_out);
+  c->rect_on = false;
 }
 void free_images(cspm_ctx *c) {
   for (int v = 0; v < 2; ++v) dfree(c->img0[v]);
@@ -1961,6 +1981,103 @@ int ca_local_view(cspm_ctx *c, int method, int v) {
   return CSPM_OK;
 }
 
+// ---- rectification (cspm_rect.h) ---------------------------------------------------------------------------
+const cspm_rect_params kRectDefaults = {0.0, NAN, NAN, 0, 0};
+inline bool all_finite(const double *p, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(p[i])) return false;
+  return true;
+}
+const char *rig_error(const cspm_rig *rig) {
+  if (!rig) return "rectification: no rig";
+  for (int v = 0; v < 2; ++v) {
+    if (!all_finite(&rig->cam[v].fx, 10)) return "rectification: the cameras must be finite";
+    if (!(rig->cam[v].fx > 0.0) || !(rig->cam[v].fy > 0.0)) return "rectification: fx and fy must be positive";
+  }
+  if (!all_finite(rig->R, 9) || !all_finite(rig->T, 3)) return "rectification: R and T must be finite";
+  if (rig->T[0] == 0.0 && rig->T[1] == 0.0 && rig->T[2] == 0.0) return "rectification: T is zero, the cameras share their centre";
+  if (rig->raw_w < 1 || rig->raw_h < 1) return "rectification: the raw size must be at least 1 x 1";
+  if ((long long)rig->raw_w * rig->raw_h >= (1LL << 31)) return "rectification: raw_w * raw_h must be below 2^31";
+  return nullptr;
+}
+const char *rect_error(const cspm_rectification *r) {
+  if (!r) return "rectification: no rectification (cspm_rectify_compute)";
+  if (!all_finite(r->R0, 9) || !all_finite(r->R1, 9) || !std::isfinite(r->f) || !std::isfinite(r->cx) || !std::isfinite(r->cy) || !std::isfinite(r->baseline))
+    return "rectification: the rectification must be finite";
+  if (!(r->f > 0.0) || !(r->baseline > 0.0)) return "rectification: f and baseline must be positive";
+  if (r->w < 1 || r->h < 1) return "rectification: the rectified size must be at least 1 x 1";
+  if ((long long)r->w * r->h >= (1LL << 31)) return "rectification: w * h must be below 2^31";
+  return nullptr;
+}
+inline void cross3(const double *p, const double *q, double *o) {
+  o[0] = p[1] * q[2] - p[2] * q[1];
+  o[1] = p[2] * q[0] - p[0] * q[2];
+  o[2] = p[0] * q[1] - p[1] * q[0];
+}
+// the derivation of R (cspm.h "rectification"); the rig has passed rig_error
+const char *rect_compute(const cspm_rig *rig, const cspm_rect_params *p, cspm_rectification *out) {
+  const double *R = rig->R, *T = rig->T;
+  double C1[3], e1[3], e2[3], e3[3], c[3];
+  for (int j = 0; j < 3; ++j) C1[j] = -((R[j] * T[0] + R[3 + j] * T[1]) + R[6 + j] * T[2]);
+  const double baseline = std::sqrt((C1[0] * C1[0] + C1[1] * C1[1]) + C1[2] * C1[2]);
+  if (!(baseline > 0.0) || !std::isfinite(baseline)) return "rectification: the baseline is zero or not finite";
+  for (int j = 0; j < 3; ++j) e1[j] = C1[j] / baseline;
+  if (!(e1[0] > 0.0) || !(std::fabs(e1[0]) >= std::fabs(e1[1])) || !(std::fabs(e1[0]) >= std::fabs(e1[2])))
+    return "rectification: camera 1 must be to the right of camera 0 and the rig horizontal (swap the cameras, or rotate the images)";
+  const double zm[3] = {R[6], R[7], 1.0 + R[8]};
+  cross3(zm, e1, c);
+  const double len = std::sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
+  if (!(len > 0.0) || !std::isfinite(len)) return "rectification: the mean optical axis is parallel to the baseline";
+  for (int j = 0; j < 3; ++j) e2[j] = c[j] / len;
+  cross3(e1, e2, e3);
+  for (int j = 0; j < 3; ++j) { out->R0[j] = e1[j]; out->R0[3 + j] = e2[j]; out->R0[6 + j] = e3[j]; }
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) out->R1[3 * i + j] = (out->R0[3 * i] * R[3 * j] + out->R0[3 * i + 1] * R[3 * j + 1]) + out->R0[3 * i + 2] * R[3 * j + 2];
+  out->baseline = baseline;
+  if (std::isinf(p->f) || std::isinf(p->cx) || std::isinf(p->cy)) return "rectification: f, cx and cy of the parameters must be finite or automatic";
+  const cspm_camera *k = rig->cam;
+  out->f = p->f > 0.0 ? p->f : 0.25 * (((k[0].fx + k[0].fy) + k[1].fx) + k[1].fy);
+  out->w = p->w > 0 ? p->w : rig->raw_w;
+  out->h = p->h > 0 ? p->h : rig->raw_h;
+  if ((long long)out->w * out->h >= (1LL << 31)) return "rectification: w * h must be below 2^31";
+  double q[2][2];
+  for (int v = 0; v < 2; ++v) {
+    const double *Rv = v ? out->R1 : out->R0;
+    const double yn = ((double)(rig->raw_h - 1) / 2.0 - k[v].cy) / k[v].fy;
+    const double xn = (((double)(rig->raw_w - 1) / 2.0 - k[v].cx) - k[v].skew * yn) / k[v].fx;
+    double P[3];
+    for (int i = 0; i < 3; ++i) P[i] = (Rv[3 * i] * xn + Rv[3 * i + 1] * yn) + Rv[3 * i + 2];
+    q[v][0] = (out->f * P[0]) / P[2];
+    q[v][1] = (out->f * P[1]) / P[2];
+  }
+  out->cx = std::isnan(p->cx) ? (double)(out->w - 1) / 2.0 - 0.5 * (q[0][0] + q[1][0]) : p->cx;
+  out->cy = std::isnan(p->cy) ? (double)(out->h - 1) / 2.0 - 0.5 * (q[0][1] + q[1][1]) : p->cy;
+  if (const char *msg = rect_error(out)) return msg;
+  return nullptr;
+}
+RectView rect_view(const cspm_rig *rig, const cspm_rectification *r, int view) {
+  RectView k;
+  k.f = r->f; k.cx = r->cx; k.cy = r->cy;
+  for (int i = 0; i < 9; ++i) k.r[i] = (view ? r->R1 : r->R0)[i];
+  const cspm_camera &c = rig->cam[view];
+  k.fx = c.fx; k.fy = c.fy; k.cxraw = c.cx; k.cyraw = c.cy; k.skew = c.skew;
+  k.k1 = c.k1; k.k2 = c.k2; k.p1 = c.p1; k.p2 = c.p2; k.k3 = c.k3;
+  k.raw_w = rig->raw_w; k.raw_h = rig->raw_h;
+  return k;
+}
+inline void rect_map_launch(hipStream_t stream, const RectView &k, int w, int h, double *map, uint8_t *valid) {
+  const long long n = (long long)w * h;
+  hipLaunchKernelGGL(k_rect_map, dim3(ew_grid(n, kRectBlock)), dim3(kRectBlock), 0, stream, k, w, n, map, valid);
+}
+// raw_bgr (rows of raw_stride bytes) -> rawpix (packed words) -> dst (8UC3 rows of dst_stride bytes) through one view's map
+inline void rect_remap_launch(hipStream_t stream, const uint8_t *raw_bgr, size_t raw_stride, int raw_w, int raw_h, uint32_t *rawpix, const double *map,
+                              const uint8_t *valid, int w, int h, uint8_t *dst, size_t dst_stride) {
+  hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)raw_w * raw_h)), dim3(256), 0, stream, raw_bgr, raw_stride, raw_w, raw_h, raw_w, 0, rawpix);
+  const long long items = (((long long)w + kWave - 1) / kWave) * h;
+  hipLaunchKernelGGL(k_rect_remap, dim3((unsigned)((items + kRectWaves - 1) / kRectWaves)), dim3(kRectBlock), 0, stream, map, valid, (const uint32_t *)rawpix,
+                     raw_w, raw_h, w, h, dst, dst_stride);
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -2020,6 +2137,7 @@ void cspm_destroy(cspm_ctx *c) {
   free_cost(c);
   free_field(c);
   free_images(c);
+  free_rect(c);
   for (void *p : c->ca_allocs) (void)hipFree(p);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
@@ -2257,6 +2375,148 @@ struct Scratch {
     cspm_destroy(c);
   }
 };
+
+// ---- rectification (cspm.h "rectification") ----
+int cspm_rect_default_params(cspm_rect_params *p) {
+  if (!p) return CSPM_ERR_ARG;
+  *p = kRectDefaults;
+  return CSPM_OK;
+}
+
+int cspm_rectify_compute(const cspm_rig *rig, const cspm_rect_params *params, cspm_rectification *rect_out, cspm_calib *calib_out) {
+  if (const char *msg = rig_error(rig)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  cspm_rectification r;
+  if (const char *msg = rect_compute(rig, params ? params : &kRectDefaults, &r)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (rect_out) *rect_out = r;
+  if (calib_out) *calib_out = cspm_calib{r.f, r.cx, r.cy, r.baseline, 0.0};
+  return CSPM_OK;
+}
+
+// R alone on caller memory: the launches cspm_set_rectification and cspm_set_images_raw enqueue, on one view.  Arguments first, then the device.
+int cspm_rectify_host(int device, const cspm_rig *rig, const cspm_rectification *rect, int view, const uint8_t *raw, size_t raw_stride, uint8_t *bgr_out,
+                      size_t out_stride, double *map_out, uint8_t *valid_out) {
+  if (const char *msg = rig_error(rig)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (const char *msg = rect_error(rect)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (view < 0 || view > 1) return fail(nullptr, CSPM_ERR_ARG, "rectification: view must be 0 or 1");
+  if (bgr_out && !raw) return fail(nullptr, CSPM_ERR_ARG, "rectification: a remapped image needs the raw image");
+  if (bgr_out && raw_stride < (size_t)rig->raw_w * 3) return fail(nullptr, CSPM_ERR_ARG, "rectification: raw_stride is below 3 * raw_w");
+  if (bgr_out && out_stride < (size_t)rect->w * 3) return fail(nullptr, CSPM_ERR_ARG, "rectification: out_stride is below 3 * w");
+  Scratch S;
+  int rc = cspm_create(&S.c, device);
+  if (rc) return rc;
+  cspm_ctx *c = S.c;
+  const int w = rect->w, h = rect->h, rw = rig->raw_w, rh = rig->raw_h;
+  const size_t n = (size_t)w * h, rn = (size_t)rw * rh;
+  double *dmap = nullptr;
+  uint8_t *dvalid = nullptr, *draw = nullptr, *dout = nullptr;
+  uint32_t *dpix = nullptr;
+  if ((rc = dalloc(c, &dmap, 2 * n, &S.tmp)) || (rc = dalloc(c, &dvalid, n, &S.tmp)) ||
+      (bgr_out && ((rc = dalloc(c, &draw, 3 * rn, &S.tmp)) || (rc = dalloc(c, &dpix, rn, &S.tmp)) || (rc = dalloc(c, &dout, 3 * n, &S.tmp)))))
+    return S.done(rc);
+  if (bgr_out && hipMemcpy2DAsync(draw, (size_t)rw * 3, raw, raw_stride, (size_t)rw * 3, rh, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  rect_map_launch(c->stream, rect_view(rig, rect, view), w, h, dmap, dvalid);
+  if (bgr_out) rect_remap_launch(c->stream, draw, (size_t)rw * 3, rw, rh, dpix, dmap, dvalid, w, h, dout, (size_t)w * 3);
+  if (hipGetLastError() != hipSuccess || (map_out && hipMemcpyAsync(map_out, dmap, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      (valid_out && hipMemcpyAsync(valid_out, dvalid, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      (bgr_out && hipMemcpy2DAsync(bgr_out, out_stride, dout, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, "rectification kernels failed"));
+  return S.done(CSPM_OK);
+}
+
+int cspm_set_rectification(cspm_ctx *c, const cspm_rig *rig, const cspm_rectification *rect) {
+  if (!c) return CSPM_ERR_ARG;
+  if (!rig) {  // back to a context without a rectification
+    if (!c->rect_on && !c->rect_map[0]) return CSPM_OK;
+    ON_DEVICE(c);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    free_rect(c);
+    return CSPM_OK;
+  }
+  if (const char *msg = rig_error(rig)) return fail(c, CSPM_ERR_ARG, msg);
+  if (const char *msg = rect_error(rect)) return fail(c, CSPM_ERR_ARG, msg);
+  if (c->rect_on && memcmp(&c->rect_rig, rig, sizeof *rig) == 0 && memcmp(&c->rect, rect, sizeof *rect) == 0) return CSPM_OK;  // one rig, many pairs
+  ON_DEVICE(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  free_rect(c);
+  const size_t n = (size_t)rect->w * rect->h;
+  int rc;
+  for (int v = 0; v < 2; ++v)
+    if ((rc = dalloc(c, &c->rect_map[v], 2 * n, nullptr)) || (rc = dalloc(c, &c->rect_valid[v], n, nullptr))) {
+      free_rect(c);
+      return rc;
+    }
+  {
+    Timed t(c, CSPM_K_MISC, 2 * (long long)n);
+    for (int v = 0; v < 2; ++v) rect_map_launch(c->stream, rect_view(rig, rect, v), rect->w, rect->h, c->rect_map[v], c->rect_valid[v]);
+  }
+  HIPCHK(c, hipGetLastError());
+  c->rect_rig = *rig;
+  c->rect = *rect;
+  c->rect_on = true;
+  return CSPM_OK;
+}
+
+int cspm_get_rect_map(cspm_ctx *c, int view, double *xy_out, uint8_t *valid_out) {
+  if (!c) return CSPM_ERR_ARG;
+  if (view < 0 || view > 1) return fail(c, CSPM_ERR_ARG, "rectification: view must be 0 or 1");
+  if (!c->rect_on) return fail(c, CSPM_ERR_STATE, "no rectification stored (cspm_set_rectification)");
+  ON_DEVICE(c);
+  const size_t n = (size_t)c->rect.w * c->rect.h;
+  if (xy_out) HIPCHK(c, hipMemcpyAsync(xy_out, c->rect_map[view], sizeof(double) * 2 * n, hipMemcpyDeviceToHost, c->stream));
+  if (valid_out) HIPCHK(c, hipMemcpyAsync(valid_out, c->rect_valid[view], n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return CSPM_OK;
+}
+
+// both raw images through the stored maps into the rectified 8UC3 pair, which then takes cspm_set_images_device's path
+static int set_images_raw_enqueue(cspm_ctx *c, const void *l, const void *r, size_t stride, bool on_device);
+static int set_images_raw_impl(cspm_ctx *c, const void *l, const void *r, size_t stride, bool on_device) {
+  const int rc = set_images_raw_enqueue(c, l, r, stride, on_device);
+  if (rc == CSPM_OK || on_device || !c || !c->rect_on || !l || !r) return rc;
+  // a host source: whatever failed behind an upload that was already enqueued, the caller may reuse its buffers when this returns
+  DevGuard guard_(c->device);
+  (void)hipStreamSynchronize(c->stream);
+  return rc;
+}
+static int set_images_raw_enqueue(cspm_ctx *c, const void *l, const void *r, size_t stride, bool on_device) {
+  if (!c) return CSPM_ERR_ARG;
+  if (!c->rect_on) return fail(c, CSPM_ERR_STATE, "raw images need a stored rectification (cspm_set_rectification)");
+  const int rw = c->rect_rig.raw_w, rh = c->rect_rig.raw_h, w = c->rect.w, h = c->rect.h;
+  if (!l || !r || stride < (size_t)rw * 3) return fail(c, CSPM_ERR_ARG, "bad raw image arguments: two images with rows of at least 3 * raw_w bytes, the rig's size");
+  ON_DEVICE(c);
+  const size_t rn = (size_t)rw * rh, n = (size_t)w * h, raw_row = (size_t)rw * 3, row = (size_t)w * 3;
+  int rc;
+  if (!c->rect_rawpix && (rc = dalloc(c, &c->rect_rawpix, 2 * rn, nullptr))) return rc;
+  if (!c->rect_out && (rc = dalloc(c, &c->rect_out, 2 * 3 * n, nullptr))) return rc;
+  if (!on_device && !c->rect_stage && (rc = dalloc(c, &c->rect_stage, 2 * 3 * rn, nullptr))) return rc;
+  const void *src[2] = {l, r};
+  const uint8_t *d_src[2];
+  size_t d_stride = stride;
+  for (int v = 0; v < 2; ++v) {
+    d_src[v] = (const uint8_t *)src[v];
+    if (!on_device) {
+      uint8_t *dst = c->rect_stage + (size_t)v * 3 * rn;
+      HIPCHK(c, hipMemcpy2DAsync(dst, raw_row, src[v], stride, raw_row, rh, hipMemcpyHostToDevice, c->stream));
+      d_src[v] = dst;
+      d_stride = raw_row;
+    }
+  }
+  {
+    Timed t(c, CSPM_K_MISC, 2 * (long long)n);
+    for (int v = 0; v < 2; ++v)
+      rect_remap_launch(c->stream, d_src[v], d_stride, rw, rh, c->rect_rawpix + (size_t)v * rn, c->rect_map[v], c->rect_valid[v], w, h,
+                        c->rect_out + (size_t)v * 3 * n, row);
+  }
+  HIPCHK(c, hipGetLastError());
+  if ((rc = set_images_impl(c, c->rect_out, c->rect_out + 3 * n, w, h, row, true))) return rc;
+  if (!on_device) HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller may reuse its host buffers
+  return CSPM_OK;
+}
+
+int cspm_set_images_raw(cspm_ctx *c, const uint8_t *l, const uint8_t *r, size_t stride) { return set_images_raw_impl(c, l, r, stride, false); }
+int cspm_set_images_raw_device(cspm_ctx *c, const void *l, const void *r, size_t stride) { return set_images_raw_impl(c, l, r, stride, true); }
 
 // CCMethod::buildCV / buildRightCV on host buffers (cc_method.h:31-32): the cells of slabs 0 .. maxDis-1 from CV_64FC3 images
 static int build_cv_host(CostKind kind, int device, const double *l_rgb, const double *r_rgb, int w, int h, int maxDis, int right_view, double *vol_out) {

@@ -41,6 +41,14 @@ void SmoothDisparity(const Mat &src, const Mat *conf, const Mat *guide, const cs
 // CV_8UC1 mask or NULL (every pixel).  planes: rows x cols Planes, row-major, those of unfitted segments with NaN entries; fitted:
 // CV_8UC1 or NULL; seg_abc: three doubles (a, b, c) per segment or NULL.  Both throw std::runtime_error for another type, differing
 // sizes and for what the C ABI refuses (labels outside the 3 x 3 cells of their pixel among it).  Defined in host_impl.cc.
+// an addition (include/cspm.h "rectification", cspm_rectify_host): two RAW CV_8UC3 photographs of the rig's size undistorted and
+// row-aligned on the calling thread's device; rect comes from cspm_rectify_compute.  l_out / r_out: CV_8UC3 of rect.w x rect.h, pixels
+// without a source black; l_valid / r_valid: CV_8UC1 masks of the pixels that have one, or NULL.  Throws std::runtime_error for another
+// type or size and for what the C ABI refuses.  Defined in host_impl.cc.
+struct cspm_rig;
+struct cspm_rectification;
+void RectifyPair(const cspm_rig &rig, const cspm_rectification &rect, const Mat &l_raw, const Mat &r_raw, Mat &l_out, Mat &r_out, Mat *l_valid,
+                 Mat *r_valid);
 struct cspm_seg_params;
 class Plane;
 void SegmentImage(const Mat &img, Mat &labels, const cspm_seg_params *params);

@@ -1,6 +1,8 @@
 // cs_patchmatch.h -- class CSPatchMatch with the reference's public interface (CSPM/cs_patchmatch.h:17-68).
 #pragma once
 #include "../../include/cspm.h"
+#include <utility>
+
 #include "commfunc.h"
 #include "plane.h"
 #include "plane_cost/i_plane_cost.h"
@@ -10,6 +12,10 @@
 class CSPatchMatch {
  public:
   CSPatchMatch(const Mat &l_img, const Mat &r_img, const int &max_dis, const int &dis_scale);
+  // RAW photographs of a calibrated rig (an addition; include/cspm.h "rectification"): the pair is rectified on the device (RectifyPair)
+  // and the object is the one the constructor above makes of the result; rect comes from cspm_rectify_compute.  The plane cost it runs
+  // on must see the same rectified pair: a device cost built from the raw pair through a DeviceSlot with SetRectification does.
+  CSPatchMatch(const Mat &l_raw, const Mat &r_raw, const cspm_rig &rig, const cspm_rectification &rect, const int &max_dis, const int &dis_scale);
   ~CSPatchMatch();
   // init, iter_num x (spatial, view, refinement), PlaneToDisp, optional PostProcessing (cs_patchmatch.cc:51-109).
   // A device cost (PreSSPC / PreCSPC / GrdPC / CSPC of this host layer) runs the whole loop on its GPU.  Any other IPlaneCost
@@ -139,4 +145,5 @@ class CSPatchMatch {
   void SeededBegin(bool keep, int iter_num, const IPlaneCost *plane_cost, bool use_pp);
   void PatchMatchForeign(int iter_num, const IPlaneCost *plane_cost, bool use_pp);
   CSPatchMatch(const CSPatchMatch &);
+  CSPatchMatch(const std::pair<Mat, Mat> &rectified, const int &max_dis, const int &dis_scale);  // the raw-pair constructor delegates through here
 };

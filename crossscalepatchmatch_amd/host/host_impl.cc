@@ -167,6 +167,7 @@ void DevicePlaneCost::open_context(const Mat &l_img, const Mat &r_img) {
   CV_Assert(l_img.rows == r_img.rows && l_img.cols == r_img.cols);
   if (!slot_) slot_ = &DeviceSlot::current();
   ctx_ = slot_->take();
+  const bool parked = ctx_ != NULL;
   if (!ctx_) {
     check(cspm_create(&ctx_, slot_->device()), NULL, "cspm_create");
     adopt(ctx_);
@@ -176,7 +177,48 @@ void DevicePlaneCost::open_context(const Mat &l_img, const Mat &r_img) {
   base_sweep_fallbacks_ = option(ctx_, CSPM_OPT_SWEEP_FALLBACKS);
   base_volume_fallbacks_ = option(ctx_, CSPM_OPT_VOLUME_FALLBACKS);
   const Mat l = l_img.clone(), r = r_img.clone();  // packed rows
+  if (slot_->rect_on_) {  // raw photographs: the maps are built by the context's first pair and kept, every pair is remapped on the device
+    if (l.cols != slot_->rig_.raw_w || l.rows != slot_->rig_.raw_h) throw std::runtime_error("the raw images are not of the rig's size");
+    check(cspm_set_rectification(ctx_, &slot_->rig_, &slot_->rect_), ctx_, "cspm_set_rectification");
+    check(cspm_set_images_raw(ctx_, l.data, r.data, l.step), ctx_, "cspm_set_images_raw");
+    return;
+  }
+  if (parked) check(cspm_set_rectification(ctx_, NULL, NULL), ctx_, "cspm_set_rectification");  // no launch, nothing to free unless the slot rectified before
   check(cspm_set_images(ctx_, l.data, r.data, l.cols, l.rows, l.step), ctx_, "cspm_set_images");
+}
+
+void DevicePlaneCost::LevelImages(Mat *l_img, Mat *r_img) const {
+  int w = 0, h = 0, d = 0;
+  check(cspm_get_level_dims(ctx_, 0, &w, &h, &d), ctx_, "cspm_get_level_dims");
+  Mat *out[kViewNum] = {l_img, r_img};
+  for (int v = 0; v < kViewNum; ++v) {
+    if (!out[v]) continue;
+    Mat m(h, w, CV_8UC3);  // packed rows
+    check(cspm_get_level_image(ctx_, v, 0, m.data), ctx_, "cspm_get_level_image");
+    *out[v] = m;
+  }
+}
+
+// include/cspm.h R on two raw Mats (cspm_rectify_host per view on the calling thread's device)
+void RectifyPair(const cspm_rig &rig, const cspm_rectification &rect, const Mat &l_raw, const Mat &r_raw, Mat &l_out, Mat &r_out, Mat *l_valid,
+                 Mat *r_valid) {
+  const Mat *raw[kViewNum] = {&l_raw, &r_raw};
+  Mat *valid[kViewNum] = {l_valid, r_valid};
+  Mat res[kViewNum];
+  for (int v = 0; v < kViewNum; ++v) {
+    if (raw[v]->empty() || raw[v]->type() != CV_8UC3 || raw[v]->cols != rig.raw_w || raw[v]->rows != rig.raw_h)
+      throw std::runtime_error("RectifyPair: two CV_8UC3 images of the rig's size expected");
+    if (rect.w < 1 || rect.h < 1) throw std::runtime_error("RectifyPair: an empty rectification");
+    res[v].create(rect.h, rect.w, CV_8UC3);
+    Mat m;
+    if (valid[v]) m.create(rect.h, rect.w, CV_8UC1);
+    check(cspm_rectify_host(DeviceSlot::current().device(), &rig, &rect, v, raw[v]->data, raw[v]->step, res[v].data, res[v].step, NULL,
+                            valid[v] ? m.data : NULL),
+          NULL, "RectifyPair");
+    if (valid[v]) *valid[v] = m;
+  }
+  l_out = res[kLeft];
+  r_out = res[kRight];
 }
 
 // a constructor that throws never runs the destructor: hand the context back (or destroy it) before the exception leaves
@@ -281,6 +323,17 @@ CSPatchMatch::CSPatchMatch(const Mat &l_img, const Mat &r_img, const int &max_di
   hei_ = l_img.rows;
   for (int v = 0; v < kViewNum; ++v) dis_[v] = Mat::zeros(hei_, wid_, CV_8UC1);
 }
+
+// raw photographs of a calibrated rig: rectified here (RectifyPair), then the object is what the constructor above makes of the result
+static std::pair<Mat, Mat> RectifiedPair(const cspm_rig &rig, const cspm_rectification &rect, const Mat &l_raw, const Mat &r_raw) {
+  std::pair<Mat, Mat> out;
+  RectifyPair(rig, rect, l_raw, r_raw, out.first, out.second, NULL, NULL);
+  return out;
+}
+CSPatchMatch::CSPatchMatch(const Mat &l_raw, const Mat &r_raw, const cspm_rig &rig, const cspm_rectification &rect, const int &max_dis, const int &dis_scale)
+    : CSPatchMatch(RectifiedPair(rig, rect, l_raw, r_raw), max_dis, dis_scale) {}
+CSPatchMatch::CSPatchMatch(const std::pair<Mat, Mat> &rectified, const int &max_dis, const int &dis_scale)
+    : CSPatchMatch(rectified.first, rectified.second, max_dis, dis_scale) {}
 
 // A foreign IPlaneCost (i_plane_cost.h:28-33): the device owns the plane field, the random streams and the accept rules
 // (cspm_fpm_*, csrc/cspm_foreign.h); every candidate is priced by the plugin's GetPlaneCost, exactly the calls the reference

@@ -8,7 +8,9 @@
 // --iters iterations, merged where it costs less, then warm iterations; include/cspm.h "segment planes")
 // --calib --l_ply --r_ply --l_depth_pfm --r_depth_pfm --geom_min_cos --geom_z_far --geom_left_frame --geom_fit_radius (metric depth maps and
 // point clouds of the final plane field; include/cspm.h "reprojection") --synth_t --synth_png --synth_dis_pfm --synth_views --synth_max_stretch
-// --synth_merge_diff --synth_fill (the scene rendered from a camera between the two views; include/cspm.h "view synthesis").
+// --synth_merge_diff --synth_fill (the scene rendered from a camera between the two views; include/cspm.h "view synthesis")
+// --rig --rect_f --rect_w --rect_h --l_rect_file --r_rect_file (the inputs are RAW photographs of a calibrated rig, undistorted and
+// row-aligned on the device before matching; include/cspm.h "rectification").
 #include "../../include/cspm.h"
 #include "commfunc.h"
 #include "cs_patchmatch.h"
@@ -20,6 +22,7 @@
 #include "calib_io.h"
 #include "pfm_io.h"
 #include "ply_io.h"
+#include "rig_io.h"
 
 #include <atomic>
 #include <cmath>
@@ -100,7 +103,17 @@ DEFINE_double(pp_smooth_fill_conf, 0.25, "with --pp_smooth_lambda: the confidenc
 DEFINE_string(calib, "", "a Middlebury-2014 calib.txt (cam0, cam1, doffs, baseline, width, height) of the pair: needed by the point-cloud and depth "
                          "outputs below.  When its width differs from the image width, f, cx, cy and doffs are scaled by image width / width");
 DEFINE_string(l_ply, "", "write the left view's point cloud (binary little-endian PLY: x y z nx ny nz, red green blue; the baseline's unit) from the "
-                         "final plane field: the raw plane disparities, or with --use_pp the sub-pixel post-processed map.  Needs --calib; not with --batch_list");
+                         "final plane field: the raw plane disparities, or with --use_pp the sub-pixel post-processed map.  Needs --calib or --rig; "
+                         "not with --batch_list");
+DEFINE_string(rig, "", "a rig file (cam0, dist0, cam1, dist1, R, T, width, height; INTEGRATION.md \"rig files\"): --l_img_file / --r_img_file (or the "
+                       "batch list's images) are then RAW photographs of that size, undistorted and row-aligned on the device before matching "
+                       "(include/cspm.h \"rectification\"); the maps are built once per device context.  The calibration of the rectified pair is "
+                       "derived from the rig and serves the point-cloud and depth outputs: not with --calib");
+DEFINE_double(rect_f, 0.0, "with --rig: the focal length of the rectified pair in pixels; 0 = the mean of the four raw focal lengths");
+DEFINE_int32(rect_w, 0, "with --rig: the width of the rectified pair; 0 = the raw width");
+DEFINE_int32(rect_h, 0, "with --rig: the height of the rectified pair; 0 = the raw height");
+DEFINE_string(l_rect_file, "", "with --rig: also write the rectified left image (8-bit colour PNG / PPM).  Not with --batch_list");
+DEFINE_string(r_rect_file, "", "with --rig: also write the rectified right image");
 DEFINE_string(r_ply, "", "the same for the right view, in its own camera frame unless --geom_left_frame");
 DEFINE_string(l_depth_pfm, "", "write the left view's metric depth Z as float32 PFM, NaN where there is none (see --l_ply)");
 DEFINE_string(r_depth_pfm, "", "the same for the right view");
@@ -135,6 +148,12 @@ namespace {
 const int kWindow = 35;  // main.cc:94
 const int kScales = 5;   // main.cc:100
 
+// --rig: what run() derived before any device was opened; read-only afterwards
+bool g_rectify = false;
+cspm_rig g_rig;
+cspm_rectification g_rect;
+cspm_calib g_rect_calib;
+
 struct PairFiles {
   string l_img, r_img, l_dis, r_dis, l_pfm, r_pfm, synth_png, synth_pfm;
 };
@@ -168,6 +187,9 @@ void load(PairRun &p) {
     // the reference waits for a key press here (main.cc:70-75); a batch tool must not
     p.log << "Error: can not open image\n";
     p.rc = EXIT_FAILURE;
+  } else if (g_rectify && (p.left.cols != g_rig.raw_w || p.left.rows != g_rig.raw_h || p.right.cols != g_rig.raw_w || p.right.rows != g_rig.raw_h)) {
+    p.log << "Error: the images are not of the rig's size " << g_rig.raw_w << " x " << g_rig.raw_h << "\n";
+    p.rc = EXIT_FAILURE;
   }
 }
 
@@ -191,6 +213,12 @@ void begin(PairRun &p, CCMethod *cost_fn) {
       pc = FLAGS_use_cs ? static_cast<IPlaneCost *>(new PreCSPC(p.left, p.right, FLAGS_max_dis, kWindow, kScales, cost_fn, FLAGS_reg_lambda))
                         : static_cast<IPlaneCost *>(new PreSSPC(p.left, p.right, FLAGS_max_dis, kWindow, cost_fn));
     p.cost.reset(pc);  // released on every path, exceptions included (batch mode goes on)
+    if (g_rectify) {  // the slot's context has remapped the raw pair: everything from here on works on the rectified one
+      const DevicePlaneCost *dev = dynamic_cast<const DevicePlaneCost *>(pc);
+      if (!dev) throw std::runtime_error("--rig needs one of this library's plane costs");
+      dev->LevelImages(&p.left, &p.right);
+      p.calib = g_rect_calib;
+    }
     p.matcher.reset(new CSPatchMatch(p.left, p.right, FLAGS_max_dis, FLAGS_dis_scale));
     p.matcher->set_seed(static_cast<uint64_t>(FLAGS_seed));
     p.matcher->SetSpeckleFilter(FLAGS_pp_speckle_size, FLAGS_pp_speckle_diff);
@@ -318,6 +346,8 @@ void write(PairRun &p) {
     if (!dpfm[v]->empty()) written = WritePFM(*dpfm[v], p.depth[v].data(), p.left.cols, p.left.rows);
     if (written && !ply[v]->empty()) written = WritePLY(*ply[v], p.cloud[v].data(), p.cloud[v].size());
   }
+  if (written && g_rectify && !FLAGS_l_rect_file.empty()) written = imwrite(FLAGS_l_rect_file, p.left);
+  if (written && g_rectify && !FLAGS_r_rect_file.empty()) written = imwrite(FLAGS_r_rect_file, p.right);
   if (written && !p.synth.empty()) written = imwrite(p.files.synth_png, p.synth);
   if (written && !p.synth_dis.empty()) written = WritePFM(p.files.synth_pfm, p.synth_dis.data(), p.left.cols, p.left.rows);
   if (!written) {
@@ -376,6 +406,7 @@ int run_batch(const std::vector<BatchJob> &jobs, int skipped, int bad_lines) {
   const double t0 = static_cast<double>(getTickCount());
   auto worker = [&](int device) {
     DeviceSlot slot(device, /*keep_context=*/true, /*shared_gpu=*/on_gpu[device] >= 2);
+    if (g_rectify) slot.SetRectification(&g_rig, &g_rect);  // one rig: the worker's parked context keeps its maps from pair to pair
     DeviceSlot::Use use(slot);
     const std::unique_ptr<CCMethod> cost_fn(GetCCType(FLAGS_cc_name));  // NULL for unknown names, rejected by the cost constructors
     if (CenGrdCC *cg = dynamic_cast<CenGrdCC *>(cost_fn.get())) cg->set_fused(FLAGS_cc_fused);
@@ -540,8 +571,28 @@ int run() {
     return EXIT_FAILURE;
   }
   const bool geom_out = !FLAGS_l_ply.empty() || !FLAGS_r_ply.empty() || !FLAGS_l_depth_pfm.empty() || !FLAGS_r_depth_pfm.empty();
-  if (geom_out && FLAGS_calib.empty()) {  // checked before anything opens a device
-    cout << "Error: --l_ply / --r_ply / --l_depth_pfm / --r_depth_pfm need --calib\n";
+  if (!FLAGS_rig.empty() && !FLAGS_calib.empty()) {  // checked before anything opens a device
+    cout << "Error: --rig derives the calibration of the rectified pair itself: not with --calib\n";
+    return EXIT_FAILURE;
+  }
+  if (FLAGS_rig.empty() && (FLAGS_rect_f != 0.0 || FLAGS_rect_w != 0 || FLAGS_rect_h != 0 || !FLAGS_l_rect_file.empty() || !FLAGS_r_rect_file.empty())) {
+    cout << "Error: --rect_f / --rect_w / --rect_h / --l_rect_file / --r_rect_file need --rig\n";
+    return EXIT_FAILURE;
+  }
+  if (!(FLAGS_rect_f >= 0.0) || !std::isfinite(FLAGS_rect_f) || FLAGS_rect_w < 0 || FLAGS_rect_h < 0) {
+    cout << "Error: --rect_f must be finite and >= 0, --rect_w and --rect_h >= 0 (0 = automatic)\n";
+    return EXIT_FAILURE;
+  }
+  if ((!FLAGS_l_rect_file.empty() || !FLAGS_r_rect_file.empty()) && !FLAGS_batch_list.empty()) {
+    cout << "Error: --l_rect_file / --r_rect_file belong to one pair: not with --batch_list\n";
+    return EXIT_FAILURE;
+  }
+  if (!FLAGS_rig.empty() && FLAGS_pc_name != "PRE" && FLAGS_pc_name != "IMG") {
+    cout << "Error: --rig needs one of this library's plane costs (--pc_name=PRE or IMG), not " << FLAGS_pc_name << "\n";
+    return EXIT_FAILURE;
+  }
+  if (geom_out && FLAGS_calib.empty() && FLAGS_rig.empty()) {
+    cout << "Error: --l_ply / --r_ply / --l_depth_pfm / --r_depth_pfm need --calib or --rig\n";
     return EXIT_FAILURE;
   }
   if ((geom_out || !FLAGS_calib.empty()) && !FLAGS_batch_list.empty()) {
@@ -580,6 +631,25 @@ int run() {
     cout << "Error: can not read " << FLAGS_calib << " as a Middlebury calib.txt (cam0, cam1, doffs, baseline, width, height)\n";
     return EXIT_FAILURE;
   }
+  if (!FLAGS_rig.empty()) {  // the file and the derivation are host work: a bad rig is reported before a device is opened
+    if (!ReadRigFile(FLAGS_rig, &g_rig)) {
+      cout << "Error: can not read " << FLAGS_rig << " as a rig file (cam0, dist0, cam1, dist1, R, T, width, height)\n";
+      return EXIT_FAILURE;
+    }
+    cspm_rect_params rp;
+    cspm_rect_default_params(&rp);
+    rp.f = FLAGS_rect_f;
+    rp.w = FLAGS_rect_w;
+    rp.h = FLAGS_rect_h;
+    if (cspm_rectify_compute(&g_rig, &rp, &g_rect, &g_rect_calib) != CSPM_OK) {
+      cout << "Error: " << FLAGS_rig << ": " << cspm_last_error(NULL) << "\n";
+      return EXIT_FAILURE;
+    }
+    g_rectify = true;
+    if (!FLAGS_quiet)
+      cout << "Rectification: " << g_rig.raw_w << " x " << g_rig.raw_h << " raw -> " << g_rect.w << " x " << g_rect.h << ", f " << g_rect.f << ", cx "
+           << g_rect.cx << ", cy " << g_rect.cy << ", baseline " << g_rect.baseline << "\n";
+  }
   DevicePlaneCost::device = FLAGS_device;
   if (FLAGS_use_pp && !FLAGS_pp_pfm && !(FLAGS_l_disp_pfm.empty() && FLAGS_r_disp_pfm.empty()) && !FLAGS_quiet)
     cout << "Note: the PFM maps hold the plane disparities before post-processing (--pp_pfm writes the post-processed ones)\n";
@@ -592,6 +662,7 @@ int run() {
               0);
     load(p);
     if (!FLAGS_calib.empty() && p.rc == EXIT_SUCCESS) p.calib = ScaledCalib(calib_file, p.left.cols);
+    if (g_rectify) DeviceSlot::current().SetRectification(&g_rig, &g_rect);
     begin(p, cost_fn.get());
     finish(p);
     write(p);

@@ -2,6 +2,7 @@
 // DeviceSlot: where a host thread's cost objects live (which GPU, which options, which parked context).
 #pragma once
 #include <vector>
+#include "../../../include/cspm.h"
 #include "../cc_method.h"
 #include "i_plane_cost.h"
 
@@ -18,7 +19,8 @@ class DeviceSlot {
   // of equally sized pairs allocates once.  shared_gpu: other slots keep pairs in flight on the same GPU -- the contexts opened through
   // this one then get CSPM_OPT_SWEEP_FOLD (four-wavefront sweep workgroups that leave the other pairs' kernels room, include/cspm.h).
   explicit DeviceSlot(int device = 0, bool keep_context = false, bool shared_gpu = false)
-      : device_(device), keep_(keep_context), shared_gpu_(shared_gpu), parked_(NULL), sweep_fallbacks_(0), volume_fallbacks_(0) {}
+      : device_(device), keep_(keep_context), shared_gpu_(shared_gpu), parked_(NULL), sweep_fallbacks_(0), volume_fallbacks_(0), rect_on_(false),
+        rig_(), rect_() {}
   ~DeviceSlot() { release(); }
   int device() const { return device_; }
   bool keep_context() const { return keep_; }
@@ -27,6 +29,16 @@ class DeviceSlot {
   // sums over the contexts this slot has seen: raster sweeps repeated after a hand-over timeout / optional volumes given up (include/cspm.h)
   long long sweep_fallbacks() const { return sweep_fallbacks_; }
   long long volume_fallbacks() const { return volume_fallbacks_; }
+  // rectification (an addition; include/cspm.h "rectification"): from now on the images given to the cost constructors of this slot are
+  // RAW photographs of the rig's size; every context opened through the slot keeps the two sampling maps (built once per context, so one
+  // rig serves a stream of pairs) and remaps each pair on the device into its level-0 images (cspm_set_rectification,
+  // cspm_set_images_raw).  rect comes from cspm_rectify_compute.  rig == NULL: back to rectified inputs.  Set it before the slot's first
+  // cost object, from the thread that uses the slot.
+  void SetRectification(const cspm_rig *rig, const cspm_rectification *rect) {
+    rect_on_ = rig != NULL && rect != NULL;
+    if (rect_on_) { rig_ = *rig; rect_ = *rect; }
+  }
+  bool rectifies() const { return rect_on_; }
 
   // makes `slot` the calling thread's current slot for the lifetime of the Use object (nestable)
   class Use {
@@ -50,6 +62,9 @@ class DeviceSlot {
   bool shared_gpu_;
   cspm_ctx *parked_;
   long long sweep_fallbacks_, volume_fallbacks_;
+  bool rect_on_;
+  cspm_rig rig_;
+  cspm_rectification rect_;
 };
 
 class DevicePlaneCost : public IPlaneCost, public IDevicePlaneCost {
@@ -63,6 +78,9 @@ class DevicePlaneCost : public IPlaneCost, public IDevicePlaneCost {
   ~DevicePlaneCost();
   virtual double GetPlaneCost(const int &ref_x, const int &ref_y, const Plane &plane, const RefView &view) const;
   virtual cspm_ctx *device_ctx() const { return ctx_; }
+  // the level-0 images the cost object works on (CV_8UC3): the constructor's own, or -- through a slot with a rectification -- the
+  // rectified pair the device made of the raw photographs
+  void LevelImages(Mat *l_img, Mat *r_img) const;
   // the DEFAULT slot's settings (threads without a DeviceSlot::Use): GPU index (the CLI's --device) and batch mode
   static int device;
   static bool keep_context;

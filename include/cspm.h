@@ -700,6 +700,97 @@ int cspm_synthesize(cspm_ctx *ctx, int source, const cspm_synth_params *params, 
 int cspm_synthesize_device(cspm_ctx *ctx, int source, const cspm_synth_params *params, double t, void *d_bgr_out, size_t out_stride,
                            void *d_disp_out, void *d_mask_out);
 
+/* ---- rectification (an addition): a calibrated RAW pair undistorted and row-aligned on the device ----------------------
+ * Every entry above that takes images assumes an undistorted, row-aligned pair, and cspm_reproject a cspm_calib of that pair.  This section
+ * produces both from a rig description: two pinhole cameras with Brown-Conrady distortion and the pose of camera 1 in camera 0's frame.
+ * The specification R.  Every product, sum, quotient and square root is one IEEE f64 operation in the association written here, nothing
+ * contracted, no reciprocal, no trigonometry.  M[i][j] is entry 3*i + j of a row-major matrix.
+ *
+ * Derivation (host, cspm_rectify_compute): the axis construction of Fusiello et al. with the mean optical axis.
+ *     C1[j]    = -((R[0][j]*T[0] + R[1][j]*T[1]) + R[2][j]*T[2])          the centre of camera 1 in camera 0's frame, -R^T T
+ *     baseline = sqrt((C1[0]*C1[0] + C1[1]*C1[1]) + C1[2]*C1[2])
+ *     e1       = C1 / baseline                                            three divisions
+ *     zm       = (R[2][0], R[2][1], 1.0 + R[2][2])                        (0, 0, 1) + the third row of R: the sum of the two optical axes
+ *     c        = zm x e1,  (p x q)[0] = p[1]*q[2] - p[2]*q[1], [1] = p[2]*q[0] - p[0]*q[2], [2] = p[0]*q[1] - p[1]*q[0]
+ *     e2       = c / sqrt((c[0]*c[0] + c[1]*c[1]) + c[2]*c[2])            three divisions
+ *     e3       = e1 x e2
+ *     R0       = rows e1, e2, e3          R1[i][j] = (R0[i][0]*R[j][0] + R0[i][1]*R[j][1]) + R0[i][2]*R[j][2]         R1 = R0 R^T
+ *   X_rect = R_v X_cam_v; camera 1's centre is (baseline, 0, 0) in the rectified frame.  CSPM_ERR_ARG unless e1[0] > 0, |e1[0]| >= |e1[1]| and
+ *   |e1[0]| >= |e1[2]| (camera 1 is to the right of camera 0 and the rig is horizontal: otherwise the caller swaps the cameras), and
+ *   when zm is parallel to e1.
+ *   Projection.  params NULL or a field "automatic" (f not > 0; cx or cy NaN; w or h <= 0):
+ *     f    = 0.25 * (((fx0 + fy0) + fx1) + fy1)            w, h = raw_w, raw_h
+ *     per view v, from the centre pixel of the raw image through K_v^-1 (skew honoured, distortion ignored), rotated and projected:
+ *       yn = ((double)(raw_h-1)/2.0 - cy_v) / fy_v         xn = (((double)(raw_w-1)/2.0 - cx_v) - skew_v*yn) / fx_v
+ *       P[i] = (R_v[i][0]*xn + R_v[i][1]*yn) + R_v[i][2]   q_v = ((f*P[0]) / P[2], (f*P[1]) / P[2])
+ *     cx = (double)(w-1)/2.0 - 0.5*(q_0.x + q_1.x)         cy = (double)(h-1)/2.0 - 0.5*(q_0.y + q_1.y)
+ *   Both views share cx: the derived cspm_calib is {f, cx, cy, baseline, doffs = 0} and every point in front of the rig has a disparity >= 0.
+ *   CSPM_ERR_ARG for any non-finite input (an infinite f, cx or cy in params included), fx or fy <= 0, T = 0, raw_w, raw_h, w or h < 1,
+ *   w*h >= 2^31, or a derived f, cx or cy that is not finite (a centre ray with P[2] = 0).
+ *
+ * Map M_v(x, y) -> (sx, sy, front), on the device, r_ij = R_v[i][j] (applied transposed: the ray in camera v), cxraw = cx_v, cyraw = cy_v:
+ *     u = ((double)x - cx) / f          wv = ((double)y - cy) / f
+ *     X = (r00*u + r10*wv) + r20        Y = (r01*u + r11*wv) + r21        Z = (r02*u + r12*wv) + r22
+ *     front = Z > 0.0
+ *     a = X / Z    b = Y / Z    r2 = a*a + b*b
+ *     rad = 1.0 + r2*(k1 + r2*(k2 + r2*k3))
+ *     ad = a*rad + ((2.0*p1)*a*b + p2*(r2 + 2.0*a*a))
+ *     bd = b*rad + (p1*(r2 + 2.0*b*b) + (2.0*p2)*a*b)
+ *     sx = (fx*ad + skew*bd) + cxraw    sy = fy*bd + cyraw
+ *   Rectified -> raw is the forward distortion model: no iteration anywhere.  valid = front && 0 <= sx <= raw_w-1 && 0 <= sy <= raw_h-1, every
+ *   comparison false for NaN.  The stored map holds sx, sy as computed, also where they are invalid or NaN.
+ *
+ * Remap.  A valid pixel: x0 = (int)floor(sx), x1 = min(x0+1, raw_w-1), y0, y1 likewise, tx = sx - x0, ty = sy - y0 and per channel, the
+ * four taps I[y][x] as doubles:
+ *     top = I00 + tx*(I01 - I00)        bot = I10 + tx*(I11 - I10)        val = top + ty*(bot - top)
+ *   the output byte is Round2Int(val) (round half to even) saturated to 0 .. 255.  An invalid pixel is (0, 0, 0) and its valid byte is 0. */
+typedef struct cspm_camera {
+  double fx, fy, cx, cy, skew; /* K = [fx skew cx; 0 fy cy; 0 0 1] */
+  double k1, k2, p1, p2, k3;   /* Brown-Conrady: radial k1, k2, k3, tangential p1, p2 */
+} cspm_camera;
+typedef struct cspm_rig {
+  cspm_camera cam[2];
+  double R[9], T[3]; /* X1 = R*X0 + T, row-major R */
+  int raw_w, raw_h;  /* both raw images */
+} cspm_rig;
+typedef struct cspm_rect_params {
+  double f, cx, cy; /* f <= 0, NaN cx / cy: automatic */
+  int w, h;         /* <= 0: automatic (the raw size) */
+} cspm_rect_params;
+typedef struct cspm_rectification {
+  double R0[9], R1[9]; /* X_rect = Rv * X_camv */
+  double f, cx, cy, baseline;
+  int w, h;
+} cspm_rectification;
+/* everything automatic */
+int cspm_rect_default_params(cspm_rect_params *p);
+/* the derivation: pure host logic, answers without a GPU.  params may be NULL (all automatic); rect_out and calib_out are each optional.
+ * The message of a CSPM_ERR_ARG is cspm_last_error(NULL)'s. */
+int cspm_rectify_compute(const cspm_rig *rig, const cspm_rect_params *params, cspm_rectification *rect_out, cspm_calib *calib_out);
+/* R alone on caller memory, no context needed, synchronous: the map of `view` and, with bgr_out, the remap of one raw image (packed 8UC3
+ * rows of raw_stride bytes, rig->raw_w x rig->raw_h) into rect->w x rect->h rows of out_stride bytes (bytes beyond 3*w are untouched).
+ * Each output is optional: map_out 2*w*h doubles (the plane sx, then the plane sy), valid_out w*h bytes.  Arguments are checked before a
+ * device is opened: CSPM_ERR_ARG for a NULL rig or rect, a rig or rectification cspm_rectify_compute would refuse or could not have
+ * produced (non-finite values, f <= 0, sizes < 1, w*h or raw_w*raw_h >= 2^31), a view outside 0 .. 1, bgr_out without raw, a raw_stride
+ * below 3*raw_w or an out_stride below 3*w. */
+int cspm_rectify_host(int device, const cspm_rig *rig, const cspm_rectification *rect, int view, const uint8_t *raw, size_t raw_stride,
+                      uint8_t *bgr_out, size_t out_stride, double *map_out, uint8_t *valid_out);
+/* builds both views' maps on the ctx stream and keeps them with the context (17 bytes per pixel and view) until the context goes or a
+ * call with rig == NULL (then rect is ignored) drops them; a call with the rig and rectification already stored launches nothing.
+ * One rig serves many pairs.  With no rectification stored no other entry changes a byte or a launch.  Argument checks as above. */
+int cspm_set_rectification(cspm_ctx *ctx, const cspm_rig *rig, const cspm_rectification *rect);
+/* the stored map of one view, layouts as cspm_rectify_host; each output optional.  Synchronous.  CSPM_ERR_STATE without a rectification. */
+int cspm_get_rect_map(cspm_ctx *ctx, int view, double *xy_out, uint8_t *valid_out);
+/* cspm_set_images with a RAW pair of the rig's size (rows of `stride` bytes, >= 3*raw_w): both images are remapped through the stored maps
+ * on the ctx stream and the rectified rect.w x rect.h pair goes down exactly the path of cspm_set_images_device; afterwards the context
+ * is in the state cspm_set_images would have left it in with the rectified bytes (cspm_get_level_image(ctx, v, 0, ...) returns them).
+ * Synchronous like cspm_set_images.  The remap of both views is timed as one CSPM_K_MISC bracket.  Scratch (the packed raw pair and the
+ * rectified 8UC3 pair) is allocated by the first call and kept with the rectification.  CSPM_ERR_STATE without a stored rectification;
+ * CSPM_ERR_ARG for a NULL image or a stride below 3*raw_w. */
+int cspm_set_images_raw(cspm_ctx *ctx, const uint8_t *l_raw, const uint8_t *r_raw, size_t stride);
+/* the same from device memory, asynchronous, with the contract of cspm_set_images_device */
+int cspm_set_images_raw_device(cspm_ctx *ctx, const void *d_l_raw, const void *d_r_raw, size_t stride);
+
 /* ---- CSPatchMatch::PatchMatch over a FOREIGN IPlaneCost (plane_cost/i_plane_cost.h:28-33) ------------------------------
  * Any object with a GetPlaneCost(x, y, plane, view) that is not one of this library's device costs: the reference drives it
  * through the virtual call (call sites cs_patchmatch.cc:144,181,191,200,208,269,334).  Here the device keeps the plane field,
