@@ -629,7 +629,12 @@ int alloc_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg
         L.cvW = W + 2 * cvpad_all;
         if (with_vol) {
           double *vol;
-          if ((rc = dalloc(c, &vol, (size_t)(D + 2) * px, &c->cost_allocs))) return rc;  // D+1 slabs and one guard slab (clamped taps of a level with D < 2)
+          // D+1 slabs and one guard slab behind them (clamped taps of a level with D == 1 form addresses in slabs 0 .. 2).  A level with
+          // D == 0 (max_dis < 2^s) clamps to [-1, 1] (cspm_tap.h split_disp: med3(f, 1, D - 1)) and addresses slabs -1 .. 2: one more guard
+          // slab on either side, the volume starts behind the first.  No tap of such a level is valid; the guard values are never used.
+          const size_t lead = D < 1 ? px : 0;
+          if ((rc = dalloc(c, &vol, (size_t)(D + 2) * px + 2 * lead, &c->cost_allocs))) return rc;
+          vol += lead;
           L.vol[v] = vol;
         }
         if (need_grd) {
@@ -2357,7 +2362,13 @@ int cspm_build_cost_cengrd(cspm_ctx *c, int max_dis, int wnd_size, int scale_num
 // `new GrdPC(l, r, max_dis, wnd)` (scale_num == 0; plane_cost/grd_pc.cc:11-66) / `new CSPC(l, r, max_dis, wnd, scale_num,
 // reg_lambda)` (cspc.cc:11-93): pyramid, 8U gray and its x-gradient per level; no volumes, no CCMethod.  max_cost_ has no
 // counterpart in these classes: the "impossible disparity" cost is a constant (grd_pc.cc:131-132, cspc.cc:150-152).
+// max_dis > width is refused: HandleBorder (commfunc.h:129-145) wraps a column ONCE, so q_x + q_disp up to width - 1 + max_dis leaves
+// ceil_x - width >= width and the reference reads I_ohter_y / G_other_y beyond the row (grd_pc.cc:153-165, cspc.cc:153-166) -- there is
+// no value to reproduce.  With max_dis <= width every level stays in range (D_s = floor(D / 2^s) <= W_s = ceil(W / 2^s)).
 int cspm_build_cost_img(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg_lambda) {
+  if (!c) return CSPM_ERR_ARG;
+  if (c->img0[0] && max_dis > c->W)
+    return fail(c, CSPM_ERR_ARG, "cspm_build_cost_img: max_dis must not exceed the image width (the reference's single wrap-around leaves the row)");
   return build_cost(c, kKindImg, max_dis, wnd_size, scale_num, reg_lambda);
 }
 

@@ -381,7 +381,9 @@ void CSPatchMatch::PatchMatchForeign(int iter_num, const IPlaneCost *plane_cost,
     for (int st = 0; st < steps; ++st) batch(CSPM_FPM_REFINE, it, st);
   }
   if (use_pp) {  // PostProcessing reads the level-0 images of a cost object: the cheapest one provides them
-    check(cspm_build_cost_img(ctx, max_dis_, 35, 0, 0.0), ctx, "cspm_build_cost_img");
+    // (cspm_build_cost_img refuses max_dis > width, include/cspm.h: the fused GRD object holds the same images)
+    if (max_dis_ <= wid_) check(cspm_build_cost_img(ctx, max_dis_, 35, 0, 0.0), ctx, "cspm_build_cost_img");
+    else check(cspm_build_cost_grd(ctx, max_dis_, 35, 0, 0.0), ctx, "cspm_build_cost_grd");
     ApplyPostFilters(ctx);
     check(cspm_postprocess(ctx, dis_scale_, dis_[kLeft].data, dis_[kRight].data, dis_[kLeft].step), ctx, "cspm_postprocess");
   } else {

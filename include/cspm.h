@@ -218,7 +218,10 @@ int cspm_build_cost_cengrd(cspm_ctx *ctx, int max_dis, int wnd_size, int scale_n
  *   scale_num >= 1 -> `new CSPC(l_img, r_img, max_disp, wnd_size, scale_num, reg_lambda)`    plane_cost/cspc.h:21-23,  cspc.cc:11-93
  * GetPlaneCost (grd_pc.cc:72-176, cspc.cc:107-183) interpolates the other view's colour and 8U-gray x-gradient at the
  * real-valued column x -+ q_disp (wrap-around HandleBorder) instead of interpolating pre-computed cells; the "impossible
- * disparity" cost is the constant COST_ALPHA*TAU_CLR + (1-COST_ALPHA)*TAU_GRD.  cspm_get_cost_slab is an error for these. */
+ * disparity" cost is the constant COST_ALPHA*TAU_CLR + (1-COST_ALPHA)*TAU_GRD.  cspm_get_cost_slab is an error for these.
+ * max_dis > image width is refused with CSPM_ERR_ARG: HandleBorder (commfunc.h:129-145) wraps a column once, so with a disparity
+ * beyond the width floor_x / ceil_x stay outside [0, width) and the reference reads past the row (grd_pc.cc:153-165,
+ * cspc.cc:153-166); the other cost kinds take such a pair. */
 int cspm_build_cost_img(cspm_ctx *ctx, int max_dis, int wnd_size, int scale_num, double reg_lambda);
 /* Foreign CCMethod plugins (cc_method.h:31-32): allocate like the constructors above, then upload
  * the host volumes the plugin filled slab by slab, then finalize (max_cost reduction). */
