@@ -60,6 +60,7 @@ SYMBOLS = [
     "cspm_fit_default_params", "cspm_fit_planes_host", "cspm_fit_planes",
     "cspm_seg_default_params", "cspm_segment_count", "cspm_segment_host", "cspm_segment_planes_host", "cspm_segment_planes", "cspm_get_segments",
     "cspm_geom_default_params", "cspm_reproject_host", "cspm_reproject", "cspm_reproject_device",
+    "cspm_mesh_default_params", "cspm_mesh_host", "cspm_mesh", "cspm_mesh_device",
     "cspm_synth_default_params", "cspm_synthesize_host", "cspm_synthesize", "cspm_synthesize_device",
     "cspm_rect_default_params", "cspm_rectify_compute", "cspm_rectify_host", "cspm_set_rectification", "cspm_get_rect_map",
     "cspm_set_images_raw", "cspm_set_images_raw_device",
@@ -101,6 +102,11 @@ class GeomParams(C.Structure):
     _fields_ = [("z_near", C.c_double), ("z_far", C.c_double), ("min_cos", C.c_double), ("left_frame", C.c_int), ("consistent_only", C.c_int)]
 
 
+class MeshParams(C.Structure):
+    """struct cspm_mesh_params"""
+    _fields_ = [("max_diff", C.c_double), ("all_vertices", C.c_int)]
+
+
 class SynthParams(C.Structure):
     """struct cspm_synth_params"""
     _fields_ = [("views", C.c_int), ("fill", C.c_int), ("max_stretch", C.c_double), ("merge_diff", C.c_double)]
@@ -137,6 +143,9 @@ class Rectification(C.Structure):
 Point = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
                   ("b", "u1"), ("g", "u1"), ("r", "u1"), ("a", "u1"), ("pixel", "<u4")])
 assert Point.itemsize == 32
+# struct cspm_face: the three vertex numbers of one triangle
+Face = np.dtype([("v", "<u4", 3)])
+assert Face.itemsize == 12
 
 
 def library_path():
@@ -171,6 +180,7 @@ def load_library():
     qp, i32p = C.POINTER(SegParams), C.POINTER(C.c_int32)
     kp, gp, up = C.POINTER(Calib), C.POINTER(GeomParams), C.POINTER(C.c_uint)
     sp, svp = C.POINTER(SynthParams), C.POINTER(SynthView)
+    mshp = C.POINTER(MeshParams)
     rgp, rpp, rcp = C.POINTER(Rig), C.POINTER(RectParams), C.POINTER(Rectification)
     sig = {
         "cspm_device_count": (C.c_int, []),
@@ -256,6 +266,11 @@ def load_library():
         "cspm_reproject_host": (C.c_int, [C.c_int, kp, gp, C.c_int, dp, u8p, dp, dp, u8p, C.c_size_t, C.c_int, C.c_int, dp, dp, dp, u8p, vp, C.c_size_t, up]),
         "cspm_reproject": (C.c_int, [vp, C.c_int, C.c_int, kp, gp, fp, dp, dp, dp, u8p, vp, C.c_size_t, up]),
         "cspm_reproject_device": (C.c_int, [vp, C.c_int, C.c_int, kp, gp, fp, vp, vp, vp, vp, vp, C.c_size_t, vp]),
+        "cspm_mesh_default_params": (C.c_int, [mshp]),
+        "cspm_mesh_host": (C.c_int, [C.c_int, kp, gp, mshp, C.c_int, dp, u8p, dp, dp, u8p, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t,
+                                     u8p, up, up]),
+        "cspm_mesh": (C.c_int, [vp, C.c_int, C.c_int, kp, gp, fp, mshp, vp, C.c_size_t, vp, C.c_size_t, u8p, up, up]),
+        "cspm_mesh_device": (C.c_int, [vp, C.c_int, C.c_int, kp, gp, fp, mshp, vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp]),
         "cspm_synth_default_params": (C.c_int, [sp]),
         "cspm_synthesize_host": (C.c_int, [C.c_int, sp, C.c_double, svp, svp, C.c_int, C.c_int, u8p, C.c_size_t, dp, u8p]),
         "cspm_synthesize": (C.c_int, [vp, C.c_int, sp, C.c_double, u8p, C.c_size_t, dp, u8p]),
@@ -699,6 +714,44 @@ class StereoContext:
         self._chk(self.L.cspm_reproject_device(self.p, int(view), int(source), C.byref(k), C.byref(g), C.byref(f) if f is not None else None,
                                                vp(d_depth), vp(d_xyz), vp(d_normal), vp(d_keep), vp(d_cloud), int(cloud_cap), vp(d_count)))
 
+    # ---- triangle meshes ----
+    def mesh(self, view, calib, source=GEOM_RAW, fit=None, max_diff=1.0, all_vertices=0, vertices=True, faces=True, quad=True, vertex_cap=None,
+             face_cap=None, **params):
+        """a triangle mesh of one view of the stored plane field (cspm_mesh): calib, source, fit and params (z_near, z_far, min_cos,
+        left_frame, consistent_only) as for reproject; max_diff and all_vertices are the cspm_mesh_params.  Returns a dict: n_vertices and
+        n_faces always; with vertices the Point records (at most vertex_cap of them; None = all), with faces the Face records (at most
+        face_cap), with quad the (h, w) uint8 quad bytes.  The mesh is complete only when both counts fit their capacities."""
+        k, g, m = calib_struct(calib), geom_params(**params), mesh_params(max_diff=max_diff, all_vertices=all_vertices)
+        f = fit_params(**dict(fit)) if fit is not None else None
+        vcap = self.w * self.h if vertex_cap is None else int(vertex_cap)
+        fcap = 2 * (self.w - 1) * (self.h - 1) if face_cap is None else int(face_cap)
+        pts = np.zeros(vcap, Point) if vertices else None
+        tri = np.zeros(fcap, Face) if faces else None
+        q = np.zeros((self.h, self.w), np.uint8) if quad else None
+        nv, nf = C.c_uint(0), C.c_uint(0)
+        self._chk(self.L.cspm_mesh(self.p, int(view), int(source), C.byref(k), C.byref(g), C.byref(f) if f is not None else None, C.byref(m),
+                                   C.c_void_p(pts.ctypes.data) if vertices else None, vcap if vertices else 0,
+                                   C.c_void_p(tri.ctypes.data) if faces else None, fcap if faces else 0, _u8(q) if quad else None,
+                                   C.byref(nv), C.byref(nf)))
+        out = {"n_vertices": nv.value, "n_faces": nf.value}
+        if vertices:
+            out["vertices"] = pts[:min(nv.value, vcap)]
+        if faces:
+            out["faces"] = tri[:min(nf.value, fcap)]
+        if quad:
+            out["quad"] = q
+        return out
+
+    def mesh_device(self, view, calib, source=GEOM_RAW, fit=None, max_diff=1.0, all_vertices=0, d_vertices=0, vertex_cap=0, d_faces=0, face_cap=0,
+                    d_quad=0, d_n_vertices=0, d_n_faces=0, **params):
+        """the same with device pointers (integers; 0 = not requested) for every output and device unsigned ints for the two counts;
+        asynchronous on the context's stream (cspm_mesh_device)"""
+        k, g, m = calib_struct(calib), geom_params(**params), mesh_params(max_diff=max_diff, all_vertices=all_vertices)
+        f = fit_params(**dict(fit)) if fit is not None else None
+        vp = lambda a: C.c_void_p(a) if a else None
+        self._chk(self.L.cspm_mesh_device(self.p, int(view), int(source), C.byref(k), C.byref(g), C.byref(f) if f is not None else None, C.byref(m),
+                                          vp(d_vertices), int(vertex_cap), vp(d_faces), int(face_cap), vp(d_quad), vp(d_n_vertices), vp(d_n_faces)))
+
     # ---- view synthesis (DESIGN.md section 20) ----
     def synthesize(self, t, source=GEOM_RAW, outputs=("bgr", "disp", "mask"), out=None, **params):
         """the scene from the camera at fraction t of the baseline (0 = view 0, 1 = view 1), rendered from the stored plane field and the
@@ -942,6 +995,68 @@ def reproject_host(calib, view, disp, valid=None, slope_a=None, slope_b=None, bg
         res["count"] = cnt.value
     if pts is not None:
         res["cloud"] = pts[:min(cnt.value, cap)] if count else pts
+    return res
+
+
+def mesh_params(**params):
+    """struct cspm_mesh_params: cspm_mesh_default_params with the given fields replaced"""
+    p = MeshParams()
+    rc = load_library().cspm_mesh_default_params(C.byref(p))
+    assert rc == 0
+    for k, v in params.items():
+        if k not in ("max_diff", "all_vertices"):
+            raise TypeError(f"unknown mesh parameter {k!r}")
+        setattr(p, k, int(v) if k == "all_vertices" else float(v))
+    return p
+
+
+def mesh_host(calib, view, disp, valid=None, slope_a=None, slope_b=None, bgr=None, max_diff=1.0, all_vertices=0, vertices=True, faces=True, quad=True,
+              vertex_cap=None, face_cap=None, counts=True, device=0, out=None, **params):
+    """M alone on host maps (cspm_mesh_host): the inputs as for reproject_host; max_diff and all_vertices are the
+    cspm_mesh_params, params the reprojection parameters.  out: a dict of preallocated arrays ("vertex_buffer", "face_buffer", "quad")
+    to write into instead of fresh ones (tests poison them).  Returns a dict with n_vertices, n_faces (with counts) and the requested
+    vertices, faces and quad."""
+    L = load_library()
+    d = np.ascontiguousarray(disp, dtype=np.float64)
+    assert d.ndim == 2
+    h, w = d.shape
+    vm = None if valid is None else np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+    a = None if slope_a is None else np.ascontiguousarray(slope_a, dtype=np.float64)
+    b = None if slope_b is None else np.ascontiguousarray(slope_b, dtype=np.float64)
+    img = None if bgr is None else np.ascontiguousarray(bgr, dtype=np.uint8)
+    assert (vm is None or vm.shape == d.shape) and (a is None or a.shape == d.shape) and (b is None or b.shape == d.shape)
+    assert img is None or img.shape == (h, w, 3)
+    k, g, m = calib_struct(calib), geom_params(**params), mesh_params(max_diff=max_diff, all_vertices=all_vertices)
+    res = dict(out or {})
+    vcap = w * h if vertex_cap is None else int(vertex_cap)
+    fcap = 2 * (w - 1) * (h - 1) if face_cap is None else int(face_cap)
+    pts = tri = q = None
+    if vertices:
+        pts = res.get("vertex_buffer")
+        if pts is None:
+            pts = np.zeros(vcap, Point)
+    if faces:
+        tri = res.get("face_buffer")
+        if tri is None:
+            tri = np.zeros(fcap, Face)
+    if quad:
+        q = res.get("quad")
+        if q is None:
+            q = res["quad"] = np.zeros((h, w), np.uint8)
+    nv, nf = C.c_uint(0), C.c_uint(0)
+    rc = L.cspm_mesh_host(device, C.byref(k), C.byref(g), C.byref(m), int(view), _dp(d), _u8(vm) if vm is not None else None,
+                          _dp(a) if a is not None else None, _dp(b) if b is not None else None, _u8(img) if img is not None else None, w * 3, w, h,
+                          C.c_void_p(pts.ctypes.data) if pts is not None else None, vcap if pts is not None else 0,
+                          C.c_void_p(tri.ctypes.data) if tri is not None else None, fcap if tri is not None else 0, _u8(q) if q is not None else None,
+                          C.byref(nv) if counts else None, C.byref(nf) if counts else None)
+    if rc != 0:
+        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    if counts:
+        res["n_vertices"], res["n_faces"] = nv.value, nf.value
+    if pts is not None:
+        res["vertices"] = pts[:min(nv.value, vcap)] if counts else pts
+    if tri is not None:
+        res["faces"] = tri[:min(nf.value, fcap)] if counts else tri
     return res
 
 

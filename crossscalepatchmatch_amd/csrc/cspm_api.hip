@@ -18,6 +18,7 @@
 #include "cspm_fit.h"
 #include "cspm_seg.h"
 #include "cspm_geom.h"
+#include "cspm_mesh.h"
 #include "cspm_synth.h"
 #include "cspm_rect.h"
 #include "cspm_ca.h"
@@ -212,6 +213,8 @@ struct cspm_ctx {
   double *geom_disp = nullptr;        // cspm_reproject: the CSPM_GEOM_RAW disparity map (1 array); allocated by the first such call and kept with the field
   double *geom_fit = nullptr;         // cspm_reproject with a fit: the fitted planes (6 arrays) and, behind them, the exp(-k/10) table
   unsigned int *geom_counts = nullptr;  // cspm_reproject: the kept pixels per workgroup, then the total
+  uint8_t *mesh_bytes = nullptr;      // cspm_mesh: keep and Q (2 byte maps); allocated by the first such call and kept with the field
+  uint32_t *mesh_map = nullptr;       // cspm_mesh: the pixel -> vertex map, then the vertex and the face counts per workgroup, each with its total
   double *synth_disp = nullptr;       // cspm_synthesize: both views' CSPM_GEOM_RAW disparity maps (2 arrays); allocated by the first such call and kept with the field
   // rectification (cspm_set_rectification): kept until the context goes or the rectification is dropped
   bool rect_on = false;
@@ -385,6 +388,8 @@ void free_field(cspm_ctx *c) {
   dfree(c->geom_disp);
   dfree(c->geom_fit);
   dfree(c->geom_counts);
+  dfree(c->mesh_bytes);
+  dfree(c->mesh_map);
   dfree(c->synth_disp);
   dfree(c->vc.cost);
   dfree(c->vc.c);
@@ -1713,6 +1718,44 @@ void geom_launch(hipStream_t stream, const GeomCam &cam, const GeomIn &in, const
   else hipLaunchKernelGGL(k_geom_cloud<false>, dim3(nb), dim3(kGeomBlock), 0, stream, cam, in, w, n, (const unsigned int *)counts, cloud, cap32);
 }
 
+// the inputs of G on the stored field, shared by the reprojection and the mesh: geom_inputs_alloc before the timing bracket (scratch
+// and, for CSPM_GEOM_PP, the post-processing with its own brackets), geom_inputs_launch inside it.
+int geom_inputs_alloc(cspm_ctx *c, int source, const cspm_fit_params *fit) {
+  int rc = CSPM_OK;
+  const size_t n = (size_t)c->W * c->H;
+  if (source == CSPM_GEOM_RAW && !c->geom_disp && (rc = dalloc(c, &c->geom_disp, n, nullptr))) return rc;
+  if (fit && !c->geom_fit) {
+    if ((rc = dalloc(c, &c->geom_fit, 6 * n + kFitLut, nullptr))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->geom_fit + 6 * n, fit_lut(), sizeof(double) * kFitLut, hipMemcpyHostToDevice, c->stream));
+  }
+  if (source == CSPM_GEOM_PP && (rc = postprocess_f64_enqueue(c))) return rc;
+  return CSPM_OK;
+}
+GeomIn geom_inputs_launch(cspm_ctx *c, int view, int source, const cspm_geom_params *g, const cspm_fit_params *fit) {
+  const size_t n = (size_t)c->W * c->H;
+  const Field &f = c->f[view];
+  GeomIn in{};
+  in.pix = c->img0[view];
+  if (source == CSPM_GEOM_RAW) {
+    hipLaunchKernelGGL(k_plane_to_disp_f64, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, field_pm(c), view, c->geom_disp);
+    in.disp = c->geom_disp;
+    in.a = f.a; in.b = f.b;
+  } else {
+    in.disp = c->d_pp[view];
+    in.valid = g->consistent_only ? c->d_valid[view] : nullptr;
+    in.a = f.a; in.b = f.b;
+    in.slope_mask = c->d_valid[view];
+  }
+  if (fit) {
+    double *b = c->geom_fit;
+    fit_launch(c->stream, FitIn{in.disp, in.valid, c->img0[view], c->geom_fit + 6 * n}, FitOut{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, nullptr, 0},
+               c->W, c->H, fit, c->max_dis);
+    in.a = b + 3 * n; in.b = b + 4 * n;
+    in.slope_mask = nullptr;
+  }
+  return in;
+}
+
 // cspm_reproject / cspm_reproject_device after their argument checks: the pending-run check, the inputs of the chosen source, the
 // passes.  Every output is a device pointer; d_total == nullptr: the total goes behind the context's counts.
 int reproject_enqueue(cspm_ctx *c, int view, int source, const cspm_calib *calib, const cspm_geom_params *g, const cspm_fit_params *fit, const GeomOut &out,
@@ -1722,34 +1765,10 @@ int reproject_enqueue(cspm_ctx *c, int view, int source, const cspm_calib *calib
   const size_t n = (size_t)c->W * c->H;
   const unsigned nb = geom_blocks((long long)n);
   if (!c->geom_counts && (rc = dalloc(c, &c->geom_counts, (size_t)nb + 1, nullptr))) return rc;
-  if (source == CSPM_GEOM_RAW && !c->geom_disp && (rc = dalloc(c, &c->geom_disp, n, nullptr))) return rc;
-  if (fit && !c->geom_fit) {
-    if ((rc = dalloc(c, &c->geom_fit, 6 * n + kFitLut, nullptr))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->geom_fit + 6 * n, fit_lut(), sizeof(double) * kFitLut, hipMemcpyHostToDevice, c->stream));
-  }
-  if (source == CSPM_GEOM_PP && (rc = postprocess_f64_enqueue(c))) return rc;
-  const Field &f = c->f[view];
-  GeomIn in{};
-  in.pix = c->img0[view];
+  if ((rc = geom_inputs_alloc(c, source, fit))) return rc;
   {
     Timed t(c, CSPM_K_MISC, (long long)n);
-    if (source == CSPM_GEOM_RAW) {
-      hipLaunchKernelGGL(k_plane_to_disp_f64, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, field_pm(c), view, c->geom_disp);
-      in.disp = c->geom_disp;
-      in.a = f.a; in.b = f.b;
-    } else {
-      in.disp = c->d_pp[view];
-      in.valid = g->consistent_only ? c->d_valid[view] : nullptr;
-      in.a = f.a; in.b = f.b;
-      in.slope_mask = c->d_valid[view];
-    }
-    if (fit) {
-      double *b = c->geom_fit;
-      fit_launch(c->stream, FitIn{in.disp, in.valid, c->img0[view], c->geom_fit + 6 * n}, FitOut{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, nullptr, 0},
-                 c->W, c->H, fit, c->max_dis);
-      in.a = b + 3 * n; in.b = b + 4 * n;
-      in.slope_mask = nullptr;
-    }
+    const GeomIn in = geom_inputs_launch(c, view, source, g, fit);
     geom_launch(c->stream, geom_cam(calib, g, view), in, out, c->W, c->H, cloud, cap, want_count, c->geom_counts, d_total);
   }
   HIPCHK(c, hipGetLastError());
@@ -1768,6 +1787,75 @@ int reproject_check(cspm_ctx *c, int view, int source, const cspm_calib *calib, 
     return fail(c, CSPM_ERR_STATE, "reprojection of the post-processed map or with a plane fit needs a cost object (its max_dis)");
   if ((long long)c->W * c->H >= (1LL << 31)) return fail(c, CSPM_ERR_ARG, "w * h must be below 2^31: cloud records hold 32-bit pixel indices");
   if (fit && c->H > kFitMaxRows) return fail(c, CSPM_ERR_ARG, "image too high for the plane fit");
+  return CSPM_OK;
+}
+
+// ---- triangle meshes (cspm_mesh.h) ------------------------------------------------------------------------
+static_assert(sizeof(cspm_face) == 12, "cspm_face is one 12-byte record");
+const cspm_mesh_params kMeshDefaults = {1.0, 0};
+const char *mesh_args_error(const cspm_mesh_params *m) {
+  if (!(m->max_diff >= 0.0)) return "mesh: max_diff must be >= 0 (it may be +infinity)";
+  return nullptr;
+}
+inline size_t mesh_max_faces(int w, int h) { return 2 * (size_t)(w - 1) * (size_t)(h - 1); }
+// the unsigned ints behind the pixel -> vertex map: vertex counts per workgroup and their total, then the same for the faces
+inline size_t mesh_count_words(unsigned nb) { return 2 * ((size_t)nb + 1); }
+// the passes of M on one view.  maps: keep, Q and the vertex map; counts: mesh_count_words(nb) unsigned ints; the totals go behind
+// their count arrays unless d_nv / d_nf name another place.
+void mesh_launch(hipStream_t stream, const GeomCam &cam, const GeomIn &in, const cspm_mesh_params *m, int w, int h, const MeshMaps &maps, unsigned int *counts,
+                 uint4 *vertices, size_t vertex_cap, uint32_t *faces, size_t face_cap, unsigned int *d_nv, unsigned int *d_nf) {
+  const long long n = (long long)w * h;
+  const unsigned nb = geom_blocks(n);
+  const bool slopes = in.a != nullptr;
+  const int all = m->all_vertices ? 1 : 0;
+  unsigned int *vcounts = counts, *fcounts = counts + nb + 1;
+  const GeomOut keep_only{nullptr, nullptr, nullptr, maps.keep};
+  if (slopes) hipLaunchKernelGGL(k_geom_dense<true>, dim3(nb), dim3(kGeomBlock), 0, stream, cam, in, keep_only, w, n, (unsigned int *)nullptr);
+  else hipLaunchKernelGGL(k_geom_dense<false>, dim3(nb), dim3(kGeomBlock), 0, stream, cam, in, keep_only, w, n, (unsigned int *)nullptr);
+  if (slopes) hipLaunchKernelGGL(k_mesh_quad<true>, dim3(nb), dim3(kGeomBlock), 0, stream, in, (const uint8_t *)maps.keep, w, h, n, m->max_diff, maps.quad, fcounts);
+  else hipLaunchKernelGGL(k_mesh_quad<false>, dim3(nb), dim3(kGeomBlock), 0, stream, in, (const uint8_t *)maps.keep, w, h, n, m->max_diff, maps.quad, fcounts);
+  hipLaunchKernelGGL(k_mesh_use, dim3(nb), dim3(kGeomBlock), 0, stream, (const uint8_t *)maps.keep, (const uint8_t *)maps.quad, w, n, all, vcounts);
+  hipLaunchKernelGGL(k_geom_scan, dim3(1), dim3(kGeomScanBlock), 0, stream, vcounts, (int)nb, d_nv ? d_nv : vcounts + nb);
+  hipLaunchKernelGGL(k_geom_scan, dim3(1), dim3(kGeomScanBlock), 0, stream, fcounts, (int)nb, d_nf ? d_nf : fcounts + nb);
+  const unsigned int vcap = vertices ? (unsigned int)std::min<size_t>(vertex_cap, (size_t)n) : 0u;
+  const unsigned int fcap = faces ? (unsigned int)std::min<size_t>(face_cap, mesh_max_faces(w, h)) : 0u;
+  if (vcap == 0 && fcap == 0) return;  // the counts alone; faces need the map of the vertex pass
+  uint4 *vout = vcap ? vertices : nullptr;
+  if (slopes)
+    hipLaunchKernelGGL(k_mesh_vertex<true>, dim3(nb), dim3(kGeomBlock), 0, stream, cam, in, (const uint8_t *)maps.keep, (const uint8_t *)maps.quad, w, n, all,
+                       (const unsigned int *)vcounts, maps.vmap, vout, vcap);
+  else
+    hipLaunchKernelGGL(k_mesh_vertex<false>, dim3(nb), dim3(kGeomBlock), 0, stream, cam, in, (const uint8_t *)maps.keep, (const uint8_t *)maps.quad, w, n, all,
+                       (const unsigned int *)vcounts, maps.vmap, vout, vcap);
+  if (fcap == 0) return;
+  hipLaunchKernelGGL(k_mesh_face, dim3(nb), dim3(kGeomBlock), 0, stream, (const uint8_t *)maps.quad, (const uint32_t *)maps.vmap, w, n,
+                     (const unsigned int *)fcounts, faces, fcap);
+}
+
+// the checks cspm_mesh and cspm_mesh_device share: those of the reprojection, then the mesh parameters
+int mesh_check(cspm_ctx *c, int view, int source, const cspm_calib *calib, const cspm_geom_params **g, const cspm_fit_params *fit, const cspm_mesh_params **m) {
+  if (!*m) *m = &kMeshDefaults;
+  if (const char *msg = mesh_args_error(*m)) return fail(c, CSPM_ERR_ARG, msg);
+  return reproject_check(c, view, source, calib, g, fit);
+}
+// cspm_mesh / cspm_mesh_device after their checks: the pending-run check, the inputs of the chosen source by the reprojection's own
+// code, the passes.  Every output is a device pointer; d_quad == nullptr: Q stays in the context's scratch.
+int mesh_enqueue(cspm_ctx *c, int view, int source, const cspm_calib *calib, const cspm_geom_params *g, const cspm_fit_params *fit, const cspm_mesh_params *m,
+                 uint4 *vertices, size_t vertex_cap, uint32_t *faces, size_t face_cap, uint8_t *d_quad, unsigned int *d_nv, unsigned int *d_nf) {
+  int rc = check_sweep(c);  // BEFORE the field is read, as in reproject_enqueue
+  if (rc) return rc;
+  const size_t n = (size_t)c->W * c->H;
+  const unsigned nb = geom_blocks((long long)n);
+  if (!c->mesh_bytes && (rc = dalloc(c, &c->mesh_bytes, 2 * n, nullptr))) return rc;
+  if (!c->mesh_map && (rc = dalloc(c, &c->mesh_map, n + mesh_count_words(nb), nullptr))) return rc;
+  if ((rc = geom_inputs_alloc(c, source, fit))) return rc;
+  {
+    Timed t(c, CSPM_K_MISC, (long long)n);
+    const GeomIn in = geom_inputs_launch(c, view, source, g, fit);
+    const MeshMaps maps{c->mesh_bytes, d_quad ? d_quad : c->mesh_bytes + n, c->mesh_map};
+    mesh_launch(c->stream, geom_cam(calib, g, view), in, m, c->W, c->H, maps, c->mesh_map + n, vertices, vertex_cap, faces, face_cap, d_nv, d_nf);
+  }
+  HIPCHK(c, hipGetLastError());
   return CSPM_OK;
 }
 
@@ -3403,6 +3491,115 @@ int cspm_reproject_device(cspm_ctx *c, int view, int source, const cspm_calib *c
   ON_DEVICE(c);
   return reproject_enqueue(c, view, source, calib, g, fit, GeomOut{(double *)d_depth_out, (double *)d_xyz_out, (double *)d_normal_out, (uint8_t *)d_keep_out},
                            (uint4 *)d_cloud_out, d_cloud_out ? cloud_cap : 0, d_count_out != nullptr || d_cloud_out != nullptr, (unsigned int *)d_count_out);
+}
+
+// M alone on caller maps: the launches cspm_mesh enqueues, on one view.  Arguments first, then the device.
+int cspm_mesh_default_params(cspm_mesh_params *p) {
+  if (!p) return CSPM_ERR_ARG;
+  *p = kMeshDefaults;
+  return CSPM_OK;
+}
+
+int cspm_mesh_host(int device, const cspm_calib *calib, const cspm_geom_params *g, const cspm_mesh_params *m, int view, const double *disp, const uint8_t *valid,
+                   const double *slope_a, const double *slope_b, const uint8_t *bgr, size_t bgr_stride, int w, int h, cspm_point *vertices_out, size_t vertex_cap,
+                   cspm_face *faces_out, size_t face_cap, uint8_t *quad_out, unsigned int *n_vertices_out, unsigned int *n_faces_out) {
+  if (!g) g = &kGeomDefaults;
+  if (!m) m = &kMeshDefaults;
+  if (const char *msg = geom_args_error(calib, g, view)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (const char *msg = mesh_args_error(m)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (!disp || w < 1 || h < 1) return fail(nullptr, CSPM_ERR_ARG, "mesh: no disparity map or an empty one");
+  if ((long long)w * h >= (1LL << 31)) return fail(nullptr, CSPM_ERR_ARG, "w * h must be below 2^31: vertex records hold 32-bit pixel indices");
+  if ((slope_a == nullptr) != (slope_b == nullptr)) return fail(nullptr, CSPM_ERR_ARG, "mesh: the two slope maps come together or not at all");
+  if (bgr && bgr_stride < (size_t)w * 3) return fail(nullptr, CSPM_ERR_ARG, "mesh: bgr_stride is below 3 * w");
+  Scratch S;
+  int rc = cspm_create(&S.c, device);
+  if (rc) return rc;
+  cspm_ctx *c = S.c;
+  const size_t n = (size_t)w * h;
+  const unsigned nb = geom_blocks((long long)n);
+  const size_t vcap = std::min(vertices_out ? vertex_cap : (size_t)0, n), fcap = std::min(faces_out ? face_cap : (size_t)0, mesh_max_faces(w, h));
+  double *dd = nullptr, *da = nullptr, *db = nullptr;
+  uint8_t *dv = nullptr, *dbgr = nullptr, *dbytes = nullptr;
+  uint32_t *dpix = nullptr, *dmap = nullptr, *dfaces = nullptr;
+  uint4 *dverts = nullptr;
+  if ((rc = dalloc(c, &dd, n, &S.tmp)) || (rc = dalloc(c, &dbytes, 2 * n, &S.tmp)) || (rc = dalloc(c, &dmap, n + mesh_count_words(nb), &S.tmp)) ||
+      (valid && (rc = dalloc(c, &dv, n, &S.tmp))) || (slope_a && ((rc = dalloc(c, &da, n, &S.tmp)) || (rc = dalloc(c, &db, n, &S.tmp)))) ||
+      (bgr && ((rc = dalloc(c, &dbgr, 3 * n, &S.tmp)) || (rc = dalloc(c, &dpix, n, &S.tmp)))) || (vcap && (rc = dalloc(c, &dverts, 2 * vcap, &S.tmp))) ||
+      (fcap && (rc = dalloc(c, &dfaces, 3 * fcap, &S.tmp))))
+    return S.done(rc);
+  if (hipMemcpyAsync(dd, disp, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      (valid && hipMemcpyAsync(dv, valid, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
+      (slope_a && (hipMemcpyAsync(da, slope_a, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+                   hipMemcpyAsync(db, slope_b, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess)) ||
+      (bgr && hipMemcpy2DAsync(dbgr, (size_t)w * 3, bgr, bgr_stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->stream) != hipSuccess))
+    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  if (bgr) hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, dbgr, (size_t)w * 3, w, h, w, 0, dpix);
+  unsigned int *dcounts = dmap + n;
+  mesh_launch(c->stream, geom_cam(calib, g, view), GeomIn{dd, dv, da, db, nullptr, dpix}, m, w, h, MeshMaps{dbytes, dbytes + n, dmap}, dcounts, dverts, vcap,
+              dfaces, fcap, nullptr, nullptr);
+  unsigned int nv = 0, nf = 0;
+  if (hipGetLastError() != hipSuccess || (quad_out && hipMemcpyAsync(quad_out, dbytes + n, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
+      hipMemcpyAsync(&nv, dcounts + nb, sizeof nv, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipMemcpyAsync(&nf, dcounts + 2 * (size_t)nb + 1, sizeof nf, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+      hipStreamSynchronize(c->stream) != hipSuccess)
+    return S.done(fail(c, CSPM_ERR_HIP, "mesh kernels failed"));
+  const size_t wrote_v = std::min((size_t)nv, vcap), wrote_f = std::min((size_t)nf, fcap);
+  if ((wrote_v && hipMemcpy(vertices_out, dverts, sizeof(cspm_point) * wrote_v, hipMemcpyDeviceToHost) != hipSuccess) ||
+      (wrote_f && hipMemcpy(faces_out, dfaces, sizeof(cspm_face) * wrote_f, hipMemcpyDeviceToHost) != hipSuccess))
+    return S.done(fail(c, CSPM_ERR_HIP, "mesh download failed"));
+  if (n_vertices_out) *n_vertices_out = nv;
+  if (n_faces_out) *n_faces_out = nf;
+  return S.done(CSPM_OK);
+}
+
+// M on one view of the stored field (cspm.h "triangle meshes"): synchronous, host outputs
+int cspm_mesh(cspm_ctx *c, int view, int source, const cspm_calib *calib, const cspm_geom_params *g, const cspm_fit_params *fit, const cspm_mesh_params *m,
+              cspm_point *vertices_out, size_t vertex_cap, cspm_face *faces_out, size_t face_cap, uint8_t *quad_out, unsigned int *n_vertices_out,
+              unsigned int *n_faces_out) {
+  if (!c) return CSPM_ERR_ARG;
+  int rc = mesh_check(c, view, source, calib, &g, fit, &m);
+  if (rc) return rc;
+  ON_DEVICE(c);
+  const size_t n = (size_t)c->W * c->H;
+  const unsigned nb = geom_blocks((long long)n);
+  const size_t vcap = std::min(vertices_out ? vertex_cap : (size_t)0, n), fcap = std::min(faces_out ? face_cap : (size_t)0, mesh_max_faces(c->W, c->H));
+  std::vector<void *> tmp;
+  struct Free {
+    std::vector<void *> &t;
+    ~Free() { for (void *p : t) (void)hipFree(p); }
+  } free_tmp{tmp};
+  uint4 *dverts = nullptr;
+  uint32_t *dfaces = nullptr;
+  if ((vcap && (rc = dalloc(c, &dverts, 2 * vcap, &tmp))) || (fcap && (rc = dalloc(c, &dfaces, 3 * fcap, &tmp)))) return rc;
+  if ((rc = mesh_enqueue(c, view, source, calib, g, fit, m, dverts, vcap, dfaces, fcap, nullptr, nullptr, nullptr))) return rc;
+  unsigned int nv = 0, nf = 0;
+  const unsigned int *dcounts = c->mesh_map + n;
+  if (quad_out) HIPCHK(c, hipMemcpyAsync(quad_out, c->mesh_bytes + n, n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&nv, dcounts + nb, sizeof nv, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(&nf, dcounts + 2 * (size_t)nb + 1, sizeof nf, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const size_t wrote_v = std::min((size_t)nv, vcap), wrote_f = std::min((size_t)nf, fcap);
+  if (wrote_v) HIPCHK(c, hipMemcpy(vertices_out, dverts, sizeof(cspm_point) * wrote_v, hipMemcpyDeviceToHost));
+  if (wrote_f) HIPCHK(c, hipMemcpy(faces_out, dfaces, sizeof(cspm_face) * wrote_f, hipMemcpyDeviceToHost));
+  if (n_vertices_out) *n_vertices_out = nv;
+  if (n_faces_out) *n_faces_out = nf;
+  return CSPM_OK;
+}
+
+// the same with device-resident outputs: asynchronous on the ctx stream behind the pending-run check; not replayed (cspm.h)
+int cspm_mesh_device(cspm_ctx *c, int view, int source, const cspm_calib *calib, const cspm_geom_params *g, const cspm_fit_params *fit,
+                     const cspm_mesh_params *m, void *d_vertices_out, size_t vertex_cap, void *d_faces_out, size_t face_cap, void *d_quad_out,
+                     void *d_n_vertices_out, void *d_n_faces_out) {
+  if (!c) return CSPM_ERR_ARG;
+  int rc = mesh_check(c, view, source, calib, &g, fit, &m);
+  if (rc) return rc;
+  if (d_vertices_out && ((uintptr_t)d_vertices_out & 15u)) return fail(c, CSPM_ERR_ARG, "mesh: the vertex buffer must be 16-byte aligned");
+  if (d_faces_out && ((uintptr_t)d_faces_out & 3u)) return fail(c, CSPM_ERR_ARG, "mesh: the face buffer must be 4-byte aligned");
+  if ((d_n_vertices_out && ((uintptr_t)d_n_vertices_out & 3u)) || (d_n_faces_out && ((uintptr_t)d_n_faces_out & 3u)))
+    return fail(c, CSPM_ERR_ARG, "mesh: the counts must be 4-byte aligned");
+  ON_DEVICE(c);
+  return mesh_enqueue(c, view, source, calib, g, fit, m, (uint4 *)d_vertices_out, d_vertices_out ? vertex_cap : 0, (uint32_t *)d_faces_out,
+                      d_faces_out ? face_cap : 0, (uint8_t *)d_quad_out, (unsigned int *)d_n_vertices_out, (unsigned int *)d_n_faces_out);
 }
 
 // N alone on caller maps: the launch cspm_synthesize enqueues.  Arguments first, then the device.

@@ -115,6 +115,11 @@ class CSPatchMatch {
   size_t Reproject(const RefView &view, const cspm_calib &calib, const cspm_geom_params &params, int source, const cspm_fit_params *fit,
                    std::vector<double> *depth, std::vector<double> *xyz, std::vector<double> *normal, std::vector<uint8_t> *keep,
                    std::vector<cspm_point> *cloud) const;
+  // a triangle mesh of a view's final plane field (an addition; include/cspm.h "triangle meshes", cspm_mesh): view, calib, params, source
+  // and fit as for Reproject.  vertices: the mesh's cspm_point records in raster order; faces: their vertex numbers; quad: wid x hei quad
+  // bytes.  Every output may be NULL.  Returns the number of faces; throws for what the C ABI refuses.
+  size_t Mesh(const RefView &view, const cspm_calib &calib, const cspm_geom_params &params, const cspm_mesh_params &mesh_params, int source,
+              const cspm_fit_params *fit, std::vector<cspm_point> *vertices, std::vector<cspm_face> *faces, std::vector<uint8_t> *quad) const;
   // view synthesis (cspm.h "view synthesis"): the scene from the camera at fraction t of the baseline (0 = the left
   // view, 1 = the right one), rendered from the stored plane field and the two images.  source as for Reproject.  bgr: a wid x hei 8UC3
   // image; disp: wid x hei row-major, NaN in holes; mask: wid x hei bytes, 0 hole, 1 / 2 one view, 3 both, 4 filled.  Every output may be

@@ -651,6 +651,24 @@ size_t CSPatchMatch::Reproject(const RefView &view, const cspm_calib &calib, con
   return count;
 }
 
+size_t CSPatchMatch::Mesh(const RefView &view, const cspm_calib &calib, const cspm_geom_params &params, const cspm_mesh_params &mesh_params, int source,
+                          const cspm_fit_params *fit, std::vector<cspm_point> *vertices, std::vector<cspm_face> *faces, std::vector<uint8_t> *quad) const {
+  if (!last_ctx_) throw std::runtime_error("CSPatchMatch::Mesh before PatchMatch");
+  if (!DevicePlaneCost::is_live(last_ctx_)) throw std::runtime_error("CSPatchMatch::Mesh: the plane cost PatchMatch ran on has been deleted");
+  const size_t n = (size_t)wid_ * hei_, max_faces = 2 * (size_t)(wid_ - 1) * (size_t)(hei_ - 1);
+  if (vertices) vertices->resize(n);
+  if (faces) faces->resize(max_faces);
+  if (quad) quad->resize(n);
+  if (source == CSPM_GEOM_PP) ApplyPostFilters(last_ctx_);
+  unsigned int nv = 0, nf = 0;
+  check(cspm_mesh(last_ctx_, view, source, &calib, &params, fit, &mesh_params, vertices ? vertices->data() : NULL, vertices ? n : 0,
+                  faces ? faces->data() : NULL, faces ? max_faces : 0, quad ? quad->data() : NULL, &nv, &nf),
+        last_ctx_, "cspm_mesh");
+  if (vertices) vertices->resize(nv);
+  if (faces) faces->resize(nf);
+  return nf;
+}
+
 void CSPatchMatch::Synthesize(double t, const cspm_synth_params &params, int source, Mat *bgr, std::vector<double> *disp, std::vector<uint8_t> *mask) const {
   if (!last_ctx_) throw std::runtime_error("CSPatchMatch::Synthesize before PatchMatch");
   if (!DevicePlaneCost::is_live(last_ctx_)) throw std::runtime_error("CSPatchMatch::Synthesize: the plane cost PatchMatch ran on has been deleted");

@@ -7,7 +7,8 @@
 // --seg_step --seg_compactness --seg_iters --seg_tau --seg_rounds --seg_warm_iters (one robust plane per superpixel of the field after the
 // --iters iterations, merged where it costs less, then warm iterations; include/cspm.h "segment planes")
 // --calib --l_ply --r_ply --l_depth_pfm --r_depth_pfm --geom_min_cos --geom_z_far --geom_left_frame --geom_fit_radius (metric depth maps and
-// point clouds of the final plane field; include/cspm.h "reprojection") --synth_t --synth_png --synth_dis_pfm --synth_views --synth_max_stretch
+// point clouds of the final plane field; include/cspm.h "reprojection") --l_mesh_ply --r_mesh_ply --mesh_max_diff --mesh_all_vertices
+// (triangle meshes of the final plane field; include/cspm.h "triangle meshes") --synth_t --synth_png --synth_dis_pfm --synth_views --synth_max_stretch
 // --synth_merge_diff --synth_fill (the scene rendered from a camera between the two views; include/cspm.h "view synthesis")
 // --rig --rect_f --rect_w --rect_h --l_rect_file --r_rect_file (the inputs are RAW photographs of a calibrated rig, undistorted and
 // row-aligned on the device before matching; include/cspm.h "rectification").
@@ -117,6 +118,12 @@ DEFINE_string(r_rect_file, "", "with --rig: also write the rectified right image
 DEFINE_string(r_ply, "", "the same for the right view, in its own camera frame unless --geom_left_frame");
 DEFINE_string(l_depth_pfm, "", "write the left view's metric depth Z as float32 PFM, NaN where there is none (see --l_ply)");
 DEFINE_string(r_depth_pfm, "", "the same for the right view");
+DEFINE_string(l_mesh_ply, "", "write the left view's triangle mesh (binary little-endian PLY: the vertices of --l_ply, then the faces as vertex_indices "
+                              "lists) from the final plane field (include/cspm.h \"triangle meshes\"): neighbouring pixels are connected where each one's "
+                              "plane predicts the other's disparity.  Honours --use_pp and the --geom_* flags.  Needs --calib or --rig; not with --batch_list");
+DEFINE_string(r_mesh_ply, "", "the same for the right view, in its own camera frame unless --geom_left_frame");
+DEFINE_double(mesh_max_diff, 1.0, "meshes: connect two neighbouring pixels when each one's plane predicts the other's disparity to within this (>= 0)");
+DEFINE_bool(mesh_all_vertices, false, "meshes: every point of the cloud is a vertex, not only the corners of the triangles");
 DEFINE_double(geom_min_cos, 0.0, "point clouds: drop a pixel whose surface normal makes a smaller cosine than this with its view ray (0 .. 1; 0 = keep all)");
 DEFINE_double(geom_z_far, 0.0, "point clouds and depth maps: no point beyond this depth (0 = no limit)");
 DEFINE_bool(geom_left_frame, false, "the right view's points are given in the left camera's frame (X + baseline)");
@@ -171,6 +178,8 @@ struct PairRun {
   std::vector<double> pfm[kViewNum];
   std::vector<double> depth[kViewNum];      // --l_depth_pfm / --r_depth_pfm
   std::vector<cspm_point> cloud[kViewNum];  // --l_ply / --r_ply
+  std::vector<cspm_point> mesh_v[kViewNum];  // --l_mesh_ply / --r_mesh_ply
+  std::vector<cspm_face> mesh_f[kViewNum];
   Mat synth;                      // --synth_png
   std::vector<double> synth_dis;  // --synth_dis_pfm
   cspm_calib calib;
@@ -296,8 +305,9 @@ void finish(PairRun &p) {
           if (!pfm[v]->empty()) p.matcher->disparity(v == 0 ? kLeft : kRight, &p.pfm[v]);  // reads the cost object's context: before it goes
       }
       const string *ply[kViewNum] = {&FLAGS_l_ply, &FLAGS_r_ply}, *dpfm[kViewNum] = {&FLAGS_l_depth_pfm, &FLAGS_r_depth_pfm};
+      const string *mply[kViewNum] = {&FLAGS_l_mesh_ply, &FLAGS_r_mesh_ply};
       for (int v = 0; v < kViewNum; ++v) {  // reads the cost object's context: before it goes
-        if (ply[v]->empty() && dpfm[v]->empty()) continue;
+        if (ply[v]->empty() && dpfm[v]->empty() && mply[v]->empty()) continue;
         cspm_geom_params g;
         cspm_geom_default_params(&g);
         g.min_cos = FLAGS_geom_min_cos;
@@ -306,6 +316,19 @@ void finish(PairRun &p) {
         cspm_fit_params fit;
         cspm_fit_default_params(&fit);
         fit.radius = FLAGS_geom_fit_radius;
+        if (!mply[v]->empty()) {
+          cspm_mesh_params mp;
+          cspm_mesh_default_params(&mp);
+          mp.max_diff = FLAGS_mesh_max_diff;
+          mp.all_vertices = FLAGS_mesh_all_vertices ? 1 : 0;
+          const double m0 = static_cast<double>(getTickCount());
+          p.matcher->Mesh(v == 0 ? kLeft : kRight, p.calib, g, mp, FLAGS_use_pp ? CSPM_GEOM_PP : CSPM_GEOM_RAW, FLAGS_geom_fit_radius != 0 ? &fit : NULL,
+                          &p.mesh_v[v], &p.mesh_f[v], NULL);
+          if (!FLAGS_quiet)
+            p.log << "Mesh, view " << v << ": " << p.mesh_v[v].size() << " vertices, " << p.mesh_f[v].size() << " faces, "
+                  << (static_cast<double>(getTickCount()) - m0) / getTickFrequency() * 1e3 << " ms\n";
+        }
+        if (ply[v]->empty() && dpfm[v]->empty()) continue;
         const double g0 = static_cast<double>(getTickCount());
         const size_t count = p.matcher->Reproject(v == 0 ? kLeft : kRight, p.calib, g, FLAGS_use_pp ? CSPM_GEOM_PP : CSPM_GEOM_RAW,
                                                   FLAGS_geom_fit_radius != 0 ? &fit : NULL, dpfm[v]->empty() ? NULL : &p.depth[v], NULL, NULL, NULL,
@@ -345,6 +368,8 @@ void write(PairRun &p) {
   for (int v = 0; v < kViewNum && written; ++v) {
     if (!dpfm[v]->empty()) written = WritePFM(*dpfm[v], p.depth[v].data(), p.left.cols, p.left.rows);
     if (written && !ply[v]->empty()) written = WritePLY(*ply[v], p.cloud[v].data(), p.cloud[v].size());
+    const string &mply = v == 0 ? FLAGS_l_mesh_ply : FLAGS_r_mesh_ply;
+    if (written && !mply.empty()) written = WritePLYMesh(mply, p.mesh_v[v].data(), p.mesh_v[v].size(), p.mesh_f[v].data(), p.mesh_f[v].size());
   }
   if (written && g_rectify && !FLAGS_l_rect_file.empty()) written = imwrite(FLAGS_l_rect_file, p.left);
   if (written && g_rectify && !FLAGS_r_rect_file.empty()) written = imwrite(FLAGS_r_rect_file, p.right);
@@ -570,7 +595,8 @@ int run() {
     cout << "Error: --ca_name aggregates cost volumes; --pc_name=IMG (GrdPC / CSPC) has none\n";
     return EXIT_FAILURE;
   }
-  const bool geom_out = !FLAGS_l_ply.empty() || !FLAGS_r_ply.empty() || !FLAGS_l_depth_pfm.empty() || !FLAGS_r_depth_pfm.empty();
+  const bool mesh_out = !FLAGS_l_mesh_ply.empty() || !FLAGS_r_mesh_ply.empty();
+  const bool geom_out = !FLAGS_l_ply.empty() || !FLAGS_r_ply.empty() || !FLAGS_l_depth_pfm.empty() || !FLAGS_r_depth_pfm.empty() || mesh_out;
   if (!FLAGS_rig.empty() && !FLAGS_calib.empty()) {  // checked before anything opens a device
     cout << "Error: --rig derives the calibration of the rectified pair itself: not with --calib\n";
     return EXIT_FAILURE;
@@ -592,15 +618,19 @@ int run() {
     return EXIT_FAILURE;
   }
   if (geom_out && FLAGS_calib.empty() && FLAGS_rig.empty()) {
-    cout << "Error: --l_ply / --r_ply / --l_depth_pfm / --r_depth_pfm need --calib or --rig\n";
+    cout << "Error: --l_ply / --r_ply / --l_depth_pfm / --r_depth_pfm / --l_mesh_ply / --r_mesh_ply need --calib or --rig\n";
     return EXIT_FAILURE;
   }
   if ((geom_out || !FLAGS_calib.empty()) && !FLAGS_batch_list.empty()) {
-    cout << "Error: --calib and the point-cloud and depth outputs belong to one pair: not with --batch_list\n";
+    cout << "Error: --calib and the point-cloud, depth and mesh outputs belong to one pair: not with --batch_list\n";
     return EXIT_FAILURE;
   }
   if (!(FLAGS_geom_min_cos >= 0.0 && FLAGS_geom_min_cos <= 1.0) || !(FLAGS_geom_z_far >= 0.0) || FLAGS_geom_fit_radius < 0 || FLAGS_geom_fit_radius > 17) {
     cout << "Error: --geom_min_cos must be 0 .. 1, --geom_z_far >= 0 (0 = no limit) and --geom_fit_radius 0 .. 17\n";
+    return EXIT_FAILURE;
+  }
+  if (!(FLAGS_mesh_max_diff >= 0.0)) {
+    cout << "Error: --mesh_max_diff must be >= 0\n";
     return EXIT_FAILURE;
   }
   if (geom_out && FLAGS_pc_name != "PRE" && FLAGS_pc_name != "IMG") {

@@ -631,6 +631,71 @@ int cspm_reproject_device(cspm_ctx *ctx, int view, int source, const cspm_calib 
                           const cspm_fit_params *fit, void *d_depth_out, void *d_xyz_out, void *d_normal_out, void *d_keep_out, void *d_cloud_out,
                           size_t cloud_cap, void *d_count_out);
 
+/* ---- triangle meshes (an addition): a surface from one view's plane field --------------------------------------------
+ * Neighbouring pixels are connected when each one's plane predicts the other's disparity, so a steep surface stays whole where the plain
+ * difference test |D_p - D_q| <= tau tears it, and a real step is cut where a larger tau would bridge it.
+ * M(calib, geom params, mesh params, view v, D, V, A, Bs, I): the inputs of one view are exactly those of G above, and
+ * cspm_mesh_params { max_diff (tau), all_vertices }.  Every operation is one IEEE f64 operation in the association written here, nothing
+ * contracted.
+ * Candidate vertices: K(p) = G's keep of pixel p; a vertex sits at the pixel's point (X, Y, Z) of G with G's normal.
+ * Slopes of the edge test: (a_p, b_p) = the pixel's (A, Bs) when both are finite, else (0, 0) (no slope maps, a slope mask of 0 on the
+ * CSPM_GEOM_PP source, NaN or infinite slopes).
+ * Edge predicate, for two kept pixels s, t at most one pixel apart in x and in y:
+ *     pred(s,t) = (D_s + a_s * (double)(x_t - x_s)) + b_s * (double)(y_t - y_s)
+ *     E(s,t)    = fabs(pred(s,t) - D_t) <= tau  &&  fabs(pred(t,s) - D_s) <= tau
+ * E is symmetric and depends on the two end points only: an edge shared by two quads gets one answer.
+ * Quads: one at every origin (x, y), 0 <= x < w-1, 0 <= y < h-1, with corners p00 = (x,y), p10 = (x+1,y), p01 = (x,y+1), p11 = (x+1,y+1):
+ *     main_ok = K(p00) && K(p11);   anti_ok = K(p10) && K(p01)
+ *     split = none   if !main_ok && !anti_ok
+ *           = main   if main_ok && !anti_ok
+ *           = anti   if anti_ok && !main_ok
+ *           = (fabs(D00 - D11) <= fabs(D10 - D01)) ? main : anti     otherwise (a tie takes main)
+ *     main:  T0 = (p00, p01, p11)   T1 = (p00, p11, p10)
+ *     anti:  T0 = (p00, p01, p10)   T1 = (p10, p01, p11)
+ * A triangle of the chosen split is emitted iff its three corners are kept and E holds on its three edges.  All four triangles have the
+ * same orientation in the image plane; seen from the camera (x right, y down) the corners run counter-clockwise, so that the geometric
+ * normal (P1 - P0) x (P2 - P0) faces the camera like G's normals.
+ * Quad byte Q(x,y): bit 0 = T0 is emitted, bit 1 = T1 is emitted, bit 2 = the split is anti; 0 in the last column, the last row and for
+ * split none.
+ * Vertices: pixel p is a vertex iff K(p) && (all_vertices || p is a corner of an emitted triangle); numbered in raster order (y outer, x
+ * inner); each one cspm_point built exactly as G's cloud record of that pixel (with all_vertices the vertices ARE G's cloud).
+ * Faces: one 12-byte cspm_face each, in raster order of the quad origin, T0 before T1; v[] = the vertex numbers of the corners in the order
+ * written above.
+ * Counts and capacities: *n_vertices and *n_faces are reported whatever the capacities; when a count exceeds its capacity the first `cap`
+ * records are written and the rest of the buffer is untouched.  Faces always carry full vertex numbers, so THE MESH IS COMPLETE ONLY WHEN
+ * BOTH COUNTS FIT: a face may then name a vertex beyond vertex_cap.  NULL buffers ask for the counts only; the count pointers may be NULL.
+ * w*h < 2^31.  An image with w == 1 or h == 1 has no quads and so no faces.
+ * Parameters (NULL = the defaults 1.0, 0): CSPM_ERR_ARG for a NaN or negative max_diff; +infinity is allowed. */
+typedef struct cspm_mesh_params {
+  double max_diff;  /* tau of the edge predicate, in disparity units */
+  int all_vertices; /* 1: every kept pixel is a vertex; 0: only the corners of emitted triangles */
+} cspm_mesh_params;
+typedef struct cspm_face {
+  uint32_t v[3];
+} cspm_face;
+int cspm_mesh_default_params(cspm_mesh_params *p);
+/* M alone on caller memory with a temporary context, synchronous; the inputs as for cspm_reproject_host.  quad_out: w*h bytes or NULL.
+ * Arguments are checked before a device is opened: CSPM_ERR_ARG for what cspm_reproject_host refuses in these inputs and for a bad
+ * max_diff. */
+int cspm_mesh_host(int device, const cspm_calib *calib, const cspm_geom_params *geom_params, const cspm_mesh_params *mesh_params, int view,
+                   const double *disp, const uint8_t *valid, const double *slope_a, const double *slope_b, const uint8_t *bgr, size_t bgr_stride,
+                   int w, int h, cspm_point *vertices_out, size_t vertex_cap, cspm_face *faces_out, size_t face_cap, uint8_t *quad_out,
+                   unsigned int *n_vertices_out, unsigned int *n_faces_out);
+/* M on one view of the context's stored plane field.  source, consistent_only and fit mean exactly what they mean in cspm_reproject, and
+ * the inputs are prepared by the same code; the same pending-run check is made before the field is read.  Synchronous; host outputs.
+ * Timed as one CSPM_K_MISC bracket per call with w*h evaluations (CSPM_GEOM_PP: behind the post-processing's own CSPM_K_POST brackets).
+ * Scratch (keep and Q bytes, a 32-bit pixel -> vertex map and two count arrays) is allocated on first use and freed with the plane field.
+ * The error classes of cspm_reproject, and CSPM_ERR_ARG for a bad max_diff. */
+int cspm_mesh(cspm_ctx *ctx, int view, int source, const cspm_calib *calib, const cspm_geom_params *geom_params, const cspm_fit_params *fit,
+              const cspm_mesh_params *mesh_params, cspm_point *vertices_out, size_t vertex_cap, cspm_face *faces_out, size_t face_cap,
+              uint8_t *quad_out, unsigned int *n_vertices_out, unsigned int *n_faces_out);
+/* the same with device pointers for every output (vertices 16-byte aligned, faces and the counts 4-byte aligned; the two counts are device
+ * unsigned ints).  Makes the same pending-run check on entry, then enqueues on the ctx stream and returns.  Like cspm_reproject_device
+ * it is NOT part of the deferred-output replay, for the reason given there. */
+int cspm_mesh_device(cspm_ctx *ctx, int view, int source, const cspm_calib *calib, const cspm_geom_params *geom_params, const cspm_fit_params *fit,
+                     const cspm_mesh_params *mesh_params, void *d_vertices_out, size_t vertex_cap, void *d_faces_out, size_t face_cap,
+                     void *d_quad_out, void *d_n_vertices_out, void *d_n_faces_out);
+
 /* ---- view synthesis (an addition): the scene rendered from a camera between (or at) the two views ----------------------
  * A rectified warp never leaves its image row, and a slanted plane says how one source pixel stretches or compresses in the target view,
  * so a surface is rasterised exactly, without cracks, instead of splatting rounded disparities.
