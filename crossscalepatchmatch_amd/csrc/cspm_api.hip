@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -37,7 +38,8 @@ struct TimingRec {
 
 }  // namespace
 
-// every extern "C" entry that touches HIP runs on the ctx's device and leaves the caller's current device as it found it
+// every extern "C" entry that touches HIP runs on the ctx's device (ON_DEVICE), a one-shot host entry on the device it names (OneShot),
+// and leaves the caller's current device as it found it
 struct DevGuard {
   int prev = -1;
   bool ok = true;
@@ -279,6 +281,21 @@ int dalloc(cspm_ctx *c, T **p, size_t n, std::vector<void *> *track) {
   *p = (T *)q;
   if (track) track->push_back(q);
   return CSPM_OK;
+}
+
+// the device temporaries of one call (dalloc(.., &tmp.ptrs)): freed when the scope ends, on every path.  Declared behind ON_DEVICE, so that
+// the frees run on the buffers' device
+struct DevBufs {
+  std::vector<void *> ptrs;
+  ~DevBufs() {
+    for (void *p : ptrs) (void)hipFree(p);
+  }
+};
+
+// channel-major planes (six slabs of n values, as the device holds a field) into the interleaved records of the ABI
+void interleave_planes(const double *planar, size_t n, double *np_out) {
+  for (size_t i = 0; i < n; ++i)
+    for (int k = 0; k < 6; ++k) np_out[6 * i + k] = planar[k * n + i];
 }
 
 hipEvent_t get_event(cspm_ctx *c) {
@@ -2171,6 +2188,81 @@ inline void rect_remap_launch(hipStream_t stream, const uint8_t *raw_bgr, size_t
                      raw_w, raw_h, w, h, dst, dst_stride);
 }
 
+// A one-shot host entry (cspm_*_host: one kernel family alone on caller memory) checks its arguments, then stages
+// its buffers on a OneShot, launches on S.c->stream, downloads and returns S.finish(..).  The OneShot is a temporary context on `device`
+// with device buffers of its own, and everything between its construction and its destruction runs on that device; the caller's current
+// device comes back when it goes.  The first failure sticks in `rc` and turns every later member call into a no-op (a null pointer), so a
+// body is straight-line code with one `if (S.rc) return S.finish();` before its launches.  The message of a failure stays behind as the
+// thread's creation error (cspm_last_error(NULL)).
+struct OneShot {
+  cspm_ctx *c = nullptr;
+  int rc;
+  std::optional<DevGuard> guard;
+  DevBufs bufs;
+  bool broke = false;  // a launch or a download failed: finish() names it
+
+  explicit OneShot(int device) : rc(cspm_create(&c, device)) {
+    if (rc) return;
+    guard.emplace(device);
+    if (!guard->ok) fail(CSPM_ERR_HIP, "hipSetDevice failed");
+  }
+  ~OneShot() { cspm_destroy(c); }  // waits for the stream; then the buffers go, then the guard
+
+  int fail(int code, const char *msg) {
+    if (!rc) rc = ::fail(c, code, msg);
+    return rc;
+  }
+  // n elements on the device; null when !want
+  template <class T>
+  T *buf(size_t n, bool want = true) {
+    T *p = nullptr;
+    if (!rc && want) rc = dalloc(c, &p, n, &bufs.ptrs);
+    return p;
+  }
+  template <class T>
+  void put(T *dev, const T *host, size_t n) {
+    if (!rc && hipMemcpyAsync(dev, host, sizeof(T) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) fail(CSPM_ERR_HIP, "upload failed");
+  }
+  void fill(void *dev, int byte, size_t bytes) {
+    if (!rc && hipMemsetAsync(dev, byte, bytes, c->stream) != hipSuccess) fail(CSPM_ERR_HIP, "upload failed");
+  }
+  // a buffer holding host[0 .. n); null for a null host pointer
+  template <class T>
+  T *up(const T *host, size_t n) {
+    T *p = buf<T>(n, host != nullptr);
+    if (host) put(p, host, n);
+    return p;
+  }
+  // the same for `rows` rows of `row` bytes that lie `stride` bytes apart: packed on the device
+  uint8_t *up2d(const uint8_t *host, size_t stride, size_t row, size_t rows) {
+    uint8_t *p = buf<uint8_t>(row * rows, host != nullptr);
+    if (host && !rc && hipMemcpy2DAsync(p, row, host, stride, row, rows, hipMemcpyHostToDevice, c->stream) != hipSuccess) fail(CSPM_ERR_HIP, "upload failed");
+    return p;
+  }
+  // an 8UC3 image as the packed words the kernels read (k_pack_bgr); null for a null host pointer
+  uint32_t *up_bgr(const uint8_t *host, size_t stride, int w, int h) {
+    const uint8_t *bgr = up2d(host, stride, (size_t)w * 3, (size_t)h);
+    uint32_t *pix = buf<uint32_t>((size_t)w * h, host != nullptr);
+    if (host && !rc) hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)w * h)), dim3(256), 0, c->stream, bgr, (size_t)w * 3, w, h, w, 0, pix);
+    return pix;
+  }
+  // downloads: nothing for a null host pointer or no elements, and nothing behind a launch that failed
+  template <class T>
+  void down(T *host, const void *dev, size_t n) {
+    if (host && n && !rc && !broke) broke = hipGetLastError() != hipSuccess || hipMemcpyAsync(host, dev, sizeof(T) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess;
+  }
+  void down2d(uint8_t *host, size_t stride, const uint8_t *dev, size_t row, size_t rows) {
+    if (host && !rc && !broke)
+      broke = hipGetLastError() != hipSuccess || hipMemcpy2DAsync(host, stride, dev, row, row, rows, hipMemcpyDeviceToHost, c->stream) != hipSuccess;
+  }
+  // waits for the launches and downloads so far: `failed` is the message if one of them did not succeed
+  int finish(const char *failed = "") {
+    if (!rc && (broke || hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) fail(CSPM_ERR_HIP, failed);
+    if (rc && c) g_create_error = c->err;
+    return rc;
+  }
+};
+
 }  // namespace
 
 // =================================================================================================
@@ -2460,21 +2552,6 @@ int cspm_build_cost_img(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, d
   return build_cost(c, kKindImg, max_dis, wnd_size, scale_num, reg_lambda);
 }
 
-// The one-shot host entries (CCMethod::buildCV, CAMethod::aggreCV on caller-owned buffers) work on a temporary context and device buffers
-// of their own: both go when the call returns, and the message of a failure stays behind as the thread's creation error.
-struct Scratch {
-  cspm_ctx *c = nullptr;
-  std::vector<void *> tmp;
-  int done(int code) {
-    if (code) g_create_error = c->err;
-    return code;
-  }
-  ~Scratch() {
-    for (void *p : tmp) (void)hipFree(p);
-    cspm_destroy(c);
-  }
-};
-
 // ---- rectification (cspm.h "rectification") ----
 int cspm_rect_default_params(cspm_rect_params *p) {
   if (!p) return CSPM_ERR_ARG;
@@ -2500,28 +2577,21 @@ int cspm_rectify_host(int device, const cspm_rig *rig, const cspm_rectification 
   if (bgr_out && !raw) return fail(nullptr, CSPM_ERR_ARG, "rectification: a remapped image needs the raw image");
   if (bgr_out && raw_stride < (size_t)rig->raw_w * 3) return fail(nullptr, CSPM_ERR_ARG, "rectification: raw_stride is below 3 * raw_w");
   if (bgr_out && out_stride < (size_t)rect->w * 3) return fail(nullptr, CSPM_ERR_ARG, "rectification: out_stride is below 3 * w");
-  Scratch S;
-  int rc = cspm_create(&S.c, device);
-  if (rc) return rc;
-  cspm_ctx *c = S.c;
+  OneShot S(device);
   const int w = rect->w, h = rect->h, rw = rig->raw_w, rh = rig->raw_h;
   const size_t n = (size_t)w * h, rn = (size_t)rw * rh;
-  double *dmap = nullptr;
-  uint8_t *dvalid = nullptr, *draw = nullptr, *dout = nullptr;
-  uint32_t *dpix = nullptr;
-  if ((rc = dalloc(c, &dmap, 2 * n, &S.tmp)) || (rc = dalloc(c, &dvalid, n, &S.tmp)) ||
-      (bgr_out && ((rc = dalloc(c, &draw, 3 * rn, &S.tmp)) || (rc = dalloc(c, &dpix, rn, &S.tmp)) || (rc = dalloc(c, &dout, 3 * n, &S.tmp)))))
-    return S.done(rc);
-  if (bgr_out && hipMemcpy2DAsync(draw, (size_t)rw * 3, raw, raw_stride, (size_t)rw * 3, rh, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
-  rect_map_launch(c->stream, rect_view(rig, rect, view), w, h, dmap, dvalid);
-  if (bgr_out) rect_remap_launch(c->stream, draw, (size_t)rw * 3, rw, rh, dpix, dmap, dvalid, w, h, dout, (size_t)w * 3);
-  if (hipGetLastError() != hipSuccess || (map_out && hipMemcpyAsync(map_out, dmap, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      (valid_out && hipMemcpyAsync(valid_out, dvalid, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      (bgr_out && hipMemcpy2DAsync(bgr_out, out_stride, dout, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      hipStreamSynchronize(c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "rectification kernels failed"));
-  return S.done(CSPM_OK);
+  double *dmap = S.buf<double>(2 * n);
+  uint8_t *dvalid = S.buf<uint8_t>(n);
+  uint8_t *draw = S.up2d(bgr_out ? raw : nullptr, raw_stride, (size_t)rw * 3, rh);
+  uint32_t *dpix = S.buf<uint32_t>(rn, bgr_out != nullptr);
+  uint8_t *dout = S.buf<uint8_t>(3 * n, bgr_out != nullptr);
+  if (S.rc) return S.finish();
+  rect_map_launch(S.c->stream, rect_view(rig, rect, view), w, h, dmap, dvalid);
+  if (bgr_out) rect_remap_launch(S.c->stream, draw, (size_t)rw * 3, rw, rh, dpix, dmap, dvalid, w, h, dout, (size_t)w * 3);
+  S.down(map_out, dmap, 2 * n);
+  S.down(valid_out, dvalid, n);
+  S.down2d(bgr_out, out_stride, dout, (size_t)w * 3, h);
+  return S.finish("rectification kernels failed");
 }
 
 int cspm_set_rectification(cspm_ctx *c, const cspm_rig *rig, const cspm_rectification *rect) {
@@ -2620,25 +2690,25 @@ int cspm_set_images_raw_device(cspm_ctx *c, const void *l, const void *r, size_t
 // CCMethod::buildCV / buildRightCV on host buffers (cc_method.h:31-32): the cells of slabs 0 .. maxDis-1 from CV_64FC3 images
 static int build_cv_host(CostKind kind, int device, const double *l_rgb, const double *r_rgb, int w, int h, int maxDis, int right_view, double *vol_out) {
   if (!l_rgb || !r_rgb || !vol_out || w < 1 || h < 1 || maxDis < 1) return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
-  Scratch S;
-  int rc = cspm_create(&S.c, device);
-  if (rc) return rc;
+  OneShot S(device);
   cspm_ctx *c = S.c;
   const size_t px = (size_t)w * h;
   const bool need_grd = kind != kKindCen, need_code = kind != kKindGrd;
-  double *d[2] = {nullptr, nullptr}, *grd[2] = {nullptr, nullptr}, *vol = nullptr;
-  uint8_t *gray[2] = {nullptr, nullptr};
-  uint32_t *code[2] = {nullptr, nullptr};
-  unsigned long long *key = nullptr;  // k_grd_volume<SrcF64, false> reduces its max: it gets a zeroed key, the other two kernels none
+  double *d[2], *grd[2];
+  uint8_t *gray[2];
+  uint32_t *code[2];
   const double *src[2] = {l_rgb, r_rgb};
   for (int v = 0; v < 2; ++v) {
-    if ((rc = dalloc(c, &d[v], px * 3, &S.tmp)) || (need_grd && (rc = dalloc(c, &grd[v], px, &S.tmp))) ||
-        (need_code && ((rc = dalloc(c, &gray[v], px, &S.tmp)) || (rc = dalloc(c, &code[v], px * 3, &S.tmp)))))
-      return S.done(rc);
-    if (hipMemcpyAsync(d[v], src[v], sizeof(double) * px * 3, hipMemcpyHostToDevice, c->stream) != hipSuccess) return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+    d[v] = S.up(src[v], px * 3);
+    grd[v] = S.buf<double>(px, need_grd);
+    gray[v] = S.buf<uint8_t>(px, need_code);
+    code[v] = S.buf<uint32_t>(px * 3, need_code);
   }
-  if ((rc = dalloc(c, &vol, px * maxDis, &S.tmp)) || (kind == kKindGrd && (rc = dalloc(c, &key, 1, &S.tmp)))) return S.done(rc);
-  if (key && hipMemsetAsync(key, 0, sizeof *key, c->stream) != hipSuccess) return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  double *vol = S.buf<double>(px * maxDis);
+  // k_grd_volume<SrcF64, false> reduces its max: it gets a zeroed key, the other two kernels none
+  unsigned long long *key = S.buf<unsigned long long>(1, kind == kKindGrd);
+  if (key) S.fill(key, 0, sizeof *key);
+  if (S.rc) return S.finish();
   const dim3 ew(ew_grid((long long)px)), grid(stride_grid((long long)px * maxDis)), block(256);
   for (int v = 0; v < 2; ++v) {
     if (need_grd) hipLaunchKernelGGL(k_gradient<SrcF64>, ew, block, 0, c->stream, SrcF64{d[v], w}, w, h, w, 0, grd[v]);
@@ -2660,10 +2730,8 @@ static int build_cv_host(CostKind kind, int device, const double *l_rgb, const d
     hipLaunchKernelGGL(k_cengrd_volume<SrcF64>, grid, block, 0, c->stream, l, r, grd[0], grd[1], w, 0, code[0], code[1], w, h, 0, maxDis, right_view, vol,
                        (unsigned long long *)nullptr);
   }
-  if (hipMemcpyAsync(vol_out, vol, sizeof(double) * px * maxDis, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess || hipGetLastError() != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, what));
-  return S.done(CSPM_OK);
+  S.down(vol_out, vol, px * maxDis);
+  return S.finish(what);
 }
 
 // GrdCC::buildCV / buildRightCV on host buffers
@@ -2804,35 +2872,27 @@ int cspm_aggregate_cv_host(int device, int method, const double *guide, int w, i
     return fail(nullptr, CSPM_ERR_ARG, std::string(ca_name(method)) + " needs min(w, h) >= " + std::to_string(ca_min_size(method)) + ", the slabs are " +
                                            std::to_string(w) + "x" + std::to_string(h));
   if (n_slices == 1) return CSPM_OK;
-  Scratch S;
-  int rc = cspm_create(&S.c, device);
-  if (rc) return rc;
+  OneShot S(device);
   cspm_ctx *c = S.c;
   const size_t px = (size_t)w * h;
   const int nb = ca_batch(px);
-  CaWork wk;
-  double *dv = nullptr, *dout = nullptr;
-  if ((rc = ca_alloc_work(c, px, nb, &wk, &S.tmp)) || (rc = dalloc(c, &dv, (size_t)(n_slices - 1) * px, &S.tmp)) ||
-      (rc = dalloc(c, &dout, (size_t)nb * px, &S.tmp)))
-    return S.done(rc);
   std::vector<double> gn(3 * px);  // channel-major, the values as given
   for (size_t i = 0; i < px; ++i)
     for (int k = 0; k < 3; ++k) gn[k * px + i] = guide[3 * i + k];
-  if (hipMemcpyAsync(wk.gn, gn.data(), sizeof(double) * 3 * px, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipMemcpyAsync(dv, vol + px, sizeof(double) * (n_slices - 1) * px, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  CaWork wk;
+  if (!S.rc) S.rc = ca_alloc_work(c, px, nb, &wk, &S.bufs.ptrs);
+  S.put(wk.gn, gn.data(), 3 * px);
+  double *dv = S.up(vol + px, (size_t)(n_slices - 1) * px);
+  double *dout = S.buf<double>((size_t)nb * px);
+  if (S.rc) return S.finish();
   ca_prepare_guide(c, method, wk, w, h);
-  for (int d0 = 0; d0 < n_slices - 1; d0 += nb) {
+  for (int d0 = 0; d0 < n_slices - 1 && !S.rc; d0 += nb) {
     const int n = std::min(nb, n_slices - 1 - d0);
     ca_filter(c, method, wk, w, h, dv + (size_t)d0 * px, n, dout);
-    if (hipMemcpyAsync(dv + (size_t)d0 * px, dout, sizeof(double) * n * px, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-      return S.done(fail(c, CSPM_ERR_HIP, "copy failed"));
+    if (hipMemcpyAsync(dv + (size_t)d0 * px, dout, sizeof(double) * n * px, hipMemcpyDeviceToDevice, c->stream) != hipSuccess) S.fail(CSPM_ERR_HIP, "copy failed");
   }
-  if (hipGetLastError() != hipSuccess ||
-      hipMemcpyAsync(vol + px, dv, sizeof(double) * (n_slices - 1) * px, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "aggregation kernels failed"));
-  return S.done(CSPM_OK);
+  S.down(vol + px, dv, (size_t)(n_slices - 1) * px);
+  return S.finish("aggregation kernels failed");
 }
 
 // the speckle filter alone on caller maps: the launches PostProcessing enqueues, on one view
@@ -2841,27 +2901,19 @@ int cspm_filter_speckles_host(int device, const double *disp, const uint8_t *val
   if (!disp || !valid_out || w < 1 || h < 1 || max_size < 0 || !(max_diff >= 0.0)) return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
   const long long n = (long long)w * h;
   if (n >= (1LL << 31)) return fail(nullptr, CSPM_ERR_ARG, "w * h must be below 2^31: labels are 32-bit pixel indices");
-  Scratch S;
-  int rc = cspm_create(&S.c, device);
-  if (rc) return rc;
-  cspm_ctx *c = S.c;
-  double *dd = nullptr;
-  uint8_t *dv = nullptr;
-  int *scratch = nullptr;  // parents, counts, n(p), the removed-pixel counter
-  if ((rc = dalloc(c, &dd, (size_t)n, &S.tmp)) || (rc = dalloc(c, &dv, (size_t)n, &S.tmp)) || (rc = dalloc(c, &scratch, 3 * (size_t)n + 1, &S.tmp)))
-    return S.done(rc);
-  if (hipMemcpyAsync(dd, disp, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      (valid ? hipMemcpyAsync(dv, valid, (size_t)n, hipMemcpyHostToDevice, c->stream) : hipMemsetAsync(dv, 1, (size_t)n, c->stream)) != hipSuccess ||
-      hipMemsetAsync(scratch + 3 * n, 0, sizeof(int), c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  OneShot S(device);
+  double *dd = S.up(disp, (size_t)n);
+  uint8_t *dv = valid ? S.up(valid, (size_t)n) : S.buf<uint8_t>((size_t)n);
+  if (!valid) S.fill(dv, 1, (size_t)n);
+  int *scratch = S.buf<int>(3 * (size_t)n + 1);  // parents, counts, n(p), the removed-pixel counter
+  if (scratch) S.fill(scratch + 3 * n, 0, sizeof(int));
+  if (S.rc) return S.finish();
   const double *d[1] = {dd};
   uint8_t *v[1] = {dv};
-  speckle_launch<double>(c->stream, d, v, 1, w, h, max_size, max_diff, scratch, (unsigned int *)(scratch + 3 * n), scratch + 2 * n);
-  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(valid_out, dv, (size_t)n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      (size_out && hipMemcpyAsync(size_out, scratch + 2 * n, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      hipStreamSynchronize(c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "speckle filter kernels failed"));
-  return S.done(CSPM_OK);
+  speckle_launch<double>(S.c->stream, d, v, 1, w, h, max_size, max_diff, scratch, (unsigned int *)(scratch + 3 * n), scratch + 2 * n);
+  S.down(valid_out, dv, (size_t)n);
+  S.down(size_out, scratch + 2 * n, (size_t)n);
+  return S.finish("speckle filter kernels failed");
 }
 
 // the plane fit alone on caller maps: the launch cspm_fit_planes enqueues, on one view
@@ -2877,34 +2929,21 @@ int cspm_fit_planes_host(int device, const double *disp, const uint8_t *valid, c
   if (const char *msg = fit_params_error(p)) return fail(nullptr, CSPM_ERR_ARG, msg);
   if (!disp || !np_out || w < 1 || h < 1 || h > kFitMaxRows || max_dis < 0 || (guide_bgr && guide_stride < (size_t)w * 3))
     return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
-  Scratch S;
-  int rc = cspm_create(&S.c, device);
-  if (rc) return rc;
-  cspm_ctx *c = S.c;
+  OneShot S(device);
   const size_t n = (size_t)w * h;
   const bool guided = guide_bgr && p->use_guide;
-  double *dd = nullptr, *dout = nullptr, *dlut = nullptr;
-  uint8_t *dv = nullptr, *dfit = nullptr, *dbgr = nullptr;
-  uint32_t *dpix = nullptr;
-  if ((rc = dalloc(c, &dd, n, &S.tmp)) || (rc = dalloc(c, &dout, 6 * n, &S.tmp)) || (rc = dalloc(c, &dfit, n, &S.tmp)) ||
-      (valid && (rc = dalloc(c, &dv, n, &S.tmp))) ||
-      (guided && ((rc = dalloc(c, &dbgr, 3 * n, &S.tmp)) || (rc = dalloc(c, &dpix, n, &S.tmp)) || (rc = dalloc(c, &dlut, (size_t)kFitLut, &S.tmp)))))
-    return S.done(rc);
-  if (hipMemcpyAsync(dd, disp, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      (valid && hipMemcpyAsync(dv, valid, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
-      (guided && (hipMemcpy2DAsync(dbgr, (size_t)w * 3, guide_bgr, guide_stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                  hipMemcpyAsync(dlut, fit_lut(), sizeof(double) * kFitLut, hipMemcpyHostToDevice, c->stream) != hipSuccess)))
-    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
-  if (guided) hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, dbgr, (size_t)w * 3, w, h, w, 0, dpix);
-  fit_launch(c->stream, FitIn{dd, dv, dpix, dlut}, FitOut{dout, dout + n, dout + 2 * n, dout + 3 * n, dout + 4 * n, dout + 5 * n, dfit, 0}, w, h, p, max_dis);
+  double *dd = S.up(disp, n), *dout = S.buf<double>(6 * n);
+  uint8_t *dfit = S.buf<uint8_t>(n), *dv = S.up(valid, n);
+  double *dlut = S.up(guided ? fit_lut() : nullptr, (size_t)kFitLut);
+  uint32_t *dpix = S.up_bgr(guided ? guide_bgr : nullptr, guide_stride, w, h);
+  if (S.rc) return S.finish();
+  fit_launch(S.c->stream, FitIn{dd, dv, dpix, dlut}, FitOut{dout, dout + n, dout + 2 * n, dout + 3 * n, dout + 4 * n, dout + 5 * n, dfit, 0}, w, h, p, max_dis);
   std::vector<double> hst(6 * n);
-  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hst.data(), dout, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      (fitted_out && hipMemcpyAsync(fitted_out, dfit, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      hipStreamSynchronize(c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "plane fit kernel failed"));
-  for (size_t i = 0; i < n; ++i)
-    for (int k = 0; k < 6; ++k) np_out[6 * i + k] = hst[k * n + i];
-  return S.done(CSPM_OK);
+  S.down(hst.data(), dout, 6 * n);
+  S.down(fitted_out, dfit, n);
+  if (S.finish("plane fit kernel failed")) return S.rc;
+  interleave_planes(hst.data(), n, np_out);
+  return CSPM_OK;
 }
 
 // the segmentation and the segment fit alone on caller memory: the launches cspm_segment_planes enqueues, on one view
@@ -2926,30 +2965,19 @@ int cspm_segment_host(int device, const uint8_t *bgr, size_t stride, int w, int 
   if (const char *msg = seg_params_error(p)) return fail(nullptr, CSPM_ERR_ARG, msg);
   if (!bgr || !labels_out || w < 1 || h < 1 || h > kSegMaxRows || stride < (size_t)w * 3 || (long long)w * h >= (1LL << 31))
     return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
-  Scratch S;
-  int rc = cspm_create(&S.c, device);
-  if (rc) return rc;
-  cspm_ctx *c = S.c;
+  OneShot S(device);
   const size_t n = (size_t)w * h;
   const SegGrid g = seg_grid(w, h, p->step);
   const size_t K = (size_t)g.nx * g.ny;
-  uint8_t *dbgr = nullptr, *dseg = nullptr;
-  uint32_t *dpix = nullptr;
-  int *dlab = nullptr;
-  if ((rc = dalloc(c, &dbgr, 3 * n, &S.tmp)) || (rc = dalloc(c, &dpix, n, &S.tmp)) || (rc = dalloc(c, &dlab, n, &S.tmp)) ||
-      (rc = dalloc(c, &dseg, SegMem::bytes(K), &S.tmp)))
-    return S.done(rc);
-  const SegMem m(dseg, K);
-  if (hipMemcpy2DAsync(dbgr, (size_t)w * 3, bgr, stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
-  hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, dbgr, (size_t)w * 3, w, h, w, 0, dpix);
-  seg_segment_launch(c->stream, g, dpix, p, dlab, m);
-  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(labels_out, dlab, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      (centres_out && hipMemcpyAsync(centres_out, m.cen, sizeof(int) * 5 * K, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      (counts_out && hipMemcpyAsync(counts_out, m.counts, sizeof(int) * K, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      hipStreamSynchronize(c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "segmentation kernels failed"));
-  return S.done(CSPM_OK);
+  uint32_t *dpix = S.up_bgr(bgr, stride, w, h);
+  int *dlab = S.buf<int>(n);
+  const SegMem m(S.buf<uint8_t>(SegMem::bytes(K)), K);
+  if (S.rc) return S.finish();
+  seg_segment_launch(S.c->stream, g, dpix, p, dlab, m);
+  S.down(labels_out, dlab, n);
+  S.down(centres_out, m.cen, 5 * K);
+  S.down(counts_out, m.counts, K);
+  return S.finish("segmentation kernels failed");
 }
 
 int cspm_segment_planes_host(int device, const double *disp, const uint8_t *valid, const int32_t *labels, int w, int h, int max_dis, const cspm_seg_params *p,
@@ -2965,38 +2993,27 @@ int cspm_segment_planes_host(int device, const double *disp, const uint8_t *vali
       if (k < 0 || (size_t)k >= K || std::abs(k % g.nx - x / g.s) > 1 || std::abs(k / g.nx - y / g.s) > 1)
         return fail(nullptr, CSPM_ERR_ARG, "segment planes: a label is no segment of the 3 x 3 cells around its pixel");
     }
-  Scratch S;
-  int rc = cspm_create(&S.c, device);
-  if (rc) return rc;
-  cspm_ctx *c = S.c;
-  double *dd = nullptr, *dout = nullptr;
-  uint8_t *dv = nullptr, *dfit = nullptr, *dseg = nullptr;
-  int *dlab = nullptr;
-  if ((rc = dalloc(c, &dd, n, &S.tmp)) || (rc = dalloc(c, &dout, 6 * n, &S.tmp)) || (rc = dalloc(c, &dfit, n, &S.tmp)) || (rc = dalloc(c, &dlab, n, &S.tmp)) ||
-      (valid && (rc = dalloc(c, &dv, n, &S.tmp))) || (rc = dalloc(c, &dseg, SegMem::bytes(K), &S.tmp)))
-    return S.done(rc);
-  const SegMem m(dseg, K);
-  if (hipMemcpyAsync(dd, disp, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipMemcpyAsync(dlab, labels, sizeof(int) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      (valid && hipMemcpyAsync(dv, valid, n, hipMemcpyHostToDevice, c->stream) != hipSuccess))
-    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
-  seg_fit_launch(c->stream, g, SegFitIn{dd, dv, dlab}, p, max_dis, m, FitOut{dout, dout + n, dout + 2 * n, dout + 3 * n, dout + 4 * n, dout + 5 * n, dfit, 0});
+  OneShot S(device);
+  double *dd = S.up(disp, n), *dout = S.buf<double>(6 * n);
+  int *dlab = S.up(labels, n);
+  uint8_t *dv = S.up(valid, n), *dfit = S.buf<uint8_t>(n);
+  const SegMem m(S.buf<uint8_t>(SegMem::bytes(K)), K);
+  if (S.rc) return S.finish();
+  seg_fit_launch(S.c->stream, g, SegFitIn{dd, dv, dlab}, p, max_dis, m, FitOut{dout, dout + n, dout + 2 * n, dout + 3 * n, dout + 4 * n, dout + 5 * n, dfit, 0});
   std::vector<double> hst(6 * n), hseg(4 * K);
-  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(hst.data(), dout, sizeof(double) * 6 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipMemcpyAsync(hseg.data(), m.planes, sizeof(double) * 4 * K, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      (inliers_out && hipMemcpyAsync(inliers_out, m.inliers, sizeof(int) * K, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      (fitted_out && hipMemcpyAsync(fitted_out, dfit, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      hipStreamSynchronize(c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "segment fit kernels failed"));
-  for (size_t i = 0; i < n; ++i)
-    for (int k = 0; k < 6; ++k) np_out[6 * i + k] = hst[k * n + i];
+  S.down(hst.data(), dout, 6 * n);
+  S.down(hseg.data(), m.planes, 4 * K);
+  S.down(inliers_out, m.inliers, K);
+  S.down(fitted_out, dfit, n);
+  if (S.finish("segment fit kernels failed")) return S.rc;
+  interleave_planes(hst.data(), n, np_out);
   if (seg_planes_out)
     for (size_t k = 0; k < K; ++k) {
       seg_planes_out[3 * k] = hseg[4 * k];
       seg_planes_out[3 * k + 1] = hseg[4 * k + 1];
       seg_planes_out[3 * k + 2] = hseg[4 * k + 3];
     }
-  return S.done(CSPM_OK);
+  return CSPM_OK;
 }
 
 // the median filter alone on caller memory: the launch PostProcessing enqueues, on one image
@@ -3005,40 +3022,27 @@ int cspm_median_filter_u8_host(int device, const uint8_t *src, size_t src_stride
     return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
   const size_t row = (size_t)w * channels;
   if (src_stride < row || dst_stride < row) return fail(nullptr, CSPM_ERR_ARG, "a stride is below w * channels");
-  Scratch S;
-  int rc = cspm_create(&S.c, device);
-  if (rc) return rc;
-  cspm_ctx *c = S.c;
-  uint8_t *ds = nullptr, *dd = nullptr;  // packed rows on the device
-  if ((rc = dalloc(c, &ds, row * h, &S.tmp)) || (rc = dalloc(c, &dd, row * h, &S.tmp))) return S.done(rc);
-  if (hipMemcpy2DAsync(ds, row, src, src_stride, row, (size_t)h, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  OneShot S(device);
+  uint8_t *ds = S.up2d(src, src_stride, row, (size_t)h), *dd = S.buf<uint8_t>(row * h);  // packed rows on the device
+  if (S.rc) return S.finish();
   const uint8_t *s1[1] = {ds};
   uint8_t *d1[1] = {dd};
-  median_launch_u8(c->stream, s1, d1, 1, row, row, w, h, channels, r);
-  if (hipGetLastError() != hipSuccess || hipMemcpy2DAsync(dst, dst_stride, dd, row, row, (size_t)h, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "median filter kernel failed"));
-  return S.done(CSPM_OK);
+  median_launch_u8(S.c->stream, s1, d1, 1, row, row, w, h, channels, r);
+  S.down2d(dst, dst_stride, dd, row, (size_t)h);
+  return S.finish("median filter kernel failed");
 }
 
 int cspm_median_filter_f64_host(int device, const double *src, int w, int h, int r, double *dst) {
   if (!src || !dst || src == dst || w < 1 || h < 1 || r < 1 || r > CSPM_MEDIAN_MAX_RADIUS) return fail(nullptr, CSPM_ERR_ARG, "bad arguments");
-  Scratch S;
-  int rc = cspm_create(&S.c, device);
-  if (rc) return rc;
-  cspm_ctx *c = S.c;
+  OneShot S(device);
   const size_t n = (size_t)w * h;
-  double *ds = nullptr, *dd = nullptr;
-  if ((rc = dalloc(c, &ds, n, &S.tmp)) || (rc = dalloc(c, &dd, n, &S.tmp))) return S.done(rc);
-  if (hipMemcpyAsync(ds, src, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
+  double *ds = S.up(src, n), *dd = S.buf<double>(n);
+  if (S.rc) return S.finish();
   const double *s1[1] = {ds};
   double *d1[1] = {dd};
-  median_launch_f64(c->stream, s1, d1, 1, w, h, r);
-  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(dst, dd, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "median filter kernel failed"));
-  return S.done(CSPM_OK);
+  median_launch_f64(S.c->stream, s1, d1, 1, w, h, r);
+  S.down(dst, dd, n);
+  return S.finish("median filter kernel failed");
 }
 
 // the smoother alone on caller memory: the launches PostProcessing enqueues, on one view
@@ -3051,35 +3055,22 @@ int cspm_smooth_disparity_host(int device, const double *disp, const double *con
   if (conf)
     for (size_t i = 0; i < n; ++i)
       if (!(conf[i] >= 0.0 && conf[i] <= 1.0)) return fail(nullptr, CSPM_ERR_ARG, "smoothing: a confidence outside [0, 1] or a NaN");
-  Scratch S;
-  int rc = cspm_create(&S.c, device);
-  if (rc) return rc;
-  cspm_ctx *c = S.c;
-  double *dd = nullptr, *work = nullptr, *dconf = nullptr, *dlut = nullptr;
-  uint8_t *dbgr = nullptr;
-  uint32_t *dpix = nullptr;
-  if ((rc = dalloc(c, &dd, n, &S.tmp)) || (rc = dalloc(c, &work, 3 * n, &S.tmp)) || (conf && (rc = dalloc(c, &dconf, n, &S.tmp))) ||
-      (guide_bgr && ((rc = dalloc(c, &dbgr, 3 * n, &S.tmp)) || (rc = dalloc(c, &dpix, n, &S.tmp)) || (rc = dalloc(c, &dlut, (size_t)kSmLut, &S.tmp)))))
-    return S.done(rc);
+  OneShot S(device);
   std::vector<double> lut(kSmLut);
   smooth_lut_fill(p->sigma_color, lut.data());
-  if (hipMemcpyAsync(dd, disp, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      (conf && hipMemcpyAsync(dconf, conf, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
-      (guide_bgr && (hipMemcpyAsync(dbgr, guide_bgr, 3 * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                     hipMemcpyAsync(dlut, lut.data(), sizeof(double) * kSmLut, hipMemcpyHostToDevice, c->stream) != hipSuccess)))
-    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
-  if (guide_bgr) hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, dbgr, (size_t)w * 3, w, h, w, 0, dpix);
+  double *dd = S.up(disp, n), *work = S.buf<double>(3 * n), *dconf = S.up(conf, n);
+  double *dlut = S.up(guide_bgr ? lut.data() : nullptr, (size_t)kSmLut);
+  uint32_t *dpix = S.up_bgr(guide_bgr, (size_t)w * 3, w, h);
+  if (S.rc) return S.finish();
   SmoothPair s;
   s.v[0] = s.v[1] = SmoothView{work, work + n, work + 2 * n, dpix};
   s.Wp = w;
   s.pad = 0;
   const SmoothConf cf{{dconf, dconf}, {nullptr, nullptr}, 0.0};
   double *d1[1] = {dd};
-  smooth_launch(c->stream, d1, cf, s, 1, w, h, p, (double)max_dis, dlut);
-  if (hipGetLastError() != hipSuccess || hipMemcpyAsync(out, dd, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "smoothing kernels failed"));
-  return S.done(CSPM_OK);
+  smooth_launch(S.c->stream, d1, cf, s, 1, w, h, p, (double)max_dis, dlut);
+  S.down(out, dd, n);
+  return S.finish("smoothing kernels failed");
 }
 
 // local stereo over the ctx's cost object (cspm.h): asynchronous on the ctx stream like cspm_patchmatch
@@ -3114,12 +3105,9 @@ int cspm_plane_cost_batch(cspm_ctx *c, int view, int n, const int *xy, const dou
   ON_DEVICE(c);
   int *dxy = nullptr;
   double *dnp = nullptr, *dout = nullptr;
-  std::vector<void *> tmp;
+  DevBufs tmp;
   int rc;
-  if ((rc = dalloc(c, &dxy, (size_t)2 * n, &tmp)) || (rc = dalloc(c, &dnp, (size_t)6 * n, &tmp)) || (rc = dalloc(c, &dout, (size_t)n, &tmp))) {
-    for (void *p : tmp) (void)hipFree(p);
-    return rc;
-  }
+  if ((rc = dalloc(c, &dxy, (size_t)2 * n, &tmp.ptrs)) || (rc = dalloc(c, &dnp, (size_t)6 * n, &tmp.ptrs)) || (rc = dalloc(c, &dout, (size_t)n, &tmp.ptrs))) return rc;
   hipError_t e = hipMemcpyAsync(dxy, xy, sizeof(int) * 2 * n, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(dnp, np, sizeof(double) * 6 * n, hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess) {
@@ -3128,7 +3116,6 @@ int cspm_plane_cost_batch(cspm_ctx *c, int view, int n, const int *xy, const dou
   }
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e == hipSuccess) e = hipGetLastError();
-  for (void *p : tmp) (void)hipFree(p);
   if (e != hipSuccess) return fail(c, CSPM_ERR_HIP, hipGetErrorString(e));
   return CSPM_OK;
 }
@@ -3402,47 +3389,34 @@ int cspm_reproject_host(int device, const cspm_calib *calib, const cspm_geom_par
   if ((slope_a == nullptr) != (slope_b == nullptr)) return fail(nullptr, CSPM_ERR_ARG, "reprojection: the two slope maps come together or not at all");
   if (normal_out && !slope_a) return fail(nullptr, CSPM_ERR_ARG, "reprojection: normals need the slope maps");
   if (bgr && bgr_stride < (size_t)w * 3) return fail(nullptr, CSPM_ERR_ARG, "reprojection: bgr_stride is below 3 * w");
-  Scratch S;
-  int rc = cspm_create(&S.c, device);
-  if (rc) return rc;
-  cspm_ctx *c = S.c;
+  OneShot S(device);
   const size_t n = (size_t)w * h;
   const unsigned nb = geom_blocks((long long)n);
   const size_t cap = std::min(cloud_out ? cloud_cap : (size_t)0, n);
-  double *dd = nullptr, *da = nullptr, *db = nullptr, *ddepth = nullptr, *dxyz = nullptr, *dnormal = nullptr;
-  uint8_t *dv = nullptr, *dbgr = nullptr, *dkeep = nullptr;
-  uint32_t *dpix = nullptr;
-  unsigned int *dcounts = nullptr;
-  uint4 *dcloud = nullptr;
-  if ((rc = dalloc(c, &dd, n, &S.tmp)) || (rc = dalloc(c, &dcounts, (size_t)nb + 1, &S.tmp)) || (valid && (rc = dalloc(c, &dv, n, &S.tmp))) ||
-      (slope_a && ((rc = dalloc(c, &da, n, &S.tmp)) || (rc = dalloc(c, &db, n, &S.tmp)))) ||
-      (bgr && ((rc = dalloc(c, &dbgr, 3 * n, &S.tmp)) || (rc = dalloc(c, &dpix, n, &S.tmp)))) || (depth_out && (rc = dalloc(c, &ddepth, n, &S.tmp))) ||
-      (xyz_out && (rc = dalloc(c, &dxyz, 3 * n, &S.tmp))) || (normal_out && (rc = dalloc(c, &dnormal, 3 * n, &S.tmp))) ||
-      (keep_out && (rc = dalloc(c, &dkeep, n, &S.tmp))) || (cap && (rc = dalloc(c, &dcloud, 2 * cap, &S.tmp))))
-    return S.done(rc);
-  if (hipMemcpyAsync(dd, disp, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      (valid && hipMemcpyAsync(dv, valid, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
-      (slope_a && (hipMemcpyAsync(da, slope_a, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                   hipMemcpyAsync(db, slope_b, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess)) ||
-      (bgr && hipMemcpy2DAsync(dbgr, (size_t)w * 3, bgr, bgr_stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->stream) != hipSuccess))
-    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
-  if (bgr) hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, dbgr, (size_t)w * 3, w, h, w, 0, dpix);
+  unsigned int *dcounts = S.buf<unsigned int>((size_t)nb + 1);
+  double *ddepth = S.buf<double>(n, depth_out != nullptr), *dxyz = S.buf<double>(3 * n, xyz_out != nullptr);
+  double *dnormal = S.buf<double>(3 * n, normal_out != nullptr);
+  uint8_t *dkeep = S.buf<uint8_t>(n, keep_out != nullptr);
+  uint4 *dcloud = S.buf<uint4>(2 * cap, cap != 0);
+  double *dd = S.up(disp, n);
+  uint8_t *dv = S.up(valid, n);
+  double *da = S.up(slope_a, n), *db = S.up(slope_b, n);
+  uint32_t *dpix = S.up_bgr(bgr, bgr_stride, w, h);
+  if (S.rc) return S.finish();
   const bool want_count = count_out != nullptr || cloud_out != nullptr;
-  geom_launch(c->stream, geom_cam(calib, g, view), GeomIn{dd, dv, da, db, nullptr, dpix}, GeomOut{ddepth, dxyz, dnormal, dkeep}, w, h, dcloud, cap, want_count,
+  geom_launch(S.c->stream, geom_cam(calib, g, view), GeomIn{dd, dv, da, db, nullptr, dpix}, GeomOut{ddepth, dxyz, dnormal, dkeep}, w, h, dcloud, cap, want_count,
               dcounts, nullptr);
   unsigned int total = 0;
-  if (hipGetLastError() != hipSuccess || (depth_out && hipMemcpyAsync(depth_out, ddepth, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      (xyz_out && hipMemcpyAsync(xyz_out, dxyz, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      (normal_out && hipMemcpyAsync(normal_out, dnormal, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      (keep_out && hipMemcpyAsync(keep_out, dkeep, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      (want_count && hipMemcpyAsync(&total, dcounts + nb, sizeof total, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      hipStreamSynchronize(c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "reprojection kernels failed"));
-  const size_t wrote = std::min((size_t)total, cap);
-  if (wrote && hipMemcpy(cloud_out, dcloud, sizeof(cspm_point) * wrote, hipMemcpyDeviceToHost) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "cloud download failed"));
+  S.down(depth_out, ddepth, n);
+  S.down(xyz_out, dxyz, 3 * n);
+  S.down(normal_out, dnormal, 3 * n);
+  S.down(keep_out, dkeep, n);
+  S.down(want_count ? &total : nullptr, dcounts + nb, 1);
+  if (S.finish("reprojection kernels failed")) return S.rc;
+  S.down(cloud_out, dcloud, std::min((size_t)total, cap));  // the count first, then the records that were written
+  if (S.finish("cloud download failed")) return S.rc;
   if (count_out) *count_out = total;
-  return S.done(CSPM_OK);
+  return CSPM_OK;
 }
 
 // G on one view of the stored field (cspm.h "reprojection"): synchronous, host outputs
@@ -3455,16 +3429,13 @@ int cspm_reproject(cspm_ctx *c, int view, int source, const cspm_calib *calib, c
   const size_t n = (size_t)c->W * c->H;
   const unsigned nb = geom_blocks((long long)n);
   const size_t cap = std::min(cloud_out ? cloud_cap : (size_t)0, n);
-  std::vector<void *> tmp;
-  struct Free {
-    std::vector<void *> &t;
-    ~Free() { for (void *p : t) (void)hipFree(p); }
-  } free_tmp{tmp};
+  DevBufs tmp;
   double *ddepth = nullptr, *dxyz = nullptr, *dnormal = nullptr;
   uint8_t *dkeep = nullptr;
   uint4 *dcloud = nullptr;
-  if ((depth_out && (rc = dalloc(c, &ddepth, n, &tmp))) || (xyz_out && (rc = dalloc(c, &dxyz, 3 * n, &tmp))) ||
-      (normal_out && (rc = dalloc(c, &dnormal, 3 * n, &tmp))) || (keep_out && (rc = dalloc(c, &dkeep, n, &tmp))) || (cap && (rc = dalloc(c, &dcloud, 2 * cap, &tmp))))
+  if ((depth_out && (rc = dalloc(c, &ddepth, n, &tmp.ptrs))) || (xyz_out && (rc = dalloc(c, &dxyz, 3 * n, &tmp.ptrs))) ||
+      (normal_out && (rc = dalloc(c, &dnormal, 3 * n, &tmp.ptrs))) || (keep_out && (rc = dalloc(c, &dkeep, n, &tmp.ptrs))) ||
+      (cap && (rc = dalloc(c, &dcloud, 2 * cap, &tmp.ptrs))))
     return rc;
   const bool want_count = count_out != nullptr || cloud_out != nullptr;
   if ((rc = reproject_enqueue(c, view, source, calib, g, fit, GeomOut{ddepth, dxyz, dnormal, dkeep}, dcloud, cap, want_count, nullptr))) return rc;
@@ -3511,45 +3482,33 @@ int cspm_mesh_host(int device, const cspm_calib *calib, const cspm_geom_params *
   if ((long long)w * h >= (1LL << 31)) return fail(nullptr, CSPM_ERR_ARG, "w * h must be below 2^31: vertex records hold 32-bit pixel indices");
   if ((slope_a == nullptr) != (slope_b == nullptr)) return fail(nullptr, CSPM_ERR_ARG, "mesh: the two slope maps come together or not at all");
   if (bgr && bgr_stride < (size_t)w * 3) return fail(nullptr, CSPM_ERR_ARG, "mesh: bgr_stride is below 3 * w");
-  Scratch S;
-  int rc = cspm_create(&S.c, device);
-  if (rc) return rc;
-  cspm_ctx *c = S.c;
+  OneShot S(device);
   const size_t n = (size_t)w * h;
   const unsigned nb = geom_blocks((long long)n);
   const size_t vcap = std::min(vertices_out ? vertex_cap : (size_t)0, n), fcap = std::min(faces_out ? face_cap : (size_t)0, mesh_max_faces(w, h));
-  double *dd = nullptr, *da = nullptr, *db = nullptr;
-  uint8_t *dv = nullptr, *dbgr = nullptr, *dbytes = nullptr;
-  uint32_t *dpix = nullptr, *dmap = nullptr, *dfaces = nullptr;
-  uint4 *dverts = nullptr;
-  if ((rc = dalloc(c, &dd, n, &S.tmp)) || (rc = dalloc(c, &dbytes, 2 * n, &S.tmp)) || (rc = dalloc(c, &dmap, n + mesh_count_words(nb), &S.tmp)) ||
-      (valid && (rc = dalloc(c, &dv, n, &S.tmp))) || (slope_a && ((rc = dalloc(c, &da, n, &S.tmp)) || (rc = dalloc(c, &db, n, &S.tmp)))) ||
-      (bgr && ((rc = dalloc(c, &dbgr, 3 * n, &S.tmp)) || (rc = dalloc(c, &dpix, n, &S.tmp)))) || (vcap && (rc = dalloc(c, &dverts, 2 * vcap, &S.tmp))) ||
-      (fcap && (rc = dalloc(c, &dfaces, 3 * fcap, &S.tmp))))
-    return S.done(rc);
-  if (hipMemcpyAsync(dd, disp, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      (valid && hipMemcpyAsync(dv, valid, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
-      (slope_a && (hipMemcpyAsync(da, slope_a, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                   hipMemcpyAsync(db, slope_b, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess)) ||
-      (bgr && hipMemcpy2DAsync(dbgr, (size_t)w * 3, bgr, bgr_stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->stream) != hipSuccess))
-    return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
-  if (bgr) hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, dbgr, (size_t)w * 3, w, h, w, 0, dpix);
+  uint8_t *dbytes = S.buf<uint8_t>(2 * n);
+  uint32_t *dmap = S.buf<uint32_t>(n + mesh_count_words(nb));
+  uint4 *dverts = S.buf<uint4>(2 * vcap, vcap != 0);
+  uint32_t *dfaces = S.buf<uint32_t>(3 * fcap, fcap != 0);
+  double *dd = S.up(disp, n);
+  uint8_t *dv = S.up(valid, n);
+  double *da = S.up(slope_a, n), *db = S.up(slope_b, n);
+  uint32_t *dpix = S.up_bgr(bgr, bgr_stride, w, h);
+  if (S.rc) return S.finish();
   unsigned int *dcounts = dmap + n;
-  mesh_launch(c->stream, geom_cam(calib, g, view), GeomIn{dd, dv, da, db, nullptr, dpix}, m, w, h, MeshMaps{dbytes, dbytes + n, dmap}, dcounts, dverts, vcap,
+  mesh_launch(S.c->stream, geom_cam(calib, g, view), GeomIn{dd, dv, da, db, nullptr, dpix}, m, w, h, MeshMaps{dbytes, dbytes + n, dmap}, dcounts, dverts, vcap,
               dfaces, fcap, nullptr, nullptr);
   unsigned int nv = 0, nf = 0;
-  if (hipGetLastError() != hipSuccess || (quad_out && hipMemcpyAsync(quad_out, dbytes + n, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      hipMemcpyAsync(&nv, dcounts + nb, sizeof nv, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipMemcpyAsync(&nf, dcounts + 2 * (size_t)nb + 1, sizeof nf, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-      hipStreamSynchronize(c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "mesh kernels failed"));
-  const size_t wrote_v = std::min((size_t)nv, vcap), wrote_f = std::min((size_t)nf, fcap);
-  if ((wrote_v && hipMemcpy(vertices_out, dverts, sizeof(cspm_point) * wrote_v, hipMemcpyDeviceToHost) != hipSuccess) ||
-      (wrote_f && hipMemcpy(faces_out, dfaces, sizeof(cspm_face) * wrote_f, hipMemcpyDeviceToHost) != hipSuccess))
-    return S.done(fail(c, CSPM_ERR_HIP, "mesh download failed"));
+  S.down(quad_out, dbytes + n, n);
+  S.down(&nv, dcounts + nb, 1);
+  S.down(&nf, dcounts + 2 * (size_t)nb + 1, 1);
+  if (S.finish("mesh kernels failed")) return S.rc;
+  S.down(vertices_out, dverts, std::min((size_t)nv, vcap));  // the counts first, then the records that were written
+  S.down(faces_out, dfaces, std::min((size_t)nf, fcap));
+  if (S.finish("mesh download failed")) return S.rc;
   if (n_vertices_out) *n_vertices_out = nv;
   if (n_faces_out) *n_faces_out = nf;
-  return S.done(CSPM_OK);
+  return CSPM_OK;
 }
 
 // M on one view of the stored field (cspm.h "triangle meshes"): synchronous, host outputs
@@ -3563,14 +3522,10 @@ int cspm_mesh(cspm_ctx *c, int view, int source, const cspm_calib *calib, const 
   const size_t n = (size_t)c->W * c->H;
   const unsigned nb = geom_blocks((long long)n);
   const size_t vcap = std::min(vertices_out ? vertex_cap : (size_t)0, n), fcap = std::min(faces_out ? face_cap : (size_t)0, mesh_max_faces(c->W, c->H));
-  std::vector<void *> tmp;
-  struct Free {
-    std::vector<void *> &t;
-    ~Free() { for (void *p : t) (void)hipFree(p); }
-  } free_tmp{tmp};
+  DevBufs tmp;
   uint4 *dverts = nullptr;
   uint32_t *dfaces = nullptr;
-  if ((vcap && (rc = dalloc(c, &dverts, 2 * vcap, &tmp))) || (fcap && (rc = dalloc(c, &dfaces, 3 * fcap, &tmp)))) return rc;
+  if ((vcap && (rc = dalloc(c, &dverts, 2 * vcap, &tmp.ptrs))) || (fcap && (rc = dalloc(c, &dfaces, 3 * fcap, &tmp.ptrs)))) return rc;
   if ((rc = mesh_enqueue(c, view, source, calib, g, fit, m, dverts, vcap, dfaces, fcap, nullptr, nullptr, nullptr))) return rc;
   unsigned int nv = 0, nf = 0;
   const unsigned int *dcounts = c->mesh_map + n;
@@ -3619,39 +3574,24 @@ int cspm_synthesize_host(int device, const cspm_synth_params *p, double t, const
     if (!in[v] || !in[v]->disp || !in[v]->bgr) return fail(nullptr, CSPM_ERR_ARG, "view synthesis: a view that `views` names has no disparity map or no image");
     if (in[v]->stride < (size_t)w * 3) return fail(nullptr, CSPM_ERR_ARG, "view synthesis: an image stride is below 3 * w");
   }
-  Scratch S;
-  int rc = cspm_create(&S.c, device);
-  if (rc) return rc;
-  cspm_ctx *c = S.c;
+  OneShot S(device);
   const size_t n = (size_t)w * h;
   SynthView sv[2] = {};
   for (int v = 0; v < 2; ++v) {
     if (!(p->views >> v & 1)) continue;
-    double *dd = nullptr, *da = nullptr;
-    uint8_t *dv = nullptr, *dbgr = nullptr;
-    uint32_t *dpix = nullptr;
-    if ((rc = dalloc(c, &dd, n, &S.tmp)) || (in[v]->valid && (rc = dalloc(c, &dv, n, &S.tmp))) || (in[v]->slope_a && (rc = dalloc(c, &da, n, &S.tmp))) ||
-        (rc = dalloc(c, &dbgr, 3 * n, &S.tmp)) || (rc = dalloc(c, &dpix, n, &S.tmp)))
-      return S.done(rc);
-    if (hipMemcpyAsync(dd, in[v]->disp, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-        (dv && hipMemcpyAsync(dv, in[v]->valid, n, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
-        (da && hipMemcpyAsync(da, in[v]->slope_a, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) ||
-        hipMemcpy2DAsync(dbgr, (size_t)w * 3, in[v]->bgr, in[v]->stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-      return S.done(fail(c, CSPM_ERR_HIP, "upload failed"));
-    hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, dbgr, (size_t)w * 3, w, h, w, 0, dpix);
-    sv[v] = SynthView{dd, dv, da, nullptr, dpix};
+    double *dd = S.up(in[v]->disp, n);
+    uint8_t *dv = S.up(in[v]->valid, n);
+    double *da = S.up(in[v]->slope_a, n);
+    sv[v] = SynthView{dd, dv, da, nullptr, S.up_bgr(in[v]->bgr, in[v]->stride, w, h)};
   }
-  uint8_t *dout = nullptr, *dmask = nullptr;
-  double *ddisp = nullptr;
-  if ((bgr_out && (rc = dalloc(c, &dout, 3 * n, &S.tmp))) || (disp_out && (rc = dalloc(c, &ddisp, n, &S.tmp))) || (mask_out && (rc = dalloc(c, &dmask, n, &S.tmp))))
-    return S.done(rc);
-  synth_launch(c->stream, sv[0], sv[1], p, t, SynthOut{dout, (size_t)w * 3, ddisp, dmask}, w, h);
-  if (hipGetLastError() != hipSuccess ||
-      (bgr_out && hipMemcpy2DAsync(bgr_out, out_stride, dout, (size_t)w * 3, (size_t)w * 3, h, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      (disp_out && hipMemcpyAsync(disp_out, ddisp, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) ||
-      (mask_out && hipMemcpyAsync(mask_out, dmask, n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) || hipStreamSynchronize(c->stream) != hipSuccess)
-    return S.done(fail(c, CSPM_ERR_HIP, "view synthesis kernel failed"));
-  return S.done(CSPM_OK);
+  uint8_t *dout = S.buf<uint8_t>(3 * n, bgr_out != nullptr), *dmask = S.buf<uint8_t>(n, mask_out != nullptr);
+  double *ddisp = S.buf<double>(n, disp_out != nullptr);
+  if (S.rc) return S.finish();
+  synth_launch(S.c->stream, sv[0], sv[1], p, t, SynthOut{dout, (size_t)w * 3, ddisp, dmask}, w, h);
+  S.down2d(bgr_out, out_stride, dout, (size_t)w * 3, h);
+  S.down(disp_out, ddisp, n);
+  S.down(mask_out, dmask, n);
+  return S.finish("view synthesis kernel failed");
 }
 
 // N on the stored field (cspm.h "view synthesis"): synchronous, host outputs
@@ -3661,14 +3601,12 @@ int cspm_synthesize(cspm_ctx *c, int source, const cspm_synth_params *p, double 
   if (rc) return rc;
   ON_DEVICE(c);
   const size_t n = (size_t)c->W * c->H, row = (size_t)c->W * 3;
-  std::vector<void *> tmp;
-  struct Free {
-    std::vector<void *> &t;
-    ~Free() { for (void *q : t) (void)hipFree(q); }
-  } free_tmp{tmp};
+  DevBufs tmp;
   uint8_t *dout = nullptr, *dmask = nullptr;
   double *ddisp = nullptr;
-  if ((bgr_out && (rc = dalloc(c, &dout, 3 * n, &tmp))) || (disp_out && (rc = dalloc(c, &ddisp, n, &tmp))) || (mask_out && (rc = dalloc(c, &dmask, n, &tmp)))) return rc;
+  if ((bgr_out && (rc = dalloc(c, &dout, 3 * n, &tmp.ptrs))) || (disp_out && (rc = dalloc(c, &ddisp, n, &tmp.ptrs))) ||
+      (mask_out && (rc = dalloc(c, &dmask, n, &tmp.ptrs))))
+    return rc;
   if ((rc = synthesize_enqueue(c, source, p, t, SynthOut{dout, row, ddisp, dmask}))) return rc;
   if (bgr_out) HIPCHK(c, hipMemcpy2DAsync(bgr_out, out_stride, dout, row, row, c->H, hipMemcpyDeviceToHost, c->stream));
   if (disp_out) HIPCHK(c, hipMemcpyAsync(disp_out, ddisp, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
@@ -3705,9 +3643,7 @@ int cspm_get_planes(cspm_ctx *c, int view, double *np_out, double *cost_out) {
   std::vector<double> h(7 * n);
   HIPCHK(c, hipMemcpyAsync(h.data(), c->f[view].nx, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  if (np_out)
-    for (size_t i = 0; i < n; ++i)
-      for (int k = 0; k < 6; ++k) np_out[6 * i + k] = h[k * n + i];
+  if (np_out) interleave_planes(h.data(), n, np_out);
   if (cost_out) memcpy(cost_out, h.data() + 6 * n, sizeof(double) * n);
   return CSPM_OK;
 }

@@ -42,6 +42,121 @@ def test_no_cpu_fallback_without_a_device():
     assert L.cspm_pm_default_params(C.byref(p)) == 0 and p.early_exit == 1  # pure host logic still answers
 
 
+def _one_shot_call(name, bad):
+    """One call of a one-shot host entry on 2 x 2 inputs, every output pre-filled with the byte 0xAB.  Returns (rc, outputs, the
+    message its argument check gives).  With `bad`, one argument is invalid, taken from the entry's own check."""
+    import numpy as np
+    L = cs.load_library()
+    dp, u8p, i32p = C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_int32)
+    outs = []
+
+    def out(nbytes):
+        outs.append(np.full(nbytes, 0xAB, np.uint8))
+        return outs[-1]
+
+    f64 = lambda n: out(8 * n).ctypes.data_as(dp)
+    u8 = lambda n: out(n).ctypes.data_as(u8p)
+    i32 = lambda n: out(4 * n).ctypes.data_as(i32p)
+    u32 = lambda n: out(4 * n).ctypes.data_as(C.POINTER(C.c_uint))
+    raw = lambda n: out(n).ctypes.data_as(C.c_void_p)
+    w = h = 2
+    n = w * h
+    disp = np.ones((h, w))
+    bgr = np.arange(3 * n, dtype=np.uint8).reshape(h, w, 3)
+    rgb = bgr.astype(np.float64)
+    calib = capi.Calib(100.0, 0.5, 0.5, 0.1, 0.0)
+    keep = [disp, bgr, rgb]  # inputs stay alive over the call
+    if name in ("cspm_grd_build_cv_host", "cspm_cen_build_cv_host", "cspm_cengrd_build_cv_host"):
+        rc = getattr(L, name)(0, capi._dp(rgb), capi._dp(rgb), w, h, 0 if bad else 2, 0, f64(2 * n))
+        msg = "bad arguments"
+    elif name == "cspm_aggregate_cv_host":
+        # 7 x 7: the smallest slabs BOX takes (its own check refuses 2 x 2 before the device), and two slices, since one is no work
+        guide = np.zeros((7, 7, 3))
+        keep.append(guide)
+        rc = L.cspm_aggregate_cv_host(0, 99 if bad else capi.CA_BOX, capi._dp(guide), 7, 7, 2, f64(2 * 49))
+        msg = "unknown aggregation method (CSPM_CA_BOX / GF / BF)"
+    elif name == "cspm_filter_speckles_host":
+        rc = L.cspm_filter_speckles_host(0, capi._dp(disp), None, w, h, -1 if bad else 1, 1.0, u8(n), i32(n))
+        msg = "bad arguments"
+    elif name == "cspm_fit_planes_host":
+        rc = L.cspm_fit_planes_host(0, capi._dp(disp), None, None, 0, w, h, -1 if bad else 4, None, f64(6 * n), u8(n))
+        msg = "bad arguments"
+    elif name == "cspm_segment_host":
+        K = L.cspm_segment_count(w, h, 16)
+        assert K == 1
+        rc = L.cspm_segment_host(0, capi._u8(bgr), 5 if bad else 6, w, h, None, i32(n), i32(5 * K), i32(K))
+        msg = "bad arguments"
+    elif name == "cspm_segment_planes_host":
+        labels = np.zeros(n, np.int32)
+        keep.append(labels)
+        rc = L.cspm_segment_planes_host(0, capi._dp(disp), None, capi._i32(labels), w, h, -1 if bad else 4, None, f64(3), i32(1), f64(6 * n), u8(n))
+        msg = "bad arguments"
+    elif name == "cspm_median_filter_u8_host":
+        src = np.arange(n, dtype=np.uint8)
+        keep.append(src)
+        rc = L.cspm_median_filter_u8_host(0, capi._u8(src), w, w, h, 1, 0 if bad else 1, u8(n), w)
+        msg = "bad arguments"
+    elif name == "cspm_median_filter_f64_host":
+        rc = L.cspm_median_filter_f64_host(0, capi._dp(disp), w, h, 0 if bad else 1, f64(n))
+        msg = "bad arguments"
+    elif name == "cspm_smooth_disparity_host":
+        rc = L.cspm_smooth_disparity_host(0, capi._dp(disp), None, None, w, h, None, -1 if bad else 4, f64(n))
+        msg = "bad arguments"
+    elif name == "cspm_reproject_host":
+        rc = L.cspm_reproject_host(0, C.byref(calib), None, 2 if bad else 0, capi._dp(disp), None, None, None, None, 0, w, h, f64(n), f64(3 * n), None,
+                                   u8(n), raw(32 * n), n, u32(1))
+        msg = "reprojection: view must be 0 or 1"
+    elif name == "cspm_mesh_host":
+        rc = L.cspm_mesh_host(0, C.byref(calib), None, None, 2 if bad else 0, capi._dp(disp), None, None, None, None, 0, w, h, raw(32 * n), n, raw(12 * 2), 2,
+                              u8(n), u32(1), u32(1))
+        msg = "reprojection: view must be 0 or 1"
+    elif name == "cspm_synthesize_host":
+        view = capi.SynthView(capi._dp(disp), None, None, capi._u8(bgr), 3 * w)
+        rc = L.cspm_synthesize_host(0, None, 2.0 if bad else 0.5, C.byref(view), C.byref(view), w, h, u8(3 * n), 3 * w, f64(n), u8(n))
+        msg = "view synthesis: t must be in [0, 1]"
+    elif name == "cspm_rectify_host":
+        cam = capi.Camera(2.0, 2.0, 0.5, 0.5, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+        eye = (C.c_double * 9)(1, 0, 0, 0, 1, 0, 0, 0, 1)
+        rig = capi.Rig((capi.Camera * 2)(cam, cam), eye, (C.c_double * 3)(-1.0, 0.0, 0.0), w, h)
+        rect = capi.Rectification()
+        assert L.cspm_rectify_compute(C.byref(rig), None, C.byref(rect), None) == 0, L.cspm_last_error(None)
+        m = rect.w * rect.h
+        rc = L.cspm_rectify_host(0, C.byref(rig), C.byref(rect), 2 if bad else 0, capi._u8(bgr), 3 * w, u8(3 * m), 3 * rect.w, f64(2 * m), u8(m))
+        msg = "rectification: view must be 0 or 1"
+    else:
+        raise AssertionError(name)
+    del keep
+    return rc, outs, msg
+
+
+ONE_SHOT_ENTRIES = sorted(s for s in capi.SYMBOLS if s.endswith("_host") and s != "cspm_merge_planes_host")  # that one works on a context
+
+
+def test_there_are_fifteen_one_shot_entries():
+    assert len(ONE_SHOT_ENTRIES) == 15
+
+
+@pytest.mark.parametrize("name", ONE_SHOT_ENTRIES)
+def test_one_shot_entry_without_a_device(name):
+    """valid arguments and no device: the HIP error code, cspm_create's message in the thread's creation error, no output written"""
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is present")
+    rc, outs, _ = _one_shot_call(name, bad=False)
+    assert rc == -2  # CSPM_ERR_HIP
+    assert cs.load_library().cspm_last_error(None).decode().startswith("no HIP device")
+    assert outs and all((o == 0xAB).all() for o in outs)
+
+
+@pytest.mark.parametrize("name", ONE_SHOT_ENTRIES)
+def test_one_shot_entry_checks_its_arguments_before_the_device(name):
+    """one invalid argument: CSPM_ERR_ARG and the check's own message, whether there is a device or not; no output written"""
+    rc, outs, msg = _one_shot_call(name, bad=True)
+    assert rc == -1  # CSPM_ERR_ARG
+    assert cs.load_library().cspm_last_error(None).decode() == msg and msg
+    assert outs and all((o == 0xAB).all() for o in outs)
+
+
 def test_product_does_not_reference_the_oracle():
     """The oracle is test infrastructure: nothing under crossscalepatchmatch_amd/ (the product) or tools/ (profiling and build
     helpers) may import, link or load it -- only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg do."""
