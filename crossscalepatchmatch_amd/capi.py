@@ -303,6 +303,54 @@ def _i32(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
+def _vp(a):
+    return C.c_void_p(a.ctypes.data)
+
+
+def _opt(conv, a):
+    """conv(a), or NULL for an optional argument that is not given"""
+    return None if a is None else conv(a)
+
+
+def _dev(a):
+    """a device pointer given as an integer; 0 = not requested"""
+    return C.c_void_p(a) if a else None
+
+
+def _check(rc, ctx=None):
+    """a failed call raises with the library's message: the context's, or the thread's for an entry that has none"""
+    if rc != 0:
+        raise CspmError(f"cspm error {rc}: {load_library().cspm_last_error(ctx).decode()}")
+
+
+def _params(cls, name, what, params, aliases={}):
+    """cls as cspm_<name>_default_params fills it, with the given fields replaced; a value becomes its field's C type"""
+    p = cls()
+    rc = getattr(load_library(), f"cspm_{name}_default_params")(C.byref(p))
+    assert rc == 0
+    kinds = dict(cls._fields_)
+    for k, v in params.items():
+        field = aliases.get(k, k)
+        if field not in kinds:
+            raise TypeError(f"unknown {what} parameter {k!r}")
+        setattr(p, field, float(v) if kinds[field] is C.c_double else int(v))
+    return p
+
+
+def _maps(disp, valid=None, maps=(), bgr=None):
+    """the host inputs the one-shot entries share, as the library reads them: disp (h, w) f64; valid (h, w) -> 0 / 1 bytes, or None;
+    every further f64 map (slopes, confidences) (h, w) or None; bgr (h, w, 3) uint8 or None"""
+    d = np.ascontiguousarray(disp, dtype=np.float64)
+    assert d.ndim == 2, d.shape
+    m = None if valid is None else np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+    assert m is None or m.shape == d.shape, m.shape
+    more = [None if a is None else np.ascontiguousarray(a, dtype=np.float64) for a in maps]
+    assert all(a is None or a.shape == d.shape for a in more)
+    g = None if bgr is None else np.ascontiguousarray(bgr, dtype=np.uint8)
+    assert g is None or g.shape == d.shape + (3,), g.shape
+    return d, m, more, g
+
+
 class StereoContext:
     """One cspm_ctx: one stereo pair on one GPU / stream."""
 
@@ -327,8 +375,7 @@ class StereoContext:
             pass
 
     def _chk(self, rc):
-        if rc != 0:
-            raise CspmError(f"cspm error {rc}: {self.L.cspm_last_error(self.p).decode()}")
+        _check(rc, self.p)
 
     # ---- images / cost ----
     def set_images(self, l_bgr, r_bgr):
@@ -551,7 +598,7 @@ class StereoContext:
         if mask is not None:
             m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
             assert m.shape == (self.h, self.w), m.shape
-        self._chk(self.L.cspm_merge_planes_host(self.p, view, _dp(f), _u8(m) if m is not None else None))
+        self._chk(self.L.cspm_merge_planes_host(self.p, view, _dp(f), _opt(_u8, m)))
 
     def merge_disparity(self, view, disp, fit=None):
         """a disparity map (h, w) offered as the fronto-parallel planes (0, 0, 1, 0, 0, d); a non-finite d is no candidate.
@@ -695,10 +742,9 @@ class StereoContext:
         cap = n if cloud_cap is None else int(cloud_cap)
         pts = np.zeros(cap, Point) if cloud else None
         count = C.c_uint(0)
-        self._chk(self.L.cspm_reproject(self.p, int(view), int(source), C.byref(k), C.byref(g), C.byref(f) if f is not None else None,
-                                        _dp(out["depth"]) if dense else None, _dp(out["xyz"]) if dense else None,
-                                        _dp(out["normal"]) if dense else None, _u8(out["keep"]) if dense else None,
-                                        C.c_void_p(pts.ctypes.data) if cloud else None, cap if cloud else 0, C.byref(count)))
+        self._chk(self.L.cspm_reproject(self.p, int(view), int(source), C.byref(k), C.byref(g), _opt(C.byref, f), _opt(_dp, out.get("depth")),
+                                        _opt(_dp, out.get("xyz")), _opt(_dp, out.get("normal")), _opt(_u8, out.get("keep")), _opt(_vp, pts),
+                                        cap if cloud else 0, C.byref(count)))
         out["count"] = count.value
         if cloud:
             out["cloud"] = pts[:min(count.value, cap)]
@@ -710,9 +756,8 @@ class StereoContext:
         asynchronous on the context's stream (cspm_reproject_device)"""
         k, g = calib_struct(calib), geom_params(**params)
         f = fit_params(**dict(fit)) if fit is not None else None
-        vp = lambda a: C.c_void_p(a) if a else None
-        self._chk(self.L.cspm_reproject_device(self.p, int(view), int(source), C.byref(k), C.byref(g), C.byref(f) if f is not None else None,
-                                               vp(d_depth), vp(d_xyz), vp(d_normal), vp(d_keep), vp(d_cloud), int(cloud_cap), vp(d_count)))
+        self._chk(self.L.cspm_reproject_device(self.p, int(view), int(source), C.byref(k), C.byref(g), _opt(C.byref, f), _dev(d_depth), _dev(d_xyz),
+                                               _dev(d_normal), _dev(d_keep), _dev(d_cloud), int(cloud_cap), _dev(d_count)))
 
     # ---- triangle meshes (DESIGN.md section 24) ----
     def mesh(self, view, calib, source=GEOM_RAW, fit=None, max_diff=1.0, all_vertices=0, vertices=True, faces=True, quad=True, vertex_cap=None,
@@ -729,10 +774,8 @@ class StereoContext:
         tri = np.zeros(fcap, Face) if faces else None
         q = np.zeros((self.h, self.w), np.uint8) if quad else None
         nv, nf = C.c_uint(0), C.c_uint(0)
-        self._chk(self.L.cspm_mesh(self.p, int(view), int(source), C.byref(k), C.byref(g), C.byref(f) if f is not None else None, C.byref(m),
-                                   C.c_void_p(pts.ctypes.data) if vertices else None, vcap if vertices else 0,
-                                   C.c_void_p(tri.ctypes.data) if faces else None, fcap if faces else 0, _u8(q) if quad else None,
-                                   C.byref(nv), C.byref(nf)))
+        self._chk(self.L.cspm_mesh(self.p, int(view), int(source), C.byref(k), C.byref(g), _opt(C.byref, f), C.byref(m), _opt(_vp, pts),
+                                   vcap if vertices else 0, _opt(_vp, tri), fcap if faces else 0, _opt(_u8, q), C.byref(nv), C.byref(nf)))
         out = {"n_vertices": nv.value, "n_faces": nf.value}
         if vertices:
             out["vertices"] = pts[:min(nv.value, vcap)]
@@ -748,9 +791,8 @@ class StereoContext:
         asynchronous on the context's stream (cspm_mesh_device)"""
         k, g, m = calib_struct(calib), geom_params(**params), mesh_params(max_diff=max_diff, all_vertices=all_vertices)
         f = fit_params(**dict(fit)) if fit is not None else None
-        vp = lambda a: C.c_void_p(a) if a else None
-        self._chk(self.L.cspm_mesh_device(self.p, int(view), int(source), C.byref(k), C.byref(g), C.byref(f) if f is not None else None, C.byref(m),
-                                          vp(d_vertices), int(vertex_cap), vp(d_faces), int(face_cap), vp(d_quad), vp(d_n_vertices), vp(d_n_faces)))
+        self._chk(self.L.cspm_mesh_device(self.p, int(view), int(source), C.byref(k), C.byref(g), _opt(C.byref, f), C.byref(m), _dev(d_vertices),
+                                          int(vertex_cap), _dev(d_faces), int(face_cap), _dev(d_quad), _dev(d_n_vertices), _dev(d_n_faces)))
 
     # ---- view synthesis (DESIGN.md section 20) ----
     def synthesize(self, t, source=GEOM_RAW, outputs=("bgr", "disp", "mask"), out=None, **params):
@@ -761,18 +803,16 @@ class StereoContext:
         p = synth_params(**params)
         res = _synth_outputs(self.h, self.w, outputs, out)
         b = res.get("bgr")
-        self._chk(self.L.cspm_synthesize(self.p, int(source), C.byref(p), float(t), _u8(b) if b is not None else None,
-                                         b.strides[0] if b is not None else 0, _dp(res["disp"]) if "disp" in res else None,
-                                         _u8(res["mask"]) if "mask" in res else None))
+        self._chk(self.L.cspm_synthesize(self.p, int(source), C.byref(p), float(t), _opt(_u8, b), b.strides[0] if b is not None else 0,
+                                         _opt(_dp, res.get("disp")), _opt(_u8, res.get("mask"))))
         return res
 
     def synthesize_device(self, t, source=GEOM_RAW, d_bgr=0, out_stride=0, d_disp=0, d_mask=0, **params):
         """the same with device pointers (integers; 0 = not requested): d_bgr rows of out_stride bytes (0 = 3 * w), d_disp h*w f64, d_mask
         h*w bytes; asynchronous on the context's stream (cspm_synthesize_device)"""
         p = synth_params(**params)
-        vp = lambda a: C.c_void_p(a) if a else None
-        self._chk(self.L.cspm_synthesize_device(self.p, int(source), C.byref(p), float(t), vp(d_bgr), int(out_stride) or 3 * self.w, vp(d_disp),
-                                                vp(d_mask)))
+        self._chk(self.L.cspm_synthesize_device(self.p, int(source), C.byref(p), float(t), _dev(d_bgr), int(out_stride) or 3 * self.w, _dev(d_disp),
+                                                _dev(d_mask)))
 
     # ---- measurement ----
     def enable_timing(self, on=True):
@@ -803,9 +843,7 @@ def aggregate_cv_host(device, method, guide, vol):
     g = np.ascontiguousarray(guide, dtype=np.float64)
     v = np.array(vol, dtype=np.float64, order="C", copy=True)
     assert g.ndim == 3 and g.shape[2] == 3 and v.ndim == 3 and v.shape[1:] == g.shape[:2]
-    rc = L.cspm_aggregate_cv_host(device, int(method), _dp(g), g.shape[1], g.shape[0], v.shape[0], _dp(v))
-    if rc != 0:
-        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    _check(L.cspm_aggregate_cv_host(device, int(method), _dp(g), g.shape[1], g.shape[0], v.shape[0], _dp(v)))
     return v
 
 
@@ -813,70 +851,36 @@ def filter_speckles(device, disp, valid, max_size, max_diff):
     """the speckle filter alone on a host map: disp (h, w) f64, valid (h, w) or None (every pixel).  Returns
     (valid_out u8, sizes int32): the mask without the components of at most max_size pixels, and every pixel's component size
     (0 outside the mask)."""
-    L = load_library()
-    d = np.ascontiguousarray(disp, dtype=np.float64)
-    assert d.ndim == 2
-    m = None
-    if valid is not None:
-        m = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
-        assert m.shape == d.shape, m.shape
+    d, m, _, _ = _maps(disp, valid)
     out = np.zeros(d.shape, np.uint8)
     sizes = np.zeros(d.shape, np.int32)
-    rc = L.cspm_filter_speckles_host(device, _dp(d), _u8(m) if m is not None else None, d.shape[1], d.shape[0], int(max_size), float(max_diff),
-                                     _u8(out), sizes.ctypes.data_as(C.POINTER(C.c_int32)))
-    if rc != 0:
-        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    _check(load_library().cspm_filter_speckles_host(device, _dp(d), _opt(_u8, m), d.shape[1], d.shape[0], int(max_size), float(max_diff), _u8(out),
+                                                    _i32(sizes)))
     return out, sizes
 
 
 def fit_params(**params):
     """struct cspm_fit_params: cspm_fit_default_params with the given fields replaced"""
-    p = FitParams()
-    rc = load_library().cspm_fit_default_params(C.byref(p))
-    assert rc == 0
-    for k, v in params.items():
-        if k not in ("radius", "max_diff", "min_support", "use_guide"):
-            raise TypeError(f"unknown plane-fit parameter {k!r}")
-        setattr(p, k, float(v) if k == "max_diff" else int(v))
-    return p
+    return _params(FitParams, "fit", "plane-fit", params)
 
 
 def fit_planes_host(disp, valid=None, guide=None, max_dis=0, device=0, **params):
     """slanted planes fitted to a host disparity map (cspm_fit_planes_host): disp (h, w) f64, valid (h, w) or
     None (every pixel), guide (h, w, 3) uint8 BGR or None (no guide weights).  Returns ((h, w, 6) planes in the layout of get_planes,
     (h, w) uint8 fitted); a pixel that is masked out or not finite gets six NaNs and fitted = 0."""
-    L = load_library()
-    d = np.ascontiguousarray(disp, dtype=np.float64)
-    assert d.ndim == 2
+    d, m, _, g = _maps(disp, valid, bgr=guide)
     h, w = d.shape
-    m = None
-    if valid is not None:
-        m = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
-        assert m.shape == d.shape, m.shape
-    g = None
-    if guide is not None:
-        g = np.ascontiguousarray(guide, dtype=np.uint8)
-        assert g.shape == (h, w, 3), g.shape
     p = fit_params(**params)
     planes = np.zeros((h, w, 6))
     fitted = np.zeros((h, w), np.uint8)
-    rc = L.cspm_fit_planes_host(device, _dp(d), _u8(m) if m is not None else None, _u8(g) if g is not None else None, w * 3, w, h, int(max_dis),
-                                C.byref(p), _dp(planes), _u8(fitted))
-    if rc != 0:
-        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    _check(load_library().cspm_fit_planes_host(device, _dp(d), _opt(_u8, m), _opt(_u8, g), w * 3, w, h, int(max_dis), C.byref(p), _dp(planes),
+                                               _u8(fitted)))
     return planes, fitted
 
 
 def seg_params(**params):
     """struct cspm_seg_params: cspm_seg_default_params with the given fields replaced"""
-    p = SegParams()
-    rc = load_library().cspm_seg_default_params(C.byref(p))
-    assert rc == 0
-    for k, v in params.items():
-        if k not in ("step", "compactness", "iters", "tau", "rounds", "min_support"):
-            raise TypeError(f"unknown segment-plane parameter {k!r}")
-        setattr(p, k, float(v) if k == "tau" else int(v))
-    return p
+    return _params(SegParams, "seg", "segment-plane", params)
 
 
 def segment_count(w, h, step):
@@ -899,9 +903,7 @@ def segment_host(bgr, device=0, **params):
     labels = np.zeros((h, w), np.int32)
     centres = np.zeros((K, 5), np.int32)
     counts = np.zeros(K, np.int32)
-    rc = L.cspm_segment_host(device, _u8(g), w * 3, w, h, C.byref(p), _i32(labels), _i32(centres), _i32(counts))
-    if rc != 0:
-        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    _check(L.cspm_segment_host(device, _u8(g), w * 3, w, h, C.byref(p), _i32(labels), _i32(centres), _i32(counts)))
     return labels, centres, counts
 
 
@@ -910,14 +912,8 @@ def segment_planes_host(disp, valid, labels, max_dis=0, device=0, **params):
     (h, w) or None (every pixel), labels (h, w) int32 for the grid of `step`.  Returns (seg_planes (K, 3) f64 (a, b, c), inliers (K,)
     int32, planes (h, w, 6) in the layout of get_planes, fitted (h, w) uint8); an unfitted segment has NaNs, 0 inliers, and its pixels six
     NaNs and fitted = 0.  params: step, tau, rounds, min_support."""
-    L = load_library()
-    d = np.ascontiguousarray(disp, dtype=np.float64)
-    assert d.ndim == 2
+    d, m, _, _ = _maps(disp, valid)
     h, w = d.shape
-    m = None
-    if valid is not None:
-        m = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
-        assert m.shape == d.shape, m.shape
     lab = np.ascontiguousarray(labels, dtype=np.int32)
     assert lab.shape == d.shape, lab.shape
     p = seg_params(**params)
@@ -926,10 +922,8 @@ def segment_planes_host(disp, valid, labels, max_dis=0, device=0, **params):
     inl = np.zeros(K, np.int32)
     planes = np.zeros((h, w, 6))
     fitted = np.zeros((h, w), np.uint8)
-    rc = L.cspm_segment_planes_host(device, _dp(d), _u8(m) if m is not None else None, _i32(lab), w, h, int(max_dis), C.byref(p), _dp(seg), _i32(inl),
-                                    _dp(planes), _u8(fitted))
-    if rc != 0:
-        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    _check(load_library().cspm_segment_planes_host(device, _dp(d), _opt(_u8, m), _i32(lab), w, h, int(max_dis), C.byref(p), _dp(seg), _i32(inl),
+                                                   _dp(planes), _u8(fitted)))
     return seg, inl, planes, fitted
 
 
@@ -943,14 +937,7 @@ def calib_struct(calib):
 
 def geom_params(**params):
     """struct cspm_geom_params: cspm_geom_default_params with the given fields replaced"""
-    p = GeomParams()
-    rc = load_library().cspm_geom_default_params(C.byref(p))
-    assert rc == 0
-    for k, v in params.items():
-        if k not in ("z_near", "z_far", "min_cos", "left_frame", "consistent_only"):
-            raise TypeError(f"unknown reprojection parameter {k!r}")
-        setattr(p, k, int(v) if k in ("left_frame", "consistent_only") else float(v))
-    return p
+    return _params(GeomParams, "geom", "reprojection", params)
 
 
 def reproject_host(calib, view, disp, valid=None, slope_a=None, slope_b=None, bgr=None, dense=("depth", "xyz", "normal", "keep"), cloud=True,
@@ -959,16 +946,8 @@ def reproject_host(calib, view, disp, valid=None, slope_a=None, slope_b=None, bg
     bgr (h, w, 3) uint8 or None.  dense: the dense outputs to compute (normal is dropped without slopes); cloud / cloud_cap / count as
     for StereoContext.reproject.  out: a dict of preallocated arrays to write into instead of fresh ones (tests poison them).
     Returns a dict with the requested arrays, `count` and `cloud`."""
-    L = load_library()
-    d = np.ascontiguousarray(disp, dtype=np.float64)
-    assert d.ndim == 2
+    d, m, (a, b), img = _maps(disp, valid, (slope_a, slope_b), bgr)
     h, w = d.shape
-    m = None if valid is None else np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
-    a = None if slope_a is None else np.ascontiguousarray(slope_a, dtype=np.float64)
-    b = None if slope_b is None else np.ascontiguousarray(slope_b, dtype=np.float64)
-    img = None if bgr is None else np.ascontiguousarray(bgr, dtype=np.uint8)
-    assert (m is None or m.shape == d.shape) and (a is None or a.shape == d.shape) and (b is None or b.shape == d.shape)
-    assert img is None or img.shape == (h, w, 3)
     k, g = calib_struct(calib), geom_params(**params)
     res = dict(out or {})
     shapes = {"depth": (h, w), "xyz": (3, h, w), "normal": (3, h, w), "keep": (h, w)}
@@ -985,12 +964,9 @@ def reproject_host(calib, view, disp, valid=None, slope_a=None, slope_b=None, bg
             pts = np.zeros(cap, Point)
     cnt = C.c_uint(0)
     ptr = lambda name, f: f(res[name]) if name in res and name in dense else None
-    rc = L.cspm_reproject_host(device, C.byref(k), C.byref(g), int(view), _dp(d), _u8(m) if m is not None else None,
-                               _dp(a) if a is not None else None, _dp(b) if b is not None else None, _u8(img) if img is not None else None, w * 3, w, h,
-                               ptr("depth", _dp), ptr("xyz", _dp), ptr("normal", _dp), ptr("keep", _u8),
-                               C.c_void_p(pts.ctypes.data) if pts is not None else None, cap if pts is not None else 0, C.byref(cnt) if count else None)
-    if rc != 0:
-        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    _check(load_library().cspm_reproject_host(device, C.byref(k), C.byref(g), int(view), _dp(d), _opt(_u8, m), _opt(_dp, a), _opt(_dp, b), _opt(_u8, img),
+                                              w * 3, w, h, ptr("depth", _dp), ptr("xyz", _dp), ptr("normal", _dp), ptr("keep", _u8), _opt(_vp, pts),
+                                              cap if pts is not None else 0, C.byref(cnt) if count else None))
     if count:
         res["count"] = cnt.value
     if pts is not None:
@@ -1000,14 +976,7 @@ def reproject_host(calib, view, disp, valid=None, slope_a=None, slope_b=None, bg
 
 def mesh_params(**params):
     """struct cspm_mesh_params: cspm_mesh_default_params with the given fields replaced"""
-    p = MeshParams()
-    rc = load_library().cspm_mesh_default_params(C.byref(p))
-    assert rc == 0
-    for k, v in params.items():
-        if k not in ("max_diff", "all_vertices"):
-            raise TypeError(f"unknown mesh parameter {k!r}")
-        setattr(p, k, int(v) if k == "all_vertices" else float(v))
-    return p
+    return _params(MeshParams, "mesh", "mesh", params)
 
 
 def mesh_host(calib, view, disp, valid=None, slope_a=None, slope_b=None, bgr=None, max_diff=1.0, all_vertices=0, vertices=True, faces=True, quad=True,
@@ -1016,16 +985,8 @@ def mesh_host(calib, view, disp, valid=None, slope_a=None, slope_b=None, bgr=Non
     cspm_mesh_params, params the reprojection parameters.  out: a dict of preallocated arrays ("vertex_buffer", "face_buffer", "quad")
     to write into instead of fresh ones (tests poison them).  Returns a dict with n_vertices, n_faces (with counts) and the requested
     vertices, faces and quad."""
-    L = load_library()
-    d = np.ascontiguousarray(disp, dtype=np.float64)
-    assert d.ndim == 2
+    d, vm, (a, b), img = _maps(disp, valid, (slope_a, slope_b), bgr)
     h, w = d.shape
-    vm = None if valid is None else np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
-    a = None if slope_a is None else np.ascontiguousarray(slope_a, dtype=np.float64)
-    b = None if slope_b is None else np.ascontiguousarray(slope_b, dtype=np.float64)
-    img = None if bgr is None else np.ascontiguousarray(bgr, dtype=np.uint8)
-    assert (vm is None or vm.shape == d.shape) and (a is None or a.shape == d.shape) and (b is None or b.shape == d.shape)
-    assert img is None or img.shape == (h, w, 3)
     k, g, m = calib_struct(calib), geom_params(**params), mesh_params(max_diff=max_diff, all_vertices=all_vertices)
     res = dict(out or {})
     vcap = w * h if vertex_cap is None else int(vertex_cap)
@@ -1044,13 +1005,9 @@ def mesh_host(calib, view, disp, valid=None, slope_a=None, slope_b=None, bgr=Non
         if q is None:
             q = res["quad"] = np.zeros((h, w), np.uint8)
     nv, nf = C.c_uint(0), C.c_uint(0)
-    rc = L.cspm_mesh_host(device, C.byref(k), C.byref(g), C.byref(m), int(view), _dp(d), _u8(vm) if vm is not None else None,
-                          _dp(a) if a is not None else None, _dp(b) if b is not None else None, _u8(img) if img is not None else None, w * 3, w, h,
-                          C.c_void_p(pts.ctypes.data) if pts is not None else None, vcap if pts is not None else 0,
-                          C.c_void_p(tri.ctypes.data) if tri is not None else None, fcap if tri is not None else 0, _u8(q) if q is not None else None,
-                          C.byref(nv) if counts else None, C.byref(nf) if counts else None)
-    if rc != 0:
-        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    _check(load_library().cspm_mesh_host(device, C.byref(k), C.byref(g), C.byref(m), int(view), _dp(d), _opt(_u8, vm), _opt(_dp, a), _opt(_dp, b),
+                                         _opt(_u8, img), w * 3, w, h, _opt(_vp, pts), vcap if pts is not None else 0, _opt(_vp, tri),
+                                         fcap if tri is not None else 0, _opt(_u8, q), C.byref(nv) if counts else None, C.byref(nf) if counts else None))
     if counts:
         res["n_vertices"], res["n_faces"] = nv.value, nf.value
     if pts is not None:
@@ -1076,23 +1033,14 @@ def make_rig(cam0, cam1, R, T, raw_w, raw_h):
 
 def rect_params(**params):
     """a RectParams from keywords f, cx, cy, w, h over the library's defaults (everything automatic)"""
-    p = RectParams()
-    load_library().cspm_rect_default_params(C.byref(p))
-    for k, v in params.items():
-        if k not in ("f", "cx", "cy", "w", "h"):
-            raise TypeError(f"unknown rectification parameter {k!r}")
-        setattr(p, k, v)
-    return p
+    return _params(RectParams, "rect", "rectification", params)
 
 
 def rectify_compute(rig, **params):
     """the rectifying rotations, the common projection and the cspm_calib of the rectified pair (cspm_rectify_compute): pure host logic,
     answers without a GPU.  Returns (Rectification, Calib)."""
-    L = load_library()
     p, rect, calib = rect_params(**params), Rectification(), Calib()
-    rc = L.cspm_rectify_compute(C.byref(rig), C.byref(p), C.byref(rect), C.byref(calib))
-    if rc != 0:
-        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    _check(load_library().cspm_rectify_compute(C.byref(rig), C.byref(p), C.byref(rect), C.byref(calib)))
     return rect, calib
 
 
@@ -1111,11 +1059,8 @@ def rectify_host(rig, rect, view, raw=None, outputs=("bgr", "map", "valid"), raw
         res["valid"] = np.empty((h, w), np.uint8)
     r = np.ascontiguousarray(raw, dtype=np.uint8) if raw is not None else None
     stride = raw_stride if raw_stride is not None else rig.raw_w * 3
-    rc = L.cspm_rectify_host(device, C.byref(rig), C.byref(rect), int(view), _u8(r) if r is not None else None, stride,
-                             _u8(res["bgr_rows"]) if "bgr_rows" in res else None, out_stride if out_stride is not None else w * 3,
-                             _dp(res["map"]) if "map" in res else None, _u8(res["valid"]) if "valid" in res else None)
-    if rc != 0:
-        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    _check(L.cspm_rectify_host(device, C.byref(rig), C.byref(rect), int(view), _opt(_u8, r), stride, _opt(_u8, res.get("bgr_rows")),
+                               out_stride if out_stride is not None else w * 3, _opt(_dp, res.get("map")), _opt(_u8, res.get("valid"))))
     if "bgr_rows" in res:
         res["bgr"] = np.ascontiguousarray(res["bgr_rows"][:, :w * 3]).reshape(h, w, 3)
     return res
@@ -1123,14 +1068,7 @@ def rectify_host(rig, rect, view, raw=None, outputs=("bgr", "map", "valid"), raw
 
 def synth_params(**params):
     """struct cspm_synth_params: cspm_synth_default_params with the given fields replaced"""
-    p = SynthParams()
-    rc = load_library().cspm_synth_default_params(C.byref(p))
-    assert rc == 0
-    for k, v in params.items():
-        if k not in ("views", "fill", "max_stretch", "merge_diff"):
-            raise TypeError(f"unknown view-synthesis parameter {k!r}")
-        setattr(p, k, int(v) if k in ("views", "fill") else float(v))
-    return p
+    return _params(SynthParams, "synth", "view-synthesis", params)
 
 
 def _synth_outputs(h, w, outputs, out):
@@ -1171,55 +1109,31 @@ def synthesize_host(t, disp, bgr, valid=(None, None), slope_a=(None, None), outp
         a = None if slope_a[v] is None else np.ascontiguousarray(slope_a[v], dtype=np.float64)
         assert (m is None or m.shape == shape) and (a is None or a.shape == shape)
         keep += [d, img, m, a]
-        views.append(SynthView(_dp(d), _u8(m) if m is not None else None, _dp(a) if a is not None else None, _u8(img), img.strides[0]))
+        views.append(SynthView(_dp(d), _opt(_u8, m), _opt(_dp, a), _u8(img), img.strides[0]))
     assert shape is not None, "no source view"
     h, w = shape
     res = _synth_outputs(h, w, outputs, out)
     b = res.get("bgr")
-    rc = L.cspm_synthesize_host(device, C.byref(p), float(t), C.byref(views[0]) if views[0] is not None else None,
-                                C.byref(views[1]) if views[1] is not None else None, w, h, _u8(b) if b is not None else None,
-                                b.strides[0] if b is not None else 0, _dp(res["disp"]) if "disp" in res else None,
-                                _u8(res["mask"]) if "mask" in res else None)
-    if rc != 0:
-        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    _check(L.cspm_synthesize_host(device, C.byref(p), float(t), _opt(C.byref, views[0]), _opt(C.byref, views[1]), w, h, _opt(_u8, b),
+                                  b.strides[0] if b is not None else 0, _opt(_dp, res.get("disp")), _opt(_u8, res.get("mask"))))
     return res
 
 
 def smooth_params(**params):
     """struct cspm_smooth_params: cspm_smooth_default_params with the given fields replaced.  `lambda` is a Python keyword: the field
     is given as lam (or as "lambda" through a dict)."""
-    p = SmoothParams()
-    rc = load_library().cspm_smooth_default_params(C.byref(p))
-    assert rc == 0
-    for k, v in params.items():
-        if k in ("lam", "lambda", "lambda_"):
-            p.lambda_ = float(v)
-        elif k in ("sigma_color", "fill_conf"):
-            setattr(p, k, float(v))
-        elif k == "iterations":
-            p.iterations = int(v)
-        else:
-            raise TypeError(f"unknown smoothing parameter {k!r}")
-    return p
+    return _params(SmoothParams, "smooth", "smoothing", params, {"lam": "lambda_", "lambda": "lambda_"})
 
 
 def smooth_disparity(device, disp, conf=None, guide=None, max_dis=0, **params):
     """the edge-aware global smoother alone (cspm_smooth_disparity_host) on a host map: disp (h, w) f64 (a
     non-finite pixel is a hole), conf (h, w) f64 in [0, 1] or None (all 1), guide (h, w, 3) uint8 BGR or None (every weight 1);
     params: lam, sigma_color, iterations; max_dis > 0 clamps the smoothed values to [0, max_dis].  Returns a new (h, w) f64 map."""
-    L = load_library()
     p = smooth_params(**params)
-    d = np.ascontiguousarray(disp, dtype=np.float64)
-    assert d.ndim == 2, d.shape
-    h, w = d.shape
-    c = None if conf is None else np.ascontiguousarray(conf, dtype=np.float64)
-    g = None if guide is None else np.ascontiguousarray(guide, dtype=np.uint8)
-    assert (c is None or c.shape == (h, w)) and (g is None or g.shape == (h, w, 3))
+    d, _, (c,), g = _maps(disp, None, (conf,), guide)
     out = np.zeros_like(d)
-    rc = L.cspm_smooth_disparity_host(device, _dp(d), _dp(c) if c is not None else None, _u8(g) if g is not None else None, w, h, C.byref(p),
-                                      int(max_dis), _dp(out))
-    if rc != 0:
-        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    _check(load_library().cspm_smooth_disparity_host(device, _dp(d), _opt(_dp, c), _opt(_u8, g), d.shape[1], d.shape[0], C.byref(p), int(max_dis),
+                                                     _dp(out)))
     return out
 
 
@@ -1242,8 +1156,7 @@ def median_filter(device, img, r):
         rc = L.cspm_median_filter_f64_host(device, _dp(src), src.shape[1], src.shape[0], int(r), _dp(out))
     else:
         raise TypeError(f"median_filter takes uint8 or float64 images, not {a.dtype}")
-    if rc != 0:
-        raise CspmError(f"cspm error {rc}: {L.cspm_last_error(None).decode()}")
+    _check(rc)
     return out
 
 

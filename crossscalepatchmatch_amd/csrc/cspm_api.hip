@@ -208,7 +208,7 @@ struct cspm_ctx {
   long long sweep_timeout_ms = 3000;  // CSPM_OPT_SWEEP_TIMEOUT_MS (env CSPM_SWEEP_TIMEOUT_MS): bound of one wait for a predecessor pixel
   Repeat repeat;                      // when a run is repeated after a sweep timeout
   double *warm_snap = nullptr;        // the starting field of the last warm run (both views, 7 arrays each), kept with the field
-  double *cand_mem = nullptr;         // cspm_merge_planes_host: one view's candidate planes (6 arrays) and, behind them, its mask bytes; allocated by the first such call and kept with the field
+  double *cand_mem = nullptr;         // cspm_merge_planes_host, cspm_fit_planes, cspm_segment_planes: one view's candidate planes (6 arrays) and, behind them, its mask bytes (ensure_cand); allocated by the first such call and kept with the field
   double *fit_mem = nullptr;          // cspm_fit_planes: both views' disparity snapshots (2 arrays) and, behind them, the exp(-k/10) table; allocated by the first such call and kept with the field
   char *seg_mem = nullptr;            // cspm_segment_planes: both views' disparity snapshots and labels, then centres, counts and segment planes for the finest grid (step 4); allocated by the first such call and kept with the field
   bool seg_ran = false;               // cspm_get_segments: seg_mem holds the labels of a call
@@ -283,19 +283,42 @@ int dalloc(cspm_ctx *c, T **p, size_t n, std::vector<void *> *track) {
   return CSPM_OK;
 }
 
-// the device temporaries of one call (dalloc(.., &tmp.ptrs)): freed when the scope ends, on every path.  Declared behind ON_DEVICE, so that
-// the frees run on the buffers' device
-struct DevBufs {
-  std::vector<void *> ptrs;
-  ~DevBufs() {
-    for (void *p : ptrs) (void)hipFree(p);
-  }
-};
-
-// channel-major planes (six slabs of n values, as the device holds a field) into the interleaved records of the ABI
+// channel-major planes (six slabs of n values, as the device holds a field) into the interleaved records of the ABI, and back
 void interleave_planes(const double *planar, size_t n, double *np_out) {
   for (size_t i = 0; i < n; ++i)
     for (int k = 0; k < 6; ++k) np_out[6 * i + k] = planar[k * n + i];
+}
+void deinterleave_planes(const double *np, size_t n, double *planar_out) {
+  for (size_t i = 0; i < n; ++i)
+    for (int k = 0; k < 6; ++k) planar_out[k * n + i] = np[6 * i + k];
+}
+
+// six slabs of n doubles behind one base: the plane arrays of a field without its costs, to read (SnapField) or to fit into (FitOut)
+struct Slabs6 {
+  double *p[6];
+  SnapField snap() const { return SnapField{p[0], p[1], p[2], p[3], p[4], p[5]}; }
+  FitOut fit_out(uint8_t *fitted, int keep_unfitted) const { return FitOut{p[0], p[1], p[2], p[3], p[4], p[5], fitted, keep_unfitted}; }
+};
+inline Slabs6 six_slabs(double *b, size_t n) { return Slabs6{{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n}}; }
+
+// the candidate buffer cand_mem of cspm_merge_planes_host, cspm_fit_planes and cspm_segment_planes: one view's candidate planes and, behind
+// them, its mask bytes (48 + 1 bytes per pixel); allocated by the first call that needs it and kept with the field
+struct CandBuf {
+  Slabs6 planes;
+  uint8_t *mask;
+  FitOut fit_out() const { return planes.fit_out(mask, 0); }  // a non-node's planes become NaN, its mask byte 0
+  CandField field(int view, bool masked = true) const {       // the one-view candidate field do_merge reads
+    CandField cf{};
+    cf.s[view] = planes.snap();
+    cf.mask[view] = masked ? mask : nullptr;
+    return cf;
+  }
+};
+int ensure_cand(cspm_ctx *c, CandBuf *out) {
+  const size_t n = (size_t)c->W * c->H;
+  int rc = c->cand_mem ? CSPM_OK : dalloc(c, &c->cand_mem, 6 * n + (n + 7) / 8, nullptr);
+  if (!rc) *out = CandBuf{six_slabs(c->cand_mem, n), reinterpret_cast<uint8_t *>(c->cand_mem + 6 * n)};
+  return rc;
 }
 
 hipEvent_t get_event(cspm_ctx *c) {
@@ -1122,10 +1145,7 @@ int do_spatial(cspm_ctx *c, int iter, const cspm_pm_params *p) {
       df.off[k][0] = (signed char)(inc * off[k][0]);
       df.off[k][1] = (signed char)(inc * off[k][1]);
     }
-    for (int v = 0; v < 2; ++v) {
-      const double *b = c->diffuse_snap + (size_t)v * 6 * n;
-      df.s[v] = SnapField{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n};
-    }
+    for (int v = 0; v < 2; ++v) df.s[v] = six_slabs(c->diffuse_snap + (size_t)v * 6 * n, n).snap();
     const long long items = 2LL * c->W * c->H;
     for (int r = 0; r < p->rb_rounds; ++r) {
       Timed t(c, CSPM_K_SPATIAL, items * df.K);  // the snapshot copies are part of the round's time: not LAUNCH_ROWS, which times the launch alone
@@ -1765,8 +1785,7 @@ GeomIn geom_inputs_launch(cspm_ctx *c, int view, int source, const cspm_geom_par
   }
   if (fit) {
     double *b = c->geom_fit;
-    fit_launch(c->stream, FitIn{in.disp, in.valid, c->img0[view], c->geom_fit + 6 * n}, FitOut{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, nullptr, 0},
-               c->W, c->H, fit, c->max_dis);
+    fit_launch(c->stream, FitIn{in.disp, in.valid, c->img0[view], c->geom_fit + 6 * n}, six_slabs(b, n).fit_out(nullptr, 0), c->W, c->H, fit, c->max_dis);
     in.a = b + 3 * n; in.b = b + 4 * n;
     in.slope_mask = nullptr;
   }
@@ -2188,40 +2207,48 @@ inline void rect_remap_launch(hipStream_t stream, const uint8_t *raw_bgr, size_t
                      raw_w, raw_h, w, h, dst, dst_stride);
 }
 
-// A one-shot host entry (cspm_*_host: one kernel family alone on caller memory) checks its arguments, then stages
-// its buffers on a OneShot, launches on S.c->stream, downloads and returns S.finish(..).  The OneShot is a temporary context on `device`
-// with device buffers of its own, and everything between its construction and its destruction runs on that device; the caller's current
-// device comes back when it goes.  The first failure sticks in `rc` and turns every later member call into a no-op (a null pointer), so a
-// body is straight-line code with one `if (S.rc) return S.finish();` before its launches.  The message of a failure stays behind as the
-// thread's creation error (cspm_last_error(NULL)).
-struct OneShot {
-  cspm_ctx *c = nullptr;
+// What an entry moves between caller memory and the device goes through a Staging on the context's stream: device
+// temporaries, uploads, downloads and one latched status.  The first failure sticks in `rc` and turns every later member call into a
+// no-op (a null pointer), so a body is straight-line code: stage, `if (S.rc) return S.finish();`, launch on S.c->stream, download,
+// `return S.finish("what failed")`.  The temporaries are freed when the Staging goes, on every path.  No path returns while a copy to or
+// from caller memory that this call enqueued is outstanding: a failure waits on the stream before it is latched, finish() waits, and
+// whichever other way the body returns, ~Staging waits (a host buffer of the body's own that a copy uses is declared BEFORE the Staging).
+// The message of a failure is the context's.  A context entry declares its Staging behind ON_DEVICE, so that the frees run on the
+// buffers' device; a one-shot entry uses a OneShot.
+struct Staging {
+  cspm_ctx *c;
   int rc;
-  std::optional<DevGuard> guard;
-  DevBufs bufs;
-  bool broke = false;  // a launch or a download failed: finish() names it
+  std::vector<void *> bufs;
+  bool broke = false;   // a launch or a download failed: finish() names it
+  bool settled = true;  // no copy enqueued here since the last wait
 
-  explicit OneShot(int device) : rc(cspm_create(&c, device)) {
-    if (rc) return;
-    guard.emplace(device);
-    if (!guard->ok) fail(CSPM_ERR_HIP, "hipSetDevice failed");
+  explicit Staging(cspm_ctx *ctx, int status = CSPM_OK) : c(ctx), rc(status) {}
+  Staging(const Staging &) = delete;
+  ~Staging() {
+    if (!settled) wait();
+    for (void *p : bufs) (void)hipFree(p);
   }
-  ~OneShot() { cspm_destroy(c); }  // waits for the stream; then the buffers go, then the guard
-
-  int fail(int code, const char *msg) {
-    if (!rc) rc = ::fail(c, code, msg);
-    return rc;
+  bool wait() { return settled = hipStreamSynchronize(c->stream) == hipSuccess; }
+  bool copied(hipError_t e) { return settled = false, e == hipSuccess; }  // the result of a copy that was just enqueued
+  int latch(int status) {
+    if (status && !rc && !settled) wait();
+    return rc = rc ? rc : status;
   }
+  int fail(int code, const char *msg) { return rc ? rc : latch(::fail(c, code, msg)); }
   // n elements on the device; null when !want
   template <class T>
   T *buf(size_t n, bool want = true) {
     T *p = nullptr;
-    if (!rc && want) rc = dalloc(c, &p, n, &bufs.ptrs);
+    if (!rc && want) latch(dalloc(c, &p, n, &bufs));
     return p;
   }
   template <class T>
   void put(T *dev, const T *host, size_t n) {
-    if (!rc && hipMemcpyAsync(dev, host, sizeof(T) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) fail(CSPM_ERR_HIP, "upload failed");
+    if (!rc && !copied(hipMemcpyAsync(dev, host, sizeof(T) * n, hipMemcpyHostToDevice, c->stream))) fail(CSPM_ERR_HIP, "upload failed");
+  }
+  // `rows` rows of `row` bytes that lie `stride` bytes apart, `pitch` bytes apart on the device
+  void put2d(void *dev, size_t pitch, const void *host, size_t stride, size_t row, size_t rows) {
+    if (!rc && !copied(hipMemcpy2DAsync(dev, pitch, host, stride, row, rows, hipMemcpyHostToDevice, c->stream))) fail(CSPM_ERR_HIP, "upload failed");
   }
   void fill(void *dev, int byte, size_t bytes) {
     if (!rc && hipMemsetAsync(dev, byte, bytes, c->stream) != hipSuccess) fail(CSPM_ERR_HIP, "upload failed");
@@ -2233,10 +2260,10 @@ struct OneShot {
     if (host) put(p, host, n);
     return p;
   }
-  // the same for `rows` rows of `row` bytes that lie `stride` bytes apart: packed on the device
+  // the same for rows that lie `stride` bytes apart: packed on the device
   uint8_t *up2d(const uint8_t *host, size_t stride, size_t row, size_t rows) {
     uint8_t *p = buf<uint8_t>(row * rows, host != nullptr);
-    if (host && !rc && hipMemcpy2DAsync(p, row, host, stride, row, rows, hipMemcpyHostToDevice, c->stream) != hipSuccess) fail(CSPM_ERR_HIP, "upload failed");
+    if (host) put2d(p, row, host, stride, row, rows);
     return p;
   }
   // an 8UC3 image as the packed words the kernels read (k_pack_bgr); null for a null host pointer
@@ -2249,19 +2276,80 @@ struct OneShot {
   // downloads: nothing for a null host pointer or no elements, and nothing behind a launch that failed
   template <class T>
   void down(T *host, const void *dev, size_t n) {
-    if (host && n && !rc && !broke) broke = hipGetLastError() != hipSuccess || hipMemcpyAsync(host, dev, sizeof(T) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess;
+    if (host && n && !rc && !broke) broke = hipGetLastError() != hipSuccess || !copied(hipMemcpyAsync(host, dev, sizeof(T) * n, hipMemcpyDeviceToHost, c->stream));
   }
   void down2d(uint8_t *host, size_t stride, const uint8_t *dev, size_t row, size_t rows) {
     if (host && !rc && !broke)
-      broke = hipGetLastError() != hipSuccess || hipMemcpy2DAsync(host, stride, dev, row, row, rows, hipMemcpyDeviceToHost, c->stream) != hipSuccess;
+      broke = hipGetLastError() != hipSuccess || !copied(hipMemcpy2DAsync(host, stride, dev, row, row, rows, hipMemcpyDeviceToHost, c->stream));
   }
-  // waits for the launches and downloads so far: `failed` is the message if one of them did not succeed
+  // waits for the launches and copies so far: `failed` is the message if one of them did not succeed
   int finish(const char *failed = "") {
-    if (!rc && (broke || hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess)) fail(CSPM_ERR_HIP, failed);
-    if (rc && c) g_create_error = c->err;
+    if (!rc && (broke || hipGetLastError() != hipSuccess || !wait())) fail(CSPM_ERR_HIP, failed);
     return rc;
   }
 };
+
+// A one-shot host entry (cspm_*_host: one kernel family alone on caller memory) checks its arguments, then stages on a OneShot: a
+// temporary context on `device` and the Staging on it.  Everything between its construction and its destruction runs on that device; the
+// caller's current device comes back when it goes.  The message of a failure stays behind as the thread's creation error
+// (cspm_last_error(NULL)).
+struct TempCtx {
+  cspm_ctx *ctx = nullptr;
+  int created;
+  std::optional<DevGuard> guard;
+  explicit TempCtx(int device) : created(cspm_create(&ctx, device)) {
+    if (!created && !guard.emplace(device).ok) created = fail(ctx, CSPM_ERR_HIP, "hipSetDevice failed");
+  }
+  ~TempCtx() { cspm_destroy(ctx); }  // behind ~Staging; waits for the stream, then the guard goes
+};
+struct OneShot : TempCtx, Staging {
+  explicit OneShot(int device) : TempCtx(device), Staging(ctx, created) {}
+  int finish(const char *failed = "") {
+    if (Staging::finish(failed) && c) g_create_error = c->err;
+    return rc;
+  }
+};
+
+// cspm_fit_planes and cspm_segment_planes behind their parameter checks: planes fitted to the stored field's own disparity maps replace
+// the field or, with `merge`, are merged into it as candidates, view by view.  `scratch` allocates what the entry keeps and names the
+// two disparity snapshots (n doubles per view); `fit_view(v, d, out)` enqueues the launches that fit view v's snapshot d into `out`.
+template <class Scratch, class FitView>
+int fit_stored_field(cspm_ctx *c, int merge, int max_rows, const char *too_high, Scratch scratch, FitView fit_view) {
+  if (!c->img0[0]) return fail(c, CSPM_ERR_STATE, "cspm_set_images first");
+  int rc;
+  if ((rc = need_field(c, "no plane field to fit (cspm_local_stereo, cspm_set_planes, cspm_pm_init or an earlier run)"))) return rc;
+  if (merge && (rc = need_cost(c))) return rc;
+  if (c->max_dis < 1) return fail(c, CSPM_ERR_STATE, "no max_dis known: build a cost object (or cspm_fpm_begin) first");
+  if (c->H > max_rows) return fail(c, CSPM_ERR_ARG, too_high);
+  ON_DEVICE(c);
+  const size_t n = (size_t)c->W * c->H;
+  double *snap = nullptr;
+  if ((rc = scratch(&snap))) return rc;
+  CandBuf cand{};
+  if (merge) {
+    if ((rc = ensure_cand(c, &cand)) || (rc = ensure_consistent(c))) return rc;
+  } else {
+    c->field_consistent = false;  // min_cost still belongs to the planes that were replaced
+  }
+  c->repeat.taint_unchecked_run();  // it can no longer be repeated over these planes
+  const Pm pm = field_pm(c);
+  for (int v = 0; v < 2; ++v) {
+    double *d = snap + (size_t)v * n;
+    const Field &f = c->f[v];
+    const FitOut out = merge ? cand.fit_out() : FitOut{f.nx, f.ny, f.nz, f.a, f.b, f.c, nullptr, 1};
+    {
+      Timed t(c, CSPM_K_MISC, (long long)n);
+      hipLaunchKernelGGL(k_plane_to_disp_f64, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, pm, v, d);
+      fit_view(v, d, out);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (merge) {
+      const CandField cf = cand.field(v);
+      if ((rc = do_merge(c, &cf, &kDefaultParams, v, 1, (long long)n))) return rc;
+    }
+  }
+  return CSPM_OK;
+}
 
 }  // namespace
 
@@ -2379,32 +2467,24 @@ static int set_images_impl(cspm_ctx *c, const void *l, const void *r, int w, int
   if (!on_device && c->stage_bytes < 2 * row * h) {
     dfree(c->stage);
     c->stage_bytes = 0;
-    HIPCHK(c, hipMalloc((void **)&c->stage, 2 * row * h));
+    if (int rc = dalloc(c, &c->stage, 2 * row * h, nullptr)) return rc;
     c->stage_bytes = 2 * row * h;
   }
+  Staging S(c);
   for (int v = 0; v < 2; ++v) {
-    const uint8_t *d_src = (const uint8_t *)src[v];
-    size_t d_stride = stride;
-    if (!on_device) {
-      uint8_t *dst = c->stage + (size_t)v * row * h;
-      HIPCHK(c, hipMemcpy2DAsync(dst, row, src[v], stride, row, h, hipMemcpyHostToDevice, c->stream));
-      d_src = dst;
-      d_stride = row;
-    }
+    uint8_t *staged = on_device ? nullptr : c->stage + (size_t)v * row * h;
+    if (staged) S.put2d(staged, row, src[v], stride, row, h);
+    if (S.rc) return S.rc;
     Timed t(c, CSPM_K_MISC, 0);
-    hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)w * h)), dim3(256), 0, c->stream, d_src, d_stride, w, h, w, 0, c->img0[v]);
+    hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)w * h)), dim3(256), 0, c->stream, staged ? staged : (const uint8_t *)src[v], staged ? row : stride, w,
+                       h, w, 0, c->img0[v]);
   }
   HIPCHK(c, hipGetLastError());
-  if (!on_device) HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller may reuse its host buffers
-  return CSPM_OK;
+  return on_device ? CSPM_OK : S.finish("image upload failed");  // the caller may reuse its host buffers
 }
 
-int cspm_set_images(cspm_ctx *c, const uint8_t *l, const uint8_t *r, int w, int h, size_t stride) {
-  return set_images_impl(c, l, r, w, h, stride, false);
-}
-int cspm_set_images_device(cspm_ctx *c, const void *l, const void *r, int w, int h, size_t stride) {
-  return set_images_impl(c, l, r, w, h, stride, true);
-}
+int cspm_set_images(cspm_ctx *c, const uint8_t *l, const uint8_t *r, int w, int h, size_t stride) { return set_images_impl(c, l, r, w, h, stride, false); }
+int cspm_set_images_device(cspm_ctx *c, const void *l, const void *r, int w, int h, size_t stride) { return set_images_impl(c, l, r, w, h, stride, true); }
 
 int cspm_set_option(cspm_ctx *c, int key, long long value) {
   if (!c) return CSPM_ERR_ARG;
@@ -2633,23 +2713,14 @@ int cspm_get_rect_map(cspm_ctx *c, int view, double *xy_out, uint8_t *valid_out)
   if (!c->rect_on) return fail(c, CSPM_ERR_STATE, "no rectification stored (cspm_set_rectification)");
   ON_DEVICE(c);
   const size_t n = (size_t)c->rect.w * c->rect.h;
-  if (xy_out) HIPCHK(c, hipMemcpyAsync(xy_out, c->rect_map[view], sizeof(double) * 2 * n, hipMemcpyDeviceToHost, c->stream));
-  if (valid_out) HIPCHK(c, hipMemcpyAsync(valid_out, c->rect_valid[view], n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return CSPM_OK;
+  Staging S(c);
+  S.down(xy_out, c->rect_map[view], 2 * n);
+  S.down(valid_out, c->rect_valid[view], n);
+  return S.finish("rectification map download failed");
 }
 
 // both raw images through the stored maps into the rectified 8UC3 pair, which then takes cspm_set_images_device's path
-static int set_images_raw_enqueue(cspm_ctx *c, const void *l, const void *r, size_t stride, bool on_device);
 static int set_images_raw_impl(cspm_ctx *c, const void *l, const void *r, size_t stride, bool on_device) {
-  const int rc = set_images_raw_enqueue(c, l, r, stride, on_device);
-  if (rc == CSPM_OK || on_device || !c || !c->rect_on || !l || !r) return rc;
-  // a host source: whatever failed behind an upload that was already enqueued, the caller may reuse its buffers when this returns
-  DevGuard guard_(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  return rc;
-}
-static int set_images_raw_enqueue(cspm_ctx *c, const void *l, const void *r, size_t stride, bool on_device) {
   if (!c) return CSPM_ERR_ARG;
   if (!c->rect_on) return fail(c, CSPM_ERR_STATE, "raw images need a stored rectification (cspm_set_rectification)");
   const int rw = c->rect_rig.raw_w, rh = c->rect_rig.raw_h, w = c->rect.w, h = c->rect.h;
@@ -2660,18 +2731,15 @@ static int set_images_raw_enqueue(cspm_ctx *c, const void *l, const void *r, siz
   if (!c->rect_rawpix && (rc = dalloc(c, &c->rect_rawpix, 2 * rn, nullptr))) return rc;
   if (!c->rect_out && (rc = dalloc(c, &c->rect_out, 2 * 3 * n, nullptr))) return rc;
   if (!on_device && !c->rect_stage && (rc = dalloc(c, &c->rect_stage, 2 * 3 * rn, nullptr))) return rc;
-  const void *src[2] = {l, r};
-  const uint8_t *d_src[2];
-  size_t d_stride = stride;
-  for (int v = 0; v < 2; ++v) {
-    d_src[v] = (const uint8_t *)src[v];
-    if (!on_device) {
-      uint8_t *dst = c->rect_stage + (size_t)v * 3 * rn;
-      HIPCHK(c, hipMemcpy2DAsync(dst, raw_row, src[v], stride, raw_row, rh, hipMemcpyHostToDevice, c->stream));
-      d_src[v] = dst;
-      d_stride = raw_row;
-    }
+  const uint8_t *d_src[2] = {(const uint8_t *)l, (const uint8_t *)r};
+  const size_t d_stride = on_device ? stride : raw_row;
+  Staging S(c);  // a host source: whatever fails behind an upload that was enqueued, the caller may reuse its buffers when this returns
+  for (int v = 0; v < 2 && !on_device; ++v) {
+    uint8_t *dst = c->rect_stage + (size_t)v * 3 * rn;
+    S.put2d(dst, raw_row, d_src[v], stride, raw_row, rh);
+    d_src[v] = dst;
   }
+  if (S.rc) return S.rc;
   {
     Timed t(c, CSPM_K_MISC, 2 * (long long)n);
     for (int v = 0; v < 2; ++v)
@@ -2680,8 +2748,7 @@ static int set_images_raw_enqueue(cspm_ctx *c, const void *l, const void *r, siz
   }
   HIPCHK(c, hipGetLastError());
   if ((rc = set_images_impl(c, c->rect_out, c->rect_out + 3 * n, w, h, row, true))) return rc;
-  if (!on_device) HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller may reuse its host buffers
-  return CSPM_OK;
+  return on_device ? CSPM_OK : S.finish("raw image upload failed");
 }
 
 int cspm_set_images_raw(cspm_ctx *c, const uint8_t *l, const uint8_t *r, size_t stride) { return set_images_raw_impl(c, l, r, stride, false); }
@@ -2773,9 +2840,9 @@ int cspm_upload_cost_slab(cspm_ctx *c, int view, int level, int d, const double 
   if (d < 0 || d > L.D || stride_elems < (size_t)L.W) return fail(c, CSPM_ERR_ARG, "bad slab index or stride");
   ON_DEVICE(c);
   double *dst = (double *)L.vol[view] + (size_t)d * L.W * L.H;
-  HIPCHK(c, hipMemcpy2DAsync(dst, sizeof(double) * L.W, slab, sizeof(double) * stride_elems, sizeof(double) * L.W, L.H,
-                             hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));  // caller may reuse the slab buffer
+  Staging S(c);
+  S.put2d(dst, sizeof(double) * L.W, slab, sizeof(double) * stride_elems, sizeof(double) * L.W, L.H);
+  if (S.finish("cost slab upload failed")) return S.rc;  // caller may reuse the slab buffer
   c->cost_ready = false;
   return CSPM_OK;
 }
@@ -2815,13 +2882,12 @@ int cspm_get_level_image(cspm_ctx *c, int view, int level, uint8_t *out) {
   ON_DEVICE(c);
   const Level &L = c->cost.lv[level];
   const size_t px = (size_t)L.W * L.H;
-  uint8_t *tmp;
-  HIPCHK(c, hipMalloc((void **)&tmp, px * 3));
+  Staging S(c);
+  uint8_t *tmp = S.buf<uint8_t>(px * 3);
+  if (S.rc) return S.finish();
   hipLaunchKernelGGL(k_unpack_bgr, dim3(ew_grid((long long)px)), dim3(256), 0, c->stream, L.pix[view], L.W, L.H, L.Wp, L.pad, tmp);
-  HIPCHK(c, hipMemcpyAsync(out, tmp, px * 3, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  (void)hipFree(tmp);
-  return CSPM_OK;
+  S.down(out, tmp, px * 3);
+  return S.finish("level image download failed");
 }
 
 int cspm_get_cost_slab(cspm_ctx *c, int view, int level, int d, double *out) {
@@ -2831,21 +2897,18 @@ int cspm_get_cost_slab(cspm_ctx *c, int view, int level, int d, double *out) {
   if (d < 0 || d > L.D) return fail(c, CSPM_ERR_ARG, "bad slab index");
   ON_DEVICE(c);
   const size_t px = (size_t)L.W * L.H;
-  if (L.vol[view]) {
-    HIPCHK(c, hipMemcpyAsync(out, L.vol[view] + (size_t)d * px, sizeof(double) * px, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return CSPM_OK;
+  Staging S(c);
+  const double *src = L.vol[view] ? L.vol[view] + (size_t)d * px : nullptr;
+  if (!src) {
+    if (c->cost_key.kind == kKindImg) return fail(c, CSPM_ERR_STATE, "GrdPC / CSPC have no cost volumes");
+    // fused cost: materialise the requested slab with the volume kernel
+    double *tmp = S.buf<double>(px);
+    if (S.rc) return S.finish();
+    launch_cells(c, level, view, d, 1, tmp, nullptr);
+    src = tmp;
   }
-  if (c->cost_key.kind == kKindImg) return fail(c, CSPM_ERR_STATE, "GrdPC / CSPC have no cost volumes");
-  // fused cost: materialise the requested slab with the volume kernel
-  double *tmp;
-  HIPCHK(c, hipMalloc((void **)&tmp, sizeof(double) * px));
-  launch_cells(c, level, view, d, 1, tmp, nullptr);
-  hipError_t e = hipMemcpyAsync(out, tmp, sizeof(double) * px, hipMemcpyDeviceToHost, c->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  (void)hipFree(tmp);
-  if (e != hipSuccess) return fail(c, CSPM_ERR_HIP, hipGetErrorString(e));
-  return CSPM_OK;
+  S.down(out, src, px);
+  return S.finish("cost slab download failed");
 }
 
 int cspm_get_max_cost(cspm_ctx *c, int view, int level, double *out) {
@@ -2880,7 +2943,7 @@ int cspm_aggregate_cv_host(int device, int method, const double *guide, int w, i
   for (size_t i = 0; i < px; ++i)
     for (int k = 0; k < 3; ++k) gn[k * px + i] = guide[3 * i + k];
   CaWork wk;
-  if (!S.rc) S.rc = ca_alloc_work(c, px, nb, &wk, &S.bufs.ptrs);
+  if (!S.rc) S.latch(ca_alloc_work(c, px, nb, &wk, &S.bufs));
   S.put(wk.gn, gn.data(), 3 * px);
   double *dv = S.up(vol + px, (size_t)(n_slices - 1) * px);
   double *dout = S.buf<double>((size_t)nb * px);
@@ -2937,7 +3000,7 @@ int cspm_fit_planes_host(int device, const double *disp, const uint8_t *valid, c
   double *dlut = S.up(guided ? fit_lut() : nullptr, (size_t)kFitLut);
   uint32_t *dpix = S.up_bgr(guided ? guide_bgr : nullptr, guide_stride, w, h);
   if (S.rc) return S.finish();
-  fit_launch(S.c->stream, FitIn{dd, dv, dpix, dlut}, FitOut{dout, dout + n, dout + 2 * n, dout + 3 * n, dout + 4 * n, dout + 5 * n, dfit, 0}, w, h, p, max_dis);
+  fit_launch(S.c->stream, FitIn{dd, dv, dpix, dlut}, six_slabs(dout, n).fit_out(dfit, 0), w, h, p, max_dis);
   std::vector<double> hst(6 * n);
   S.down(hst.data(), dout, 6 * n);
   S.down(fitted_out, dfit, n);
@@ -2999,7 +3062,7 @@ int cspm_segment_planes_host(int device, const double *disp, const uint8_t *vali
   uint8_t *dv = S.up(valid, n), *dfit = S.buf<uint8_t>(n);
   const SegMem m(S.buf<uint8_t>(SegMem::bytes(K)), K);
   if (S.rc) return S.finish();
-  seg_fit_launch(S.c->stream, g, SegFitIn{dd, dv, dlab}, p, max_dis, m, FitOut{dout, dout + n, dout + 2 * n, dout + 3 * n, dout + 4 * n, dout + 5 * n, dfit, 0});
+  seg_fit_launch(S.c->stream, g, SegFitIn{dd, dv, dlab}, p, max_dis, m, six_slabs(dout, n).fit_out(dfit, 0));
   std::vector<double> hst(6 * n), hseg(4 * K);
   S.down(hst.data(), dout, 6 * n);
   S.down(hseg.data(), m.planes, 4 * K);
@@ -3103,21 +3166,15 @@ int cspm_plane_cost_batch(cspm_ctx *c, int view, int n, const int *xy, const dou
   for (int i = 0; i < n; ++i)
     if (xy[2 * i] < 0 || xy[2 * i] >= c->W || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= c->H) return fail(c, CSPM_ERR_ARG, "pixel outside the image");
   ON_DEVICE(c);
-  int *dxy = nullptr;
-  double *dnp = nullptr, *dout = nullptr;
-  DevBufs tmp;
-  int rc;
-  if ((rc = dalloc(c, &dxy, (size_t)2 * n, &tmp.ptrs)) || (rc = dalloc(c, &dnp, (size_t)6 * n, &tmp.ptrs)) || (rc = dalloc(c, &dout, (size_t)n, &tmp.ptrs))) return rc;
-  hipError_t e = hipMemcpyAsync(dxy, xy, sizeof(int) * 2 * n, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dnp, np, sizeof(double) * 6 * n, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) {
-    LAUNCH_CS(k_cost_batch, dim3(eval_grid(n)), dim3(kEvalBlock), 0, c->cost, view, n, dxy, dnp, dout);
-    e = hipMemcpyAsync(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (e == hipSuccess) e = hipGetLastError();
-  if (e != hipSuccess) return fail(c, CSPM_ERR_HIP, hipGetErrorString(e));
-  return CSPM_OK;
+  Staging S(c);
+  int *dxy = S.buf<int>((size_t)2 * n);
+  double *dnp = S.buf<double>((size_t)6 * n), *dout = S.buf<double>((size_t)n);
+  S.put(dxy, xy, (size_t)2 * n);
+  S.put(dnp, np, (size_t)6 * n);
+  if (S.rc) return S.finish();
+  LAUNCH_CS(k_cost_batch, dim3(eval_grid(n)), dim3(kEvalBlock), 0, c->cost, view, n, dxy, dnp, dout);
+  S.down(out, dout, (size_t)n);
+  return S.finish("plane cost batch failed");
 }
 
 int cspm_pm_default_params(cspm_pm_params *p) {
@@ -3237,27 +3294,19 @@ int cspm_merge_planes_host(cspm_ctx *c, int view, const double *np, const uint8_
   if ((rc = need_cost(c)) || (rc = need_field(c, kNoMergeTarget))) return rc;
   ON_DEVICE(c);
   const size_t n = (size_t)c->W * c->H;
-  if (!c->cand_mem && (rc = dalloc(c, &c->cand_mem, 6 * n + (n + 7) / 8, nullptr))) return rc;  // 48 + 1 bytes per pixel
-  unsigned char *d_mask = reinterpret_cast<unsigned char *>(c->cand_mem + 6 * n);
+  CandBuf cand;
+  if ((rc = ensure_cand(c, &cand))) return rc;
   std::vector<double> h(6 * n);
+  deinterleave_planes(np, n, h.data());
   long long evals = 0;  // pixels that have a candidate
-  for (size_t i = 0; i < n; ++i) {
-    bool has = !mask || mask[i] != 0;
-    for (int k = 0; k < 6; ++k) {
-      h[k * n + i] = np[6 * i + k];
-      has = has && std::isfinite(np[6 * i + k]);
-    }
-    evals += has;
-  }
+  for (size_t i = 0; i < n; ++i) evals += (!mask || mask[i] != 0) && all_finite(np + 6 * i, 6);
   // the copies out of caller memory are complete when the call returns; the merge itself is asynchronous
-  HIPCHK(c, hipMemcpyAsync(c->cand_mem, h.data(), sizeof(double) * 6 * n, hipMemcpyHostToDevice, c->stream));
-  if (mask) HIPCHK(c, hipMemcpyAsync(d_mask, mask, n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  Staging S(c);
+  S.put(c->cand_mem, h.data(), 6 * n);
+  if (mask) S.put(cand.mask, mask, n);
+  if (S.finish("candidate upload failed")) return S.rc;
   if ((rc = ensure_consistent(c))) return rc;
-  CandField cf{};
-  const double *b = c->cand_mem;
-  cf.s[view] = SnapField{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n};
-  cf.mask[view] = mask ? d_mask : nullptr;
+  const CandField cf = cand.field(view, mask != nullptr);
   c->repeat.taint_unchecked_run();
   return do_merge(c, &cf, &kDefaultParams, view, 1, evals);
 }
@@ -3267,109 +3316,58 @@ int cspm_fit_planes(cspm_ctx *c, const cspm_fit_params *p, int merge) {
   if (!c) return CSPM_ERR_ARG;
   if (!p) p = &kFitDefaults;
   if (const char *msg = fit_params_error(p)) return fail(c, CSPM_ERR_ARG, msg);
-  if (!c->img0[0]) return fail(c, CSPM_ERR_STATE, "cspm_set_images first");
-  int rc;
-  if ((rc = need_field(c, "no plane field to fit (cspm_local_stereo, cspm_set_planes, cspm_pm_init or an earlier run)"))) return rc;
-  if (merge && (rc = need_cost(c))) return rc;
-  if (c->max_dis < 1) return fail(c, CSPM_ERR_STATE, "no max_dis known: build a cost object (or cspm_fpm_begin) first");
-  if (c->H > kFitMaxRows) return fail(c, CSPM_ERR_ARG, "image too high for the plane fit");
-  ON_DEVICE(c);
-  const size_t n = (size_t)c->W * c->H;
-  if (!c->fit_mem) {
-    if ((rc = dalloc(c, &c->fit_mem, 2 * n + kFitLut, nullptr))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->fit_mem + 2 * n, fit_lut(), sizeof(double) * kFitLut, hipMemcpyHostToDevice, c->stream));
-  }
-  if (merge) {
-    if (!c->cand_mem && (rc = dalloc(c, &c->cand_mem, 6 * n + (n + 7) / 8, nullptr))) return rc;  // the buffer of cspm_merge_planes_host
-    if ((rc = ensure_consistent(c))) return rc;
-  } else {
-    c->field_consistent = false;  // min_cost still belongs to the planes that were replaced
-  }
-  c->repeat.taint_unchecked_run();  // it can no longer be repeated over these planes
-  const Pm pm = field_pm(c);
-  for (int v = 0; v < 2; ++v) {
-    double *d = c->fit_mem + (size_t)v * n;
-    double *b = merge ? c->cand_mem : nullptr;
-    uint8_t *d_mask = merge ? reinterpret_cast<uint8_t *>(c->cand_mem + 6 * n) : nullptr;
-    const Field &f = c->f[v];
-    const FitOut out = merge ? FitOut{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, d_mask, 0} : FitOut{f.nx, f.ny, f.nz, f.a, f.b, f.c, nullptr, 1};
-    {
-      Timed t(c, CSPM_K_MISC, (long long)n);
-      hipLaunchKernelGGL(k_plane_to_disp_f64, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, pm, v, d);
-      fit_launch(c->stream, FitIn{d, nullptr, c->img0[v], c->fit_mem + 2 * n}, out, c->W, c->H, p, c->max_dis);
-    }
-    HIPCHK(c, hipGetLastError());
-    if (merge) {
-      CandField cf{};
-      cf.s[v] = SnapField{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n};
-      cf.mask[v] = d_mask;
-      if ((rc = do_merge(c, &cf, &kDefaultParams, v, 1, (long long)n))) return rc;
-    }
-  }
-  return CSPM_OK;
+  return fit_stored_field(
+      c, merge, kFitMaxRows, "image too high for the plane fit",
+      [&](double **snap) -> int {
+        const size_t n = (size_t)c->W * c->H;
+        if (!c->fit_mem) {
+          if (int rc = dalloc(c, &c->fit_mem, 2 * n + kFitLut, nullptr)) return rc;
+          HIPCHK(c, hipMemcpyAsync(c->fit_mem + 2 * n, fit_lut(), sizeof(double) * kFitLut, hipMemcpyHostToDevice, c->stream));
+        }
+        *snap = c->fit_mem;
+        return CSPM_OK;
+      },
+      [&](int v, const double *d, const FitOut &out) {
+        fit_launch(c->stream, FitIn{d, nullptr, c->img0[v], c->fit_mem + 2 * (size_t)c->W * c->H}, out, c->W, c->H, p, c->max_dis);
+      });
 }
+
+// seg_mem: both views' disparity snapshots (2n doubles), then view v's n labels; seg_labels(c, 2) is where the SegMem begins
+inline int *seg_labels(cspm_ctx *c, int v) { return reinterpret_cast<int *>(reinterpret_cast<double *>(c->seg_mem) + 2 * (size_t)c->W * c->H) + (size_t)v * c->W * c->H; }
 
 // one robustly fitted plane per superpixel of the stored field's own disparity maps (cspm.h "segment planes"); asynchronous on the ctx stream
 int cspm_segment_planes(cspm_ctx *c, const cspm_seg_params *p, int merge) {
   if (!c) return CSPM_ERR_ARG;
   if (!p) p = &kSegDefaults;
   if (const char *msg = seg_params_error(p)) return fail(c, CSPM_ERR_ARG, msg);
-  if (!c->img0[0]) return fail(c, CSPM_ERR_STATE, "cspm_set_images first");
-  int rc;
-  if ((rc = need_field(c, "no plane field to fit (cspm_local_stereo, cspm_set_planes, cspm_pm_init or an earlier run)"))) return rc;
-  if (merge && (rc = need_cost(c))) return rc;
-  if (c->max_dis < 1) return fail(c, CSPM_ERR_STATE, "no max_dis known: build a cost object (or cspm_fpm_begin) first");
-  if (c->H > kSegMaxRows) return fail(c, CSPM_ERR_ARG, "image too high for the segmentation");
-  ON_DEVICE(c);
-  const size_t n = (size_t)c->W * c->H;
-  const SegGrid finest = seg_grid(c->W, c->H, kSegMinStep), g = seg_grid(c->W, c->H, p->step);
-  const size_t Kmax = (size_t)finest.nx * finest.ny, K = (size_t)g.nx * g.ny;
-  if (!c->seg_mem && (rc = dalloc(c, &c->seg_mem, 2 * n * (sizeof(double) + sizeof(int)) + SegMem::bytes(Kmax), nullptr))) return rc;
-  double *snap = reinterpret_cast<double *>(c->seg_mem);
-  int *labels = reinterpret_cast<int *>(snap + 2 * n);
-  const SegMem m(labels + 2 * n, K);  // 8-byte aligned: 2n ints behind 2n doubles
-  if (merge) {
-    if (!c->cand_mem && (rc = dalloc(c, &c->cand_mem, 6 * n + (n + 7) / 8, nullptr))) return rc;  // the buffer of cspm_merge_planes_host
-    if ((rc = ensure_consistent(c))) return rc;
-  } else {
-    c->field_consistent = false;  // min_cost still belongs to the planes that were replaced
-  }
-  c->repeat.taint_unchecked_run();  // it can no longer be repeated over these planes
-  c->seg_ran = true;
-  const Pm pm = field_pm(c);
-  for (int v = 0; v < 2; ++v) {
-    double *d = snap + (size_t)v * n;
-    int *lab = labels + (size_t)v * n;
-    double *b = merge ? c->cand_mem : nullptr;
-    uint8_t *d_mask = merge ? reinterpret_cast<uint8_t *>(c->cand_mem + 6 * n) : nullptr;
-    const Field &f = c->f[v];
-    const FitOut out = merge ? FitOut{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, d_mask, 0} : FitOut{f.nx, f.ny, f.nz, f.a, f.b, f.c, nullptr, 1};
-    {
-      Timed t(c, CSPM_K_MISC, (long long)n);
-      hipLaunchKernelGGL(k_plane_to_disp_f64, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, pm, v, d);
-      seg_segment_launch(c->stream, g, c->img0[v], p, lab, m);
-      seg_fit_launch(c->stream, g, SegFitIn{d, nullptr, lab}, p, c->max_dis, m, out);
-    }
-    HIPCHK(c, hipGetLastError());
-    if (merge) {
-      CandField cf{};
-      cf.s[v] = SnapField{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n};
-      cf.mask[v] = d_mask;
-      if ((rc = do_merge(c, &cf, &kDefaultParams, v, 1, (long long)n))) return rc;
-    }
-  }
-  return CSPM_OK;
+  return fit_stored_field(
+      c, merge, kSegMaxRows, "image too high for the segmentation",
+      [&](double **snap) -> int {
+        const size_t n = (size_t)c->W * c->H;
+        const SegGrid finest = seg_grid(c->W, c->H, kSegMinStep);
+        const size_t Kmax = (size_t)finest.nx * finest.ny;
+        if (!c->seg_mem)
+          if (int rc = dalloc(c, &c->seg_mem, 2 * n * (sizeof(double) + sizeof(int)) + SegMem::bytes(Kmax), nullptr)) return rc;
+        *snap = reinterpret_cast<double *>(c->seg_mem);
+        return CSPM_OK;
+      },
+      [&](int v, const double *d, const FitOut &out) {
+        const SegGrid g = seg_grid(c->W, c->H, p->step);
+        int *lab = seg_labels(c, v);
+        const SegMem m(seg_labels(c, 2), (size_t)g.nx * g.ny);  // 8-byte aligned: 2n ints behind 2n doubles
+        c->seg_ran = true;
+        seg_segment_launch(c->stream, g, c->img0[v], p, lab, m);
+        seg_fit_launch(c->stream, g, SegFitIn{d, nullptr, lab}, p, c->max_dis, m, out);
+      });
 }
 
 int cspm_get_segments(cspm_ctx *c, int view, int32_t *labels_out) {
   if (!c || view < 0 || view > 1 || !labels_out) return CSPM_ERR_ARG;
   if (!c->seg_mem || !c->seg_ran) return fail(c, CSPM_ERR_STATE, "no segmentation yet (cspm_segment_planes)");
   ON_DEVICE(c);
-  const size_t n = (size_t)c->W * c->H;
-  const int *labels = reinterpret_cast<const int *>(reinterpret_cast<const double *>(c->seg_mem) + 2 * n) + (size_t)view * n;
-  HIPCHK(c, hipMemcpyAsync(labels_out, labels, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return CSPM_OK;
+  Staging S(c);
+  S.down(labels_out, seg_labels(c, view), (size_t)c->W * c->H);
+  return S.finish("label download failed");
 }
 
 // G alone on caller maps: the launches cspm_reproject enqueues, on one view.  Arguments first, then the device.
@@ -3429,25 +3427,22 @@ int cspm_reproject(cspm_ctx *c, int view, int source, const cspm_calib *calib, c
   const size_t n = (size_t)c->W * c->H;
   const unsigned nb = geom_blocks((long long)n);
   const size_t cap = std::min(cloud_out ? cloud_cap : (size_t)0, n);
-  DevBufs tmp;
-  double *ddepth = nullptr, *dxyz = nullptr, *dnormal = nullptr;
-  uint8_t *dkeep = nullptr;
-  uint4 *dcloud = nullptr;
-  if ((depth_out && (rc = dalloc(c, &ddepth, n, &tmp.ptrs))) || (xyz_out && (rc = dalloc(c, &dxyz, 3 * n, &tmp.ptrs))) ||
-      (normal_out && (rc = dalloc(c, &dnormal, 3 * n, &tmp.ptrs))) || (keep_out && (rc = dalloc(c, &dkeep, n, &tmp.ptrs))) ||
-      (cap && (rc = dalloc(c, &dcloud, 2 * cap, &tmp.ptrs))))
-    return rc;
+  unsigned int total = 0;  // in front of the Staging: a download writes it
+  Staging S(c);
+  double *ddepth = S.buf<double>(n, depth_out != nullptr), *dxyz = S.buf<double>(3 * n, xyz_out != nullptr), *dnormal = S.buf<double>(3 * n, normal_out != nullptr);
+  uint8_t *dkeep = S.buf<uint8_t>(n, keep_out != nullptr);
+  uint4 *dcloud = S.buf<uint4>(2 * cap, cap != 0);
+  if (S.rc) return S.finish();
   const bool want_count = count_out != nullptr || cloud_out != nullptr;
   if ((rc = reproject_enqueue(c, view, source, calib, g, fit, GeomOut{ddepth, dxyz, dnormal, dkeep}, dcloud, cap, want_count, nullptr))) return rc;
-  unsigned int total = 0;
-  if (depth_out) HIPCHK(c, hipMemcpyAsync(depth_out, ddepth, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-  if (xyz_out) HIPCHK(c, hipMemcpyAsync(xyz_out, dxyz, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, c->stream));
-  if (normal_out) HIPCHK(c, hipMemcpyAsync(normal_out, dnormal, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, c->stream));
-  if (keep_out) HIPCHK(c, hipMemcpyAsync(keep_out, dkeep, n, hipMemcpyDeviceToHost, c->stream));
-  if (want_count) HIPCHK(c, hipMemcpyAsync(&total, c->geom_counts + nb, sizeof total, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const size_t wrote = std::min((size_t)total, cap);
-  if (wrote) HIPCHK(c, hipMemcpy(cloud_out, dcloud, sizeof(cspm_point) * wrote, hipMemcpyDeviceToHost));
+  S.down(depth_out, ddepth, n);
+  S.down(xyz_out, dxyz, 3 * n);
+  S.down(normal_out, dnormal, 3 * n);
+  S.down(keep_out, dkeep, n);
+  S.down(want_count ? &total : nullptr, c->geom_counts + nb, 1);
+  if (S.finish("reprojection download failed")) return S.rc;
+  S.down(cloud_out, dcloud, std::min((size_t)total, cap));  // the count first, then the records that were written
+  if (S.finish("cloud download failed")) return S.rc;
   if (count_out) *count_out = total;
   return CSPM_OK;
 }
@@ -3522,20 +3517,20 @@ int cspm_mesh(cspm_ctx *c, int view, int source, const cspm_calib *calib, const 
   const size_t n = (size_t)c->W * c->H;
   const unsigned nb = geom_blocks((long long)n);
   const size_t vcap = std::min(vertices_out ? vertex_cap : (size_t)0, n), fcap = std::min(faces_out ? face_cap : (size_t)0, mesh_max_faces(c->W, c->H));
-  DevBufs tmp;
-  uint4 *dverts = nullptr;
-  uint32_t *dfaces = nullptr;
-  if ((vcap && (rc = dalloc(c, &dverts, 2 * vcap, &tmp.ptrs))) || (fcap && (rc = dalloc(c, &dfaces, 3 * fcap, &tmp.ptrs)))) return rc;
+  unsigned int nv = 0, nf = 0;  // in front of the Staging: downloads write them
+  Staging S(c);
+  uint4 *dverts = S.buf<uint4>(2 * vcap, vcap != 0);
+  uint32_t *dfaces = S.buf<uint32_t>(3 * fcap, fcap != 0);
+  if (S.rc) return S.finish();
   if ((rc = mesh_enqueue(c, view, source, calib, g, fit, m, dverts, vcap, dfaces, fcap, nullptr, nullptr, nullptr))) return rc;
-  unsigned int nv = 0, nf = 0;
   const unsigned int *dcounts = c->mesh_map + n;
-  if (quad_out) HIPCHK(c, hipMemcpyAsync(quad_out, c->mesh_bytes + n, n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&nv, dcounts + nb, sizeof nv, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(&nf, dcounts + 2 * (size_t)nb + 1, sizeof nf, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  const size_t wrote_v = std::min((size_t)nv, vcap), wrote_f = std::min((size_t)nf, fcap);
-  if (wrote_v) HIPCHK(c, hipMemcpy(vertices_out, dverts, sizeof(cspm_point) * wrote_v, hipMemcpyDeviceToHost));
-  if (wrote_f) HIPCHK(c, hipMemcpy(faces_out, dfaces, sizeof(cspm_face) * wrote_f, hipMemcpyDeviceToHost));
+  S.down(quad_out, c->mesh_bytes + n, n);
+  S.down(&nv, dcounts + nb, 1);
+  S.down(&nf, dcounts + 2 * (size_t)nb + 1, 1);
+  if (S.finish("mesh download failed")) return S.rc;
+  S.down(vertices_out, dverts, std::min((size_t)nv, vcap));  // the counts first, then the records that were written
+  S.down(faces_out, dfaces, std::min((size_t)nf, fcap));
+  if (S.finish("mesh record download failed")) return S.rc;
   if (n_vertices_out) *n_vertices_out = nv;
   if (n_faces_out) *n_faces_out = nf;
   return CSPM_OK;
@@ -3601,18 +3596,16 @@ int cspm_synthesize(cspm_ctx *c, int source, const cspm_synth_params *p, double 
   if (rc) return rc;
   ON_DEVICE(c);
   const size_t n = (size_t)c->W * c->H, row = (size_t)c->W * 3;
-  DevBufs tmp;
-  uint8_t *dout = nullptr, *dmask = nullptr;
-  double *ddisp = nullptr;
-  if ((bgr_out && (rc = dalloc(c, &dout, 3 * n, &tmp.ptrs))) || (disp_out && (rc = dalloc(c, &ddisp, n, &tmp.ptrs))) ||
-      (mask_out && (rc = dalloc(c, &dmask, n, &tmp.ptrs))))
-    return rc;
+  Staging S(c);
+  uint8_t *dout = S.buf<uint8_t>(3 * n, bgr_out != nullptr);
+  double *ddisp = S.buf<double>(n, disp_out != nullptr);
+  uint8_t *dmask = S.buf<uint8_t>(n, mask_out != nullptr);
+  if (S.rc) return S.finish();
   if ((rc = synthesize_enqueue(c, source, p, t, SynthOut{dout, row, ddisp, dmask}))) return rc;
-  if (bgr_out) HIPCHK(c, hipMemcpy2DAsync(bgr_out, out_stride, dout, row, row, c->H, hipMemcpyDeviceToHost, c->stream));
-  if (disp_out) HIPCHK(c, hipMemcpyAsync(disp_out, ddisp, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-  if (mask_out) HIPCHK(c, hipMemcpyAsync(mask_out, dmask, n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return CSPM_OK;
+  S.down2d(bgr_out, out_stride, dout, row, c->H);
+  S.down(disp_out, ddisp, n);
+  S.down(mask_out, dmask, n);
+  return S.finish("view synthesis download failed");
 }
 
 // the same with device-resident outputs: asynchronous on the ctx stream behind the pending-run check; not replayed (cspm.h)
@@ -3641,8 +3634,9 @@ int cspm_get_planes(cspm_ctx *c, int view, double *np_out, double *cost_out) {
   if (int rc = check_sweep(c)) return rc;
   const size_t n = (size_t)c->W * c->H;
   std::vector<double> h(7 * n);
-  HIPCHK(c, hipMemcpyAsync(h.data(), c->f[view].nx, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  Staging S(c);
+  S.down(h.data(), c->f[view].nx, 7 * n);
+  if (S.finish("plane download failed")) return S.rc;
   if (np_out) interleave_planes(h.data(), n, np_out);
   if (cost_out) memcpy(cost_out, h.data() + 6 * n, sizeof(double) * n);
   return CSPM_OK;
@@ -3656,11 +3650,11 @@ int cspm_set_planes(cspm_ctx *c, int view, const double *np, const double *cost)
   if (rc) return rc;
   const size_t n = (size_t)c->W * c->H;
   std::vector<double> h(7 * n);
-  for (size_t i = 0; i < n; ++i)
-    for (int k = 0; k < 6; ++k) h[k * n + i] = np[6 * i + k];
+  deinterleave_planes(np, n, h.data());
   memcpy(h.data() + 6 * n, cost, sizeof(double) * n);
-  HIPCHK(c, hipMemcpyAsync(c->f[view].nx, h.data(), sizeof(double) * 7 * n, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  Staging S(c);
+  S.put(c->f[view].nx, h.data(), 7 * n);
+  if (S.finish("plane upload failed")) return S.rc;
   c->field_consistent = false;  // min_cost is whatever the caller says: the sweep may not assume cost(plane) == min_cost
   c->repeat.taint();
   return CSPM_OK;
@@ -3680,9 +3674,9 @@ int cspm_get_disparity_u8(cspm_ctx *c, int view, int dis_scale, uint8_t *out, si
   int rc = check_sweep(c);  // BEFORE PlaneToDisp: a run repeated after a sweep timeout must be the one the map is computed from
   if (rc) return rc;
   if ((rc = enqueue_disp_u8(c, view, dis_scale, c->d_dis[view]))) return rc;
-  HIPCHK(c, hipMemcpy2DAsync(out, stride, c->d_dis[view], c->W, c->W, c->H, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return CSPM_OK;
+  Staging S(c);
+  S.down2d(out, stride, c->d_dis[view], c->W, c->H);
+  return S.finish("disparity download failed");
 }
 
 int cspm_get_disparity_f64(cspm_ctx *c, int view, double *out) {
@@ -3693,9 +3687,9 @@ int cspm_get_disparity_f64(cspm_ctx *c, int view, double *out) {
   const Pm pm = field_pm(c);
   const size_t n = (size_t)c->W * c->H;
   hipLaunchKernelGGL(k_plane_to_disp_f64, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, pm, view, c->vc.cost);
-  HIPCHK(c, hipMemcpyAsync(out, c->vc.cost, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return CSPM_OK;
+  Staging S(c);
+  S.down(out, c->vc.cost, n);
+  return S.finish("disparity download failed");
 }
 
 int cspm_postprocess(cspm_ctx *c, int dis_scale, uint8_t *l_out, uint8_t *r_out, size_t stride) {
@@ -3707,10 +3701,9 @@ int cspm_postprocess(cspm_ctx *c, int dis_scale, uint8_t *l_out, uint8_t *r_out,
   if (rc) return rc;
   if ((rc = postprocess_enqueue(c, dis_scale))) return rc;
   uint8_t *outs[2] = {l_out, r_out};
-  for (int v = 0; v < 2; ++v)
-    HIPCHK(c, hipMemcpy2DAsync(outs[v], stride, c->d_dis[v], c->W, c->W, c->H, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return CSPM_OK;
+  Staging S(c);
+  for (int v = 0; v < 2; ++v) S.down2d(outs[v], stride, c->d_dis[v], c->W, c->H);
+  return S.finish("post-processing download failed");
 }
 
 // the same with device-resident outputs (W*H bytes each, packed rows): asynchronous like cspm_patchmatch
@@ -3734,12 +3727,12 @@ int cspm_postprocess_f64(cspm_ctx *c, double *l_out, double *r_out, uint8_t *l_v
   const size_t n = (size_t)c->W * c->H;
   double *outs[2] = {l_out, r_out};
   uint8_t *flags[2] = {l_valid_out, r_valid_out};
+  Staging S(c);
   for (int v = 0; v < 2; ++v) {
-    HIPCHK(c, hipMemcpyAsync(outs[v], c->d_pp[v], sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-    if (flags[v]) HIPCHK(c, hipMemcpyAsync(flags[v], c->d_valid[v], n, hipMemcpyDeviceToHost, c->stream));
+    S.down(outs[v], c->d_pp[v], n);
+    S.down(flags[v], c->d_valid[v], n);
   }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return CSPM_OK;
+  return S.finish("post-processing download failed");
 }
 
 // the same with device-resident outputs (W*H f64 each, packed rows): asynchronous like cspm_postprocess_device
