@@ -35,6 +35,7 @@ OPT_FAULT_VOLUME_ALLOC = 16  # write only, TEST HOOK: the n-th optional-volume a
 OPT_CENGRD_FUSED = 19        # set before build_cost_cengrd: 1 = no volumes, the cells are computed inside the PatchMatch kernels (default 0; identical planes)
 OPT_CENGRD_FUSED_ACTIVE = 20 # read only: the current cost object is a fused CENGRD one
 OPT_PP_SPECKLE_REMOVED = 21  # read only, synchronises: pixels the speckle filter removed from both masks in the last post-processing
+OPT_DEVICE_BYTES = 22        # read only, no synchronisation: bytes of device memory the context holds (requested sizes; staging temporaries not included)
 MEDIAN_MAX_RADIUS = 7  # CSPM_MEDIAN_MAX_RADIUS: the median filter's window is at most 15 x 15
 CA_BOX, CA_GF, CA_BF = 0, 1, 2  # cost aggregation: BoxCA, GFCA, BFCA (ca_filter/)
 SYNTH_MAX_WIDTH = 6784  # CSPM_SYNTH_MAX_WIDTH: the widest image cspm_synthesize* takes (a target row lives in one workgroup's LDS)

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "cspm_kernels.h"
+#include "cspm_pool.h"
 #include "cspm_pp.h"
 #include "cspm_speckle.h"
 #include "cspm_median.h"
@@ -35,6 +36,10 @@ struct TimingRec {
   hipEvent_t a, b;
   long long evals;
 };
+
+// the allocator pair of every DevPool of this file
+int dev_alloc(void **p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+void dev_free(void *p) { (void)hipFree(p); }
 
 }  // namespace
 
@@ -136,6 +141,12 @@ struct cspm_ctx {
   int refine_chunk = 64;  // PlaneRefinement halving steps per launch (tuning knob, env CSPM_REFINE_CHUNK)
   hipStream_t own_stream = nullptr, stream = nullptr;
   std::string err;
+  // device memory: one pool per lifetime owns every allocation the context keeps (DESIGN.md "Context memory")
+  DevPool mem_images{dev_alloc, dev_free};  // img0, stage: until the geometry changes
+  DevPool mem_cost{dev_alloc, dev_free};    // the cost object: until free_cost
+  DevPool mem_field{dev_alloc, dev_free};   // the plane field and what is "kept with the field": until free_field
+  DevPool mem_rect{dev_alloc, dev_free};    // the rectification: until free_rect
+  DevPool mem_ca{dev_alloc, dev_free};      // local-stereo scratch: until ca_ensure meets a new key or the geometry changes
   // images
   int W = 0, H = 0;
   uint32_t *img0[2] = {nullptr, nullptr};
@@ -147,7 +158,6 @@ struct cspm_ctx {
   int max_dis = 0, wnd = 0;
   double scale_wgt[CSPM_MAX_LEVELS] = {0};
   double host_max_cost[2 * CSPM_MAX_LEVELS] = {0};
-  std::vector<void *> cost_allocs;
   CostKey cost_key;
   bool max_cost_fetched = false;  // host_max_cost mirrors d_maxcost
   int *d_early_ok = nullptr;      // device flag: every max_cost (and, for uploaded volumes, every min) is >= 0
@@ -236,7 +246,6 @@ struct cspm_ctx {
   long long fpm_count = 0;
   cspm_pm_params fpm_params{};
   // local stereo (cspm_local_stereo): scratch kept between pairs of the same geometry
-  std::vector<void *> ca_allocs;
   long long ca_key[4] = {0, 0, 0, 0};  // W, H, max_dis, levels
   double *ca_gn = nullptr, *ca_t = nullptr, *ca_s = nullptr, *ca_raw = nullptr, *ca_out = nullptr, *ca_best = nullptr;
   int *ca_bestd = nullptr;
@@ -273,15 +282,15 @@ int fail(cspm_ctx *c, int code, const std::string &msg) {
   if (!guard_.ok) return fail(ctx, CSPM_ERR_HIP, "hipSetDevice failed")
 #define ON_DEVICE(ctx) ON_DEVICE_ID(ctx, (ctx)->device)
 
-template <class T>
-int dalloc(cspm_ctx *c, T **p, size_t n, std::vector<void *> *track) {
-  void *q = nullptr;
-  hipError_t e = hipMalloc(&q, n * sizeof(T) ? n * sizeof(T) : sizeof(T));
-  if (e != hipSuccess) return fail(c, CSPM_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-  *p = (T *)q;
-  if (track) track->push_back(q);
-  return CSPM_OK;
+// n elements (at least one) from `pool`.  dalloc: into a slot the pool remembers -- nothing happens when it is set already, and the pool
+// nulls it when it frees the memory.  dalloc_local: always, into a pointer the pool does not remember (a local, a member of Cost).
+inline int alloc_status(cspm_ctx *c, int e) {
+  return e ? fail(c, CSPM_ERR_HIP, std::string("hipMalloc: ") + hipGetErrorString((hipError_t)e)) : CSPM_OK;
 }
+template <class T>
+int dalloc(cspm_ctx *c, DevPool &pool, T **slot, size_t n) { return alloc_status(c, pool.get(slot, n)); }
+template <class T>
+int dalloc_local(cspm_ctx *c, DevPool &pool, T **p, size_t n, size_t lead = 0) { return alloc_status(c, pool.add(p, n, lead)); }
 
 // channel-major planes (six slabs of n values, as the device holds a field) into the interleaved records of the ABI, and back
 void interleave_planes(const double *planar, size_t n, double *np_out) {
@@ -316,7 +325,7 @@ struct CandBuf {
 };
 int ensure_cand(cspm_ctx *c, CandBuf *out) {
   const size_t n = (size_t)c->W * c->H;
-  int rc = c->cand_mem ? CSPM_OK : dalloc(c, &c->cand_mem, 6 * n + (n + 7) / 8, nullptr);
+  const int rc = dalloc(c, c->mem_field, &c->cand_mem, 6 * n + (n + 7) / 8);
   if (!rc) *out = CandBuf{six_slabs(c->cand_mem, n), reinterpret_cast<uint8_t *>(c->cand_mem + 6 * n)};
   return rc;
 }
@@ -405,80 +414,39 @@ inline unsigned ew_grid(long long n, int block = 256) { return (unsigned)((n + b
 inline unsigned stride_grid(long long n, int block = 256) { return (unsigned)std::min<long long>((n + block - 1) / block, 256 * 16); }
 
 void free_cost(cspm_ctx *c) {
-  for (void *p : c->cost_allocs) (void)hipFree(p);
-  c->cost_allocs.clear();
+  c->mem_cost.release();
   c->cost_alloc = c->cost_ready = false;
   c->cost_key = CostKey{};
   memset(&c->cost, 0, sizeof c->cost);
 }
-// hipFree of a pointer that may not be set; the pointer is null afterwards
-template <class T>
-void dfree(T *&p) {
-  if (p) (void)hipFree((void *)p);
-  p = nullptr;
-}
+// the pool's release nulls every pointer it gave out; what else describes the memory is reset here
 void free_field(cspm_ctx *c) {
-  dfree(c->field_mem);
-  dfree(c->warm_snap);
-  dfree(c->diffuse_snap);
-  dfree(c->cand_mem);
-  dfree(c->fit_mem);
-  dfree(c->seg_mem);
-  c->seg_ran = false;
-  dfree(c->geom_disp);
-  dfree(c->geom_fit);
-  dfree(c->geom_counts);
-  dfree(c->mesh_bytes);
-  dfree(c->mesh_map);
-  dfree(c->synth_disp);
-  dfree(c->vc.cost);
-  dfree(c->vc.c);
-  dfree(c->vc.cx);
-  dfree(c->vc.perm);
-  for (int v = 0; v < 2; ++v) {
-    dfree(c->d_dis[v]);
-    dfree(c->d_valid[v]);
-  }
-  dfree(c->d_todo);
-  dfree(c->d_speckle);
-  c->speckle_ran = false;
-  dfree(c->d_med8[0]);
-  dfree(c->d_med8[1]);
-  dfree(c->d_med64);
-  dfree(c->d_smooth);
+  c->mem_field.release();
+  c->d_pp[1] = nullptr;  // lies in d_pp[0]'s allocation
+  c->field_alloc = c->seg_ran = c->speckle_ran = false;
   c->smooth_lut_sigma = 0.0;
-  dfree(c->d_pp[0]);  // one allocation holds both maps
-  c->d_pp[1] = nullptr;
-  dfree(c->d_rowq);
-  dfree(c->fpm.xy);
-  dfree(c->fpm.view);
-  dfree(c->fpm.plane);
-  dfree(c->fpm.cost);
   c->fpm_cap = 0;
   c->fpm_phase = -1;
-  dfree(c->d_sweep_ctrl);
-  dfree(c->d_sweep_gran);
-  dfree(c->d_sweep_start);
-  dfree(c->d_sweep_ready);
-  dfree(c->d_sweep_qctl);
-  dfree(c->d_sweep_queue);
-  c->field_alloc = false;
 }
 void free_rect(cspm_ctx *c) {
-  for (int v = 0; v < 2; ++v) {
-    dfree(c->rect_map[v]);
-    dfree(c->rect_valid[v]);
-  }
-  dfree(c->rect_stage);
-  dfree(c->rect_rawpix);
-  dfree(c->rect_out);
+  c->mem_rect.release();
   c->rect_on = false;
 }
+void free_ca(cspm_ctx *c) {
+  c->mem_ca.release();
+  c->ca_nb = 0;
+}
 void free_images(cspm_ctx *c) {
-  for (int v = 0; v < 2; ++v) dfree(c->img0[v]);
-  dfree(c->stage);
+  c->mem_images.release();
   c->stage_bytes = 0;
   c->W = c->H = 0;
+}
+// the geometry changes (the caller has synchronised the stream): everything sized by W x H goes
+void free_geometry(cspm_ctx *c) {
+  free_cost(c);
+  free_field(c);
+  free_ca(c);
+  free_images(c);
 }
 
 void small_inverse_row0(int S, const double A[CSPM_MAX_LEVELS][CSPM_MAX_LEVELS], double *w);
@@ -658,9 +626,9 @@ int alloc_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg
       const size_t px = (size_t)W * H, ppx = (size_t)L.Wp * H;
       for (int v = 0; v < 2; ++v) {
         uint32_t *img;
-        if ((rc = dalloc(c, &img, ppx, &c->cost_allocs))) return rc;
+        if ((rc = dalloc_local(c, c->mem_cost, &img, ppx))) return rc;
         PixG *pxg;
-        if ((rc = dalloc(c, &pxg, ppx, &c->cost_allocs))) return rc;
+        if ((rc = dalloc_local(c, c->mem_cost, &pxg, ppx))) return rc;
         L.px[v] = pxg;
         L.px16[v] = nullptr;
         L.px8[v] = nullptr;
@@ -678,38 +646,29 @@ int alloc_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg
           // D == 0 (max_dis < 2^s) clamps to [-1, 1] (cspm_tap.h split_disp: med3(f, 1, D - 1)) and addresses slabs -1 .. 2: one more guard
           // slab on either side, the volume starts behind the first.  No tap of such a level is valid; the guard values are never used.
           const size_t lead = D < 1 ? px : 0;
-          if ((rc = dalloc(c, &vol, (size_t)(D + 2) * px + 2 * lead, &c->cost_allocs))) return rc;
-          vol += lead;
+          if ((rc = dalloc_local(c, c->mem_cost, &vol, (size_t)(D + 2) * px + lead, lead))) return rc;  // vol is `lead` behind what the pool frees
           L.vol[v] = vol;
         }
         if (need_grd) {
           double *g;
-          if ((rc = dalloc(c, &g, ppx + grd_slack, &c->cost_allocs))) return rc;
+          if ((rc = dalloc_local(c, c->mem_cost, &g, ppx + grd_slack))) return rc;
           L.grd[v] = g;
         }
         if (need_px16) {
           uint4 *p16;
-          if ((rc = dalloc(c, &p16, ppx + 64, &c->cost_allocs))) return rc;
+          if ((rc = dalloc_local(c, c->mem_cost, &p16, ppx + 64))) return rc;
           L.px16[v] = p16;
         }
         if (with_px8) {
           Pix8 *p8;
-          if ((rc = dalloc(c, &p8, ppx + 64, &c->cost_allocs))) return rc;  // + slack: a pair load at the last element reads one element beyond
+          if ((rc = dalloc_local(c, c->mem_cost, &p8, ppx + 64))) return rc;  // + slack: a pair load at the last element reads one element beyond
           L.px8[v] = p8;
         }
-        if (need_gray) {
-          uint8_t *gray;
-          if ((rc = dalloc(c, &gray, px, &c->cost_allocs))) return rc;
-          c->cen_gray[v][s] = gray;
-        }
-        if (need_code) {
-          uint32_t *code;
-          if ((rc = dalloc(c, &code, px * 3, &c->cost_allocs))) return rc;
-          c->cen_code[v][s] = code;
-        }
+        if (need_gray && (rc = dalloc(c, c->mem_cost, &c->cen_gray[v][s], px))) return rc;
+        if (need_code && (rc = dalloc(c, c->mem_cost, &c->cen_code[v][s], px * 3))) return rc;
         if (need_pc) {
           PixC *pc;
-          if ((rc = dalloc(c, &pc, ppx, &c->cost_allocs))) return rc;
+          if ((rc = dalloc_local(c, c->mem_cost, &pc, ppx))) return rc;
           L.pc[v] = pc;
         }
       }
@@ -728,10 +687,9 @@ int alloc_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg
         if (with_pairs && pairs_bytes > avail) with_pairs = false;
       }
     }
-    const size_t mandatory = c->cost_allocs.size();
+    const DevPool::Mark mandatory = c->mem_cost.mark();
     auto drop_optional = [&]() {  // give back whatever this pass allocated and run without either kind of volume
-      for (size_t i = mandatory; i < c->cost_allocs.size(); ++i) (void)hipFree(c->cost_allocs[i]);
-      c->cost_allocs.resize(mandatory);
+      c->mem_cost.rewind(mandatory);
       for (int s = 0; s < cd.levels; ++s)
         for (int v = 0; v < 2; ++v) cd.lv[s].cvol[v] = nullptr, cd.lv[s].vol2[v] = nullptr;
       (void)hipGetLastError();  // the out-of-memory error is handled: do not leave it as the runtime's sticky last error
@@ -745,13 +703,13 @@ int alloc_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg
         if (with_cvol) {
           double *cv;
           const size_t ncv = (size_t)(L.D + 1) * L.H * L.cvW + 64;  // + slack: the last DMA piece of the last row may run 8 bytes over
-          if ((c->fault_volume_alloc > 0 && --c->fault_volume_alloc == 0) || dalloc(c, &cv, ncv, &c->cost_allocs) != CSPM_OK) { drop_optional(); with_cvol = with_pairs = false; break; }
+          if ((c->fault_volume_alloc > 0 && --c->fault_volume_alloc == 0) || dalloc_local(c, c->mem_cost, &cv, ncv) != CSPM_OK) { drop_optional(); with_cvol = with_pairs = false; break; }
           HIPCHK(c, hipMemsetAsync(cv, 0, ncv * sizeof(double), c->stream));  // the pad columns stay 0.0; the image columns are rewritten per pair
           L.cvol[v] = cv;
         }
         if (with_pairs) {
           double2 *v2;  // slabs 0 .. D-1; a level with D < 2 is only ever addressed (slab 1), never used
-          if ((c->fault_volume_alloc > 0 && --c->fault_volume_alloc == 0) || dalloc(c, &v2, (size_t)std::max(L.D, 2) * px, &c->cost_allocs) != CSPM_OK) { drop_optional(); with_cvol = with_pairs = false; break; }
+          if ((c->fault_volume_alloc > 0 && --c->fault_volume_alloc == 0) || dalloc_local(c, c->mem_cost, &v2, (size_t)std::max(L.D, 2) * px) != CSPM_OK) { drop_optional(); with_cvol = with_pairs = false; break; }
           L.vol2[v] = v2;
         }
       }
@@ -765,13 +723,13 @@ int alloc_cost(cspm_ctx *c, int max_dis, int wnd_size, int scale_num, double reg
       clrDiff = clrDiff > 10.0 ? 10.0 : clrDiff;  // TAU_CLR
       lut[kLutSize + i] = 0.1 * clrDiff;   // ALPHA * clrDiff
     }
-    if ((rc = dalloc(c, &c->d_lut, 2 * kLutSize, &c->cost_allocs))) return rc;
+    if ((rc = dalloc(c, c->mem_cost, &c->d_lut, 2 * kLutSize))) return rc;
     c->d_lut_a = c->d_lut + kLutSize;
-    if ((rc = dalloc(c, &c->d_maxcost, 2 * CSPM_MAX_LEVELS, &c->cost_allocs))) return rc;
-    if ((rc = dalloc(c, &c->d_early_ok, 1, &c->cost_allocs))) return rc;
-    if ((rc = dalloc(c, &c->d_px8_bad, 1, &c->cost_allocs))) return rc;
+    if ((rc = dalloc(c, c->mem_cost, &c->d_maxcost, 2 * CSPM_MAX_LEVELS))) return rc;
+    if ((rc = dalloc(c, c->mem_cost, &c->d_early_ok, 1))) return rc;
+    if ((rc = dalloc(c, c->mem_cost, &c->d_px8_bad, 1))) return rc;
     HIPCHK(c, hipMemsetAsync(c->d_px8_bad, 0, sizeof(unsigned int), c->stream));
-    if ((rc = dalloc(c, &c->d_maxkeys, 4 * CSPM_MAX_LEVELS, &c->cost_allocs))) return rc;
+    if ((rc = dalloc(c, c->mem_cost, &c->d_maxkeys, 4 * CSPM_MAX_LEVELS))) return rc;
     HIPCHK(c, hipMemcpy(c->d_lut, lut, sizeof lut, hipMemcpyHostToDevice));
     cd.lut = c->d_lut;
     cd.lut_a = c->d_lut_a;
@@ -946,25 +904,25 @@ int ensure_field(cspm_ctx *c) {
   if (c->field_alloc) return CSPM_OK;
   const size_t n = (size_t)c->W * c->H;
   int rc;
-  if ((rc = dalloc(c, &c->field_mem, 14 * n, nullptr))) return rc;
+  if ((rc = dalloc(c, c->mem_field, &c->field_mem, 14 * n))) return rc;
   for (int v = 0; v < 2; ++v) {
     double *base = c->field_mem + (size_t)v * 7 * n;
     c->f[v] = Field{base, base + n, base + 2 * n, base + 3 * n, base + 4 * n, base + 5 * n, base + 6 * n};
   }
-  if ((rc = dalloc(c, &c->vc.cost, n, nullptr))) return rc;
-  if ((rc = dalloc(c, &c->vc.c, n, nullptr))) return rc;
-  if ((rc = dalloc(c, &c->vc.cx, n, nullptr))) return rc;
-  if ((rc = dalloc(c, &c->vc.perm, n, nullptr))) return rc;
+  if ((rc = dalloc(c, c->mem_field, &c->vc.cost, n))) return rc;
+  if ((rc = dalloc(c, c->mem_field, &c->vc.c, n))) return rc;
+  if ((rc = dalloc(c, c->mem_field, &c->vc.cx, n))) return rc;
+  if ((rc = dalloc(c, c->mem_field, &c->vc.perm, n))) return rc;
   for (int v = 0; v < 2; ++v) {
-    if ((rc = dalloc(c, &c->d_dis[v], n, nullptr))) return rc;
-    if ((rc = dalloc(c, &c->d_valid[v], n, nullptr))) return rc;
+    if ((rc = dalloc(c, c->mem_field, &c->d_dis[v], n))) return rc;
+    if ((rc = dalloc(c, c->mem_field, &c->d_valid[v], n))) return rc;
   }
-  if ((rc = dalloc(c, &c->d_todo, 2 * n + 2, nullptr))) return rc;
-  if ((rc = dalloc(c, &c->d_rowq, 8, nullptr))) return rc;
+  if ((rc = dalloc(c, c->mem_field, &c->d_todo, 2 * n + 2))) return rc;
+  if ((rc = dalloc(c, c->mem_field, &c->d_rowq, 8))) return rc;
   // persistent sweep state: control words, per-pixel granules (tag zero = never written), diagonal start table
-  if ((rc = dalloc(c, &c->d_sweep_ctrl, 2 + kSweepMaxBands, nullptr))) return rc;
+  if ((rc = dalloc(c, c->mem_field, &c->d_sweep_ctrl, 2 + kSweepMaxBands))) return rc;
   HIPCHK(c, hipMemsetAsync(c->d_sweep_ctrl, 0, (2 + kSweepMaxBands) * sizeof(unsigned int), c->stream));
-  if ((rc = dalloc(c, &c->d_sweep_gran, 2 * n * kGranPerPixel, nullptr))) return rc;
+  if ((rc = dalloc(c, c->mem_field, &c->d_sweep_gran, 2 * n * kGranPerPixel))) return rc;
   HIPCHK(c, hipMemsetAsync(c->d_sweep_gran, 0, sizeof(unsigned long long) * 2 * n * kGranPerPixel, c->stream));
   c->sweep_epoch = 0;
   {
@@ -980,7 +938,7 @@ int ensure_field(cspm_ctx *c) {
         st[k + 1] = st[k] + 2u * (unsigned)std::max(cnt, 0);
       }
     }
-    if ((rc = dalloc(c, &c->d_sweep_start, start.size(), nullptr))) return rc;
+    if ((rc = dalloc(c, c->mem_field, &c->d_sweep_start, start.size()))) return rc;
     HIPCHK(c, hipMemcpy(c->d_sweep_start, start.data(), start.size() * sizeof(unsigned int), hipMemcpyHostToDevice));
     c->sweep_bands_built = nb;
   }
@@ -993,13 +951,13 @@ int ensure_field(cspm_ctx *c) {
 // words -- 24 bytes per pixel that the default sweep never touches, so they are allocated by the first sweep that wants them
 // (free_field releases them).
 int ensure_flow(cspm_ctx *c) {
-  if (c->d_sweep_ready) return CSPM_OK;
+  if (c->d_sweep_ready && c->d_sweep_queue && c->d_sweep_qctl) return CSPM_OK;
   const size_t n = (size_t)c->W * c->H;
   int rc;
-  if ((rc = dalloc(c, &c->d_sweep_ready, 2 * n, nullptr))) return rc;
-  if ((rc = dalloc(c, &c->d_sweep_queue, 2 * n + 65536, nullptr))) return rc;
+  if ((rc = dalloc(c, c->mem_field, &c->d_sweep_ready, 2 * n))) return rc;
+  if ((rc = dalloc(c, c->mem_field, &c->d_sweep_queue, 2 * n + 65536))) return rc;
   HIPCHK(c, hipMemsetAsync(c->d_sweep_queue, 0, sizeof(unsigned long long) * (2 * n + 65536), c->stream));
-  if ((rc = dalloc(c, &c->d_sweep_qctl, 4, nullptr))) return rc;
+  if ((rc = dalloc(c, c->mem_field, &c->d_sweep_qctl, 4))) return rc;
   return CSPM_OK;
 }
 
@@ -1130,14 +1088,9 @@ int do_spatial(cspm_ctx *c, int iter, const cspm_pm_params *p) {
     static const signed char kOff4[4][2] = {CSPM_DIFFUSE_OFFSETS_4}, kOff8[8][2] = {CSPM_DIFFUSE_OFFSETS_8},
                              kOff20[20][2] = {CSPM_DIFFUSE_OFFSETS_20};
     const size_t n = (size_t)c->W * c->H;
-    if (!c->diffuse_snap) {
-      void *q = nullptr;
-      const hipError_t e = hipMalloc(&q, sizeof(double) * 12 * n);
-      if (e != hipSuccess)
-        return fail(c, CSPM_ERR_HIP, "CSPM_SCHED_DIFFUSE: no memory for the snapshot of the plane fields (" + std::to_string(sizeof(double) * 12 * n) +
-                                         " bytes): " + hipGetErrorString(e));
-      c->diffuse_snap = (double *)q;
-    }
+    if (const int e = c->mem_field.get(&c->diffuse_snap, 12 * n))
+      return fail(c, CSPM_ERR_HIP, "CSPM_SCHED_DIFFUSE: no memory for the snapshot of the plane fields (" + std::to_string(sizeof(double) * 12 * n) +
+                                       " bytes): " + hipGetErrorString((hipError_t)e));
     Diffuse df{};
     df.K = p->rb_neighbours;
     const signed char(*off)[2] = df.K == 4 ? kOff4 : df.K == 8 ? kOff8 : kOff20;
@@ -1307,10 +1260,7 @@ int do_merge(cspm_ctx *c, const CandField *cf, const cspm_pm_params *p, int view
 // both views' 7 arrays, field -> snapshot (save) or back (restore); the snapshot is allocated by the first warm run and kept
 int warm_snapshot(cspm_ctx *c, bool save) {
   const size_t bytes = sizeof(double) * 14 * (size_t)c->W * c->H;
-  if (!c->warm_snap) {
-    int rc = dalloc(c, &c->warm_snap, 14 * (size_t)c->W * c->H, nullptr);
-    if (rc) return rc;
-  }
+  if (int rc = dalloc(c, c->mem_field, &c->warm_snap, 14 * (size_t)c->W * c->H)) return rc;
   HIPCHK(c, hipMemcpyAsync(save ? c->warm_snap : c->field_mem, save ? c->field_mem : c->warm_snap, bytes, hipMemcpyDeviceToDevice, c->stream));
   return CSPM_OK;
 }
@@ -1422,10 +1372,7 @@ int speckle_enqueue(cspm_ctx *c, const T *d0, const T *d1, double thr) {
   if (!c->speckle_ran) return CSPM_OK;
   const long long n = (long long)c->W * c->H;
   if (n >= (1LL << 31)) return fail(c, CSPM_ERR_ARG, "image too large for the speckle filter's 32-bit labels");
-  if (!c->d_speckle) {
-    int rc = dalloc(c, &c->d_speckle, 4 * (size_t)n + 1, nullptr);
-    if (rc) return rc;
-  }
+  if (int rc = dalloc(c, c->mem_field, &c->d_speckle, 4 * (size_t)n + 1)) return rc;
   unsigned int *removed = (unsigned int *)(c->d_speckle + 4 * n);
   HIPCHK(c, hipMemsetAsync(removed, 0, sizeof(unsigned int), c->stream));
   const T *d[2] = {d0, d1};
@@ -1489,8 +1436,7 @@ void median_launch_f64(hipStream_t stream, const double *const *src, double *con
 int median_u8_enqueue(cspm_ctx *c) {
   if (c->pp_median == 0) return CSPM_OK;
   for (int v = 0; v < 2; ++v)
-    if (!c->d_med8[v])
-      if (int rc = dalloc(c, &c->d_med8[v], (size_t)c->W * c->H, nullptr)) return rc;
+    if (int rc = dalloc(c, c->mem_field, &c->d_med8[v], (size_t)c->W * c->H)) return rc;
   Timed t(c, CSPM_K_POST, 0);
   median_launch_u8(c->stream, c->d_dis, c->d_med8, 2, (size_t)c->W, (size_t)c->W, c->W, c->H, 1, c->pp_median);
   HIPCHK(c, hipGetLastError());
@@ -1501,8 +1447,7 @@ int median_u8_enqueue(cspm_ctx *c) {
 int median_f64_enqueue(cspm_ctx *c) {
   if (c->pp_median == 0) return CSPM_OK;
   const size_t n = (size_t)c->W * c->H;
-  if (!c->d_med64)
-    if (int rc = dalloc(c, &c->d_med64, 2 * n, nullptr)) return rc;
+  if (int rc = dalloc(c, c->mem_field, &c->d_med64, 2 * n)) return rc;
   double *dst[2] = {c->d_med64, c->d_med64 + n};
   Timed t(c, CSPM_K_POST, 0);
   median_launch_f64(c->stream, c->d_pp, dst, 2, c->W, c->H, c->pp_median);
@@ -1554,10 +1499,7 @@ int smooth_f64_enqueue(cspm_ctx *c) {
   const cspm_smooth_params &p = c->pp_smooth;
   if (p.lambda == 0.0) return CSPM_OK;
   const size_t n = (size_t)c->W * c->H;
-  if (!c->d_smooth) {
-    if (int rc = dalloc(c, &c->d_smooth, 6 * n + kSmLut, nullptr)) return rc;
-    c->smooth_lut_sigma = 0.0;
-  }
+  if (int rc = dalloc(c, c->mem_field, &c->d_smooth, 6 * n + kSmLut)) return rc;  // a new one has no table: free_field zeroes smooth_lut_sigma
   double *d_lut = c->d_smooth + 6 * n;
   if (c->smooth_lut_sigma != p.sigma_color) {  // a new table: the stream is drained so that no earlier launch still reads the old one
     c->smooth_lut.resize(kSmLut);
@@ -1606,11 +1548,8 @@ int enqueue_disp_u8(cspm_ctx *c, int view, int dis_scale, void *d_out) {
 // The 8-bit path's maps (c->d_dis) are not touched; the flags and the work list are scratch of whichever path runs.
 int postprocess_f64_steps(cspm_ctx *c) {
   const long long n = (long long)c->W * c->H;
-  if (!c->d_pp[0]) {
-    int rc = dalloc(c, &c->d_pp[0], 2 * (size_t)n, nullptr);
-    if (rc) return rc;
-    c->d_pp[1] = c->d_pp[0] + n;
-  }
+  if (int rc = dalloc(c, c->mem_field, &c->d_pp[0], 2 * (size_t)n)) return rc;
+  c->d_pp[1] = c->d_pp[0] + n;
   if (fill_rows_shmem(c->W) > 160 * 1024) return fail(c, CSPM_ERR_ARG, "image too wide for the row scan of FillInvalid");
   const Pm pm = field_pm(c);
   const Level &L0 = c->cost.lv[0];
@@ -1760,9 +1699,9 @@ void geom_launch(hipStream_t stream, const GeomCam &cam, const GeomIn &in, const
 int geom_inputs_alloc(cspm_ctx *c, int source, const cspm_fit_params *fit) {
   int rc = CSPM_OK;
   const size_t n = (size_t)c->W * c->H;
-  if (source == CSPM_GEOM_RAW && !c->geom_disp && (rc = dalloc(c, &c->geom_disp, n, nullptr))) return rc;
+  if (source == CSPM_GEOM_RAW && (rc = dalloc(c, c->mem_field, &c->geom_disp, n))) return rc;
   if (fit && !c->geom_fit) {
-    if ((rc = dalloc(c, &c->geom_fit, 6 * n + kFitLut, nullptr))) return rc;
+    if ((rc = dalloc(c, c->mem_field, &c->geom_fit, 6 * n + kFitLut))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->geom_fit + 6 * n, fit_lut(), sizeof(double) * kFitLut, hipMemcpyHostToDevice, c->stream));
   }
   if (source == CSPM_GEOM_PP && (rc = postprocess_f64_enqueue(c))) return rc;
@@ -1800,7 +1739,7 @@ int reproject_enqueue(cspm_ctx *c, int view, int source, const cspm_calib *calib
   if (rc) return rc;
   const size_t n = (size_t)c->W * c->H;
   const unsigned nb = geom_blocks((long long)n);
-  if (!c->geom_counts && (rc = dalloc(c, &c->geom_counts, (size_t)nb + 1, nullptr))) return rc;
+  if ((rc = dalloc(c, c->mem_field, &c->geom_counts, (size_t)nb + 1))) return rc;
   if ((rc = geom_inputs_alloc(c, source, fit))) return rc;
   {
     Timed t(c, CSPM_K_MISC, (long long)n);
@@ -1882,8 +1821,8 @@ int mesh_enqueue(cspm_ctx *c, int view, int source, const cspm_calib *calib, con
   if (rc) return rc;
   const size_t n = (size_t)c->W * c->H;
   const unsigned nb = geom_blocks((long long)n);
-  if (!c->mesh_bytes && (rc = dalloc(c, &c->mesh_bytes, 2 * n, nullptr))) return rc;
-  if (!c->mesh_map && (rc = dalloc(c, &c->mesh_map, n + mesh_count_words(nb), nullptr))) return rc;
+  if ((rc = dalloc(c, c->mem_field, &c->mesh_bytes, 2 * n))) return rc;
+  if ((rc = dalloc(c, c->mem_field, &c->mesh_map, n + mesh_count_words(nb)))) return rc;
   if ((rc = geom_inputs_alloc(c, source, fit))) return rc;
   {
     Timed t(c, CSPM_K_MISC, (long long)n);
@@ -1940,7 +1879,7 @@ int synthesize_enqueue(cspm_ctx *c, int source, const cspm_synth_params *p, doub
   int rc = check_sweep(c);  // BEFORE the field is read, as in reproject_enqueue
   if (rc) return rc;
   const size_t n = (size_t)c->W * c->H;
-  if (source == CSPM_GEOM_RAW && !c->synth_disp && (rc = dalloc(c, &c->synth_disp, 2 * n, nullptr))) return rc;
+  if (source == CSPM_GEOM_RAW && (rc = dalloc(c, c->mem_field, &c->synth_disp, 2 * n))) return rc;
   if (source == CSPM_GEOM_PP && (rc = postprocess_f64_enqueue(c))) return rc;
   {
     Timed tm(c, CSPM_K_MISC, (long long)n);
@@ -2005,13 +1944,13 @@ void ca_filter(cspm_ctx *c, int method, const CaWork &w, int W, int H, const dou
   }
 }
 
-// allocate a CaWork for images of up to px pixels and batches of nb slices
-int ca_alloc_work(cspm_ctx *c, size_t px, int nb, CaWork *w, std::vector<void *> *track) {
+// allocate a CaWork for images of up to px pixels and batches of nb slices; the pool does not remember *w, which may be a local
+int ca_alloc_work(cspm_ctx *c, size_t px, int nb, CaWork *w, DevPool &pool) {
   int rc;
   double *gt;
   w->nb = nb;
-  if ((rc = dalloc(c, &w->gn, 3 * px, track)) || (rc = dalloc(c, &gt, 16 * px, track)) || (rc = dalloc(c, &w->t, ca_t_slabs(nb) * px, track)) ||
-      (rc = dalloc(c, &w->s, (size_t)4 * nb * px, track)))
+  if ((rc = dalloc_local(c, pool, &w->gn, 3 * px)) || (rc = dalloc_local(c, pool, &gt, 16 * px)) ||
+      (rc = dalloc_local(c, pool, &w->t, ca_t_slabs(nb) * px)) || (rc = dalloc_local(c, pool, &w->s, (size_t)4 * nb * px)))
     return rc;
   w->gt = CaGuideT{gt, gt + 3 * px, gt + 6 * px, gt + 15 * px};
   return CSPM_OK;
@@ -2038,20 +1977,18 @@ int ca_ensure(cspm_ctx *c) {
   const long long key[4] = {c->W, c->H, c->max_dis, cd.levels};
   if (c->ca_nb && std::equal(key, key + 4, c->ca_key)) return CSPM_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (void *p : c->ca_allocs) (void)hipFree(p);
-  c->ca_allocs.clear();
-  c->ca_nb = 0;
+  free_ca(c);  // ca_nb == 0 until every buffer is there: a call that fails half-way leaves nothing the next one would use
   const size_t px = (size_t)c->W * c->H;
   const int nb = ca_batch(px);
   CaWork w;
   int rc;
-  if ((rc = ca_alloc_work(c, px, nb, &w, &c->ca_allocs))) return rc;
-  if ((rc = dalloc(c, &c->ca_raw, (size_t)nb * px, &c->ca_allocs)) || (rc = dalloc(c, &c->ca_out, (size_t)nb * px, &c->ca_allocs)) ||
-      (rc = dalloc(c, &c->ca_best, px, &c->ca_allocs)) || (rc = dalloc(c, &c->ca_bestd, px, &c->ca_allocs)) ||
-      (rc = dalloc(c, &c->ca_keys, CSPM_MAX_LEVELS, &c->ca_allocs)))
+  if ((rc = ca_alloc_work(c, px, nb, &w, c->mem_ca))) return rc;
+  if ((rc = dalloc(c, c->mem_ca, &c->ca_raw, (size_t)nb * px)) || (rc = dalloc(c, c->mem_ca, &c->ca_out, (size_t)nb * px)) ||
+      (rc = dalloc(c, c->mem_ca, &c->ca_best, px)) || (rc = dalloc(c, c->mem_ca, &c->ca_bestd, px)) ||
+      (rc = dalloc(c, c->mem_ca, &c->ca_keys, CSPM_MAX_LEVELS)))
     return rc;
   for (int s = 1; s < cd.levels; ++s)
-    if ((rc = dalloc(c, &c->ca_vol[s], (size_t)(cd.lv[s].D + 1) * cd.lv[s].W * cd.lv[s].H, &c->ca_allocs))) return rc;
+    if ((rc = dalloc(c, c->mem_ca, &c->ca_vol[s], (size_t)(cd.lv[s].D + 1) * cd.lv[s].W * cd.lv[s].H))) return rc;
   c->ca_gn = w.gn;
   c->ca_t = w.t;
   c->ca_s = w.s;
@@ -2218,7 +2155,7 @@ inline void rect_remap_launch(hipStream_t stream, const uint8_t *raw_bgr, size_t
 struct Staging {
   cspm_ctx *c;
   int rc;
-  std::vector<void *> bufs;
+  DevPool bufs{dev_alloc, dev_free};  // freed when the Staging goes, behind ~Staging's wait
   bool broke = false;   // a launch or a download failed: finish() names it
   bool settled = true;  // no copy enqueued here since the last wait
 
@@ -2226,7 +2163,6 @@ struct Staging {
   Staging(const Staging &) = delete;
   ~Staging() {
     if (!settled) wait();
-    for (void *p : bufs) (void)hipFree(p);
   }
   bool wait() { return settled = hipStreamSynchronize(c->stream) == hipSuccess; }
   bool copied(hipError_t e) { return settled = false, e == hipSuccess; }  // the result of a copy that was just enqueued
@@ -2239,7 +2175,7 @@ struct Staging {
   template <class T>
   T *buf(size_t n, bool want = true) {
     T *p = nullptr;
-    if (!rc && want) latch(dalloc(c, &p, n, &bufs));
+    if (!rc && want) latch(dalloc_local(c, bufs, &p, n));
     return p;
   }
   template <class T>
@@ -2407,11 +2343,8 @@ void cspm_destroy(cspm_ctx *c) {
   (void)hipStreamSynchronize(c->stream);
   for (auto &r : c->recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
   for (auto e : c->pool) (void)hipEventDestroy(e);
-  free_cost(c);
-  free_field(c);
-  free_images(c);
+  free_geometry(c);
   free_rect(c);
-  for (void *p : c->ca_allocs) (void)hipFree(p);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
 }
@@ -2450,12 +2383,10 @@ static int set_images_impl(cspm_ctx *c, const void *l, const void *r, int w, int
   ON_DEVICE(c);
   if (w != c->W || h != c->H) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_cost(c);
-    free_field(c);
-    free_images(c);
+    free_geometry(c);
     int rc;
     for (int v = 0; v < 2; ++v)
-      if ((rc = dalloc(c, &c->img0[v], (size_t)w * h, nullptr))) return rc;
+      if ((rc = dalloc(c, c->mem_images, &c->img0[v], (size_t)w * h))) return rc;
     c->W = w; c->H = h;
   } else {
     c->cost_ready = false;
@@ -2465,9 +2396,9 @@ static int set_images_impl(cspm_ctx *c, const void *l, const void *r, int w, int
   const void *src[2] = {l, r};
   const size_t row = (size_t)w * 3;
   if (!on_device && c->stage_bytes < 2 * row * h) {
-    dfree(c->stage);
+    c->mem_images.drop(&c->stage);
     c->stage_bytes = 0;
-    if (int rc = dalloc(c, &c->stage, 2 * row * h, nullptr)) return rc;
+    if (int rc = dalloc(c, c->mem_images, &c->stage, 2 * row * h)) return rc;
     c->stage_bytes = 2 * row * h;
   }
   Staging S(c);
@@ -2562,6 +2493,9 @@ int cspm_get_option(cspm_ctx *c, int key, long long *value) {
     case CSPM_OPT_RASTER_LAUNCHES: *value = c->opt_raster_launches; return CSPM_OK;
     case CSPM_OPT_SWEEP_TIMEOUT_MS: *value = c->sweep_timeout_ms; return CSPM_OK;
     case CSPM_OPT_SWEEP_FALLBACKS: *value = c->sweep_fallbacks; return CSPM_OK;
+    case CSPM_OPT_DEVICE_BYTES:
+      *value = (long long)(c->mem_images.bytes() + c->mem_cost.bytes() + c->mem_field.bytes() + c->mem_rect.bytes() + c->mem_ca.bytes());
+      return CSPM_OK;
     case CSPM_OPT_SWEEP_PAIRS: *value = c->opt_sweep_pairs; return CSPM_OK;
     case CSPM_OPT_TABLE_VOLUMES: *value = c->opt_table_volumes; return CSPM_OK;
     case CSPM_OPT_TABLE_VOLUMES_ACTIVE: *value = (c->cost_alloc && c->cost.lv[0].cvol[0]) ? 1 : 0; return CSPM_OK;
@@ -2692,7 +2626,7 @@ int cspm_set_rectification(cspm_ctx *c, const cspm_rig *rig, const cspm_rectific
   const size_t n = (size_t)rect->w * rect->h;
   int rc;
   for (int v = 0; v < 2; ++v)
-    if ((rc = dalloc(c, &c->rect_map[v], 2 * n, nullptr)) || (rc = dalloc(c, &c->rect_valid[v], n, nullptr))) {
+    if ((rc = dalloc(c, c->mem_rect, &c->rect_map[v], 2 * n)) || (rc = dalloc(c, c->mem_rect, &c->rect_valid[v], n))) {
       free_rect(c);
       return rc;
     }
@@ -2728,9 +2662,9 @@ static int set_images_raw_impl(cspm_ctx *c, const void *l, const void *r, size_t
   ON_DEVICE(c);
   const size_t rn = (size_t)rw * rh, n = (size_t)w * h, raw_row = (size_t)rw * 3, row = (size_t)w * 3;
   int rc;
-  if (!c->rect_rawpix && (rc = dalloc(c, &c->rect_rawpix, 2 * rn, nullptr))) return rc;
-  if (!c->rect_out && (rc = dalloc(c, &c->rect_out, 2 * 3 * n, nullptr))) return rc;
-  if (!on_device && !c->rect_stage && (rc = dalloc(c, &c->rect_stage, 2 * 3 * rn, nullptr))) return rc;
+  if ((rc = dalloc(c, c->mem_rect, &c->rect_rawpix, 2 * rn))) return rc;
+  if ((rc = dalloc(c, c->mem_rect, &c->rect_out, 2 * 3 * n))) return rc;
+  if (!on_device && (rc = dalloc(c, c->mem_rect, &c->rect_stage, 2 * 3 * rn))) return rc;
   const uint8_t *d_src[2] = {(const uint8_t *)l, (const uint8_t *)r};
   const size_t d_stride = on_device ? stride : raw_row;
   Staging S(c);  // a host source: whatever fails behind an upload that was enqueued, the caller may reuse its buffers when this returns
@@ -2943,7 +2877,7 @@ int cspm_aggregate_cv_host(int device, int method, const double *guide, int w, i
   for (size_t i = 0; i < px; ++i)
     for (int k = 0; k < 3; ++k) gn[k * px + i] = guide[3 * i + k];
   CaWork wk;
-  if (!S.rc) S.latch(ca_alloc_work(c, px, nb, &wk, &S.bufs));
+  if (!S.rc) S.latch(ca_alloc_work(c, px, nb, &wk, S.bufs));
   S.put(wk.gn, gn.data(), 3 * px);
   double *dv = S.up(vol + px, (size_t)(n_slices - 1) * px);
   double *dout = S.buf<double>((size_t)nb * px);
@@ -3321,7 +3255,7 @@ int cspm_fit_planes(cspm_ctx *c, const cspm_fit_params *p, int merge) {
       [&](double **snap) -> int {
         const size_t n = (size_t)c->W * c->H;
         if (!c->fit_mem) {
-          if (int rc = dalloc(c, &c->fit_mem, 2 * n + kFitLut, nullptr)) return rc;
+          if (int rc = dalloc(c, c->mem_field, &c->fit_mem, 2 * n + kFitLut)) return rc;
           HIPCHK(c, hipMemcpyAsync(c->fit_mem + 2 * n, fit_lut(), sizeof(double) * kFitLut, hipMemcpyHostToDevice, c->stream));
         }
         *snap = c->fit_mem;
@@ -3347,7 +3281,7 @@ int cspm_segment_planes(cspm_ctx *c, const cspm_seg_params *p, int merge) {
         const SegGrid finest = seg_grid(c->W, c->H, kSegMinStep);
         const size_t Kmax = (size_t)finest.nx * finest.ny;
         if (!c->seg_mem)
-          if (int rc = dalloc(c, &c->seg_mem, 2 * n * (sizeof(double) + sizeof(int)) + SegMem::bytes(Kmax), nullptr)) return rc;
+          if (int rc = dalloc(c, c->mem_field, &c->seg_mem, 2 * n * (sizeof(double) + sizeof(int)) + SegMem::bytes(Kmax))) return rc;
         *snap = reinterpret_cast<double *>(c->seg_mem);
         return CSPM_OK;
       },
@@ -3829,9 +3763,7 @@ int cspm_fpm_begin(cspm_ctx *c, int w, int h, int max_dis) {
   ON_DEVICE(c);
   if (w != c->W || h != c->H) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    free_cost(c);
-    free_field(c);
-    free_images(c);
+    free_geometry(c);
     c->W = w; c->H = h;
   }
   if (c->cost_alloc && c->max_dis != max_dis) {  // its levels, strips and init range were sized for the old disparity range
@@ -3845,8 +3777,8 @@ int cspm_fpm_begin(cspm_ctx *c, int w, int h, int max_dis) {
   if (rc) return rc;
   const long long need = std::max(2LL * w * h, 4LL * std::min(w, h));  // a diagonal batch holds 4 per pixel (tiny images)
   if (c->fpm_cap < need) {
-    if ((rc = dalloc(c, &c->fpm.xy, (size_t)need * 2, nullptr)) || (rc = dalloc(c, &c->fpm.view, (size_t)need, nullptr)) ||
-        (rc = dalloc(c, &c->fpm.plane, (size_t)need * 6, nullptr)) || (rc = dalloc(c, &c->fpm.cost, (size_t)need, nullptr)))
+    if ((rc = dalloc(c, c->mem_field, &c->fpm.xy, (size_t)need * 2)) || (rc = dalloc(c, c->mem_field, &c->fpm.view, (size_t)need)) ||
+        (rc = dalloc(c, c->mem_field, &c->fpm.plane, (size_t)need * 6)) || (rc = dalloc(c, c->mem_field, &c->fpm.cost, (size_t)need)))
       return rc;
     c->fpm_cap = need;
   }

@@ -193,6 +193,11 @@ int cspm_build_cost_grd(cspm_ctx *ctx, int max_dis, int wnd_size, int scale_num,
 /* CSPM_OPT_PP_SPECKLE_REMOVED (read only; synchronises): pixels the speckle filter (cspm_set_pp_speckle) took out of the two consistency
  * masks, both views together, in the context's last post-processing; 0 when that ran without the filter. */
 #define CSPM_OPT_PP_SPECKLE_REMOVED 21
+/* CSPM_OPT_DEVICE_BYTES (read only; does not synchronise): the device memory the context holds, in bytes: the sum of the sizes it asked
+ * of the allocator for the images, the cost object, the plane field with everything kept beside it, the rectification and the
+ * local-stereo scratch.  Requested sizes (the allocator's rounding is not in it); the temporaries an entry stages caller memory
+ * through are freed before it returns and are not counted.  0 for a fresh context; a pair that reuses every buffer leaves it unchanged. */
+#define CSPM_OPT_DEVICE_BYTES 22
 int cspm_get_option(cspm_ctx *ctx, int key, long long *value);
 int cspm_set_option(cspm_ctx *ctx, int key, long long value);
 /* The same constructors with `new CenCC` (main.cc:43-45; cc/cen_cc.cc:4-137): 9x9 census codes of every level built on
