@@ -63,6 +63,8 @@ SYMBOLS = [
     "cspm_geom_default_params", "cspm_reproject_host", "cspm_reproject", "cspm_reproject_device",
     "cspm_mesh_default_params", "cspm_mesh_host", "cspm_mesh", "cspm_mesh_device",
     "cspm_synth_default_params", "cspm_synthesize_host", "cspm_synthesize", "cspm_synthesize_device",
+    "cspm_fuse_default_params", "cspm_fuse_depth_maps", "cspm_fuse_begin", "cspm_fuse_push", "cspm_fuse_push_maps", "cspm_fuse_view_count",
+    "cspm_fuse_run", "cspm_fuse_run_device", "cspm_fuse_end",
     "cspm_rect_default_params", "cspm_rectify_compute", "cspm_rectify_host", "cspm_set_rectification", "cspm_get_rect_map",
     "cspm_set_images_raw", "cspm_set_images_raw_device",
 ]
@@ -117,6 +119,17 @@ class SynthView(C.Structure):
     """struct cspm_synth_view: one source view of cspm_synthesize_host"""
     _fields_ = [("disp", C.POINTER(C.c_double)), ("valid", C.POINTER(C.c_uint8)), ("slope_a", C.POINTER(C.c_double)),
                 ("bgr", C.POINTER(C.c_uint8)), ("stride", C.c_size_t)]
+
+
+class FuseParams(C.Structure):
+    """struct cspm_fuse_params"""
+    _fields_ = [("max_reproj", C.c_double), ("max_rel_depth", C.c_double), ("min_cos", C.c_double), ("min_views", C.c_int), ("suppress", C.c_int)]
+
+
+class FuseView(C.Structure):
+    """struct cspm_fuse_view: one view of cspm_fuse_depth_maps (maps, pinhole camera, camera -> world pose)"""
+    _fields_ = [("depth", C.POINTER(C.c_double)), ("normal", C.POINTER(C.c_double)), ("bgr", C.POINTER(C.c_uint8)), ("bgr_stride", C.c_size_t),
+                ("f", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3)]
 
 
 class Camera(C.Structure):
@@ -183,6 +196,7 @@ def load_library():
     sp, svp = C.POINTER(SynthParams), C.POINTER(SynthView)
     mshp = C.POINTER(MeshParams)
     rgp, rpp, rcp = C.POINTER(Rig), C.POINTER(RectParams), C.POINTER(Rectification)
+    fup, fuv = C.POINTER(FuseParams), C.POINTER(FuseView)
     sig = {
         "cspm_device_count": (C.c_int, []),
         "cspm_create": (C.c_int, [C.POINTER(vp), C.c_int]),
@@ -276,6 +290,15 @@ def load_library():
         "cspm_synthesize_host": (C.c_int, [C.c_int, sp, C.c_double, svp, svp, C.c_int, C.c_int, u8p, C.c_size_t, dp, u8p]),
         "cspm_synthesize": (C.c_int, [vp, C.c_int, sp, C.c_double, u8p, C.c_size_t, dp, u8p]),
         "cspm_synthesize_device": (C.c_int, [vp, C.c_int, sp, C.c_double, vp, C.c_size_t, vp, vp]),
+        "cspm_fuse_default_params": (C.c_int, [fup]),
+        "cspm_fuse_depth_maps": (C.c_int, [C.c_int, fup, fuv, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, up, up, u8p]),
+        "cspm_fuse_begin": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
+        "cspm_fuse_push": (C.c_int, [vp, C.c_int, C.c_int, kp, gp, fp, dp, dp]),
+        "cspm_fuse_push_maps": (C.c_int, [vp, dp, dp, u8p, C.c_size_t, C.c_double, C.c_double, C.c_double, dp, dp]),
+        "cspm_fuse_view_count": (C.c_int, [vp]),
+        "cspm_fuse_run": (C.c_int, [vp, fup, vp, C.c_size_t, up, up, u8p]),
+        "cspm_fuse_run_device": (C.c_int, [vp, fup, vp, C.c_size_t, vp, vp, vp]),
+        "cspm_fuse_end": (C.c_int, [vp]),
         "cspm_rect_default_params": (C.c_int, [rpp]),
         "cspm_rectify_compute": (C.c_int, [rgp, rpp, rcp, kp]),
         "cspm_rectify_host": (C.c_int, [C.c_int, rgp, rcp, C.c_int, u8p, C.c_size_t, u8p, C.c_size_t, dp, u8p]),
@@ -795,6 +818,63 @@ class StereoContext:
         self._chk(self.L.cspm_mesh_device(self.p, int(view), int(source), C.byref(k), C.byref(g), _opt(C.byref, f), C.byref(m), _dev(d_vertices),
                                           int(vertex_cap), _dev(d_faces), int(face_cap), _dev(d_quad), _dev(d_n_vertices), _dev(d_n_faces)))
 
+    # ---- depth-map fusion ----
+    def fuse_begin(self, w, h, max_views):
+        """slots for max_views fusion views of w x h, kept until fuse_end whatever happens to the images (cspm_fuse_begin)"""
+        self._chk(self.L.cspm_fuse_begin(self.p, int(w), int(h), int(max_views)))
+        self._fuse = (int(w), int(h))
+
+    def fuse_push(self, view, calib, R, t, source=GEOM_RAW, fit=None, **params):
+        """appends one view of the stored plane field (cspm_fuse_push): view, calib, source, fit and params as for reproject; R (3, 3)
+        and t (3,) the camera -> world pose of the pair's view-0 rectified camera"""
+        k, g = calib_struct(calib), geom_params(**params)
+        f = fit_params(**dict(fit)) if fit is not None else None
+        R, t = _pose(R, t)
+        self._chk(self.L.cspm_fuse_push(self.p, int(view), int(source), C.byref(k), C.byref(g), _opt(C.byref, f), _dp(R), _dp(t)))
+
+    def fuse_push_maps(self, depth, f, cx, cy, R, t, normal=None, bgr=None):
+        """appends one view from host maps (cspm_fuse_push_maps): depth (h, w) f64, normal (3, h, w) f64 or None, bgr (h, w, 3) uint8 or None"""
+        w, h = self._fuse
+        d, n, img = _fuse_maps(depth, normal, bgr, w, h)
+        R, t = _pose(R, t)
+        self._chk(self.L.cspm_fuse_push_maps(self.p, _dp(d), _opt(_dp, n), _opt(_u8, img), 3 * w, float(f), float(cx), float(cy), _dp(R), _dp(t)))
+
+    def fuse_view_count(self):
+        return self.L.cspm_fuse_view_count(self.p)
+
+    def fuse_run(self, cloud=True, cloud_cap=None, state=True, out=None, **params):
+        """F over the views pushed so far (cspm_fuse_run): params max_reproj, max_rel_depth, min_cos, min_views, suppress.  Returns a
+        dict: count, view_counts (K,), with cloud the Point records in (view, raster) order (at most cloud_cap; None = all), with state
+        the S bytes (K, h, w).  out: a dict with a preallocated cloud_buffer to write into (tests poison it)."""
+        w, h = self._fuse
+        K = self.fuse_view_count()
+        p = fuse_params(**params)
+        cap = max(K, 0) * w * h if cloud_cap is None else int(cloud_cap)
+        pts = None
+        if cloud:
+            pts = (out or {}).get("cloud_buffer")
+            if pts is None:
+                pts = np.zeros(cap, Point)
+        S = np.zeros((max(K, 0), h, w), np.uint8) if state else None
+        vc = np.zeros(max(K, 1), np.uint32)
+        cnt = C.c_uint(0)
+        self._chk(self.L.cspm_fuse_run(self.p, C.byref(p), _opt(_vp, pts), cap if cloud else 0, C.byref(cnt), vc.ctypes.data_as(C.POINTER(C.c_uint)),
+                                       _opt(_u8, S)))
+        res = dict(count=cnt.value, view_counts=vc[:K])
+        if cloud:
+            res["cloud"] = pts[:min(cnt.value, cap)]
+        if state:
+            res["state"] = S
+        return res
+
+    def fuse_run_device(self, d_cloud=0, cloud_cap=0, d_count=0, d_view_counts=0, d_state=0, **params):
+        """the same with device pointers (integers; 0 = not requested); asynchronous on the context's stream (cspm_fuse_run_device)"""
+        p = fuse_params(**params)
+        self._chk(self.L.cspm_fuse_run_device(self.p, C.byref(p), _dev(d_cloud), int(cloud_cap), _dev(d_count), _dev(d_view_counts), _dev(d_state)))
+
+    def fuse_end(self):
+        self._chk(self.L.cspm_fuse_end(self.p))
+
     # ---- view synthesis (DESIGN.md section 20) ----
     def synthesize(self, t, source=GEOM_RAW, outputs=("bgr", "disp", "mask"), out=None, **params):
         """the scene from the camera at fraction t of the baseline (0 = view 0, 1 = view 1), rendered from the stored plane field and the
@@ -1064,6 +1144,64 @@ def rectify_host(rig, rect, view, raw=None, outputs=("bgr", "map", "valid"), raw
                                out_stride if out_stride is not None else w * 3, _opt(_dp, res.get("map")), _opt(_u8, res.get("valid"))))
     if "bgr_rows" in res:
         res["bgr"] = np.ascontiguousarray(res["bgr_rows"][:, :w * 3]).reshape(h, w, 3)
+    return res
+
+
+def fuse_params(**params):
+    """struct cspm_fuse_params: cspm_fuse_default_params with the given fields replaced"""
+    return _params(FuseParams, "fuse", "fusion", params)
+
+
+def _pose(R, t):
+    R = np.ascontiguousarray(R, dtype=np.float64).reshape(9)
+    t = np.ascontiguousarray(t, dtype=np.float64).reshape(3)
+    return R, t
+
+
+def _fuse_maps(depth, normal, bgr, w, h):
+    d = np.ascontiguousarray(depth, dtype=np.float64)
+    assert d.shape == (h, w), d.shape
+    n = None if normal is None else np.ascontiguousarray(normal, dtype=np.float64)
+    assert n is None or n.shape == (3, h, w), n.shape
+    img = None if bgr is None else np.ascontiguousarray(bgr, dtype=np.uint8)
+    assert img is None or img.shape == (h, w, 3), img.shape
+    return d, n, img
+
+
+def fuse_depth_maps(views, w, h, cloud=True, cloud_cap=None, state=True, device=0, out=None, **params):
+    """F alone on host maps (cspm_fuse_depth_maps).  views: a sequence of dicts with depth (h, w) f64, f, cx, cy,
+    R (3, 3), t (3,) camera -> world, and optionally normal (3, h, w) f64 and bgr (h, w, 3) uint8.  params: max_reproj, max_rel_depth,
+    min_cos, min_views, suppress.  Returns what StereoContext.fuse_run returns."""
+    K = len(views)
+    p = fuse_params(**params)
+    arr = (FuseView * max(K, 1))()
+    keep = []
+    for k, v in enumerate(views):
+        d, n, img = _fuse_maps(v["depth"], v.get("normal"), v.get("bgr"), w, h)
+        R, t = _pose(v["R"], v["t"])
+        keep.append((d, n, img))
+        arr[k] = FuseView(_dp(d), _opt(_dp, n), _opt(_u8, img), 3 * w, float(v["f"]), float(v["cx"]), float(v["cy"]), (C.c_double * 9)(*R), (C.c_double * 3)(*t))
+    cap = K * w * h if cloud_cap is None else int(cloud_cap)
+    pts = None
+    if cloud:
+        pts = (out or {}).get("cloud_buffer")
+        if pts is None:
+            pts = np.zeros(cap, Point)
+    S = (out or {}).get("state")
+    if S is None and state:
+        S = np.zeros((K, h, w), np.uint8)
+    vc = (out or {}).get("view_counts")
+    if vc is None:
+        vc = np.zeros(max(K, 1), np.uint32)
+    cnt = C.c_uint(0)
+    _check(load_library().cspm_fuse_depth_maps(device, C.byref(p), arr, K, w, h, _opt(_vp, pts), cap if cloud else 0, C.byref(cnt),
+                                               vc.ctypes.data_as(C.POINTER(C.c_uint)), _opt(_u8, S)))
+    del keep
+    res = dict(count=cnt.value, view_counts=vc[:K])
+    if cloud:
+        res["cloud"] = pts[:min(cnt.value, cap)]
+    if S is not None:
+        res["state"] = S
     return res
 
 

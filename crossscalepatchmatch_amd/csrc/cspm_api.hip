@@ -21,6 +21,7 @@
 #include "cspm_seg.h"
 #include "cspm_geom.h"
 #include "cspm_mesh.h"
+#include "cspm_fuse.h"
 #include "cspm_synth.h"
 #include "cspm_rect.h"
 #include "cspm_ca.h"
@@ -147,6 +148,7 @@ struct cspm_ctx {
   DevPool mem_field{dev_alloc, dev_free};   // the plane field and what is "kept with the field": until free_field
   DevPool mem_rect{dev_alloc, dev_free};    // the rectification: until free_rect
   DevPool mem_ca{dev_alloc, dev_free};      // local-stereo scratch: until ca_ensure meets a new key or the geometry changes
+  DevPool mem_fuse{dev_alloc, dev_free};    // the fusion views: from cspm_fuse_begin until cspm_fuse_end, whatever the geometry does
   // images
   int W = 0, H = 0;
   uint32_t *img0[2] = {nullptr, nullptr};
@@ -228,6 +230,16 @@ struct cspm_ctx {
   uint8_t *mesh_bytes = nullptr;      // cspm_mesh: keep and Q (2 byte maps); allocated by the first such call and kept with the field
   uint32_t *mesh_map = nullptr;       // cspm_mesh: the pixel -> vertex map, then the vertex and the face counts per workgroup, each with its total
   double *synth_disp = nullptr;       // cspm_synthesize: both views' CSPM_GEOM_RAW disparity maps (2 arrays); allocated by the first such call and kept with the field
+  // depth-map fusion (cspm_fuse_*): the slots of max_views views of fuse_w x fuse_h, kept in mem_fuse
+  bool fuse_on = false;
+  int fuse_w = 0, fuse_h = 0, fuse_max = 0, fuse_views = 0;
+  bool fuse_normals = false, fuse_images = false;  // the views pushed so far carry normals / at least one of them an image
+  double *fuse_depth = nullptr, *fuse_normal = nullptr;  // per view w*h depths; three planes of w*h normals
+  uint32_t *fuse_pix = nullptr;                          // per view w*h packed pixels, 0 in a view without an image
+  uint8_t *fuse_bytes = nullptr;                         // used of all views, then S of all views
+  FuseCam *fuse_cams = nullptr;                          // the camera table
+  std::vector<FuseCam> fuse_cams_host;                   // ... and the host's copy of it, max_views rows
+  unsigned int *fuse_counts = nullptr;                   // kept pixels per workgroup of every pass, the total, the kept pixels per view
   // rectification (cspm_set_rectification): kept until the context goes or the rectification is dropped
   bool rect_on = false;
   cspm_rig rect_rig{};
@@ -2287,6 +2299,164 @@ int fit_stored_field(cspm_ctx *c, int merge, int max_rows, const char *too_high,
   return CSPM_OK;
 }
 
+// ---- depth-map fusion (cspm_fuse.h) -----------------------------------------------------------------------
+static_assert(sizeof(FuseCam) == 15 * sizeof(double), "the camera table is 15 doubles per view");
+static_assert(CSPM_FUSE_MAX_VIEWS == kFuseMaxViews, "cspm.h and cspm_fuse.h agree on the number of views");
+const cspm_fuse_params kFuseDefaults = {2.0, 0.01, 0.0, 2, 1};
+const char *fuse_params_error(const cspm_fuse_params *p) {
+  if (!(p->max_reproj >= 0.0)) return "fusion: max_reproj must be >= 0";
+  if (!(p->max_rel_depth >= 0.0)) return "fusion: max_rel_depth must be >= 0";
+  if (!(p->min_cos >= 0.0 && p->min_cos <= 1.0)) return "fusion: min_cos must be in [0, 1]";
+  if (p->min_views < 0 || p->min_views > kFuseMaxViews - 1) return "fusion: min_views must be in 0 .. 63";
+  return nullptr;
+}
+const char *fuse_camera_error(double f, double cx, double cy, const double *R, const double *t) {
+  if (!R || !t) return "fusion: no pose";
+  bool finite = std::isfinite(f) && std::isfinite(cx) && std::isfinite(cy);
+  for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(R[i]);
+  for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(t[i]);
+  if (!finite) return "fusion: the camera and its pose must be finite";
+  if (!(f > 0.0)) return "fusion: f must be positive";
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double d = R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1] + R[3 * i + 2] * R[3 * j + 2] - (i == j ? 1.0 : 0.0);
+      if (!(std::fabs(d) <= 1e-6)) return "fusion: R is not a rotation (max |R R^T - I| > 1e-6)";
+    }
+  return nullptr;
+}
+const char *fuse_size_error(int w, int h) {
+  if (w < 1 || h < 1) return "fusion: w and h must be at least 1";
+  if ((long long)w * h >= (1LL << 31)) return "w * h must be below 2^31: cloud records hold 32-bit pixel indices";
+  return nullptr;
+}
+const char *fuse_maps_error(const double *depth, const uint8_t *bgr, size_t bgr_stride, int w) {
+  if (!depth) return "fusion: no depth map";
+  if (bgr && bgr_stride < (size_t)w * 3) return "fusion: bgr_stride is below 3 * w";
+  return nullptr;
+}
+inline size_t fuse_count_words(int max_views, unsigned nb) { return (size_t)max_views * nb + 1 + (size_t)max_views; }
+
+int fuse_begin(cspm_ctx *c, int w, int h, int max_views) {
+  if (const char *msg = fuse_size_error(w, h)) return fail(c, CSPM_ERR_ARG, msg);
+  if (max_views < 1 || max_views > kFuseMaxViews) return fail(c, CSPM_ERR_ARG, "fusion: max_views must be in 1 .. 64");
+  if (c->fuse_on) return fail(c, CSPM_ERR_STATE, "fusion: cspm_fuse_begin twice without cspm_fuse_end");
+  const size_t n = (size_t)w * h, K = (size_t)max_views;
+  int rc;
+  if ((rc = dalloc(c, c->mem_fuse, &c->fuse_depth, K * n)) || (rc = dalloc(c, c->mem_fuse, &c->fuse_normal, K * 3 * n)) ||
+      (rc = dalloc(c, c->mem_fuse, &c->fuse_pix, K * n)) || (rc = dalloc(c, c->mem_fuse, &c->fuse_bytes, 2 * K * n)) ||
+      (rc = dalloc(c, c->mem_fuse, &c->fuse_cams, K)) ||
+      (rc = dalloc(c, c->mem_fuse, &c->fuse_counts, fuse_count_words(max_views, geom_blocks((long long)n))))) {
+    c->mem_fuse.release();
+    return rc;
+  }
+  c->fuse_cams_host.assign(K, FuseCam{});
+  c->fuse_on = true;
+  c->fuse_w = w; c->fuse_h = h; c->fuse_max = max_views; c->fuse_views = 0;
+  c->fuse_normals = c->fuse_images = false;
+  return CSPM_OK;
+}
+void fuse_release(cspm_ctx *c) {
+  c->mem_fuse.release();
+  c->fuse_on = false;
+  c->fuse_views = c->fuse_max = c->fuse_w = c->fuse_h = 0;
+}
+// what every push checks before it touches the slot: a begin, a free slot, a valid camera, normals in all views or in none
+int fuse_slot_check(cspm_ctx *c, bool normals, double f, double cx, double cy, const double *R, const double *t) {
+  if (!c->fuse_on) return fail(c, CSPM_ERR_STATE, "fusion: cspm_fuse_begin first");
+  if (c->fuse_views >= c->fuse_max) return fail(c, CSPM_ERR_STATE, "fusion: every view slot is taken (max_views of cspm_fuse_begin)");
+  if (const char *msg = fuse_camera_error(f, cx, cy, R, t)) return fail(c, CSPM_ERR_ARG, msg);
+  if (c->fuse_views > 0 && normals != c->fuse_normals) return fail(c, CSPM_ERR_ARG, "fusion: normals in some views but not all");
+  return CSPM_OK;
+}
+// the slot is filled: its row of the camera table goes up and the view counts
+int fuse_slot_commit(cspm_ctx *c, bool normals, bool image, double f, double cx, double cy, const double *R, const double *t) {
+  FuseCam &cam = c->fuse_cams_host[(size_t)c->fuse_views];  // lives as long as the slots: the copy may read it later
+  cam.f = f; cam.cx = cx; cam.cy = cy;
+  for (int i = 0; i < 9; ++i) cam.R[i] = R[i];
+  for (int i = 0; i < 3; ++i) cam.t[i] = t[i];
+  HIPCHK(c, hipMemcpyAsync(c->fuse_cams + c->fuse_views, &cam, sizeof cam, hipMemcpyHostToDevice, c->stream));
+  c->fuse_normals = normals;
+  c->fuse_images = c->fuse_images || image;
+  c->fuse_views += 1;
+  return CSPM_OK;
+}
+// a view from caller memory (the caller runs on the context's device)
+int fuse_push_maps(cspm_ctx *c, const double *depth, const double *normal, const uint8_t *bgr, size_t bgr_stride, double f, double cx, double cy,
+                   const double *R, const double *t) {
+  if (int rc = fuse_slot_check(c, normal != nullptr, f, cx, cy, R, t)) return rc;
+  if (const char *msg = fuse_maps_error(depth, bgr, bgr_stride, c->fuse_w)) return fail(c, CSPM_ERR_ARG, msg);
+  const int w = c->fuse_w, h = c->fuse_h;
+  const size_t n = (size_t)w * h, k = (size_t)c->fuse_views;
+  Staging S(c);
+  S.put(c->fuse_depth + k * n, depth, n);
+  if (normal) S.put(c->fuse_normal + k * 3 * n, normal, 3 * n);
+  if (bgr) {
+    const uint8_t *dbgr = S.up2d(bgr, bgr_stride, (size_t)w * 3, (size_t)h);
+    if (!S.rc) hipLaunchKernelGGL(k_pack_bgr, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, dbgr, (size_t)w * 3, w, h, w, 0, c->fuse_pix + k * n);
+  } else {
+    S.fill(c->fuse_pix + k * n, 0, sizeof(uint32_t) * n);
+  }
+  if (S.finish("fusion: the upload of a view failed")) return S.rc;
+  return fuse_slot_commit(c, normal != nullptr, bgr != nullptr, f, cx, cy, R, t);
+}
+// F over the views pushed so far; every output a device pointer or null
+int fuse_enqueue(cspm_ctx *c, const cspm_fuse_params *p, uint4 *cloud, size_t cap, unsigned int *d_count, unsigned int *d_view_counts, uint8_t *d_state) {
+  const int K = c->fuse_views, w = c->fuse_w, h = c->fuse_h;
+  const long long n = (long long)w * h;
+  const unsigned nb = geom_blocks(n);
+  const FuseMaps maps{c->fuse_depth, c->fuse_normals ? c->fuse_normal : nullptr, c->fuse_images ? c->fuse_pix : nullptr, c->fuse_bytes,
+                      c->fuse_bytes + (size_t)c->fuse_max * n};
+  const FusePar par{p->max_reproj * p->max_reproj, p->max_rel_depth, p->min_cos, p->min_views, p->suppress ? 1 : 0};
+  unsigned int *counts = c->fuse_counts, *total = d_count ? d_count : counts + (size_t)K * nb;  // behind the counts of the K passes
+  {
+    Timed t(c, CSPM_K_MISC, (long long)K * n);
+    HIPCHK(c, hipMemsetAsync(maps.used, 0, (size_t)K * n, c->stream));
+    for (int r = 0; r < K; ++r) {
+      if (maps.normal) hipLaunchKernelGGL(k_fuse_view<true>, dim3(nb), dim3(kGeomBlock), 0, c->stream, (const FuseCam *)c->fuse_cams, maps, par, K, r, w, h, n, counts + (size_t)r * nb);
+      else hipLaunchKernelGGL(k_fuse_view<false>, dim3(nb), dim3(kGeomBlock), 0, c->stream, (const FuseCam *)c->fuse_cams, maps, par, K, r, w, h, n, counts + (size_t)r * nb);
+    }
+    hipLaunchKernelGGL(k_geom_scan, dim3(1), dim3(kGeomScanBlock), 0, c->stream, counts, (int)(K * nb), total);
+    if (d_view_counts)
+      hipLaunchKernelGGL(k_fuse_counts, dim3(1), dim3(kFuseMaxViews), 0, c->stream, (const unsigned int *)counts, (const unsigned int *)total, K, nb, d_view_counts);
+    const unsigned int cap32 = (unsigned int)std::min<size_t>(cap, 0xFFFFFFFFull);  // ranks are 32-bit, like the count
+    if (cloud && cap32 != 0) {
+      if (maps.normal) hipLaunchKernelGGL(k_fuse_cloud<true>, dim3(nb, K), dim3(kGeomBlock), 0, c->stream, (const FuseCam *)c->fuse_cams, maps, par, K, w, h, n, (const unsigned int *)counts, cloud, cap32);
+      else hipLaunchKernelGGL(k_fuse_cloud<false>, dim3(nb, K), dim3(kGeomBlock), 0, c->stream, (const FuseCam *)c->fuse_cams, maps, par, K, w, h, n, (const unsigned int *)counts, cloud, cap32);
+    }
+    if (d_state) HIPCHK(c, hipMemcpyAsync(d_state, maps.state, (size_t)K * n, hipMemcpyDeviceToDevice, c->stream));
+  }
+  HIPCHK(c, hipGetLastError());
+  return CSPM_OK;
+}
+int fuse_run_check(cspm_ctx *c, const cspm_fuse_params **p) {
+  if (!*p) *p = &kFuseDefaults;
+  if (const char *msg = fuse_params_error(*p)) return fail(c, CSPM_ERR_ARG, msg);
+  if (!c->fuse_on) return fail(c, CSPM_ERR_STATE, "fusion: cspm_fuse_begin first");
+  if (c->fuse_views < 1) return fail(c, CSPM_ERR_STATE, "fusion: no view has been pushed");
+  return CSPM_OK;
+}
+// cspm_fuse_run behind its checks, on the context's device: host outputs
+int fuse_run(cspm_ctx *c, const cspm_fuse_params *p, cspm_point *cloud_out, size_t cloud_cap, unsigned int *count_out, unsigned int *view_counts_out,
+             uint8_t *state_out) {
+  const size_t K = (size_t)c->fuse_views, n = (size_t)c->fuse_w * c->fuse_h;
+  const unsigned nb = geom_blocks((long long)n);
+  const size_t cap = std::min(cloud_out ? cloud_cap : (size_t)0, K * n);
+  unsigned int total = 0;  // in front of the Staging: a download writes it
+  unsigned int *vcounts = c->fuse_counts + (size_t)c->fuse_max * nb + 1;
+  Staging S(c);
+  uint4 *dcloud = S.buf<uint4>(2 * cap, cap != 0);
+  if (S.rc) return S.finish();
+  if (int rc = fuse_enqueue(c, p, dcloud, cap, nullptr, view_counts_out ? vcounts : nullptr, nullptr)) return rc;
+  S.down(&total, c->fuse_counts + K * nb, 1);
+  if (S.finish("fusion kernels failed")) return S.rc;
+  S.down(cloud_out, dcloud, std::min((size_t)total, cap));  // the count first, then the records that were written
+  S.down(view_counts_out, vcounts, K);
+  S.down(state_out, c->fuse_bytes + (size_t)c->fuse_max * n, K * n);
+  if (S.finish("fusion download failed")) return S.rc;
+  if (count_out) *count_out = total;
+  return CSPM_OK;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -2345,6 +2515,7 @@ void cspm_destroy(cspm_ctx *c) {
   for (auto e : c->pool) (void)hipEventDestroy(e);
   free_geometry(c);
   free_rect(c);
+  fuse_release(c);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
 }
@@ -2494,7 +2665,7 @@ int cspm_get_option(cspm_ctx *c, int key, long long *value) {
     case CSPM_OPT_SWEEP_TIMEOUT_MS: *value = c->sweep_timeout_ms; return CSPM_OK;
     case CSPM_OPT_SWEEP_FALLBACKS: *value = c->sweep_fallbacks; return CSPM_OK;
     case CSPM_OPT_DEVICE_BYTES:
-      *value = (long long)(c->mem_images.bytes() + c->mem_cost.bytes() + c->mem_field.bytes() + c->mem_rect.bytes() + c->mem_ca.bytes());
+      *value = (long long)(c->mem_images.bytes() + c->mem_cost.bytes() + c->mem_field.bytes() + c->mem_rect.bytes() + c->mem_ca.bytes() + c->mem_fuse.bytes());
       return CSPM_OK;
     case CSPM_OPT_SWEEP_PAIRS: *value = c->opt_sweep_pairs; return CSPM_OK;
     case CSPM_OPT_TABLE_VOLUMES: *value = c->opt_table_volumes; return CSPM_OK;
@@ -3484,6 +3655,113 @@ int cspm_mesh_device(cspm_ctx *c, int view, int source, const cspm_calib *calib,
   ON_DEVICE(c);
   return mesh_enqueue(c, view, source, calib, g, fit, m, (uint4 *)d_vertices_out, d_vertices_out ? vertex_cap : 0, (uint32_t *)d_faces_out,
                       d_faces_out ? face_cap : 0, (uint8_t *)d_quad_out, (unsigned int *)d_n_vertices_out, (unsigned int *)d_n_faces_out);
+}
+
+// F: the fusion views of a context, and the one-shot form on caller maps
+int cspm_fuse_default_params(cspm_fuse_params *p) {
+  if (!p) return CSPM_ERR_ARG;
+  *p = kFuseDefaults;
+  return CSPM_OK;
+}
+
+int cspm_fuse_begin(cspm_ctx *c, int w, int h, int max_views) {
+  if (!c) return CSPM_ERR_ARG;
+  ON_DEVICE(c);
+  return fuse_begin(c, w, h, max_views);
+}
+
+int cspm_fuse_end(cspm_ctx *c) {
+  if (!c) return CSPM_ERR_ARG;
+  if (!c->fuse_on) return fail(c, CSPM_ERR_STATE, "fusion: cspm_fuse_begin first");
+  ON_DEVICE(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  fuse_release(c);
+  return CSPM_OK;
+}
+
+int cspm_fuse_view_count(const cspm_ctx *c) { return c && c->fuse_on ? c->fuse_views : -1; }
+
+int cspm_fuse_push_maps(cspm_ctx *c, const double *depth, const double *normal, const uint8_t *bgr, size_t bgr_stride, double f, double cx, double cy,
+                        const double *R, const double *t) {
+  if (!c) return CSPM_ERR_ARG;
+  ON_DEVICE(c);
+  return fuse_push_maps(c, depth, normal, bgr, bgr_stride, f, cx, cy, R, t);
+}
+
+// one view of the stored field: the preparation of cspm_reproject_device, G's dense pass straight into the slot, then k_fuse_store
+int cspm_fuse_push(cspm_ctx *c, int view, int source, const cspm_calib *calib, const cspm_geom_params *g, const cspm_fit_params *fit, const double *R,
+                   const double *t) {
+  if (!c) return CSPM_ERR_ARG;
+  int rc = reproject_check(c, view, source, calib, &g, fit);
+  if (rc) return rc;
+  cspm_geom_params own = *g;
+  own.left_frame = 0;  // a view is stored in its own camera frame
+  const double cx = calib->cx + (double)view * calib->doffs;
+  double tv[3] = {0.0, 0.0, 0.0};
+  if (R && t)
+    for (int i = 0; i < 3; ++i) tv[i] = view == 1 ? t[i] + R[3 * i] * calib->baseline : t[i];
+  if ((rc = fuse_slot_check(c, true, calib->f, cx, calib->cy, R, R && t ? tv : nullptr))) return rc;
+  if (c->W != c->fuse_w || c->H != c->fuse_h) return fail(c, CSPM_ERR_STATE, "fusion: the context's images are not of the size given to cspm_fuse_begin");
+  ON_DEVICE(c);
+  if ((rc = check_sweep(c))) return rc;  // BEFORE the field is read, as in reproject_enqueue
+  if ((rc = geom_inputs_alloc(c, source, fit))) return rc;
+  const size_t n = (size_t)c->W * c->H, k = (size_t)c->fuse_views;
+  double *depth = c->fuse_depth + k * n;
+  uint8_t *keep = c->fuse_bytes + ((size_t)c->fuse_max + k) * n;  // the slot's S bytes: every run rewrites them
+  {
+    Timed tm(c, CSPM_K_MISC, (long long)n);
+    const GeomIn in = geom_inputs_launch(c, view, source, &own, fit);
+    geom_launch(c->stream, geom_cam(calib, &own, view), in, GeomOut{depth, nullptr, c->fuse_normal + k * 3 * n, keep}, c->W, c->H, nullptr, 0, false, nullptr,
+                nullptr);
+    hipLaunchKernelGGL(k_fuse_store, dim3(ew_grid((long long)n)), dim3(256), 0, c->stream, depth, (const uint8_t *)keep, (const uint32_t *)c->img0[view],
+                       c->fuse_pix + k * n, (long long)n);
+  }
+  HIPCHK(c, hipGetLastError());
+  return fuse_slot_commit(c, true, true, calib->f, cx, calib->cy, R, tv);
+}
+
+int cspm_fuse_run(cspm_ctx *c, const cspm_fuse_params *p, cspm_point *cloud_out, size_t cloud_cap, unsigned int *count_out, unsigned int *view_counts_out,
+                  uint8_t *state_out) {
+  if (!c) return CSPM_ERR_ARG;
+  if (int rc = fuse_run_check(c, &p)) return rc;
+  ON_DEVICE(c);
+  return fuse_run(c, p, cloud_out, cloud_cap, count_out, view_counts_out, state_out);
+}
+
+int cspm_fuse_run_device(cspm_ctx *c, const cspm_fuse_params *p, void *d_cloud_out, size_t cloud_cap, void *d_count_out, void *d_view_counts_out,
+                         void *d_state_out) {
+  if (!c) return CSPM_ERR_ARG;
+  if (int rc = fuse_run_check(c, &p)) return rc;
+  if (d_cloud_out && ((uintptr_t)d_cloud_out & 15u)) return fail(c, CSPM_ERR_ARG, "fusion: the cloud buffer must be 16-byte aligned");
+  if (((uintptr_t)d_count_out & 3u) || ((uintptr_t)d_view_counts_out & 3u)) return fail(c, CSPM_ERR_ARG, "fusion: the counts must be 4-byte aligned");
+  ON_DEVICE(c);
+  return fuse_enqueue(c, p, (uint4 *)d_cloud_out, d_cloud_out ? cloud_cap : 0, (unsigned int *)d_count_out, (unsigned int *)d_view_counts_out,
+                      (uint8_t *)d_state_out);
+}
+
+int cspm_fuse_depth_maps(int device, const cspm_fuse_params *p, const cspm_fuse_view *views, int n_views, int w, int h, cspm_point *cloud_out, size_t cloud_cap,
+                         unsigned int *count_out, unsigned int *view_counts_out, uint8_t *state_out) {
+  if (!p) p = &kFuseDefaults;
+  if (const char *msg = fuse_params_error(p)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (n_views < 1 || n_views > kFuseMaxViews) return fail(nullptr, CSPM_ERR_ARG, "fusion: the number of views must be in 1 .. 64");
+  if (!views) return fail(nullptr, CSPM_ERR_ARG, "fusion: no views");
+  if (const char *msg = fuse_size_error(w, h)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  for (int k = 0; k < n_views; ++k) {
+    const cspm_fuse_view &v = views[k];
+    if (const char *msg = fuse_camera_error(v.f, v.cx, v.cy, v.R, v.t)) return fail(nullptr, CSPM_ERR_ARG, msg);
+    if (const char *msg = fuse_maps_error(v.depth, v.bgr, v.bgr_stride, w)) return fail(nullptr, CSPM_ERR_ARG, msg);
+    if ((v.normal != nullptr) != (views[0].normal != nullptr)) return fail(nullptr, CSPM_ERR_ARG, "fusion: normals in some views but not all");
+  }
+  OneShot S(device);
+  if (S.rc) return S.finish();
+  int rc = fuse_begin(S.c, w, h, n_views);
+  for (int k = 0; k < n_views && !rc; ++k) {
+    const cspm_fuse_view &v = views[k];
+    rc = fuse_push_maps(S.c, v.depth, v.normal, v.bgr, v.bgr_stride, v.f, v.cx, v.cy, v.R, v.t);
+  }
+  if (!rc) rc = fuse_run(S.c, p, cloud_out, cloud_cap, count_out, view_counts_out, state_out);
+  S.latch(rc);
+  return S.finish("fusion failed");
 }
 
 // N alone on caller maps: the launch cspm_synthesize enqueues.  Arguments first, then the device.

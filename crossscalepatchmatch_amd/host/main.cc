@@ -11,7 +11,9 @@
 // (triangle meshes of the final plane field; include/cspm.h "triangle meshes") --synth_t --synth_png --synth_dis_pfm --synth_views --synth_max_stretch
 // --synth_merge_diff --synth_fill (the scene rendered from a camera between the two views; include/cspm.h "view synthesis")
 // --rig --rect_f --rect_w --rect_h --l_rect_file --r_rect_file (the inputs are RAW photographs of a calibrated rig, undistorted and
-// row-aligned on the device before matching; include/cspm.h "rectification").
+// row-aligned on the device before matching; include/cspm.h "rectification") --fuse_poses --fuse_ply --fuse_right --fuse_source
+// --fuse_max_reproj --fuse_max_rel_depth --fuse_min_cos --fuse_min_views --fuse_no_suppress (with --batch_list and --calib or --rig: the
+// depth maps of all pairs of the list fused into one point cloud in world coordinates; include/cspm.h "depth-map fusion").
 #include "../../include/cspm.h"
 #include "commfunc.h"
 #include "cs_patchmatch.h"
@@ -21,6 +23,7 @@
 #include "plane_cost/pre_cs_pc.h"
 #include "plane_cost/pre_ss_pc.h"
 #include "calib_io.h"
+#include "depth_fusion.h"
 #include "pfm_io.h"
 #include "ply_io.h"
 #include "rig_io.h"
@@ -139,6 +142,17 @@ DEFINE_int32(synth_views, 3, "with --synth_t: the source views used, 1 = left, 2
 DEFINE_double(synth_max_stretch, 4.0, "with --synth_t: a source pixel is dropped when its plane stretches it over more target pixels than this (>= 1)");
 DEFINE_double(synth_merge_diff, 1.0, "with --synth_t: the two views are blended where their disparities differ by at most this (>= 0)");
 DEFINE_bool(synth_fill, true, "with --synth_t: holes take the nearest pixel of their row on the background side");
+DEFINE_string(fuse_poses, "", "with --batch_list and --calib (or --rig): fuse the depth maps of all pairs of the list into one point cloud "
+                                "(include/cspm.h \"depth-map fusion\").  A poses file: line i holds the 12 numbers of the row-major camera -> world "
+                                "[R | t] of pair i's RECTIFIED left camera (also with --rig); '#' starts a comment.  Needs --fuse_ply");
+DEFINE_string(fuse_ply, "", "with --fuse_poses: the fused cloud in world coordinates, in the format of --l_ply");
+DEFINE_bool(fuse_right, false, "with --fuse_poses: the right view of every pair is fused too");
+DEFINE_string(fuse_source, "raw", "with --fuse_poses: raw = the plane field's own disparities, pp = the sub-pixel post-processed maps, consistent pixels only");
+DEFINE_double(fuse_max_reproj, 2.0, "with --fuse_poses: the forward-backward reprojection error a confirming view may have, in pixels");
+DEFINE_double(fuse_max_rel_depth, 0.01, "with --fuse_poses: the relative depth difference a confirming view may have");
+DEFINE_double(fuse_min_cos, 0.0, "with --fuse_poses: the least cosine between the normals of a pixel and of a confirming view (0 = no test)");
+DEFINE_int32(fuse_min_views, 2, "with --fuse_poses: a pixel is kept when at least this many other views confirm it");
+DEFINE_bool(fuse_no_suppress, false, "with --fuse_poses: emit a surface from every view that sees it, not only from the first");
 DEFINE_string(batch_list, "", "text file, one stereo pair per line: l_img r_img l_dis r_dis [l_pfm r_pfm [synth_png [synth_pfm]]] (the last two with "
                               "--synth_t, and then `-` skips an optional column); all pairs run with the "
                               "matching flags of this command line on one device context (buffers are reused between pairs). A pair "
@@ -160,6 +174,12 @@ bool g_rectify = false;
 cspm_rig g_rig;
 cspm_rectification g_rect;
 cspm_calib g_rect_calib;
+// --calib with --batch_list (the fusion): every pair of the list has this calibration
+bool g_batch_calib = false;
+CalibFile g_calib_file;
+// --fuse_poses: one pose per pair, and the views the workers collect (slot = pair index, or 2 * pair index + view with --fuse_right)
+std::vector<CameraPose> g_poses;
+std::unique_ptr<DepthFusion> g_fusion;
 
 struct PairFiles {
   string l_img, r_img, l_dis, r_dis, l_pfm, r_pfm, synth_png, synth_pfm;
@@ -172,6 +192,7 @@ struct PairFiles {
 struct PairRun {
   PairFiles files;
   int line_no;
+  size_t index;  // of the pair in the batch list
   Mat left, right;
   std::unique_ptr<IPlaneCost> cost;
   std::unique_ptr<CSPatchMatch> matcher;
@@ -186,7 +207,7 @@ struct PairRun {
   double t0;
   int rc;
   std::ostringstream log;
-  PairRun(const PairFiles &f, int line) : files(f), line_no(line), t0(0.0), rc(EXIT_SUCCESS) {}
+  PairRun(const PairFiles &f, int line, size_t idx = 0) : files(f), line_no(line), index(idx), t0(0.0), rc(EXIT_SUCCESS) {}
 };
 
 void load(PairRun &p) {
@@ -337,6 +358,26 @@ void finish(PairRun &p) {
           p.log << "Reprojection, view " << v << ": " << count << " points, " << (static_cast<double>(getTickCount()) - g0) / getTickFrequency() * 1e3
                 << " ms\n";
       }
+      if (g_fusion) {  // reads the cost object's context: before it goes
+        cspm_geom_params g;
+        cspm_geom_default_params(&g);
+        g.min_cos = FLAGS_geom_min_cos;
+        if (FLAGS_geom_z_far > 0.0) g.z_far = FLAGS_geom_z_far;
+        const bool pp = FLAGS_fuse_source == "pp";
+        g.consistent_only = pp ? 1 : 0;
+        cspm_fit_params fit;
+        cspm_fit_default_params(&fit);
+        fit.radius = FLAGS_geom_fit_radius;
+        const int views = FLAGS_fuse_right ? 2 : 1;
+        for (int v = 0; v < views; ++v) {
+          std::vector<double> depth, normal;
+          std::vector<uint8_t> keep;
+          p.matcher->Reproject(v == 0 ? kLeft : kRight, p.calib, g, pp ? CSPM_GEOM_PP : CSPM_GEOM_RAW, FLAGS_geom_fit_radius != 0 ? &fit : NULL, &depth, NULL,
+                               &normal, &keep, NULL);
+          const Mat &img = v == 0 ? p.left : p.right;
+          g_fusion->SetPairView(p.index * views + v, v, p.calib, g_poses[p.index], img.cols, img.rows, depth, keep, normal, img.ptr<unsigned char>(0), img.step);
+        }
+      }
       if (FLAGS_synth_t >= 0.0 && (!p.files.synth_png.empty() || !p.files.synth_pfm.empty())) {  // reads the cost object's context: before it goes
         cspm_synth_params sp;
         cspm_synth_default_params(&sp);
@@ -449,9 +490,10 @@ int run_batch(const std::vector<BatchJob> &jobs, int skipped, int bad_lines) {
       for (;;) {
         const size_t k = next.fetch_add(1);
         if (k >= jobs.size()) return std::unique_ptr<PairRun>();
-        std::unique_ptr<PairRun> p(new PairRun(jobs[k].files, jobs[k].line_no));
+        std::unique_ptr<PairRun> p(new PairRun(jobs[k].files, jobs[k].line_no, k));
         if (!FLAGS_quiet) p->log << "Load Image: " << p->files.l_img << " " << p->files.r_img << "\n";
         load(*p);
+        if (g_batch_calib && p->rc == EXIT_SUCCESS) p->calib = ScaledCalib(g_calib_file, p->left.cols);
         if (p->rc == EXIT_SUCCESS) return p;
         report(*p);
       }
@@ -490,6 +532,26 @@ int run_batch(const std::vector<BatchJob> &jobs, int skipped, int bad_lines) {
          << " in flight), " << (done.load() ? seconds * 1e3 / done.load() : 0.0) << " ms per pair end to end, files included\n";
     cout << "Batch fallbacks: " << sweep_fallbacks.load() << " raster sweeps repeated after a hand-over timeout, " << volume_fallbacks.load()
          << " optional volumes given up\n";
+  }
+  if (g_fusion && failed.load() == 0) {  // all pairs are done: the views are fused in list order, whatever worker or GPU produced them
+    try {
+      const cspm_fuse_params fp = {FLAGS_fuse_max_reproj, FLAGS_fuse_max_rel_depth, FLAGS_fuse_min_cos, FLAGS_fuse_min_views, FLAGS_fuse_no_suppress ? 0 : 1};
+      std::vector<cspm_point> cloud;
+      const double f0 = static_cast<double>(getTickCount());
+      const size_t count = g_fusion->Fuse(devices[0], fp, &cloud, NULL);
+      if (!FLAGS_quiet)
+        cout << "Fusion: " << g_fusion->size() << " views, " << count << " points, " << (static_cast<double>(getTickCount()) - f0) / getTickFrequency() * 1e3
+             << " ms\n";
+      if (!WritePLY(FLAGS_fuse_ply, cloud.data(), cloud.size())) {
+        cout << "Error: can not write " << FLAGS_fuse_ply << "\n";
+        return EXIT_FAILURE;
+      }
+    } catch (const std::exception &e) {
+      cout << "Error: " << e.what() << "\n";
+      return EXIT_FAILURE;
+    }
+  } else if (g_fusion) {
+    cout << "Error: no fusion: not every pair of the list succeeded\n";
   }
   return failed.load() ? EXIT_FAILURE : EXIT_SUCCESS;
 }
@@ -621,9 +683,40 @@ int run() {
     cout << "Error: --l_ply / --r_ply / --l_depth_pfm / --r_depth_pfm / --l_mesh_ply / --r_mesh_ply need --calib or --rig\n";
     return EXIT_FAILURE;
   }
-  if ((geom_out || !FLAGS_calib.empty()) && !FLAGS_batch_list.empty()) {
+  const bool fusion = !FLAGS_fuse_poses.empty() || !FLAGS_fuse_ply.empty();
+  if ((geom_out || (!FLAGS_calib.empty() && !fusion)) && !FLAGS_batch_list.empty()) {
     cout << "Error: --calib and the point-cloud, depth and mesh outputs belong to one pair: not with --batch_list\n";
     return EXIT_FAILURE;
+  }
+  if (fusion) {  // checked before anything opens a device
+    if (FLAGS_fuse_poses.empty() || FLAGS_fuse_ply.empty() || FLAGS_batch_list.empty() || (FLAGS_calib.empty() && FLAGS_rig.empty())) {
+      cout << "Error: the fusion needs --fuse_poses, --fuse_ply, --batch_list and --calib or --rig\n";
+      return EXIT_FAILURE;
+    }
+    if (FLAGS_fuse_source != "raw" && FLAGS_fuse_source != "pp") {
+      cout << "Error: --fuse_source must be raw or pp\n";
+      return EXIT_FAILURE;
+    }
+    if (!(FLAGS_fuse_max_reproj >= 0.0) || !(FLAGS_fuse_max_rel_depth >= 0.0) || !(FLAGS_fuse_min_cos >= 0.0 && FLAGS_fuse_min_cos <= 1.0) ||
+        FLAGS_fuse_min_views < 0 || FLAGS_fuse_min_views > 63) {
+      cout << "Error: --fuse_max_reproj and --fuse_max_rel_depth must be >= 0, --fuse_min_cos 0 .. 1 and --fuse_min_views 0 .. 63\n";
+      return EXIT_FAILURE;
+    }
+    if (FLAGS_pc_name != "PRE" && FLAGS_pc_name != "IMG") {
+      cout << "Error: the fusion needs one of this library's plane costs (--pc_name=PRE or IMG), not " << FLAGS_pc_name << "\n";
+      return EXIT_FAILURE;
+    }
+    if (FLAGS_batch_skip_existing) {
+      cout << "Error: the fusion needs every pair of the list: not with --batch_skip_existing\n";
+      return EXIT_FAILURE;
+    }
+    int bad_line = 0;
+    if (!ReadPoseFile(FLAGS_fuse_poses, &g_poses, &bad_line)) {
+      cout << "Error: can not read " << FLAGS_fuse_poses << " as a poses file (12 numbers per line, the row-major [R | t])";
+      if (bad_line) cout << ": line " << bad_line;
+      cout << "\n";
+      return EXIT_FAILURE;
+    }
   }
   if (!(FLAGS_geom_min_cos >= 0.0 && FLAGS_geom_min_cos <= 1.0) || !(FLAGS_geom_z_far >= 0.0) || FLAGS_geom_fit_radius < 0 || FLAGS_geom_fit_radius > 17) {
     cout << "Error: --geom_min_cos must be 0 .. 1, --geom_z_far >= 0 (0 = no limit) and --geom_fit_radius 0 .. 17\n";
@@ -656,7 +749,7 @@ int run() {
       return EXIT_FAILURE;
     }
   }
-  CalibFile calib_file;
+  CalibFile &calib_file = g_calib_file;
   if (!FLAGS_calib.empty() && !ReadCalibFile(FLAGS_calib, &calib_file)) {
     cout << "Error: can not read " << FLAGS_calib << " as a Middlebury calib.txt (cam0, cam1, doffs, baseline, width, height)\n";
     return EXIT_FAILURE;
@@ -732,6 +825,20 @@ int run() {
       continue;
     }
     jobs.push_back(BatchJob{f, line_no});
+  }
+  if (fusion) {  // before any pair runs
+    const size_t views = jobs.size() * (FLAGS_fuse_right ? 2 : 1);
+    if (bad_lines != 0 || g_poses.size() != jobs.size()) {
+      cout << "Error: " << FLAGS_fuse_poses << " holds " << g_poses.size() << " poses, the batch list " << jobs.size() << " pairs"
+           << (bad_lines ? " and lines that are no pairs" : "") << "\n";
+      return EXIT_FAILURE;
+    }
+    if (views < 1 || views > CSPM_FUSE_MAX_VIEWS) {
+      cout << "Error: the fusion takes 1 .. " << CSPM_FUSE_MAX_VIEWS << " views, the list asks for " << views << "\n";
+      return EXIT_FAILURE;
+    }
+    g_batch_calib = !FLAGS_calib.empty();
+    g_fusion.reset(new DepthFusion(views));
   }
   return run_batch(jobs, skipped, bad_lines);
 }

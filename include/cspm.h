@@ -773,6 +773,105 @@ int cspm_synthesize(cspm_ctx *ctx, int source, const cspm_synth_params *params, 
 int cspm_synthesize_device(cspm_ctx *ctx, int source, const cspm_synth_params *params, double t, void *d_bgr_out, size_t out_stride,
                            void *d_disp_out, void *d_mask_out);
 
+/* ---- depth-map fusion (an addition): one consistent point cloud from many views ----------------------------------
+ * Everything above relates the two views of ONE pair.  A surface that is wrong in both of them passes the left-right check; what removes
+ * it is agreement with a third viewpoint: the geometric consistency fusion of Gipuma ("fusibile") and COLMAP.
+ * F(params, K views): view k = a w x h f64 depth map (along the optical axis, > 0; anything else is a hole), optionally three w x h planes
+ * of unit normals in the camera frame (all views or none), optionally an 8-bit BGR image, a pinhole camera and a camera -> world pose.
+ * 1 <= K <= 64 (CSPM_FUSE_MAX_VIEWS), all views w x h, w*h < 2^31.  Every product, sum, quotient, floor and square root is one IEEE f64
+ * operation in the association written here, nothing contracted, no reciprocal.
+ * Camera k is (f_k, cx_k, cy_k, R_k, t_k), R row-major (M[i][j] at entry 3*i+j), P_world = R P_cam + t.
+ * cspm_fuse_params { max_reproj, max_rel_depth, min_cos, min_views, suppress }, defaults 2.0, 0.01, 0.0, 2, 1: 2 pixels and 1 % are
+ * COLMAP's and Gipuma's values, min_cos = 0 switches the normal test off (a raw field's normals are noisy); chosen, not tuned.  The host
+ * computes once mr2 = max_reproj * max_reproj.
+ *     back(k, x, y, Z):  u = (double)x - cx_k;  wv = (double)y - cy_k;  X = (u*Z)/f_k;  Y = (wv*Z)/f_k          (G's association)
+ *     world(k, X,Y,Z):   W[i] = ((R_k[i][0]*X + R_k[i][1]*Y) + R_k[i][2]*Z) + t_k[i]
+ *     cam(k, W):         d = W - t_k (three subtractions);  Q[j] = (R_k[0][j]*d[0] + R_k[1][j]*d[1]) + R_k[2][j]*d[2]
+ *     proj(k, Q):        fails unless Q[2] > 0.0;  pu = (f_k*Q[0])/Q[2] + cx_k;  pv = (f_k*Q[1])/Q[2] + cy_k
+ *     rot(k, n):         N[i] = (R_k[i][0]*n[0] + R_k[i][1]*n[1]) + R_k[i][2]*n[2]
+ * Pixel (x, y) of reference view r, Z = depth_r[y][x], m = y*w + x:
+ *  1. !(isfinite(Z) && Z > 0.0): S = 0, nothing is emitted.
+ *  2. suppress && used_r[m]: S = 0x80, nothing is emitted.
+ *  3. P = world(r, back(r, x, y, Z)); SP = P; Nr = rot(r, n_r[m]); SN = Nr when its three components are finite, else (0,0,0);
+ *     SC = (b, g, r) of the pixel as ints; c = 0.
+ *  4. For k = 0 .. K-1, k != r, ascending:
+ *       Q = cam(k, P); if proj(k, Q) fails, continue.
+ *       fx = floor(pu + 0.5), fy = floor(pv + 0.5); continue unless fx >= 0.0 && fx <= (double)(w-1) && fy >= 0.0 && fy <= (double)(h-1)
+ *       (tested on the doubles, a NaN fails; only then are they converted to int).
+ *       Zk = depth_k[fy][fx]; continue unless it is finite and > 0.0.
+ *       Pk = world(k, back(k, fx, fy, Zk)); Q2 = cam(r, Pk); if proj(r, Q2) fails, continue; it gives (pu2, pv2).
+ *       ex = pu2 - (double)x, ey = pv2 - (double)y; continue unless ex*ex + ey*ey <= mr2.
+ *       continue unless fabs(Q2[2] - Z) <= max_rel_depth * Z.
+ *       With normals: Nk = rot(k, n_k[fy*w+fx]); when min_cos > 0.0, continue unless (Nr[0]*Nk[0] + Nr[1]*Nk[1]) + Nr[2]*Nk[2] >= min_cos
+ *       (a NaN fails; the test is against the reference pixel's own normal, not the running sum).
+ *       The view is consistent: c += 1; SP[i] = SP[i] + Pk[i]; SN[i] = SN[i] + Nk[i] iff Nk is all finite; SC += bgr_k; m_k = fy*w + fx.
+ *  5. kept = c >= min_views;  S = c | (kept ? 0x40 : 0)   (c <= 63: the flags never collide).
+ *  6. kept && suppress: used_k[m_k] = 1 for every consistent k.  Only kept pixels make marks.
+ *  7. The record of a kept pixel: den = (double)(c+1); x, y, z = (float)(SP[i]/den); len = sqrt((SN0*SN0 + SN1*SN1) + SN2*SN2);
+ *     nx, ny, nz = (float)(SN[i]/len) (a zero sum gives NaN; without normal maps the three are NaN); each colour byte
+ *     (2*SC_i + (c+1)) / (2*(c+1)) in integer arithmetic, a = 255; without an image in ANY view all four bytes are 0, otherwise a view
+ *     without an image contributes (0,0,0) to the sums; pixel = m.
+ * Order: used is all 0 when a run begins; the views are processed as passes r = 0, 1, .., K-1.  Pass r reads only used_r and writes only
+ * used_k, k != r, and every write stores 1: the result does not depend on scheduling.  With suppress == 0 the passes are independent.
+ * Outputs: the cloud = all kept pixels in (view ascending, raster) order, one cspm_point each in WORLD coordinates; *count = their number
+ * whatever the capacity, when count > cap the first cap records are written and the rest of the buffer is untouched; view_counts[K] = the
+ * kept pixels per view; state = the S bytes, K*w*h, view-major.  Each output may be NULL.
+ * CSPM_ERR_ARG: K outside 1 .. 64; f <= 0 or a non-finite camera value; max |R R^T - I| > 1e-6; a NaN or negative max_reproj or
+ * max_rel_depth; a min_cos outside [0, 1]; a min_views outside 0 .. 63; normals in some views but not all; a bgr_stride below 3*w. */
+#define CSPM_FUSE_MAX_VIEWS 64
+typedef struct cspm_fuse_params {
+  double max_reproj;    /* pixels: the forward-backward reprojection error a consistent view may have */
+  double max_rel_depth; /* the relative depth difference it may have */
+  double min_cos;       /* with normals: the least cosine between the two world normals; 0 = no normal test */
+  int min_views;        /* a pixel is kept when at least this many OTHER views are consistent with it */
+  int suppress;         /* 1: surface emitted from an earlier view is not emitted again */
+} cspm_fuse_params;
+typedef struct cspm_fuse_view {
+  const double *depth;  /* w*h */
+  const double *normal; /* three planes of w*h (the layout of cspm_reproject's normal_out) or NULL */
+  const uint8_t *bgr;   /* 8UC3 rows of bgr_stride bytes or NULL */
+  size_t bgr_stride;    /* >= 3*w when bgr is given */
+  double f, cx, cy;
+  double R[9], t[3];    /* camera -> world */
+} cspm_fuse_view;
+int cspm_fuse_default_params(cspm_fuse_params *p);
+/* F alone on caller memory with a temporary context: begin, one cspm_fuse_push_maps per view, run.  Synchronous.  Every argument is
+ * checked before a device is opened (the list above, and NULL views or depth, w or h < 1, w*h >= 2^31).  It is a one-shot entry like the
+ * cspm_*_host entries; its name deliberately does not end in _host, because it takes the views of a whole scene, not one kernel family's
+ * maps of one view. */
+int cspm_fuse_depth_maps(int device, const cspm_fuse_params *params, const cspm_fuse_view *views, int n_views, int w, int h,
+                         cspm_point *cloud_out, size_t cloud_cap, unsigned int *count_out, unsigned int *view_counts_out, uint8_t *state_out);
+/* The fusion views of a context live in a pool of their own from cspm_fuse_begin to cspm_fuse_end (or cspm_destroy), whatever happens to the
+ * image geometry, cost object and plane field in between: one context serves a video.  Per view and pixel the pool holds an 8-byte depth,
+ * a 24-byte normal, a 4-byte colour and the bytes used and S.  CSPM_ERR_ARG for w or h < 1, w*h >= 2^31 or max_views outside 1 .. 64;
+ * CSPM_ERR_STATE for a second begin without an end. */
+int cspm_fuse_begin(cspm_ctx *ctx, int w, int h, int max_views);
+/* appends one view of the context's STORED FIELD.  view, source, calib, geom_params (NULL = the defaults) and fit mean what they mean in
+ * cspm_reproject_device and the inputs are prepared by the same code behind the same pending-run check; depth and normals land in the slot
+ * without leaving the device.  The slot's depth is G's Z where G's keep holds and NaN elsewhere (so z_near, z_far and min_cos apply), the
+ * normals are G's, the colour is the view's level-0 image.  left_frame is ignored: a view is stored in its own camera frame.  R, t is the
+ * pose of the pair's view-0 rectified camera; for view == 1 the entry stores cx + doffs and t + R (baseline, 0, 0), so both views of a
+ * pair can be pushed.  Asynchronous on the ctx stream.  CSPM_ERR_STATE without a begin, when the slots are full, or when the context's
+ * current w x h differs from the begin's; CSPM_ERR_ARG for a bad pose, or when earlier views have no normals; otherwise the error classes
+ * of cspm_reproject. */
+int cspm_fuse_push(cspm_ctx *ctx, int view, int source, const cspm_calib *calib, const cspm_geom_params *geom_params, const cspm_fit_params *fit,
+                   const double *R, const double *t);
+/* appends one view from caller memory (another sensor's depth map, maps saved earlier); the maps as in cspm_fuse_view.  Synchronous. */
+int cspm_fuse_push_maps(cspm_ctx *ctx, const double *depth, const double *normal, const uint8_t *bgr, size_t bgr_stride, double f, double cx,
+                        double cy, const double *R, const double *t);
+/* the number of views pushed since the begin; -1 without a begin */
+int cspm_fuse_view_count(const cspm_ctx *ctx);
+/* F over the views pushed so far.  Synchronous; host outputs.  It clears used first, so it may be called again with other parameters and
+ * after further pushes.  Timed as one CSPM_K_MISC bracket with K*w*h evaluations.  CSPM_ERR_STATE without a begin or a view. */
+int cspm_fuse_run(cspm_ctx *ctx, const cspm_fuse_params *params, cspm_point *cloud_out, size_t cloud_cap, unsigned int *count_out,
+                  unsigned int *view_counts_out, uint8_t *state_out);
+/* the same with device pointers (the cloud 16-byte aligned, the count and the view counts 4-byte aligned unsigned ints); enqueues on the ctx
+ * stream and returns.  Like cspm_reproject_device it is NOT part of the deferred-output replay, for the reason given there. */
+int cspm_fuse_run_device(cspm_ctx *ctx, const cspm_fuse_params *params, void *d_cloud_out, size_t cloud_cap, void *d_count_out,
+                         void *d_view_counts_out, void *d_state_out);
+/* waits for the stream and frees the views.  CSPM_ERR_STATE without a begin. */
+int cspm_fuse_end(cspm_ctx *ctx);
+
 /* ---- rectification (an addition): a calibrated RAW pair undistorted and row-aligned on the device ----------------------
  * Every entry above that takes images assumes an undistorted, row-aligned pair, and cspm_reproject a cspm_calib of that pair.  This section
  * produces both from a rig description: two pinhole cameras with Brown-Conrady distortion and the pose of camera 1 in camera 0's frame.
