@@ -26,12 +26,13 @@ OPT_SWEEP_PACKED = 10        # packed 8-byte pixels for the raster sweep (defaul
 OPT_SWEEP_PACKED_ACTIVE = 11 # read only
 OPT_SWEEP_PACKED_BAD = 12    # read only, synchronises: pixels the packer could not represent (0 by construction)
 OPT_SWEEP_FLOW = 13          # persistent raster sweep scheduled by dataflow (1: measured slower) or by ordered claims (0, default)
-OPT_SWEEP_WG = 14            # persistent sweep workgroups per CU (default 0 = the library chooses: 2, and 3 where 2 * min(w, h) >= 4 * CUs unless OPT_SWEEP_FOLD is set; identical planes)
+OPT_SWEEP_WG = 14            # persistent sweep workgroups launched per CU; default 0 = the library chooses: 2, and 3 where 2 * min(w, h) >= 4 * CUs and OPT_SWEEP_FOLD is 0 (identical planes)
 OPT_VOLUME_FALLBACKS = 9     # read only: hipMalloc failures of an optional volume this context survived
 OPT_VOLUME_RETRY_PAIRS = 15  # a cost object that runs without the optional volumes it wanted asks again after this many reuses (default 16, 0 = never)
 OPT_VIEW_SORT = 17           # view propagation evaluates a row's proposals in target-column order (default 1; identical planes either way)
-OPT_SWEEP_FOLD = 18          # cross-scale sweep workgroups of levels - 1 waves, the coarsest level folded onto them (default 0: for callers with two or more pairs in flight; identical planes)
+OPT_SWEEP_FOLD = 18          # 1 = cross-scale sweep workgroups of levels - 1 waves, the coarsest level folded onto them; default 0, callers with two or more pairs in flight set 1 (identical planes)
 OPT_FAULT_VOLUME_ALLOC = 16  # write only, TEST HOOK: the n-th optional-volume allocation from now on fails
+OPT_SWEEP_GRID = 23          # write only, TEST HOOK: 0 = the library's grid (default), else the persistent sweep launches at most max(value, row bands) workgroups (identical planes)
 OPT_CENGRD_FUSED = 19        # set before build_cost_cengrd: 1 = no volumes, the cells are computed inside the PatchMatch kernels (default 0; identical planes)
 OPT_CENGRD_FUSED_ACTIVE = 20 # read only: the current cost object is a fused CENGRD one
 OPT_PP_SPECKLE_REMOVED = 21  # read only, synchronises: pixels the speckle filter removed from both masks in the last post-processing

@@ -183,6 +183,7 @@ struct cspm_ctx {
   long long optional_reuses = 0;            // pairs that reused it since
   long long volume_retry_pairs = 16;        // CSPM_OPT_VOLUME_RETRY_PAIRS: ask again for the volumes every so many reuses (0 = never)
   int fault_volume_alloc = 0;               // fault injection for the tests: the n-th optional-volume allocation of this context fails (CSPM_OPT_FAULT_VOLUME_ALLOC, a test hook: nothing in the environment reaches it)
+  int sweep_grid_cap = 0;                   // CSPM_OPT_SWEEP_GRID, a test hook: 0 = the library's grid, else at most max(this, bands) workgroups in the persistent sweep
   unsigned long long *d_maxkeys = nullptr;
   int row_claim = -1;  // row kernels: -1 = claimed column bands for launches of several rounds (default), 0 / 1 = never / always (env CSPM_ROW_CLAIM, tests)
   unsigned int *d_rowq = nullptr;  // row kernels: the eight claim counters of a launch that claims its items (cspm_rows.h row_item)
@@ -1172,6 +1173,8 @@ int do_spatial(cspm_ctx *c, int iter, const cspm_pm_params *p) {
     // the bands so that every band gets the same number
     unsigned grid = (unsigned)std::max<long long>(sw.nbands, std::min<long long>((long long)sw.total, (long long)ncu * wg_per_cu));
     grid = (grid + (unsigned)sw.nbands - 1) / (unsigned)sw.nbands * (unsigned)sw.nbands;
+    // CSPM_OPT_SWEEP_GRID (test hook): fewer workgroups, down to one per band and in uneven shares -- workgroup b serves band b mod nbands
+    if (c->sweep_grid_cap > 0) grid = std::min(grid, (unsigned)std::max(c->sweep_grid_cap, sw.nbands));
     const unsigned waves = sweep_waves(c);
     {
       Timed t(c, CSPM_K_SPATIAL, (long long)sw.total * 2);
@@ -2602,6 +2605,7 @@ int cspm_set_option(cspm_ctx *c, int key, long long value) {
     case CSPM_OPT_VIEW_SORT: c->opt_view_sort = value ? 1 : 0; return CSPM_OK;
     case CSPM_OPT_SWEEP_FOLD: c->opt_sweep_fold = value ? 1 : 0; return CSPM_OK;
     case CSPM_OPT_FAULT_VOLUME_ALLOC: c->fault_volume_alloc = value < 0 ? 0 : (int)value; return CSPM_OK;
+    case CSPM_OPT_SWEEP_GRID: c->sweep_grid_cap = value < 0 ? 0 : (value > (1LL << 20) ? (1 << 20) : (int)value); return CSPM_OK;
     case CSPM_OPT_VOLUME_RETRY_PAIRS: c->volume_retry_pairs = value < 0 ? 0 : value; return CSPM_OK;
     case CSPM_OPT_SWEEP_TIMEOUT_MS:
       if (value < 0 || value > 3600000) return fail(c, CSPM_ERR_ARG, "sweep timeout out of range");

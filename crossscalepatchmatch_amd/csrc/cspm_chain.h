@@ -533,7 +533,7 @@ constexpr int kSweepMaxWaves = CSPM_MAX_LEVELS > kMaxPasses ? CSPM_MAX_LEVELS : 
 // kernel -- another stereo pair's refinement -- still finds LDS on the CU
 struct SweepShared {
   LutMem &lut;
-  double (*lvl)[CSPM_MAX_LEVELS];  // [2][levels]: cross-scale, exact level sums
+  double (*lvl)[CSPM_MAX_LEVELS];  // [2][levels]: cross-scale, the levels' terms of the cost: exact level sum * scale weight
   ChainScratch *m;                 // one per wave (two candidates' chain sums each)
 };
 __host__ __device__ inline size_t sweep_shared_bytes(int waves) {
@@ -570,6 +570,10 @@ __device__ __forceinline__ void eval_pixel_pair(const Cost &cd, const Luts &lut,
     for (int s = 0; s < level; ++s) { cur_y /= 2; cur_x /= 2; d0 /= 2.0; d1 /= 2.0; }
     double *part0 = sh.m[level].part[0], *part1 = sh.m[level].part[1];
     if (level < cd.levels) {
+      // The level's term of :182, sum * weight, is formed HERE, by the wave that has the sum: the accepting wave then only adds the
+      // terms in level order (a product and a sum are rounded separately, contraction is off: the bits of `cost += sum * wgt`), and
+      // its serial tail has no weight loads.
+      const double wgt = cd.lv[level].wgt;
       ChainPlane pl[2];
       plane_param(c0.nx, c0.ny, c0.nz, (double)cur_x, (double)cur_y, d0, pl[0].a, pl[0].b, pl[0].c);  // :144-149
       pl[0].a = wave_uniform(pl[0].a); pl[0].b = wave_uniform(pl[0].b); pl[0].c = wave_uniform(pl[0].c);
@@ -581,15 +585,15 @@ __device__ __forceinline__ void eval_pixel_pair(const Cost &cd, const Luts &lut,
         chain_passes<SRC, 2>(cd, A, lut, pl, lane, 0, 1, parts);
         EVAL_STAMP(5);
         wave_lds_fence();
-        const double s0 = finish_level(A, part0, lane);
-        const double s1 = finish_level(A, part1, lane);
+        const double s0 = finish_level(A, part0, lane) * wgt;
+        const double s1 = finish_level(A, part1, lane) * wgt;
         if (lane == 0) { sh.lvl[0][level] = s0; sh.lvl[1][level] = s1; }
       } else {
         const ChainPlane p1[1] = {pl[0]};
         double *const parts[1] = {part0};
         chain_passes<SRC, 1>(cd, A, lut, p1, lane, 0, 1, parts);
         wave_lds_fence();
-        const double s0 = finish_level(A, part0, lane);
+        const double s0 = finish_level(A, part0, lane) * wgt;
         if (lane == 0) { sh.lvl[0][level] = s0; sh.lvl[1][level] = s0; }
       }
     }
@@ -626,19 +630,19 @@ __device__ __forceinline__ void eval_pixel_pair(const Cost &cd, const Luts &lut,
       }
       __syncthreads();  // the folded level's chain sums are complete
       if (wave == 1) {
-        const double s0 = finish_level(B, fold0, lane);
+        const double s0 = finish_level(B, fold0, lane) * cd.lv[last].wgt;
         if (lane == 0) { sh.lvl[0][last] = s0; if (!both) sh.lvl[1][last] = s0; }
       } else if (wave == 2 && both) {
-        const double s1 = finish_level(B, fold1, lane);
+        const double s1 = finish_level(B, fold1, lane) * cd.lv[last].wgt;
         if (lane == 0) sh.lvl[1][last] = s1;
       }
     }
-    __syncthreads();
+    __syncthreads();  // every level's term is in sh.lvl before wave 0 adds them
     cost0 = cost1 = 0.0;
     if (wave == 0) {
-      for (int s = 0; s < cd.levels; ++s) {  // :182, levels in order
-        cost0 += sh.lvl[0][s] * cd.lv[s].wgt;
-        cost1 += sh.lvl[1][s] * cd.lv[s].wgt;
+      for (int s = 0; s < cd.levels; ++s) {  // :182, levels in order; sh.lvl holds sum * weight
+        cost0 += sh.lvl[0][s];
+        cost1 += sh.lvl[1][s];
       }
     }
   } else {
@@ -727,6 +731,21 @@ __global__ __launch_bounds__(kSweepMaxWaves *kWave) void k_spatial_diag(Cost cd,
 // and left), so by induction over the bands every awaited pixel is reached as long as each band has one running workgroup --
 // the first `nbands` workgroups of the grid.  The plane field itself (what later kernels read) is written with plain stores: nobody reads it across workgroups
 // inside the sweep except its owner.
+//
+// The item loop.  A pixel's fixed costs are kept off the serial path of the workgroup (profiles/sweep_items_before.txt / _after.txt):
+// the pixel's own plane and stored cost -- written by nobody but this workgroup, and not before its accept -- are loaded BEFORE the wait
+// for the predecessors and cross the evaluation in LDS; every level's term sum * weight is formed by the wave that has the sum; and a turn
+// of the loop has ONE barrier of its own, (a) "the predecessors' planes are here", plus eval_pixel_pair's (b, folded only) and (c):
+// the item number, the planes and the own plane are double-buffered on the turn's parity, so that the waves which have handed in their
+// level decode the next item and set their level up while wave 0 accepts and publishes.
+// Invariants of the loop:
+//  * a workgroup never spins on item n+1's predecessors before item n's 12 granules are stored (item n+1 can be n's direct successor):
+//    the one wave that polls is the one that publishes, and it does so in program order;
+//  * a workgroup's claims stay increasing: one thread claims, one item ahead, from the band's counter;
+//  * every spin stays wall-clock bounded through wait_granules;
+//  * on a timeout all waves of the workgroup leave together: the verdict is one LDS word that is only ever cleared, read by every wave
+//    after barrier (a); likewise the end of the band is one word, the item number, read by every wave;
+//  * ctrl[1] is raised by wait_granules alone and read as before.
 // ------------------------------------------------------------------------------------------------
 constexpr int kGranPerPixel = 12;
 constexpr int kSweepMaxBands = 8;
@@ -774,9 +793,10 @@ template <bool CS, int SRC>
 __global__ __launch_bounds__(kSweepMaxWaves *kWave, kSweepMinWaves) void k_spatial_sweep(Cost cd, Pm pm, Sweep sw, int inc) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const SweepShared sh = sweep_shared(smem);
-  __shared__ double s_plane[2][6];
-  __shared__ unsigned int s_item;
-  __shared__ int s_ok;
+  __shared__ double s_plane[2][2][6];  // [item parity][predecessor]: the predecessors' final planes
+  __shared__ double s_own[2][8];       // [item parity]: the pixel's own plane (0..5) and stored cost (6), loaded before the wait
+  __shared__ unsigned int s_item[2];   // [item parity]: the item of this turn of the loop; the other slot receives the following one
+  __shared__ int s_ok;                 // 1 until a wait fails, then 0 for good
   const Luts lut = load_luts(cd, sh.lut);
   // The sweep is a chain of 1 616 dependent pixel evaluations with few waves: when it shares SIMDs with the throughput kernels
   // of other pairs in flight, its instructions go first.
@@ -790,22 +810,19 @@ __global__ __launch_bounds__(kSweepMaxWaves *kWave, kSweepMinWaves) void k_spati
   const unsigned int btotal = bstart[ndiag];
   unsigned int *claim = &sw.ctrl[2 + band];
   int k = by0;  // the band's first diagonal
-  unsigned int next_item = 0;
   if (threadIdx.x == 0) {
-    if (__hip_atomic_load(&sw.ctrl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) next_item = btotal;  // an earlier sweep failed
-    else next_item = __hip_atomic_fetch_add(claim, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (__hip_atomic_load(&sw.ctrl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) s_item[0] = btotal;  // an earlier sweep failed
+    else s_item[0] = __hip_atomic_fetch_add(claim, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_ok = 1;
   }
-  for (;;) {
-    if (threadIdx.x == 0) {
-      s_item = next_item;
-      s_ok = 1;
-      // claim the following item now: the atomic's latency hides behind this item's work.  Claims of a
-      // workgroup stay increasing, which is all the deadlock argument needs.
-      if (next_item < btotal) next_item = __hip_atomic_fetch_add(claim, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    const unsigned int item = s_item;
-    if (item >= btotal) return;
+  __syncthreads();  // once, outside the loop: the first item and s_ok are in LDS
+  for (unsigned int par = 0;; par ^= 1u) {
+    const unsigned int item = s_item[par];  // written before the previous turn's barrier (a); every wave decodes it for itself
+    if (item >= btotal) return;              // the same word for every wave: they leave together
+    // claim the following item now: the atomic's latency hides behind this item's work.  Claims of a
+    // workgroup stay increasing, which is all the deadlock argument needs.
+    unsigned int next_item = 0;
+    if (threadIdx.x == 0) next_item = __hip_atomic_fetch_add(claim, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     SWEEP_STAMP(0);
 #ifdef CSPM_SWEEP_TRACE
     if (threadIdx.x == 0) { s_tr = sw.trace ? sw.trace + ((size_t)2 * pm.W * by0 + item) * kTraceSlots : nullptr; if (s_tr) { s_tr[4] = 0; s_tr[5] = 0; for (int k = 8; k < kTraceSlots; ++k) s_tr[k] = 0; } }
@@ -842,30 +859,44 @@ __global__ __launch_bounds__(kSweepMaxWaves *kWave, kSweepMinWaves) void k_spati
     const ChainLevel A = sweep_level_setup<CS, SRC>(cd, v, x, y, wave);
     // 1. wait for the predecessors' planes: lanes 0..23 of wave 0 poll one granule each; the data arrives with the tags
     if (wave == 0) {
+      // What only this workgroup writes during a sweep -- the pixel's own plane (the own0 / own1 shortcuts, the publish of an
+      // unchanged plane) and its stored cost (the accept) -- is loaded NOW, one lane per word: the round trip overlaps the wait for
+      // the predecessors instead of following it, and the words cross the evaluation in LDS, not in registers.
+      const long long comp = f.ny - f.nx;  // the six components of a view's plane field are equally spaced arrays
+      double mine = 0.0;
+      if (lane < 6) mine = f.nx[lane * comp + i];
+      else if (lane == 6) mine = f.cost[i];
       const int pred = lane >= kGranPerPixel ? 1 : 0, part = lane - pred * kGranPerPixel;
       const bool need = lane < 2 * kGranPerPixel && (pred == 0 ? have0 : have1);
       unsigned long long g;
       const bool ok = wait_granules(sw.gran[v] + (pred == 0 ? jx : jy) * kGranPerPixel + (need ? part : 0), need, sw.epoch, &sw.ctrl[1], sw.timeout_ticks, g);
-      if (lane < 2 * kGranPerPixel) reinterpret_cast<uint32_t *>(&s_plane[0][0])[lane] = (uint32_t)g;  // s_plane[pred][part / 2], half part % 2
-      if (lane == 0 && !ok) s_ok = 0;
+      if (lane < 2 * kGranPerPixel) reinterpret_cast<uint32_t *>(&s_plane[par][0][0])[lane] = (uint32_t)g;  // s_plane[par][pred][part / 2], half part % 2
+      if (lane < 7) s_own[par][lane] = mine;
+      if (lane == 0) {
+        if (!ok) s_ok = 0;
+        s_item[par ^ 1u] = next_item;  // the claim made at the top of this turn has long returned
+      }
     }
-    __syncthreads();
-    if (!s_ok) return;
+    __syncthreads();  // (a) wave 0 -> all: the predecessors' planes, the own plane and cost, the verdict and the next item are in LDS
+    if (!s_ok) return;  // a failed wait: every wave reads the same word after the same barrier
     SWEEP_STAMP(2);
     // 2. both candidate costs in one pass over the window
     double cost0 = 0.0, cost1 = 0.0;
     bool eval0 = false, eval1 = false;
+    const double(*pl)[6] = s_plane[par];
+    const double *mine = s_own[par];
     if (have0 || have1) {
       // with one candidate missing, both slots hold the existing one (the duplicate is computed once)
       const int p0 = have0 ? 0 : 1, p1 = have1 ? 1 : 0;
-      const Cand c0{s_plane[p0][0], s_plane[p0][1], s_plane[p0][2], s_plane[p0][3], s_plane[p0][4], s_plane[p0][5]};
-      const Cand c1{s_plane[p1][0], s_plane[p1][1], s_plane[p1][2], s_plane[p1][3], s_plane[p1][4], s_plane[p1][5]};
+      const Cand c0{pl[p0][0], pl[p0][1], pl[p0][2], pl[p0][3], pl[p0][4], pl[p0][5]};
+      const Cand c1{pl[p1][0], pl[p1][1], pl[p1][2], pl[p1][3], pl[p1][4], pl[p1][5]};
       // Result-preserving shortcuts (no arithmetic skipped that could change an outcome):
       //  * both predecessors hold bitwise the same plane (very common once the sweep has passed over them): the second
       //    evaluation would return the bits of the first and `cost1 < min(cur, cost0)` would fail;
       //  * a predecessor holds bitwise the pixel's OWN plane: its cost here is the stored min_cost (same function, same
-      //    pixel, same plane), and `cost < min_cost` fails.  The own plane is only ever written by this workgroup.
-      const Cand own{f.nx[i], f.ny[i], f.nz[i], f.a[i], f.b[i], f.c[i]};
+      //    pixel, same plane), and `cost < min_cost` fails.  The own plane is only ever written by this workgroup -- and not
+      //    before the accept below, which is why the copy loaded before the wait is the plane.
+      const Cand own{mine[0], mine[1], mine[2], mine[3], mine[4], mine[5]};
       const bool same01 = c0.nx == c1.nx && c0.ny == c1.ny && c0.nz == c1.nz && c0.a == c1.a && c0.b == c1.b && c0.c == c1.c;
       const bool trust = pm.trust_cost != 0;
       const bool own0 = trust && c0.nx == own.nx && c0.ny == own.ny && c0.nz == own.nz && c0.a == own.a && c0.b == own.b && c0.c == own.c;
@@ -873,6 +904,8 @@ __global__ __launch_bounds__(kSweepMaxWaves *kWave, kSweepMinWaves) void k_spati
       eval0 = have0 && !own0;
       eval1 = have1 && !own1 && !(have0 && same01);
       SWEEP_STAMP(3);
+      // eval_pixel_pair's barriers: (b) folded workgroups only, the folded level's chain sums are complete before two waves finish
+      // them; (c) every level's term is in sh.lvl (single scale: every pass's chain sums are in wave 0's scratch) before wave 0 adds them.
       if (eval0 && eval1) {
         eval_pixel_pair<CS, SRC>(cd, lut, sh, v, x, y, c0, c1, true, wave, lane, cost0, cost1, A);
       } else if (eval0) {
@@ -882,28 +915,32 @@ __global__ __launch_bounds__(kSweepMaxWaves *kWave, kSweepMinWaves) void k_spati
       }
     }
     // 3. accept (x-predecessor first, then y-predecessor against the updated minimum; :198-212), publish the FINAL plane.
-    //    cost0 / cost1 are uniform in wave 0, so every lane of it takes the same decision.
+    //    cost0 / cost1 are uniform in wave 0, so every lane of it takes the same decision.  The other waves are already in the next
+    //    turn: they decode its item and set their level up while this runs, and meet wave 0 at barrier (a).
     if (wave == 0) {
-      double best_cost = f.cost[i];  // own pixel: nobody else writes it during the sweep
+      double best_cost = mine[6];  // the stored cost, loaded before the wait: nobody else writes it during the sweep
       int pick = -1;
       if (eval0 && cost0 < best_cost) { best_cost = cost0; pick = 0; }
       if (eval1 && cost1 < best_cost) { best_cost = cost1; pick = 1; }
       SWEEP_STAMP(6);
-      const long long comp = f.ny - f.nx;  // the six components of a view's plane field are equally spaced arrays
       if (lane < kGranPerPixel) {
         const int k = lane >> 1;
-        const double val = pick >= 0 ? s_plane[pick][k] : f.nx[k * comp + i];
+        const double val = pick >= 0 ? pl[pick][k] : mine[k];
         const unsigned int half = (lane & 1) ? (unsigned int)__double2hiint(val) : (unsigned int)__double2loint(val);
         __hip_atomic_store(sw.gran[v] + (size_t)i * kGranPerPixel + lane, ((unsigned long long)sw.epoch << 32) | half, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
       }
       if (pick >= 0) {  // the plane field, for the kernels after the sweep
-        if (lane < 6) f.nx[lane * comp + i] = s_plane[pick][lane];
+        const long long comp = f.ny - f.nx;  // the six components of a view's plane field are equally spaced arrays
+        if (lane < 6) f.nx[lane * comp + i] = pl[pick][lane];
         if (lane == 6) f.cost[i] = best_cost;
       }
       SWEEP_STAMP(7);
     }
-    __syncthreads();  // s_item / s_plane / scratch are reused by the next item
+    // No barrier here.  Everything a turn shares through LDS is either double-buffered on the turn's parity (s_item, s_plane,
+    // s_own: wave 0 refills slot `par` two turns on, after the next turn's barrier (a), which a wave reaches only when it has
+    // read this turn's) or written only after the next turn's barrier (a) (sh.lvl, the chain scratch: wave 0 arrives there
+    // after its reads above).
   }
 }
 

@@ -198,6 +198,12 @@ int cspm_build_cost_grd(cspm_ctx *ctx, int max_dis, int wnd_size, int scale_num,
  * local-stereo scratch.  Requested sizes (the allocator's rounding is not in it); the temporaries an entry stages caller memory
  * through are freed before it returns and are not counted.  0 for a fresh context; a pair that reuses every buffer leaves it unchanged. */
 #define CSPM_OPT_DEVICE_BYTES 22
+/* CSPM_OPT_SWEEP_GRID (write only, TEST HOOK; default 0 = the library's choice, see CSPM_OPT_SWEEP_WG): any other value caps the grid of
+ * the persistent raster sweep at max(value, row bands) workgroups.  On an image small enough for a test the library's grid gives every
+ * workgroup a handful of unrelated pixels; a grid of one workgroup per row band makes each workgroup walk its band pixel by pixel, so
+ * that consecutive turns of its item loop are a pixel and its direct successor.  Any value gives identical planes.  A set_option call,
+ * never the environment, like CSPM_OPT_FAULT_VOLUME_ALLOC. */
+#define CSPM_OPT_SWEEP_GRID 23
 int cspm_get_option(cspm_ctx *ctx, int key, long long *value);
 int cspm_set_option(cspm_ctx *ctx, int key, long long value);
 /* The same constructors with `new CenCC` (main.cc:43-45; cc/cen_cc.cc:4-137): 9x9 census codes of every level built on
