@@ -89,22 +89,10 @@ __device__ __forceinline__ ChainLevel make_chain_level(const Cost &cd, int s, in
 
 #ifdef CSPM_SWEEP_TRACE
 constexpr int kTraceSlots = 16;
-__shared__ long long *s_tr;  // debug: the stamps of the item this workgroup works on (slots 0-7: wall clock per stage; 8-15: shader cycles inside one chain step)
+__shared__ long long *s_tr;  // debug: the stamps of the item this workgroup works on (slots 0-7: wall clock per stage; 8-13: unused; 14-15: where the waves sit)
 #define EVAL_STAMP(slot) do { if (wave == 0 && lane == 0 && s_tr) s_tr[slot] = wall_clock64(); } while (0)
-// s_memtime ordered after the values `dep...` are available (the compiler must have them in registers before the statement); volatile
-// asm statements keep their order.  lgkmcnt(0) also drains the wave's LDS reads: the stamps sit where the code waits for them anyway.
-__device__ __forceinline__ unsigned long long step_stamp(unsigned dep0, unsigned dep1) {
-  unsigned long long t;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : "v"(dep0), "v"(dep1) : "memory");
-  return t;
-}
 #else
 #define EVAL_STAMP(slot) do { } while (0)
-#endif
-#if defined(CSPM_SWEEP_TRACE) && defined(CSPM_STEP_TRACE)
-#define STEP_STAMP(k, d0, d1) do { if (trace_step) tstamp[k] = step_stamp((unsigned)(d0), (unsigned)(d1)); } while (0)
-#else
-#define STEP_STAMP(k, d0, d1) do { } while (0)
 #endif
 // Software pipelining of the chain steps (round 5): a step is a chain of dependent round trips -- gather (260-280 cycles even on an
 // empty GPU), exp-table LDS read (110), colour-table LDS read + cell arithmetic (170), ~200 cycles of address arithmetic and
@@ -124,6 +112,65 @@ __device__ __forceinline__ double wave_uniform(double v) {
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
+// kSrcGrd8: the two cells of a tap from the 16-byte pair `pr` = {element at the lower address, element at the upper one}.  The left
+// view reads the right image at x-f and x-f-1, so there the pair is {f+1, f}.
+__device__ __forceinline__ void grd8_cell_pair(const double *lut_a, uint32_t Iq, double XP, const uint4 &pr, bool left, double &c0, double &c1) {
+  const double clo = grd8_cell(lut_a, Iq, XP, pix8_colour(pr.y), pix8_x(pr.x, pr.y));
+  const double chi = grd8_cell(lut_a, Iq, XP, pix8_colour(pr.w), pix8_x(pr.z, pr.w));
+  c0 = left ? chi : clo;
+  c1 = left ? clo : chi;
+}
+
+// The value of one tap for one candidate, whose disparity there is `q_disp`: the two cells of this tap for source SRC, interpolated
+// (:166-177).  ALLV: the level runs without clamp, validity test and select (chain_passes).  The step's part of the tap: P the own
+// element (kSrcVol2 / kSrcGrd8: the colour in P.z), XP its biased gradient (kSrcGrd8), Pg its gradient (kSrcCenGrd), `of` its byte
+// offset, (qx, qy) the tap's image coordinates, ok = inside window and image (masked taps have weight 0).
+template <int SRC, bool ALLV>
+__device__ __forceinline__ double chain_tap_value(const Cost &cd, const ChainLevel &A, const Luts &lut, const uint4 &P, double XP, double Pg,
+                                                  int of, int qx, int qy, bool ok, double q_disp) {
+  constexpr int E = SRC == kSrcVol2 ? 4 : elem_size<SRC>();
+  if constexpr (SRC == kSrcImg) {
+    const ImgSplit g = split_img(q_disp, A.sgn * q_disp, (double)qx, A.Dm1, A.has_valid);
+    const int fxc = min(max(g.fx, -A.pad), A.W + A.pad - 2);  // clamps only taps of the "impossible disparity" branch
+    const int oo = (qy * A.Wp + A.pad + fxc) * E;
+    const uint4 o0 = ld_elem<SRC>(A.opx, oo), o1 = ld_elem<SRC>(A.opx, oo + E);
+    const double cell = img_cell(pix_of<SRC>(P), g_of(P), pix_of<SRC>(o0), g_of(o0), pix_of<SRC>(o1), g_of(o1), g.fw);
+    return g.valid ? cell : A.maxc;
+  } else {
+    const DispSplit d = ALLV ? split_disp_valid(q_disp) : split_disp(q_disp, A.Dm1, A.has_valid);
+    double c0, c1;
+    if constexpr (SRC == kSrcVol2) {
+      // one 16-byte gather: {cell(f), cell(f+1)} of this tap's pixel.  Masked taps (weight 0) read the window centre's column.
+      const int cx = ok ? qx : A.ox0 + cd.half;
+      const unsigned idx = __umul24((unsigned)d.f, (unsigned)A.slab) + (unsigned)(qy * A.W + cx);  // < 2^28 (alloc_cost checks)
+      const double2 cc = *reinterpret_cast<const double2 *>(A.vol2 + (size_t)(idx << 4));
+      c0 = cc.x;
+      c1 = cc.y;
+    } else if constexpr (SRC == kSrcVolume) {
+      const int cx = ok ? qx : A.ox0 + cd.half;
+      const double *v = A.vol + (size_t)d.f * A.slab + (size_t)qy * A.W + cx;
+      c0 = v[0];
+      c1 = v[A.slab];
+    } else if constexpr (SRC == kSrcGrd8) {
+      // the two other-view elements of the tap (disparities f and f+1) are neighbours: ONE 16-byte gather from the lower address
+      const bool left = A.dirE < 0;  // the left view reads the right image at x-f and x-f-1
+      const uint4 pr = ld_pix8_pair(A.opx, of + __mul24(A.dirE, d.f) + (left ? -E : 0));
+      grd8_cell_pair(lut.a, P.z, XP, pr, left, c0, c1);
+    } else if constexpr (SRC == kSrcCenGrd) {
+      // per element one 16-byte gather from Level::pc and one 8-byte gather from Level::grd
+      const int oo = of + __mul24(A.dirE, d.f);
+      const uint4 o0 = ld_elem<SRC>(A.opx, oo), o1 = ld_elem<SRC>(A.opx, oo + A.dirE);
+      const double g0 = ld_grad(A.ogx, oo >> 1), g1 = ld_grad(A.ogx, (oo + A.dirE) >> 1);
+      c0 = cengrd_cell(lut.a, P, Pg, o0, g0);
+      c1 = cengrd_cell(lut.a, P, Pg, o1, g1);
+    } else {
+      const int oo = of + __mul24(A.dirE, d.f);
+      cell_pair_of<SRC>(lut.a, P, ld_elem<SRC>(A.opx, oo), ld_elem<SRC>(A.opx, oo + A.dirE), c0, c1);
+    }
+    return ALLV ? lerp_cells(d.fr, c0, c1) : tap_value(d, c0, c1, A.maxc);
+  }
+}
+
 // One level, NC candidates (1 or 2) at the same pixel: the plane-independent half of every tap (own element, guide
 // weight) is computed once.  `pass_first/pass_step` let several waves share the passes of one level (single-scale sweep).
 // The chain sums go straight into LDS: part[c][pass * 64 + lane] (round 5: no S[NC][passes] register array, a run-time pass loop --
@@ -134,7 +181,6 @@ __device__ __forceinline__ void chain_passes(const Cost &cd, const ChainLevel &A
   constexpr int E = SRC == kSrcVol2 ? 4 : elem_size<SRC>();
   const int lutzero = kLutZero;
   const int lr = lane / kRowMod, j = lane - lr * kRowMod;  // lane 63: lr = 9 -> never a valid chain
-#if !defined(CSPM_STEP_TRACE)
   if constexpr (PIPE && (SRC == kSrcGrd || SRC == kSrcCen || SRC == kSrcGrd8)) {
     struct PassCtx {
       bool chain_ok;
@@ -193,16 +239,8 @@ __device__ __forceinline__ void chain_passes(const Cost &cd, const ChainLevel &A
 #pragma unroll
       for (int k = 0; k < NC; ++k) {
         double c0, c1;
-        if constexpr (SRC == kSrcGrd8) {
-          const bool left = A.dirE < 0;  // the left view reads the right image at x-f and x-f-1: the pair is {f+1, f}
-          const uint4 pr = F.o0[k];
-          const double clo = grd8_cell(lut.a, Iq, XP, pix8_colour(pr.y), pix8_x(pr.x, pr.y));
-          const double chi = grd8_cell(lut.a, Iq, XP, pix8_colour(pr.w), pix8_x(pr.z, pr.w));
-          c0 = left ? chi : clo;
-          c1 = left ? clo : chi;
-        } else {
-          cell_pair_of<SRC>(lut.a, F.P, F.o0[k], F.o1[k], c0, c1);
-        }
+        if constexpr (SRC == kSrcGrd8) grd8_cell_pair(lut.a, Iq, XP, F.o0[k], A.dirE < 0, c0, c1);
+        else cell_pair_of<SRC>(lut.a, F.P, F.o0[k], F.o1[k], c0, c1);
         acc[k] = __builtin_fma(wgt, tap_value(F.d[k], c0, c1, A.maxc), acc[k]);  // :176-177
       }
     };
@@ -262,7 +300,6 @@ __device__ __forceinline__ void chain_passes(const Cost &cd, const ChainLevel &A
     }
     return;
   }
-#endif
   // All-valid levels (round 5): the disparity of a tap is linear in its column and row, so when it lies in [1 + 2^-20, D - 2^-20] at the
   // four corners of the window -- for every candidate -- every tap of the level takes the interpolation branch of pre_cs_pc.cc:166-175:
   // that level runs without clamp, validity test and select (4 of ~29 instructions per tap and candidate; the margin covers the roundings
@@ -270,9 +307,6 @@ __device__ __forceinline__ void chain_passes(const Cost &cd, const ChainLevel &A
   // its candidates are the neighbours' settled planes.  Same arithmetic for the taps that were valid anyway: identical bits.
   // (The general taps on every level lost.)
   bool allv = (SRC == kSrcGrd || census_elem<SRC>() || SRC == kSrcGrd8 || SRC == kSrcVolume || SRC == kSrcVol2) && A.has_valid;
-#if defined(CSPM_STEP_TRACE)
-  allv = false;
-#endif
   if (allv) {
     const double x0 = (double)A.ox0, x1 = (double)(A.ox0 + kRowMod * A.nsteps - 1);  // the last step's masked taps beyond the window form addresses too
     const double y0 = (double)(A.oy0 + A.r_lo), y1 = (double)(A.oy0 + A.r_lo + A.nrows - 1);
@@ -304,13 +338,6 @@ __device__ __forceinline__ void chain_passes(const Cost &cd, const ChainLevel &A
     for (int c = 0; c < NC; ++c) ty[c] = pl[c].b * (double)(A.oy0 + dy) + pl[c].c;  // q_disp_y, :155
     const double jd = (double)j;
     for (int st = 0; st < A.nsteps; ++st) {
-#if defined(CSPM_SWEEP_TRACE) && defined(CSPM_STEP_TRACE)
-      // one step of the item's first level-0 pass is stamped: wave 0 (level 0 / pass 0), its second pass, the middle step
-      const bool trace_step = (SRC == kSrcGrd || SRC == kSrcGrd8) && s_tr != nullptr && pass_first == 0 && A.n == cd.n && A.W == cd.lv[0].W && p == 1 && st == 2 &&
-                              __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0;
-      unsigned long long tstamp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      STEP_STAMP(0, st, p);
-#endif
       const double xg = (double)(A.ox0 + kRowMod * st);  // q_x of the group's first column
       const int dx = j + kRowMod * st;
       const bool ok = chain_ok & (dx < A.n) & ((unsigned)(qx0 + kRowMod * st) < (unsigned)A.W);
@@ -326,75 +353,13 @@ __device__ __forceinline__ void chain_passes(const Cost &cd, const ChainLevel &A
       if constexpr (SRC == kSrcCenGrd) Pg = ld_grad(A.gx, (ob + st * (kRowMod * E)) >> 1);
       const int sad0 = (int)__builtin_amdgcn_sad_u8(A.Ip, (SRC == kSrcVol2 || SRC == kSrcGrd8) ? P.z : pix_of<SRC>(P), 0u);
       const int sad = ok ? sad0 : lutzero;  // masked taps get weight entry kLutZero = 0.0: they add +0.0
-      STEP_STAMP(1, sad0, P.z);             // the own element has arrived
       const double wgt = lut.w[sad];        // :161-164
-      STEP_STAMP(2, __double2hiint(wgt), __double2loint(wgt));  // ... and the guide weight from the exp table
 #pragma unroll
       for (int c = 0; c < NC; ++c) {
         const double q_disp = tap_disp(pl[c].a, jd, group_disp(pl[c].a, xg, ty[c]));  // :165, device order
-        if constexpr (SRC == kSrcImg) {
-          const ImgSplit g = split_img(q_disp, A.sgn * q_disp, (double)(qx0 + kRowMod * st), A.Dm1, A.has_valid);
-          const int fxc = min(max(g.fx, -A.pad), A.W + A.pad - 2);  // clamps only taps of the "impossible disparity" branch
-          const int of = ((A.oy0 + dy) * A.Wp + A.pad + fxc) * E;
-          const uint4 o0 = ld_elem<SRC>(A.opx, of), o1 = ld_elem<SRC>(A.opx, of + E);
-          const double cell = img_cell(pix_of<SRC>(P), g_of(P), pix_of<SRC>(o0), g_of(o0), pix_of<SRC>(o1), g_of(o1), g.fw);
-          acc[c] = __builtin_fma(wgt, g.valid ? cell : A.maxc, acc[c]);
-          continue;
-        }
-        const DispSplit d = ALLV ? split_disp_valid(q_disp) : split_disp(q_disp, A.Dm1, A.has_valid);
-        double c0, c1;
-        if constexpr (SRC == kSrcVol2) {
-          // one 16-byte gather: {cell(f), cell(f+1)} of this tap's pixel.  Masked taps (weight 0) read the window centre's column.
-          const int qy = A.oy0 + dy, qx = ok ? qx0 + kRowMod * st : A.ox0 + cd.half;
-          const unsigned idx = __umul24((unsigned)d.f, (unsigned)A.slab) + (unsigned)(qy * A.W + qx);  // < 2^28 (alloc_cost checks)
-          const double2 cc = *reinterpret_cast<const double2 *>(A.vol2 + (size_t)(idx << 4));
-          c0 = cc.x;
-          c1 = cc.y;
-        } else if (SRC == kSrcVolume) {
-          const int qy = A.oy0 + dy, qx = ok ? qx0 + kRowMod * st : A.ox0 + cd.half;
-          const double *v = A.vol + (size_t)d.f * A.slab + (size_t)qy * A.W + qx;
-          c0 = v[0];
-          c1 = v[A.slab];
-        } else if constexpr (SRC == kSrcGrd8) {
-          // the two other-view elements of the tap (disparities f and f+1) are neighbours: ONE 16-byte gather from the lower address
-          const bool left = A.dirE < 0;  // the left view reads the right image at x-f and x-f-1
-          const int of = ob + st * (kRowMod * E) + __mul24(A.dirE, d.f) + (left ? -E : 0);
-          const uint4 pr = ld_pix8_pair(A.opx, of);
-          if (c == 0) STEP_STAMP(3, pr.x, pr.w);  // the other view's pair has arrived
-          const double clo = grd8_cell(lut.a, P.z, XP, pix8_colour(pr.y), pix8_x(pr.x, pr.y));
-          const double chi = grd8_cell(lut.a, P.z, XP, pix8_colour(pr.w), pix8_x(pr.z, pr.w));
-          c0 = left ? chi : clo;
-          c1 = left ? clo : chi;
-          if (c == 0) STEP_STAMP(4, __double2hiint(c0), __double2hiint(c1));  // both cells (colour table round trip included)
-        } else if constexpr (SRC == kSrcCenGrd) {
-          // per element one 16-byte gather from Level::pc and one 8-byte gather from Level::grd
-          const int of = ob + st * (kRowMod * E) + __mul24(A.dirE, d.f);
-          const uint4 o0 = ld_elem<SRC>(A.opx, of), o1 = ld_elem<SRC>(A.opx, of + A.dirE);
-          const double g0 = ld_grad(A.ogx, of >> 1), g1 = ld_grad(A.ogx, (of + A.dirE) >> 1);
-          c0 = cengrd_cell(lut.a, P, Pg, o0, g0);
-          c1 = cengrd_cell(lut.a, P, Pg, o1, g1);
-        } else {
-          const int of = ob + st * (kRowMod * E) + __mul24(A.dirE, d.f);
-#if defined(CSPM_SWEEP_TRACE) && defined(CSPM_STEP_TRACE)
-          const uint4 o0 = ld_elem<SRC>(A.opx, of), o1 = ld_elem<SRC>(A.opx, of + A.dirE);
-          if (c == 0) STEP_STAMP(3, o0.x, o1.x);
-          cell_pair_of<SRC>(lut.a, P, o0, o1, c0, c1);
-          if (c == 0) STEP_STAMP(4, __double2hiint(c0), __double2hiint(c1));
-#else
-          cell_pair_of<SRC>(lut.a, P, ld_elem<SRC>(A.opx, of), ld_elem<SRC>(A.opx, of + A.dirE), c0, c1);
-#endif
-        }
-        acc[c] = __builtin_fma(wgt, ALLV ? lerp_cells(d.fr, c0, c1) : tap_value(d, c0, c1, A.maxc), acc[c]);  // :176-177
+        acc[c] = __builtin_fma(wgt, chain_tap_value<SRC, ALLV>(cd, A, lut, P, XP, Pg, ob + st * (kRowMod * E), qx0 + kRowMod * st, A.oy0 + dy, ok, q_disp),
+                                acc[c]);  // :176-177
       }
-#if defined(CSPM_SWEEP_TRACE) && defined(CSPM_STEP_TRACE)
-      STEP_STAMP(5, __double2hiint(acc[0]), __double2hiint(acc[NC - 1]));  // the step's accumulations
-      if (trace_step) {
-        STEP_STAMP(6, 0, 0);
-        STEP_STAMP(7, 0, 0);  // two stamps back to back: what a stamp itself costs
-        if (lane == 0)
-          for (int k = 0; k < 8; ++k) s_tr[8 + k] = (long long)tstamp[k];
-      }
-#endif
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c) part[c][p * kWave + lane] = acc[c];
@@ -666,6 +631,42 @@ __device__ __forceinline__ void eval_pixel_pair(const Cost &cd, const Luts &lut,
   }
 }
 
+// ---- one sweep pixel: what the two persistent sweep kernels share.  Where the planes come from, the evaluation's dispatch, the
+// publish, the barriers, the stamps and the claiming are theirs. ----
+
+// The two candidates of a sweep pixel from the predecessors' final planes pl[0] (x-predecessor) and pl[1] (y-predecessor), and which of
+// them need an evaluation.  With one candidate missing, both slots hold the existing one (the duplicate is computed once).
+// Result-preserving shortcuts (no arithmetic skipped that could change an outcome):
+//  * both predecessors hold bitwise the same plane (very common once the sweep has passed over them): the second
+//    evaluation would return the bits of the first and `cost1 < min(cur, cost0)` would fail;
+//  * a predecessor holds bitwise the pixel's OWN plane: its cost here is the stored min_cost (same function, same
+//    pixel, same plane), and `cost < min_cost` fails.  The own plane is only ever written by this workgroup -- and not
+//    before the accept, which is why a copy loaded before the wait is the plane.  `trust` = Pm::trust_cost: the stored costs are
+//    costs of the stored planes.
+// The own plane is read here, AFTER the candidates, from own_k[k * own_stride] (LDS words, or the field's equally spaced component arrays).
+// same01 stays written out: through same_plane() the compiler forms the test differently and the register allocation of the whole
+// of k_spatial_sweep changes with it (profiles/chain_refactor_resources.txt).
+__device__ __forceinline__ void sweep_candidates(const double (*pl)[6], const double *own_k, long long own_stride, bool have0, bool have1, bool trust, Cand &c0, Cand &c1,
+                                                 bool &eval0, bool &eval1) {
+  const int p0 = have0 ? 0 : 1, p1 = have1 ? 1 : 0;
+  c0 = Cand{pl[p0][0], pl[p0][1], pl[p0][2], pl[p0][3], pl[p0][4], pl[p0][5]};
+  c1 = Cand{pl[p1][0], pl[p1][1], pl[p1][2], pl[p1][3], pl[p1][4], pl[p1][5]};
+  const Cand own{own_k[0], own_k[own_stride], own_k[2 * own_stride], own_k[3 * own_stride], own_k[4 * own_stride], own_k[5 * own_stride]};
+  const bool same01 = c0.nx == c1.nx && c0.ny == c1.ny && c0.nz == c1.nz && c0.a == c1.a && c0.b == c1.b && c0.c == c1.c;
+  const bool own0 = same_plane(c0, own, trust);
+  const bool own1 = same_plane(c1, own, trust);
+  eval0 = have0 && !own0;
+  eval1 = have1 && !own1 && !(have0 && same01);
+}
+// accept: the x-predecessor first, then the y-predecessor against the updated minimum (:198-212).  `best_cost` comes in as the pixel's
+// stored cost; returns which candidate was picked (-1: none) and leaves its cost there.
+__device__ __forceinline__ int sweep_accept(bool eval0, double cost0, bool eval1, double cost1, double &best_cost) {
+  int pick = -1;
+  if (eval0 && cost0 < best_cost) { best_cost = cost0; pick = 0; }
+  if (eval1 && cost1 < best_cost) { best_cost = cost1; pick = 1; }
+  return pick;
+}
+
 // one launch per anti-diagonal k (sweep coordinates xs+ys == k, image x = inc>0 ? xs : W-1-xs); one workgroup per pixel
 template <bool CS, int SRC>
 __global__ __launch_bounds__(kSweepMaxWaves *kWave) void k_spatial_diag(Cost cd, Pm pm, int k, int inc) {
@@ -688,19 +689,15 @@ __global__ __launch_bounds__(kSweepMaxWaves *kWave) void k_spatial_diag(Cost cd,
   const long long j0 = have0 ? jx : jy, j1 = have1 ? jy : jx;
   const Cand c0{f.nx[j0], f.ny[j0], f.nz[j0], f.a[j0], f.b[j0], f.c[j0]};
   const Cand c1{f.nx[j1], f.ny[j1], f.nz[j1], f.a[j1], f.b[j1], f.c[j1]};
-  const bool same01 = c0.nx == c1.nx && c0.ny == c1.ny && c0.nz == c1.nz && c0.a == c1.a && c0.b == c1.b && c0.c == c1.c;
+  // no own-plane shortcuts here: the persistent sweeps are tested against this kernel
+  const bool same01 = same_plane(c0, c1);
   double cost0, cost1;
   const ChainLevel A = sweep_level_setup<CS, SRC>(cd, v, x, y, wave);
   eval_pixel_pair<CS, SRC>(cd, lut, sh, v, x, y, c0, c1, have0 && have1 && !same01, wave, lane, cost0, cost1, A);
   if (threadIdx.x == 0) {
     double best_cost = f.cost[i];
-    int pick = -1;
-    if (have0 && cost0 < best_cost) { best_cost = cost0; pick = 0; }
-    if (have1 && cost1 < best_cost) { best_cost = cost1; pick = 1; }
-    if (pick >= 0) {
-      const Cand &w = pick == 0 ? c0 : c1;
-      store_plane(f, i, w.nx, w.ny, w.nz, w.a, w.b, w.c, best_cost);
-    }
+    const int pick = sweep_accept(have0, cost0, have1, cost1, best_cost);
+    if (pick >= 0) store_plane(f, i, pick == 0 ? c0 : c1, best_cost);
   }
 }
 
@@ -826,7 +823,6 @@ __global__ __launch_bounds__(kSweepMaxWaves *kWave, kSweepMinWaves) void k_spati
     SWEEP_STAMP(0);
 #ifdef CSPM_SWEEP_TRACE
     if (threadIdx.x == 0) { s_tr = sw.trace ? sw.trace + ((size_t)2 * pm.W * by0 + item) * kTraceSlots : nullptr; if (s_tr) { s_tr[4] = 0; s_tr[5] = 0; for (int k = 8; k < kTraceSlots; ++k) s_tr[k] = 0; } }
-#ifndef CSPM_STEP_TRACE
     {  // where the workgroup's waves sit: HW_ID (wave slot, SIMD, CU, SE) of every wave, 12 bits each, and the XCC in slot 15
       __shared__ unsigned int s_hwid[kSweepMaxWaves];
       unsigned int hwid, xcc;
@@ -841,7 +837,6 @@ __global__ __launch_bounds__(kSweepMaxWaves *kWave, kSweepMinWaves) void k_spati
         sw.trace[((size_t)2 * pm.W * by0 + item) * kTraceSlots + 15] = (long long)(((s_hwid[0] >> 13) & 7u) | ((xcc & 0xFu) << 4));
       }
     }
-#endif
 #endif
     while (k + 1 < ndiag && item >= bstart[k + 1]) ++k;  // items of one workgroup only increase
     const int ys_lo = max(by0, k - (pm.W - 1)), ys_hi = min(by1 - 1, k);
@@ -886,23 +881,8 @@ __global__ __launch_bounds__(kSweepMaxWaves *kWave, kSweepMinWaves) void k_spati
     const double(*pl)[6] = s_plane[par];
     const double *mine = s_own[par];
     if (have0 || have1) {
-      // with one candidate missing, both slots hold the existing one (the duplicate is computed once)
-      const int p0 = have0 ? 0 : 1, p1 = have1 ? 1 : 0;
-      const Cand c0{pl[p0][0], pl[p0][1], pl[p0][2], pl[p0][3], pl[p0][4], pl[p0][5]};
-      const Cand c1{pl[p1][0], pl[p1][1], pl[p1][2], pl[p1][3], pl[p1][4], pl[p1][5]};
-      // Result-preserving shortcuts (no arithmetic skipped that could change an outcome):
-      //  * both predecessors hold bitwise the same plane (very common once the sweep has passed over them): the second
-      //    evaluation would return the bits of the first and `cost1 < min(cur, cost0)` would fail;
-      //  * a predecessor holds bitwise the pixel's OWN plane: its cost here is the stored min_cost (same function, same
-      //    pixel, same plane), and `cost < min_cost` fails.  The own plane is only ever written by this workgroup -- and not
-      //    before the accept below, which is why the copy loaded before the wait is the plane.
-      const Cand own{mine[0], mine[1], mine[2], mine[3], mine[4], mine[5]};
-      const bool same01 = c0.nx == c1.nx && c0.ny == c1.ny && c0.nz == c1.nz && c0.a == c1.a && c0.b == c1.b && c0.c == c1.c;
-      const bool trust = pm.trust_cost != 0;
-      const bool own0 = trust && c0.nx == own.nx && c0.ny == own.ny && c0.nz == own.nz && c0.a == own.a && c0.b == own.b && c0.c == own.c;
-      const bool own1 = trust && c1.nx == own.nx && c1.ny == own.ny && c1.nz == own.nz && c1.a == own.a && c1.b == own.b && c1.c == own.c;
-      eval0 = have0 && !own0;
-      eval1 = have1 && !own1 && !(have0 && same01);
+      Cand c0, c1;
+      sweep_candidates(pl, mine, 1, have0, have1, pm.trust_cost != 0, c0, c1, eval0, eval1);
       SWEEP_STAMP(3);
       // eval_pixel_pair's barriers: (b) folded workgroups only, the folded level's chain sums are complete before two waves finish
       // them; (c) every level's term is in sh.lvl (single scale: every pass's chain sums are in wave 0's scratch) before wave 0 adds them.
@@ -919,9 +899,7 @@ __global__ __launch_bounds__(kSweepMaxWaves *kWave, kSweepMinWaves) void k_spati
     //    turn: they decode its item and set their level up while this runs, and meet wave 0 at barrier (a).
     if (wave == 0) {
       double best_cost = mine[6];  // the stored cost, loaded before the wait: nobody else writes it during the sweep
-      int pick = -1;
-      if (eval0 && cost0 < best_cost) { best_cost = cost0; pick = 0; }
-      if (eval1 && cost1 < best_cost) { best_cost = cost1; pick = 1; }
+      const int pick = sweep_accept(eval0, cost0, eval1, cost1, best_cost);
       SWEEP_STAMP(6);
       if (lane < kGranPerPixel) {
         const int k = lane >> 1;
@@ -1064,16 +1042,8 @@ __global__ __launch_bounds__(kSweepMaxWaves *kWave, kSweepMinWaves) void k_spati
     double cost0 = 0.0, cost1 = 0.0;
     bool eval0 = false, eval1 = false;
     if (have0 || have1) {
-      const int p0 = have0 ? 0 : 1, p1 = have1 ? 1 : 0;
-      const Cand c0{s_plane[p0][0], s_plane[p0][1], s_plane[p0][2], s_plane[p0][3], s_plane[p0][4], s_plane[p0][5]};
-      const Cand c1{s_plane[p1][0], s_plane[p1][1], s_plane[p1][2], s_plane[p1][3], s_plane[p1][4], s_plane[p1][5]};
-      const Cand own{f.nx[i], f.ny[i], f.nz[i], f.a[i], f.b[i], f.c[i]};
-      const bool same01 = c0.nx == c1.nx && c0.ny == c1.ny && c0.nz == c1.nz && c0.a == c1.a && c0.b == c1.b && c0.c == c1.c;
-      const bool trust = pm.trust_cost != 0;
-      const bool own0 = trust && c0.nx == own.nx && c0.ny == own.ny && c0.nz == own.nz && c0.a == own.a && c0.b == own.b && c0.c == own.c;
-      const bool own1 = trust && c1.nx == own.nx && c1.ny == own.ny && c1.nz == own.nz && c1.a == own.a && c1.b == own.b && c1.c == own.c;
-      eval0 = have0 && !own0;
-      eval1 = have1 && !own1 && !(have0 && same01);
+      Cand c0, c1;  // the own plane: from the field, now that the wait is over
+      sweep_candidates(s_plane, f.nx + i, f.ny - f.nx, have0, have1, pm.trust_cost != 0, c0, c1, eval0, eval1);
       FLOW_STAMP(3);
       if (eval0 && eval1) {
         eval_pixel_pair<CS, SRC>(cd, lut, sh, v, x, y, c0, c1, true, wave, lane, cost0, cost1, A);
@@ -1092,9 +1062,7 @@ __global__ __launch_bounds__(kSweepMaxWaves *kWave, kSweepMinWaves) void k_spati
     //    the successors and decide what this workgroup does next.
     if (wave == 0) {
       double best_cost = f.cost[i];
-      int pick = -1;
-      if (eval0 && cost0 < best_cost) { best_cost = cost0; pick = 0; }
-      if (eval1 && cost1 < best_cost) { best_cost = cost1; pick = 1; }
+      const int pick = sweep_accept(eval0, cost0, eval1, cost1, best_cost);
       FLOW_STAMP(6);
       const long long comp = f.ny - f.nx;  // the six components of a view's plane field are equally spaced arrays
       double fin = 0.0;  // lanes 0..11: component lane >> 1 of the final plane

@@ -339,5 +339,13 @@ __device__ __forceinline__ void store_plane(const Field &f, long long i, double 
 }
 
 struct Cand { double nx, ny, nz, a, b, c; };
+// the same plane, component by component: == on doubles, not a bit compare (a NaN component is never the same, +0 and -0 are).
+// `also` is a condition tested first: `same_plane(p, q, cond)` is the one chain `cond && p.nx == q.nx && ...`
+__device__ __forceinline__ bool same_plane(const Cand &p, const Cand &q, bool also = true) {
+  return also && p.nx == q.nx && p.ny == q.ny && p.nz == q.nz && p.a == q.a && p.b == q.b && p.c == q.c;
+}
+__device__ __forceinline__ void store_plane(const Field &f, long long i, const Cand &w, double cost) {
+  store_plane(f, i, w.nx, w.ny, w.nz, w.a, w.b, w.c, cost);
+}
 
 }  // namespace cspm

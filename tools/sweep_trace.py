@@ -1,9 +1,8 @@
-"""debug: per-item stage latencies and a per-STEP cycle budget of the persistent raster sweep (round-4 review, item 3).
+"""debug: per-item stage latencies of the persistent raster sweep (round-4 review, item 3).
 Needs the -DCSPM_SWEEP_TRACE build:  make -C crossscalepatchmatch_amd/csrc ../libcspm_sweeptrace.so
   CSPM_TRACE_LIB=crossscalepatchmatch_amd/libcspm_sweeptrace.so CSPM_SWEEP_TRACE_FILE=/tmp/t.bin python tools/sweep_trace.py [sweep 1|2|3]
-Per item (= pixel) 16 stamps: 0-7 wall clock (100 MHz) at the stages of the item; 8-15 shader clock (s_memtime) inside ONE chain step of
-the level-0 wave (second pass, middle step): step start, own element arrived, guide weight read, other-view elements arrived, both cells
-computed (colour-table round trip included), accumulated, and two stamps back to back (the cost of a stamp)."""
+Per item (= pixel) 16 slots: 0-7 wall clock (100 MHz) at the stages of the item; 8-13 unused; 14-15 where the workgroup's waves sit
+(HW_ID; the dataflow sweep: 15 = which predecessor the workgroup continued from)."""
 import os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -63,22 +62,6 @@ if (hw != 0).any():
 # the diagonal period: consecutive anti-diagonals finish this far apart
 W, H = cfg["w"], cfg["h"]
 print(f"  sweep span / diagonals = {(t[:, 7].max() - t0) / (W + H - 1):.2f} us per anti-diagonal")
-# per-step budget (shader cycles)
-s = raw[:, 8:16].astype(np.float64)
-have = (s[:, 0] > 0) & (s[:, 5] > 0)
-for label, sel in (("middle third", have & mid), ("first 2000 items (GPU nearly empty)", have & np.isin(np.arange(len(t)), order[:6000]))):
-    if sel.sum() < 10:
-        continue
-    d = np.diff(s[sel], axis=1)
-    stamp = np.median(d[:, 6])
-    print(f"\none chain step of the level-0 wave, {label}, shader cycles (n={int(sel.sum())}; a stamp itself costs {stamp:.0f}):")
-    for k, n in enumerate(["step start -> own element in registers (address arithmetic, gather round trip)", "-> guide weight (v_sad_u8, exp-table LDS round trip)",
-                           "-> other view's elements in registers (their gathers were issued with the own one)", "-> both cells (2 x sad, 2 x colour-table LDS round trip, sub/min/fma)",
-                           "-> accumulated (interpolation, select, fma)"]):
-        x = d[:, k]
-        print(f"  {n:88s} median {np.median(x):7.0f}  p10 {np.percentile(x, 10):7.0f}  p90 {np.percentile(x, 90):7.0f}   minus stamp: {np.median(x) - stamp:7.0f}")
-    tot = s[sel, 5] - s[sel, 0]
-    print(f"  {'whole step':88s} median {np.median(tot):7.0f}  p10 {np.percentile(tot, 10):7.0f}  p90 {np.percentile(tot, 90):7.0f}   minus 5 stamps: {np.median(tot) - 5 * stamp:7.0f}")
 
 # ---- the critical path through the dependency lattice, walked back from the last pixel of one view --------------------------------
 # item index = claim order (one band): diagonal k, then view, then sweep row.  Sweeps 1 and 3 run top-left -> bottom-right (inc > 0),
