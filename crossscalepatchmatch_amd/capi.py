@@ -66,6 +66,7 @@ SYMBOLS = [
     "cspm_synth_default_params", "cspm_synthesize_host", "cspm_synthesize", "cspm_synthesize_device",
     "cspm_fuse_default_params", "cspm_fuse_depth_maps", "cspm_fuse_begin", "cspm_fuse_push", "cspm_fuse_push_maps", "cspm_fuse_view_count",
     "cspm_fuse_run", "cspm_fuse_run_device", "cspm_fuse_end",
+    "cspm_reg_default_params", "cspm_fuse_register", "cspm_fuse_get_pose", "cspm_fuse_set_pose", "cspm_register_depth_maps",
     "cspm_rect_default_params", "cspm_rectify_compute", "cspm_rectify_host", "cspm_set_rectification", "cspm_get_rect_map",
     "cspm_set_images_raw", "cspm_set_images_raw_device",
 ]
@@ -133,6 +134,21 @@ class FuseView(C.Structure):
                 ("f", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3)]
 
 
+class RegParams(C.Structure):
+    """struct cspm_reg_params"""
+    _fields_ = [("iters", C.c_int), ("stride", C.c_int), ("max_dist", C.c_double), ("huber", C.c_double), ("min_cos", C.c_double),
+                ("min_pairs", C.c_int), ("pivot_rel", C.c_double)]
+
+
+class RegIter(C.Structure):
+    """struct cspm_reg_iter: one Gauss-Newton iteration of a registration"""
+    _fields_ = [("pairs", C.c_double), ("cost", C.c_double), ("rot2", C.c_double), ("trans2", C.c_double), ("status", C.c_int)]
+
+
+REG_ITER = np.dtype(dict(names=["pairs", "cost", "rot2", "trans2", "status"], formats=["<f8", "<f8", "<f8", "<f8", "<i4"], offsets=[0, 8, 16, 24, 32],
+                         itemsize=40))  # RegIter as a numpy record
+
+
 class Camera(C.Structure):
     """struct cspm_camera: K = [fx skew cx; 0 fy cy; 0 0 1] and Brown-Conrady distortion"""
     _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "skew", "k1", "k2", "p1", "p2", "k3")]
@@ -198,6 +214,7 @@ def load_library():
     mshp = C.POINTER(MeshParams)
     rgp, rpp, rcp = C.POINTER(Rig), C.POINTER(RectParams), C.POINTER(Rectification)
     fup, fuv = C.POINTER(FuseParams), C.POINTER(FuseView)
+    rgpp, rgip = C.POINTER(RegParams), C.POINTER(RegIter)
     sig = {
         "cspm_device_count": (C.c_int, []),
         "cspm_create": (C.c_int, [C.POINTER(vp), C.c_int]),
@@ -300,6 +317,11 @@ def load_library():
         "cspm_fuse_run": (C.c_int, [vp, fup, vp, C.c_size_t, up, up, u8p]),
         "cspm_fuse_run_device": (C.c_int, [vp, fup, vp, C.c_size_t, vp, vp, vp]),
         "cspm_fuse_end": (C.c_int, [vp]),
+        "cspm_reg_default_params": (C.c_int, [rgpp]),
+        "cspm_fuse_register": (C.c_int, [vp, C.c_int, C.c_ulonglong, rgpp, dp, dp, C.c_int, dp, dp, rgip]),
+        "cspm_fuse_get_pose": (C.c_int, [vp, C.c_int, dp, dp]),
+        "cspm_fuse_set_pose": (C.c_int, [vp, C.c_int, dp, dp]),
+        "cspm_register_depth_maps": (C.c_int, [C.c_int, rgpp, fuv, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong, dp, dp, rgip]),
         "cspm_rect_default_params": (C.c_int, [rpp]),
         "cspm_rectify_compute": (C.c_int, [rgp, rpp, rcp, kp]),
         "cspm_rectify_host": (C.c_int, [C.c_int, rgp, rcp, C.c_int, u8p, C.c_size_t, u8p, C.c_size_t, dp, u8p]),
@@ -876,6 +898,30 @@ class StereoContext:
     def fuse_end(self):
         self._chk(self.L.cspm_fuse_end(self.p))
 
+    # ---- depth-view registration ----
+    def fuse_register(self, src, targets, R0=None, t0=None, apply=False, out=None, **params):
+        """view `src` registered against the views of `targets` (a bit mask or a sequence of slots) by projective point-to-plane
+        Gauss-Newton (cspm_fuse_register).  R0, t0: the start pose (None = the slot's own); apply: the slot takes the result.  params:
+        iters, stride, max_dist, huber, min_cos, min_pairs, pivot_rel.  Returns dict(R (3, 3), t (3,), iters (REG_ITER records)).
+        out: a dict with preallocated R, t, iters to write into (tests poison them)."""
+        p = reg_params(**params)
+        R, t, it = _reg_outputs(p, out)
+        R0 = None if R0 is None else np.ascontiguousarray(R0, dtype=np.float64).reshape(9)
+        t0 = None if t0 is None else np.ascontiguousarray(t0, dtype=np.float64).reshape(3)
+        self._chk(self.L.cspm_fuse_register(self.p, int(src), _mask(targets), C.byref(p), _opt(_dp, R0), _opt(_dp, t0), int(bool(apply)), _dp(R), _dp(t),
+                                            it.ctypes.data_as(C.POINTER(RegIter))))
+        return dict(R=R.reshape(3, 3), t=t, iters=it[:p.iters])
+
+    def fuse_get_pose(self, slot):
+        """-> (R (3, 3), t (3,)): the camera -> world pose of a fusion view (cspm_fuse_get_pose)"""
+        R, t = np.zeros(9), np.zeros(3)
+        self._chk(self.L.cspm_fuse_get_pose(self.p, int(slot), _dp(R), _dp(t)))
+        return R.reshape(3, 3), t
+
+    def fuse_set_pose(self, slot, R, t):
+        R, t = _pose(R, t)
+        self._chk(self.L.cspm_fuse_set_pose(self.p, int(slot), _dp(R), _dp(t)))
+
     # ---- view synthesis (DESIGN.md section 20) ----
     def synthesize(self, t, source=GEOM_RAW, outputs=("bgr", "disp", "mask"), out=None, **params):
         """the scene from the camera at fraction t of the baseline (0 = view 0, 1 = view 1), rendered from the stored plane field and the
@@ -1204,6 +1250,45 @@ def fuse_depth_maps(views, w, h, cloud=True, cloud_cap=None, state=True, device=
     if S is not None:
         res["state"] = S
     return res
+
+
+def reg_params(**params):
+    """struct cspm_reg_params: cspm_reg_default_params with the given fields replaced"""
+    return _params(RegParams, "reg", "registration", params)
+
+
+def _mask(targets):
+    """a 64-bit view mask from an integer or a sequence of slots"""
+    if isinstance(targets, (int, np.integer)):
+        return C.c_ulonglong(int(targets))
+    return C.c_ulonglong(sum(1 << int(k) for k in set(targets)))
+
+
+def _reg_outputs(p, out):
+    R = (out or {}).get("R")
+    t = (out or {}).get("t")
+    it = (out or {}).get("iters")
+    return (np.zeros(9) if R is None else R, np.zeros(3) if t is None else t, np.zeros(max(p.iters, 1), REG_ITER) if it is None else it)
+
+
+def register_depth_maps(views, w, h, src, targets, device=0, out=None, **params):
+    """R alone on host maps (cspm_register_depth_maps): view `src` of `views` (dicts as for fuse_depth_maps, with
+    normals) registered against the views of `targets` (a bit mask or a sequence of indices), starting from its own pose.  Returns what
+    StereoContext.fuse_register returns."""
+    K = len(views)
+    p = reg_params(**params)
+    arr = (FuseView * max(K, 1))()
+    keep = []
+    for k, v in enumerate(views):
+        d, n, _ = _fuse_maps(v["depth"], v.get("normal"), None, w, h)
+        Rk, tk = _pose(v["R"], v["t"])
+        keep.append((d, n))
+        arr[k] = FuseView(_dp(d), _opt(_dp, n), None, 0, float(v["f"]), float(v["cx"]), float(v["cy"]), (C.c_double * 9)(*Rk), (C.c_double * 3)(*tk))
+    R, t, it = _reg_outputs(p, out)
+    _check(load_library().cspm_register_depth_maps(device, C.byref(p), arr, K, w, h, int(src), _mask(targets), _dp(R), _dp(t),
+                                                   it.ctypes.data_as(C.POINTER(RegIter))))
+    del keep
+    return dict(R=R.reshape(3, 3), t=t, iters=it[:p.iters])
 
 
 def synth_params(**params):

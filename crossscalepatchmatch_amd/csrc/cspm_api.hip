@@ -22,6 +22,7 @@
 #include "cspm_geom.h"
 #include "cspm_mesh.h"
 #include "cspm_fuse.h"
+#include "cspm_register.h"
 #include "cspm_synth.h"
 #include "cspm_rect.h"
 #include "cspm_ca.h"
@@ -240,6 +241,7 @@ struct cspm_ctx {
   uint8_t *fuse_bytes = nullptr;                         // used of all views, then S of all views
   FuseCam *fuse_cams = nullptr;                          // the camera table
   std::vector<FuseCam> fuse_cams_host;                   // ... and the host's copy of it, max_views rows
+  double *reg_mem = nullptr;                             // registration scratch (cspm_fuse_register): partials, pose row, records; allocated by the first call
   unsigned int *fuse_counts = nullptr;                   // kept pixels per workgroup of every pass, the total, the kept pixels per view
   // rectification (cspm_set_rectification): kept until the context goes or the rectification is dropped
   bool rect_on = false;
@@ -2460,6 +2462,80 @@ int fuse_run(cspm_ctx *c, const cspm_fuse_params *p, cspm_point *cloud_out, size
   return CSPM_OK;
 }
 
+// ---- depth-view registration (cspm_register.h) ---------------------------------------------------------------
+static_assert(CSPM_REG_MAX_ITERS == kRegMaxIters, "cspm.h and cspm_register.h agree on the number of iterations");
+static_assert(sizeof(RegRec) == sizeof(cspm_reg_iter) && sizeof(RegRec) == 5 * sizeof(double), "an iteration record is 40 bytes on both sides");
+const cspm_reg_params kRegDefaults = {8, 1, 0.5, 0.05, 0.0, 100, 1e-8};
+const char *reg_params_error(const cspm_reg_params *p) {
+  if (p->iters < 1 || p->iters > kRegMaxIters) return "registration: iters must be in 1 .. 64";
+  if (p->stride < 1) return "registration: stride must be at least 1";
+  if (!(p->max_dist >= 0.0)) return "registration: max_dist must be >= 0";
+  if (!(p->huber >= 0.0)) return "registration: huber must be >= 0";
+  if (!(p->min_cos >= 0.0 && p->min_cos <= 1.0)) return "registration: min_cos must be in [0, 1]";
+  if (p->min_pairs < 0) return "registration: min_pairs must be >= 0";
+  if (!(p->pivot_rel >= 0.0 && p->pivot_rel < 1.0)) return "registration: pivot_rel must be in [0, 1)";
+  return nullptr;
+}
+const char *reg_mask_error(int src, unsigned long long targets, int views) {
+  if (src < 0 || src >= views) return "registration: no such source view";
+  const unsigned long long below = views >= 64 ? ~0ull : (1ull << views) - 1ull;
+  if (targets == 0ull || (targets & ~below) || ((targets >> src) & 1ull)) return "registration: the targets must be other views that exist, at least one";
+  return nullptr;
+}
+// the checks of cspm_fuse_register on a context with views; *start = the camera the loop begins with
+int reg_check(cspm_ctx *c, int src, unsigned long long targets, const cspm_reg_params **p, const double *R0, const double *t0, FuseCam *start) {
+  if (!*p) *p = &kRegDefaults;
+  if (const char *msg = reg_params_error(*p)) return fail(c, CSPM_ERR_ARG, msg);
+  if (!c->fuse_on) return fail(c, CSPM_ERR_STATE, "fusion: cspm_fuse_begin first");
+  if (const char *msg = reg_mask_error(src, targets, c->fuse_views)) return fail(c, CSPM_ERR_ARG, msg);
+  if (!c->fuse_normals) return fail(c, CSPM_ERR_STATE, "registration: the views carry no normals");
+  *start = c->fuse_cams_host[(size_t)src];
+  if (R0) for (int i = 0; i < 9; ++i) start->R[i] = R0[i];
+  if (t0) for (int i = 0; i < 3; ++i) start->t[i] = t0[i];
+  if (const char *msg = fuse_camera_error(start->f, start->cx, start->cy, start->R, start->t)) return fail(c, CSPM_ERR_ARG, msg);
+  return CSPM_OK;
+}
+// R behind its checks, on the context's device; *start outlives the call's copies (the caller's local)
+int reg_run(cspm_ctx *c, int src, unsigned long long targets, const cspm_reg_params *p, const FuseCam *start, int apply, double *R_out, double *t_out,
+            cspm_reg_iter *iters_out) {
+  const int w = c->fuse_w, h = c->fuse_h, K = c->fuse_views;
+  const long long n = (long long)w * h;
+  const int ws = (w + p->stride - 1) / p->stride, hs = (h + p->stride - 1) / p->stride;
+  const long long samples = (long long)ws * hs;
+  const size_t nb = (size_t)((samples + kRegBlock - 1) / kRegBlock);
+  const size_t tail = sizeof(FuseCam) / sizeof(double) + (size_t)kRegMaxIters * sizeof(RegRec) / sizeof(double);
+  const size_t all = (size_t)((n + kRegBlock - 1) / kRegBlock);  // the partials of stride 1: every call fits
+  if (int rc = dalloc(c, c->mem_fuse, &c->reg_mem, tail + all * kRegSums)) return rc;
+  FuseCam *pose = reinterpret_cast<FuseCam *>(c->reg_mem);
+  RegRec *recs = reinterpret_cast<RegRec *>(c->reg_mem + sizeof(FuseCam) / sizeof(double));
+  double *part = c->reg_mem + tail;
+  const RegPar par{p->max_dist * p->max_dist, p->huber, p->min_cos, p->pivot_rel, (double)p->min_pairs, p->stride, ws, samples};
+  FuseCam result;                 // in front of the Staging: downloads write them
+  RegRec host_recs[kRegMaxIters];
+  Staging S(c);
+  S.put(pose, start, 1);
+  if (S.rc) return S.finish();
+  {
+    Timed t(c, CSPM_K_MISC, (long long)p->iters * samples * (long long)__builtin_popcountll(targets));
+    for (int it = 0; it < p->iters; ++it) {
+      hipLaunchKernelGGL(k_reg_pairs, dim3((unsigned)nb), dim3(kRegBlock), 0, c->stream, (const FuseCam *)c->fuse_cams, (const FuseCam *)pose,
+                         (const double *)c->fuse_depth, (const double *)c->fuse_normal, K, src, targets, w, h, n, par, part);
+      hipLaunchKernelGGL(k_reg_solve, dim3(1), dim3(kRegBlock), 0, c->stream, (const double *)part, (int)nb, par, pose, recs + it);
+    }
+  }
+  S.down(&result, pose, 1);
+  S.down(host_recs, recs, (size_t)p->iters);
+  if (S.finish("registration kernels failed")) return S.rc;
+  if (apply) {
+    c->fuse_cams_host[(size_t)src] = result;
+    HIPCHK(c, hipMemcpyAsync(c->fuse_cams + src, &c->fuse_cams_host[(size_t)src], sizeof(FuseCam), hipMemcpyHostToDevice, c->stream));
+  }
+  if (R_out) for (int i = 0; i < 9; ++i) R_out[i] = result.R[i];
+  if (t_out) for (int i = 0; i < 3; ++i) t_out[i] = result.t[i];
+  if (iters_out) std::memcpy(iters_out, host_recs, sizeof(RegRec) * (size_t)p->iters);
+  return CSPM_OK;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -3766,6 +3842,74 @@ int cspm_fuse_depth_maps(int device, const cspm_fuse_params *p, const cspm_fuse_
   if (!rc) rc = fuse_run(S.c, p, cloud_out, cloud_cap, count_out, view_counts_out, state_out);
   S.latch(rc);
   return S.finish("fusion failed");
+}
+
+// R: a fusion view registered against other fusion views, and the one-shot form on caller maps
+int cspm_reg_default_params(cspm_reg_params *p) {
+  if (!p) return CSPM_ERR_ARG;
+  *p = kRegDefaults;
+  return CSPM_OK;
+}
+
+int cspm_fuse_register(cspm_ctx *c, int src, unsigned long long targets, const cspm_reg_params *p, const double *R0, const double *t0, int apply,
+                       double *R_out, double *t_out, cspm_reg_iter *iters_out) {
+  if (!c) return CSPM_ERR_ARG;
+  FuseCam start;
+  if (int rc = reg_check(c, src, targets, &p, R0, t0, &start)) return rc;
+  ON_DEVICE(c);
+  return reg_run(c, src, targets, p, &start, apply, R_out, t_out, iters_out);
+}
+
+int cspm_fuse_get_pose(cspm_ctx *c, int slot, double *R_out, double *t_out) {
+  if (!c) return CSPM_ERR_ARG;
+  if (!c->fuse_on) return fail(c, CSPM_ERR_STATE, "fusion: cspm_fuse_begin first");
+  if (slot < 0 || slot >= c->fuse_views) return fail(c, CSPM_ERR_ARG, "fusion: no such view");
+  const FuseCam &cam = c->fuse_cams_host[(size_t)slot];
+  if (R_out) for (int i = 0; i < 9; ++i) R_out[i] = cam.R[i];
+  if (t_out) for (int i = 0; i < 3; ++i) t_out[i] = cam.t[i];
+  return CSPM_OK;
+}
+
+int cspm_fuse_set_pose(cspm_ctx *c, int slot, const double *R, const double *t) {
+  if (!c) return CSPM_ERR_ARG;
+  if (!c->fuse_on) return fail(c, CSPM_ERR_STATE, "fusion: cspm_fuse_begin first");
+  if (slot < 0 || slot >= c->fuse_views) return fail(c, CSPM_ERR_ARG, "fusion: no such view");
+  FuseCam &cam = c->fuse_cams_host[(size_t)slot];  // lives as long as the slots: the copy may read it later
+  if (const char *msg = fuse_camera_error(cam.f, cam.cx, cam.cy, R, t)) return fail(c, CSPM_ERR_ARG, msg);
+  ON_DEVICE(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier copy may still read the row
+  for (int i = 0; i < 9; ++i) cam.R[i] = R[i];
+  for (int i = 0; i < 3; ++i) cam.t[i] = t[i];
+  HIPCHK(c, hipMemcpyAsync(c->fuse_cams + slot, &cam, sizeof cam, hipMemcpyHostToDevice, c->stream));
+  return CSPM_OK;
+}
+
+int cspm_register_depth_maps(int device, const cspm_reg_params *p, const cspm_fuse_view *views, int n_views, int w, int h, int src,
+                             unsigned long long targets, double *R_out, double *t_out, cspm_reg_iter *iters_out) {
+  if (!p) p = &kRegDefaults;
+  if (const char *msg = reg_params_error(p)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (n_views < 1 || n_views > kFuseMaxViews) return fail(nullptr, CSPM_ERR_ARG, "fusion: the number of views must be in 1 .. 64");
+  if (!views) return fail(nullptr, CSPM_ERR_ARG, "fusion: no views");
+  if (const char *msg = fuse_size_error(w, h)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (const char *msg = reg_mask_error(src, targets, n_views)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  for (int k = 0; k < n_views; ++k) {
+    const cspm_fuse_view &v = views[k];
+    if (const char *msg = fuse_camera_error(v.f, v.cx, v.cy, v.R, v.t)) return fail(nullptr, CSPM_ERR_ARG, msg);
+    if (const char *msg = fuse_maps_error(v.depth, v.bgr, v.bgr_stride, w)) return fail(nullptr, CSPM_ERR_ARG, msg);
+    if (!v.normal) return fail(nullptr, CSPM_ERR_ARG, "registration: the views carry no normals");
+  }
+  FuseCam start;  // in front of the OneShot: an upload reads it
+  OneShot S(device);
+  if (S.rc) return S.finish();
+  int rc = fuse_begin(S.c, w, h, n_views);
+  for (int k = 0; k < n_views && !rc; ++k) {
+    const cspm_fuse_view &v = views[k];
+    rc = fuse_push_maps(S.c, v.depth, v.normal, nullptr, 0, v.f, v.cx, v.cy, v.R, v.t);  // R reads no colours
+  }
+  if (!rc) rc = reg_check(S.c, src, targets, &p, nullptr, nullptr, &start);
+  if (!rc) rc = reg_run(S.c, src, targets, p, &start, 0, R_out, t_out, iters_out);
+  S.latch(rc);
+  return S.finish("registration failed");
 }
 
 // N alone on caller maps: the launch cspm_synthesize enqueues.  Arguments first, then the device.

@@ -37,9 +37,46 @@ class DepthFusion {
       for (int y = 0; y < hei; ++y) std::copy(bgr + (size_t)y * bgr_stride, bgr + (size_t)y * bgr_stride + 3 * (size_t)wid, v.bgr.begin() + 3 * (size_t)wid * y);
     }
     v.f = calib.f; v.cx = calib.cx + (double)view * calib.doffs; v.cy = calib.cy;
+    v.view = view; v.baseline = calib.baseline;
     for (int i = 0; i < 9; ++i) v.R[i] = pose.R[i];
     for (int i = 0; i < 3; ++i) v.t[i] = view == 1 ? pose.t[i] + pose.R[3 * i] * calib.baseline : pose.t[i];
     v.set = true;
+  }
+
+  // The poses of the pairs refined in list order by cspm_register_depth_maps (include/cspm.h "depth-view registration", DESIGN.md section
+  // 26); per_pair = 1 (left views only) or 2 (slot 2 i + 1 is pair i's right view).  Pair 0 keeps its pose.  Pair i's left view starts from
+  // its own pose, or with `chain` from pair i - 1's refined pose, and is registered against the left views of the `window` pairs before
+  // it, which go into the call in list order with the source behind them; its right view follows by the baseline.  records: per pair the
+  // iterations of its registration (none for pair 0).  Throws like Fuse.
+  void Register(int device, const cspm_reg_params &params, int window, int per_pair, bool chain, std::vector<std::vector<cspm_reg_iter> > *records) {
+    const size_t pairs = views_.size() / (size_t)per_pair;
+    for (size_t k = 0; k < views_.size(); ++k) {
+      if (!views_[k].set) throw std::runtime_error("DepthFusion::Register: a view is missing");
+      if (views_[k].wid != views_[0].wid || views_[k].hei != views_[0].hei) throw std::runtime_error("DepthFusion::Register: the views are not of one size");
+    }
+    if (records) records->assign(pairs, std::vector<cspm_reg_iter>());
+    for (size_t i = 1; i < pairs; ++i) {
+      View &src = views_[i * per_pair];
+      if (chain) SetLeftPose(i, per_pair, views_[(i - 1) * per_pair].R, views_[(i - 1) * per_pair].t);
+      const size_t first = i > (size_t)window ? i - (size_t)window : 0;
+      std::vector<cspm_fuse_view> arr;
+      for (size_t j = first; j <= i; ++j) arr.push_back(AbiView(views_[j * per_pair]));
+      const int s = (int)arr.size() - 1;
+      double R[9], t[3];
+      std::vector<cspm_reg_iter> it((size_t)params.iters);
+      if (cspm_register_depth_maps(device, &params, arr.data(), (int)arr.size(), src.wid, src.hei, s, (1ull << s) - 1ull, R, t, it.data()) != CSPM_OK)
+        throw std::runtime_error(std::string("cspm_register_depth_maps: ") + cspm_last_error(NULL));
+      SetLeftPose(i, per_pair, R, t);
+      if (records) (*records)[i] = it;
+    }
+  }
+  // the camera -> world pose of pair i's left view
+  CameraPose LeftPose(size_t i, int per_pair) const {
+    const View &v = views_[i * per_pair];
+    CameraPose p;
+    for (int k = 0; k < 9; ++k) p.R[k] = v.R[k];
+    for (int k = 0; k < 3; ++k) p.t[k] = v.t[k];
+    return p;
   }
 
   // F over the slots in their order.  Returns the number of kept pixels; cloud: the records in (slot, raster) order; view_counts: the
@@ -51,14 +88,7 @@ class DepthFusion {
       const View &v = views_[k];
       if (!v.set) throw std::runtime_error("DepthFusion::Fuse: a view is missing");
       if (v.wid != views_[0].wid || v.hei != views_[0].hei) throw std::runtime_error("DepthFusion::Fuse: the views are not of one size");
-      cspm_fuse_view &a = arr[k];
-      a.depth = v.depth.data();
-      a.normal = v.normal.data();
-      a.bgr = v.bgr.empty() ? NULL : v.bgr.data();
-      a.bgr_stride = 3 * (size_t)v.wid;
-      a.f = v.f; a.cx = v.cx; a.cy = v.cy;
-      for (int i = 0; i < 9; ++i) a.R[i] = v.R[i];
-      for (int i = 0; i < 3; ++i) a.t[i] = v.t[i];
+      arr[k] = AbiView(v);
     }
     const int w = views_[0].wid, h = views_[0].hei;
     unsigned int count = 0;
@@ -75,9 +105,33 @@ class DepthFusion {
   }
 
  private:
+  struct View;
+  static cspm_fuse_view AbiView(const View &v) {
+    cspm_fuse_view a;
+    a.depth = v.depth.data();
+    a.normal = v.normal.data();
+    a.bgr = v.bgr.empty() ? NULL : v.bgr.data();
+    a.bgr_stride = 3 * (size_t)v.wid;
+    a.f = v.f; a.cx = v.cx; a.cy = v.cy;
+    for (int i = 0; i < 9; ++i) a.R[i] = v.R[i];
+    for (int i = 0; i < 3; ++i) a.t[i] = v.t[i];
+    return a;
+  }
+  // pair i's left view takes (R, t); its right view, if there is one, R and t + R (baseline, 0, 0) as in SetPairView
+  void SetLeftPose(size_t i, int per_pair, const double *R, const double *t) {
+    for (int v = 0; v < per_pair; ++v) {
+      View &d = views_[i * per_pair + v];
+      double Rn[9], tn[3];
+      for (int k = 0; k < 9; ++k) Rn[k] = R[k];
+      for (int k = 0; k < 3; ++k) tn[k] = d.view == 1 ? t[k] + R[3 * k] * d.baseline : t[k];
+      for (int k = 0; k < 9; ++k) d.R[k] = Rn[k];
+      for (int k = 0; k < 3; ++k) d.t[k] = tn[k];
+    }
+  }
   struct View {
     bool set = false;
-    int wid = 0, hei = 0;
+    int wid = 0, hei = 0, view = 0;
+    double baseline = 0;
     std::vector<double> depth, normal;
     std::vector<uint8_t> bgr;
     double f = 0, cx = 0, cy = 0, R[9] = {0}, t[3] = {0};

@@ -13,7 +13,9 @@
 // --rig --rect_f --rect_w --rect_h --l_rect_file --r_rect_file (the inputs are RAW photographs of a calibrated rig, undistorted and
 // row-aligned on the device before matching; include/cspm.h "rectification") --fuse_poses --fuse_ply --fuse_right --fuse_source
 // --fuse_max_reproj --fuse_max_rel_depth --fuse_min_cos --fuse_min_views --fuse_no_suppress (with --batch_list and --calib or --rig: the
-// depth maps of all pairs of the list fused into one point cloud in world coordinates; include/cspm.h "depth-map fusion").
+// depth maps of all pairs of the list fused into one point cloud in world coordinates; include/cspm.h "depth-map fusion") --fuse_register --fuse_register_window
+// --fuse_poses_out --fuse_reg_iters --fuse_reg_stride --fuse_reg_max_dist --fuse_reg_huber (the poses of that fusion refined, or found
+// without --fuse_poses, by registering the views against each other; include/cspm.h "depth-view registration").
 #include "../../include/cspm.h"
 #include "commfunc.h"
 #include "cs_patchmatch.h"
@@ -152,6 +154,15 @@ DEFINE_double(fuse_max_reproj, 2.0, "with --fuse_poses: the forward-backward rep
 DEFINE_double(fuse_max_rel_depth, 0.01, "with --fuse_poses: the relative depth difference a confirming view may have");
 DEFINE_double(fuse_min_cos, 0.0, "with --fuse_poses: the least cosine between the normals of a pixel and of a confirming view (0 = no test)");
 DEFINE_int32(fuse_min_views, 2, "with --fuse_poses: a pixel is kept when at least this many other views confirm it");
+DEFINE_bool(fuse_register, false, "with --batch_list, --fuse_ply and --calib or --rig: before the fusion the views are registered in list order on the device "
+                                  "(include/cspm.h \"depth-view registration\"): view 0 keeps its pose (the identity without --fuse_poses), view i starts from "
+                                  "the file's pose or, without --fuse_poses, from view i - 1's refined pose");
+DEFINE_int32(fuse_register_window, 3, "with --fuse_register: a view is registered against this many left views before it");
+DEFINE_string(fuse_poses_out, "", "with --fuse_register: the refined poses, in the format of --fuse_poses");
+DEFINE_int32(fuse_reg_iters, 8, "with --fuse_register: Gauss-Newton iterations per view, 1 .. 64");
+DEFINE_int32(fuse_reg_stride, 1, "with --fuse_register: every n-th pixel of a view in x and y is a sample");
+DEFINE_double(fuse_reg_max_dist, 0.5, "with --fuse_register: the largest distance between a point and its associated point, in world units");
+DEFINE_double(fuse_reg_huber, 0.05, "with --fuse_register: residuals beyond it are down-weighted, in world units (0 = plain least squares)");
 DEFINE_bool(fuse_no_suppress, false, "with --fuse_poses: emit a surface from every view that sees it, not only from the first");
 DEFINE_string(batch_list, "", "text file, one stereo pair per line: l_img r_img l_dis r_dis [l_pfm r_pfm [synth_png [synth_pfm]]] (the last two with "
                               "--synth_t, and then `-` skips an optional column); all pairs run with the "
@@ -537,6 +548,38 @@ int run_batch(const std::vector<BatchJob> &jobs, int skipped, int bad_lines) {
     try {
       const cspm_fuse_params fp = {FLAGS_fuse_max_reproj, FLAGS_fuse_max_rel_depth, FLAGS_fuse_min_cos, FLAGS_fuse_min_views, FLAGS_fuse_no_suppress ? 0 : 1};
       std::vector<cspm_point> cloud;
+      if (FLAGS_fuse_register) {
+        cspm_reg_params rp;
+        cspm_reg_default_params(&rp);
+        rp.iters = FLAGS_fuse_reg_iters; rp.stride = FLAGS_fuse_reg_stride; rp.max_dist = FLAGS_fuse_reg_max_dist; rp.huber = FLAGS_fuse_reg_huber;
+        const int per_pair = FLAGS_fuse_right ? 2 : 1;
+        const size_t pairs = g_fusion->size() / per_pair;
+        std::vector<std::vector<cspm_reg_iter> > recs;
+        const double r0 = static_cast<double>(getTickCount());
+        g_fusion->Register(devices[0], rp, FLAGS_fuse_register_window, per_pair, FLAGS_fuse_poses.empty(), &recs);
+        if (!FLAGS_quiet) {
+          for (size_t i = 1; i < pairs; ++i) {
+            int taken = 0;
+            for (size_t k = 0; k < recs[i].size(); ++k) taken += recs[i][k].status == 0;
+            cout << "Registration, pair " << i << ": " << taken << " of " << recs[i].size() << " steps taken, " << recs[i].back().pairs << " pairs, cost "
+                 << recs[i].back().cost << "\n";
+          }
+          cout << "Registration: " << pairs << " pairs, " << (static_cast<double>(getTickCount()) - r0) / getTickFrequency() * 1e3 << " ms\n";
+        }
+        if (!FLAGS_fuse_poses_out.empty()) {
+          FILE *fp_out = fopen(FLAGS_fuse_poses_out.c_str(), "w");
+          if (!fp_out) {
+            cout << "Error: can not write " << FLAGS_fuse_poses_out << "\n";
+            return EXIT_FAILURE;
+          }
+          for (size_t i = 0; i < pairs; ++i) {
+            const CameraPose q = g_fusion->LeftPose(i, per_pair);
+            for (int r = 0; r < 3; ++r)
+              fprintf(fp_out, "%.17g %.17g %.17g %.17g%s", q.R[3 * r], q.R[3 * r + 1], q.R[3 * r + 2], q.t[r], r == 2 ? "\n" : "  ");
+          }
+          fclose(fp_out);
+        }
+      }
       const double f0 = static_cast<double>(getTickCount());
       const size_t count = g_fusion->Fuse(devices[0], fp, &cloud, NULL);
       if (!FLAGS_quiet)
@@ -683,13 +726,28 @@ int run() {
     cout << "Error: --l_ply / --r_ply / --l_depth_pfm / --r_depth_pfm / --l_mesh_ply / --r_mesh_ply need --calib or --rig\n";
     return EXIT_FAILURE;
   }
-  const bool fusion = !FLAGS_fuse_poses.empty() || !FLAGS_fuse_ply.empty();
+  if (!FLAGS_fuse_register && !FLAGS_fuse_poses_out.empty()) {
+    cout << "Error: --fuse_poses_out writes the poses of --fuse_register\n";
+    return EXIT_FAILURE;
+  }
+  const bool fusion = !FLAGS_fuse_poses.empty() || !FLAGS_fuse_ply.empty() || FLAGS_fuse_register;
   if ((geom_out || (!FLAGS_calib.empty() && !fusion)) && !FLAGS_batch_list.empty()) {
     cout << "Error: --calib and the point-cloud, depth and mesh outputs belong to one pair: not with --batch_list\n";
     return EXIT_FAILURE;
   }
   if (fusion) {  // checked before anything opens a device
-    if (FLAGS_fuse_poses.empty() || FLAGS_fuse_ply.empty() || FLAGS_batch_list.empty() || (FLAGS_calib.empty() && FLAGS_rig.empty())) {
+    if (FLAGS_fuse_register) {
+      if (FLAGS_fuse_ply.empty() || FLAGS_batch_list.empty() || (FLAGS_calib.empty() && FLAGS_rig.empty())) {
+        cout << "Error: --fuse_register needs --fuse_ply, --batch_list and --calib or --rig\n";
+        return EXIT_FAILURE;
+      }
+      if (FLAGS_fuse_reg_iters < 1 || FLAGS_fuse_reg_iters > CSPM_REG_MAX_ITERS || FLAGS_fuse_reg_stride < 1 || !(FLAGS_fuse_reg_max_dist >= 0.0) ||
+          !(FLAGS_fuse_reg_huber >= 0.0) || FLAGS_fuse_register_window < 1 || FLAGS_fuse_register_window > CSPM_FUSE_MAX_VIEWS - 1) {
+        cout << "Error: --fuse_reg_iters must be 1 .. " << CSPM_REG_MAX_ITERS << ", --fuse_reg_stride >= 1, --fuse_reg_max_dist and --fuse_reg_huber >= 0 and "
+             << "--fuse_register_window 1 .. " << CSPM_FUSE_MAX_VIEWS - 1 << "\n";
+        return EXIT_FAILURE;
+      }
+    } else if (FLAGS_fuse_poses.empty() || FLAGS_fuse_ply.empty() || FLAGS_batch_list.empty() || (FLAGS_calib.empty() && FLAGS_rig.empty())) {
       cout << "Error: the fusion needs --fuse_poses, --fuse_ply, --batch_list and --calib or --rig\n";
       return EXIT_FAILURE;
     }
@@ -711,7 +769,7 @@ int run() {
       return EXIT_FAILURE;
     }
     int bad_line = 0;
-    if (!ReadPoseFile(FLAGS_fuse_poses, &g_poses, &bad_line)) {
+    if (!FLAGS_fuse_poses.empty() && !ReadPoseFile(FLAGS_fuse_poses, &g_poses, &bad_line)) {
       cout << "Error: can not read " << FLAGS_fuse_poses << " as a poses file (12 numbers per line, the row-major [R | t])";
       if (bad_line) cout << ": line " << bad_line;
       cout << "\n";
@@ -828,6 +886,10 @@ int run() {
   }
   if (fusion) {  // before any pair runs
     const size_t views = jobs.size() * (FLAGS_fuse_right ? 2 : 1);
+    if (FLAGS_fuse_poses.empty()) {  // --fuse_register alone: every pair starts as the identity
+      const CameraPose eye = {{1, 0, 0, 0, 1, 0, 0, 0, 1}, {0, 0, 0}};
+      g_poses.assign(jobs.size(), eye);
+    }
     if (bad_lines != 0 || g_poses.size() != jobs.size()) {
       cout << "Error: " << FLAGS_fuse_poses << " holds " << g_poses.size() << " poses, the batch list " << jobs.size() << " pairs"
            << (bad_lines ? " and lines that are no pairs" : "") << "\n";

@@ -878,6 +878,76 @@ int cspm_fuse_run_device(cspm_ctx *ctx, const cspm_fuse_params *params, void *d_
 /* waits for the stream and frees the views.  CSPM_ERR_STATE without a begin. */
 int cspm_fuse_end(cspm_ctx *ctx);
 
+/* ---- depth-view registration (an addition): the poses the fusion needs, from the fusion views themselves ---------------
+ * F needs every camera -> world pose to within its gates.  Each fusion view holds a metric depth map and an exact per-pixel normal, which is
+ * all that projective point-to-plane registration (the tracking step of KinectFusion) needs: a Gauss-Newton loop that stays on the device.
+ * The specification R.  Every product, sum, quotient, floor and fabs is one IEEE f64 operation in the association written here, nothing
+ * contracted, no reciprocal, no trigonometry.  back, world, cam, proj and rot are F's.
+ * Inputs: the views of the fusion pool (all with normals), a source slot s, a 64-bit target mask T (bit k = view k is a target; bit s clear,
+ * at least one bit set, every set bit below the view count), a start pose (R, t) of the source, cspm_reg_params { iters, stride, max_dist,
+ * huber, min_cos, min_pairs, pivot_rel }, defaults 8, 1, 0.5, 0.05, 0.0, 100, 1e-8: chosen, not tuned.  The host computes once
+ * md2 = max_dist * max_dist.  Camera s below is (f_s, cx_s, cy_s) of the slot with the CURRENT (R, t).
+ * Samples: source pixels (x, y) = (i*stride, j*stride), i < ws = ceil(w / stride), j < hs = ceil(h / stride); flat index q = j*ws + i.
+ * One iteration, sample q, acc[0 .. 28] = 0.0:
+ *   Z = depth_s[y][x]; nothing more unless Z is finite and > 0.0.  P = world(s, back(s, x, y, Z)); L[i] = P[i] - t[i].
+ *   For each k in T, ascending:
+ *     Q = cam(k, P); proj, the rounding fx, fy, the bounds test on the doubles and Zk = depth_k[fy][fx] finite and > 0.0: F's step 4.
+ *     Pk = world(k, back(k, fx, fy, Zk)).  N = rot(k, n_k[fy*w + fx]); continue unless its three components are finite.
+ *     d = Pk - P (three subtractions); continue unless (d0*d0 + d1*d1) + d2*d2 <= md2 (a NaN fails).
+ *     When min_cos > 0.0: Ns = rot(s, n_s[y*w + x]); continue unless (Ns0*N0 + Ns1*N1) + Ns2*N2 >= min_cos (a NaN fails).
+ *     r = (N0*d0 + N1*d1) + N2*d2.   J = (L1*N2 - L2*N1, L2*N0 - L0*N2, L0*N1 - L1*N0, N0, N1, N2).
+ *     wt = 1.0 when huber == 0.0 or fabs(r) <= huber, else huber / fabs(r).   g_a = wt * J_a.
+ *     acc[0 .. 20] += g_a * J_b for a <= b in row-major order; acc[21 + a] += g_a * r; acc[27] += (wt * r) * r; acc[28] += 1.0:
+ *     each update one product and one addition into acc.
+ * Reduction (the order is part of R): block B holds the samples [256 B, 256 B + 256), a missing sample is all 0.0.  Within a block, for
+ * s = 128, 64, .., 1: v[i] = v[i] + v[i + s] for i < s.  Across blocks, lane j of 256 computes u_j = 0.0, then u_j = u_j + part[B] for
+ * B = j, j + 256, .. ascending; the same tree over u gives A (21 entries), b (6), cost and pairs.
+ * Solve: status 1 when pairs < (double)min_pairs.  Else LDL^T without pivoting, for j = 0 .. 5: D_j = A_jj - sum_{k<j} (L_jk*L_jk)*D_k, one
+ * term subtracted at a time, k ascending; status 2 unless D_j > pivot_rel * A_jj (a NaN fails); L_ij = (A_ij - sum_{k<j} (L_ik*L_jk)*D_k) / D_j.
+ * y_i = b_i - sum_{k<i} L_ik*y_k; z_i = y_i / D_i; xi_i = z_i - sum_{k>i} L_ki*xi_k for i = 5 .. 0; k ascending throughout.  Status 3 when
+ * a component of xi is not finite.  xi = (om, v).
+ * Update (status 0 only; otherwise the pose stays and the loop goes on): a = 0.5 * om; s = (a0*a0 + a1*a1) + a2*a2; p = 1.0 - s;
+ * q = 1.0 + s; the Cayley map E = ((1 - s) I + 2 a a^T + 2 [a]x) / (1 + s), exactly orthogonal in exact arithmetic:
+ *     E_ii = (p + 2.0*(a_i*a_i)) / q
+ *     E_01 = (2.0*(a0*a1) - 2.0*a2) / q   E_02 = (2.0*(a0*a2) + 2.0*a1) / q   E_12 = (2.0*(a1*a2) - 2.0*a0) / q
+ *     E_10 = (2.0*(a0*a1) + 2.0*a2) / q   E_20 = (2.0*(a0*a2) - 2.0*a1) / q   E_21 = (2.0*(a1*a2) + 2.0*a0) / q
+ * R_ij <- (E_i0*R_0j + E_i1*R_1j) + E_i2*R_2j;  t_i <- t_i + v_i.
+ * Outputs: the final R, t and one cspm_reg_iter per iteration: pairs, cost, rot2 = (om0*om0 + om1*om1) + om2*om2, trans2 likewise of v
+ * (both 0.0 on a refused step), status.
+ * CSPM_ERR_ARG: a bad slot or mask; iters or stride < 1; iters > CSPM_REG_MAX_ITERS; a NaN or negative max_dist or huber; a min_cos outside
+ * [0, 1]; a pivot_rel outside [0, 1); a negative min_pairs; a start pose a push would refuse.  CSPM_ERR_STATE: no begin, or views without
+ * normals.  Every output stays untouched on an error. */
+#define CSPM_REG_MAX_ITERS 64
+typedef struct cspm_reg_params {
+  int iters;        /* Gauss-Newton iterations, all of them run: 1 .. CSPM_REG_MAX_ITERS */
+  int stride;       /* every stride-th source pixel in x and y */
+  double max_dist;  /* world units: the largest distance between a source point and its associated target point */
+  double huber;     /* world units: residuals beyond it are down-weighted; 0 = plain least squares */
+  double min_cos;   /* the least cosine between the source's and the target's world normal; 0 = no normal test */
+  int min_pairs;    /* fewer pairs refuse the step (status 1) */
+  double pivot_rel; /* a pivot D_j <= pivot_rel * A_jj refuses the step (status 2): the geometry does not fix all six freedoms */
+} cspm_reg_params;
+typedef struct cspm_reg_iter {
+  double pairs, cost, rot2, trans2;
+  int status; /* 0 = the step was taken; 1 = too few pairs; 2 = a pivot failed; 3 = a non-finite step */
+} cspm_reg_iter;
+int cspm_reg_default_params(cspm_reg_params *p);
+/* R for slot src against the slots of `targets`.  Synchronous: iters x (k_reg_pairs, k_reg_solve) go on the ctx stream back to back, the host
+ * waits once.  R0 / t0 NULL = the slot's own rotation / translation.  With apply != 0 the slot's row of the device camera table and its host
+ * copy take the result.  R_out (9), t_out (3), iters_out (params->iters records) may each be NULL.  Scratch (the partial sums, the pose row,
+ * the records) is allocated in the fusion pool by the first call.  Timed as one CSPM_K_MISC bracket with iters * ws * hs * |T| evaluations. */
+int cspm_fuse_register(cspm_ctx *ctx, int src, unsigned long long targets, const cspm_reg_params *params, const double *R0, const double *t0,
+                       int apply, double *R_out, double *t_out, cspm_reg_iter *iters_out);
+/* the pose of a slot (the host's copy of the camera table); set_pose makes the pose checks of a push.  CSPM_ERR_ARG for a bad slot or pose,
+ * CSPM_ERR_STATE without a begin. */
+int cspm_fuse_get_pose(cspm_ctx *ctx, int slot, double *R_out, double *t_out);
+int cspm_fuse_set_pose(cspm_ctx *ctx, int slot, const double *R, const double *t);
+/* R alone on caller memory with a temporary context: begin, one cspm_fuse_push_maps per view, one registration of view src from its own
+ * pose.  Every argument is checked before a device is opened: the list above (views without normals are CSPM_ERR_ARG here) and what
+ * cspm_fuse_depth_maps checks in views, n_views, w, h. */
+int cspm_register_depth_maps(int device, const cspm_reg_params *params, const cspm_fuse_view *views, int n_views, int w, int h, int src,
+                             unsigned long long targets, double *R_out, double *t_out, cspm_reg_iter *iters_out);
+
 /* ---- rectification (an addition): a calibrated RAW pair undistorted and row-aligned on the device ----------------------
  * Every entry above that takes images assumes an undistorted, row-aligned pair, and cspm_reproject a cspm_calib of that pair.  This section
  * produces both from a rig description: two pinhole cameras with Brown-Conrady distortion and the pose of camera 1 in camera 0's frame.
