@@ -67,6 +67,7 @@ SYMBOLS = [
     "cspm_fuse_default_params", "cspm_fuse_depth_maps", "cspm_fuse_begin", "cspm_fuse_push", "cspm_fuse_push_maps", "cspm_fuse_view_count",
     "cspm_fuse_run", "cspm_fuse_run_device", "cspm_fuse_end",
     "cspm_reg_default_params", "cspm_fuse_register", "cspm_fuse_get_pose", "cspm_fuse_set_pose", "cspm_register_depth_maps",
+    "cspm_carry_default_params", "cspm_carry_relative_pose", "cspm_carry_plane_field", "cspm_carry_planes",
     "cspm_rect_default_params", "cspm_rectify_compute", "cspm_rectify_host", "cspm_set_rectification", "cspm_get_rect_map",
     "cspm_set_images_raw", "cspm_set_images_raw_device",
 ]
@@ -149,6 +150,11 @@ REG_ITER = np.dtype(dict(names=["pairs", "cost", "rot2", "trans2", "status"], fo
                          itemsize=40))  # RegIter as a numpy record
 
 
+class CarryParams(C.Structure):
+    """struct cspm_carry_params"""
+    _fields_ = [("fill", C.c_int)]
+
+
 class Camera(C.Structure):
     """struct cspm_camera: K = [fx skew cx; 0 fy cy; 0 0 1] and Brown-Conrady distortion"""
     _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "skew", "k1", "k2", "p1", "p2", "k3")]
@@ -215,6 +221,7 @@ def load_library():
     rgp, rpp, rcp = C.POINTER(Rig), C.POINTER(RectParams), C.POINTER(Rectification)
     fup, fuv = C.POINTER(FuseParams), C.POINTER(FuseView)
     rgpp, rgip = C.POINTER(RegParams), C.POINTER(RegIter)
+    cyp = C.POINTER(CarryParams)
     sig = {
         "cspm_device_count": (C.c_int, []),
         "cspm_create": (C.c_int, [C.POINTER(vp), C.c_int]),
@@ -322,6 +329,11 @@ def load_library():
         "cspm_fuse_get_pose": (C.c_int, [vp, C.c_int, dp, dp]),
         "cspm_fuse_set_pose": (C.c_int, [vp, C.c_int, dp, dp]),
         "cspm_register_depth_maps": (C.c_int, [C.c_int, rgpp, fuv, C.c_int, C.c_int, C.c_int, C.c_int, C.c_ulonglong, dp, dp, rgip]),
+        "cspm_carry_default_params": (C.c_int, [cyp]),
+        "cspm_carry_relative_pose": (C.c_int, [dp, dp, dp, dp, dp, dp]),
+        "cspm_carry_plane_field": (C.c_int, [C.c_int, dp, u8p, kp, C.c_int, C.c_int, C.c_int, kp, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, cyp, dp, u8p,
+                                             i32p]),
+        "cspm_carry_planes": (C.c_int, [vp, vp, kp, kp, dp, dp, cyp, C.c_int]),
         "cspm_rect_default_params": (C.c_int, [rpp]),
         "cspm_rectify_compute": (C.c_int, [rgp, rpp, rcp, kp]),
         "cspm_rectify_host": (C.c_int, [C.c_int, rgp, rcp, C.c_int, u8p, C.c_size_t, u8p, C.c_size_t, dp, u8p]),
@@ -636,6 +648,14 @@ class StereoContext:
     def merge_planes_from(self, src):
         """src's plane field offered to both views of this context: a pixel takes src's plane where it costs less (asynchronous)"""
         self._chk(self.L.cspm_merge_planes(self.p, src.p))
+
+    def carry_planes_from(self, src, src_calib, dst_calib, R, t, merge=True, **params):
+        """src's plane field carried across the motion X_dst = R X_src + t between the two view-0 cameras into both views of this context
+        (cspm_carry_planes, DESIGN.md section 27; asynchronous).  merge: the carried planes are candidates under merge_planes' rule;
+        otherwise they replace the field where there is one.  params: fill."""
+        ks, kt, p = calib_struct(src_calib), calib_struct(dst_calib), carry_params(**params)
+        R, t = _pose(R, t)
+        self._chk(self.L.cspm_carry_planes(self.p, src.p, C.byref(ks), C.byref(kt), _dp(R), _dp(t), C.byref(p), int(bool(merge))))
 
     def merge_planes(self, view, field, mask=None):
         """field (h, w, 6) offered to one view; mask (h, w), 0 = no candidate, None = every pixel.  Non-finite planes are no candidates."""
@@ -1289,6 +1309,48 @@ def register_depth_maps(views, w, h, src, targets, device=0, out=None, **params)
                                                    it.ctypes.data_as(C.POINTER(RegIter))))
     del keep
     return dict(R=R.reshape(3, 3), t=t, iters=it[:p.iters])
+
+
+def carry_params(**params):
+    """struct cspm_carry_params: cspm_carry_default_params with the given fields replaced"""
+    return _params(CarryParams, "carry", "carry", params)
+
+
+def carry_relative_pose(Rs, ts, Rt, tt):
+    """two camera -> world poses into the motion X_t = R X_s + t between the cameras (cspm_carry_relative_pose): returns (R (3, 3), t)"""
+    Rs, ts = _pose(Rs, ts)
+    Rt, tt = _pose(Rt, tt)
+    R, t = np.zeros(9), np.zeros(3)
+    _check(load_library().cspm_carry_relative_pose(_dp(Rs), _dp(ts), _dp(Rt), _dp(tt), _dp(R), _dp(t)))
+    return R.reshape(3, 3), t
+
+
+def carry_plane_field(planes, src_calib, src_view, dst_calib, dst_view, w_t, h_t, max_dis, R, t, mask=None, device=0, out=None, **params):
+    """C alone on host memory (cspm_carry_plane_field): planes (h_s, w_s, 6) in the layout of get_planes (only the
+    param part is read), mask (h_s, w_s) or None, the motion X_t = R X_s + t between the two cameras.  out: a dict of preallocated
+    arrays to write into instead of fresh ones (tests poison them).  Returns dict(planes (h_t, w_t, 6), state (h_t, w_t) uint8,
+    source (h_t, w_t) int32); params: fill."""
+    f = np.ascontiguousarray(planes, dtype=np.float64)
+    assert f.ndim == 3 and f.shape[2] == 6, f.shape
+    h_s, w_s = f.shape[:2]
+    m = None
+    if mask is not None:
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        assert m.shape == (h_s, w_s), m.shape
+    ks, kt, p = calib_struct(src_calib), calib_struct(dst_calib), carry_params(**params)
+    R, t = _pose(R, t)
+    res = dict(out or {})
+    shape = (max(int(h_t), 0), max(int(w_t), 0))
+    if "planes" not in res:
+        res["planes"] = np.zeros(shape + (6,))
+    if "state" not in res:
+        res["state"] = np.zeros(shape, np.uint8)
+    if "source" not in res:
+        res["source"] = np.zeros(shape, np.int32)
+    _check(load_library().cspm_carry_plane_field(device, _dp(f), _opt(_u8, m), C.byref(ks), int(src_view), w_s, h_s, C.byref(kt), int(dst_view), int(w_t),
+                                                 int(h_t), int(max_dis), _dp(R), _dp(t), C.byref(p), _dp(res["planes"]), _u8(res["state"]),
+                                                 _i32(res["source"])))
+    return res
 
 
 def synth_params(**params):

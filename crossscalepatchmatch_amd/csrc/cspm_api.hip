@@ -23,6 +23,7 @@
 #include "cspm_mesh.h"
 #include "cspm_fuse.h"
 #include "cspm_register.h"
+#include "cspm_carry.h"
 #include "cspm_synth.h"
 #include "cspm_rect.h"
 #include "cspm_ca.h"
@@ -232,6 +233,7 @@ struct cspm_ctx {
   uint8_t *mesh_bytes = nullptr;      // cspm_mesh: keep and Q (2 byte maps); allocated by the first such call and kept with the field
   uint32_t *mesh_map = nullptr;       // cspm_mesh: the pixel -> vertex map, then the vertex and the face counts per workgroup, each with its total
   double *synth_disp = nullptr;       // cspm_synthesize: both views' CSPM_GEOM_RAW disparity maps (2 arrays); allocated by the first such call and kept with the field
+  uint32_t *carry_mem = nullptr;      // cspm_carry_planes into this context: a 64-bit depth key, then a 32-bit winner per pixel (3 words each); allocated by the first such call and kept with the field
   // depth-map fusion (cspm_fuse_*): the slots of max_views views of fuse_w x fuse_h, kept in mem_fuse
   bool fuse_on = false;
   int fuse_w = 0, fuse_h = 0, fuse_max = 0, fuse_views = 0;
@@ -2536,6 +2538,54 @@ int reg_run(cspm_ctx *c, int src, unsigned long long targets, const cspm_reg_par
   return CSPM_OK;
 }
 
+// ---- plane-field carry (cspm_carry.h) ----------------------------------------------------------------------
+const cspm_carry_params kCarryDefaults = {1};
+const char *carry_calib_error(const cspm_calib *k, int view) {
+  if (!k) return "carry: no calibration";
+  if (!std::isfinite(k->f) || !std::isfinite(k->cx) || !std::isfinite(k->cy) || !std::isfinite(k->baseline) || !std::isfinite(k->doffs))
+    return "carry: the calibration must be finite";
+  if (!(k->f > 0.0) || !(k->baseline > 0.0)) return "carry: f and baseline must be positive";
+  if (view < 0 || view > 1) return "carry: view must be 0 or 1";
+  return nullptr;
+}
+const char *carry_motion_error(const double *R, const double *t) {
+  if (!R || !t) return "carry: no motion";
+  bool finite = true;
+  for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(R[i]);
+  for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(t[i]);
+  if (!finite) return "carry: the motion must be finite";
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double d = R[3 * i] * R[3 * j] + R[3 * i + 1] * R[3 * j + 1] + R[3 * i + 2] * R[3 * j + 2] - (i == j ? 1.0 : 0.0);
+      if (!(std::fabs(d) <= 1e-6)) return "carry: R is not a rotation (max |R R^T - I| > 1e-6)";
+    }
+  return nullptr;
+}
+const char *carry_size_error(int w, int h) {
+  if (w < 1 || h < 1) return "carry: w and h must be at least 1";
+  if ((long long)w * h >= (1LL << 31)) return "carry: w * h must be below 2^31: winners are 32-bit pixel indices";
+  return nullptr;
+}
+const char *carry_params_error(const cspm_carry_params *p) {
+  if (p->fill != 0 && p->fill != 1) return "carry: fill must be 0 or 1";
+  return nullptr;
+}
+inline CarryCam carry_cam(const cspm_calib *k, int view) {
+  return CarryCam{k->f, k->cx + (double)view * k->doffs, k->cy, k->baseline, k->doffs, k->f * k->baseline};
+}
+inline CarryPar carry_par(const cspm_calib *sk, int sv, int ws, int hs, const cspm_calib *tk, int tv, int wt, int ht, double max_dis, const double *R,
+                          const double *t, const cspm_carry_params *p) {
+  CarryPar k{};
+  k.s = carry_cam(sk, sv);
+  k.t = carry_cam(tk, tv);
+  for (int i = 0; i < 9; ++i) k.R[i] = R[i];
+  for (int i = 0; i < 3; ++i) k.tr[i] = t[i];
+  k.max_dis = max_dis;
+  k.ws = ws; k.hs = hs; k.wt = wt; k.ht = ht;
+  k.fill = p->fill;
+  return k;
+}
+
 }  // namespace
 
 // =================================================================================================
@@ -3910,6 +3960,117 @@ int cspm_register_depth_maps(int device, const cspm_reg_params *p, const cspm_fu
   if (!rc) rc = reg_run(S.c, src, targets, p, &start, 0, R_out, t_out, iters_out);
   S.latch(rc);
   return S.finish("registration failed");
+}
+
+// C: a plane field carried into a moved camera, on caller memory and between two contexts
+int cspm_carry_default_params(cspm_carry_params *p) {
+  if (!p) return CSPM_ERR_ARG;
+  *p = kCarryDefaults;
+  return CSPM_OK;
+}
+
+int cspm_carry_relative_pose(const double *Rs, const double *ts, const double *Rt, const double *tt, double *R_out, double *t_out) {
+  if (!Rs || !ts || !Rt || !tt || !R_out || !t_out) return fail(nullptr, CSPM_ERR_ARG, "carry: a pose is missing");
+  double R[9], t[3];
+  const double d[3] = {ts[0] - tt[0], ts[1] - tt[1], ts[2] - tt[2]};
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) R[3 * i + j] = (Rt[i] * Rs[j] + Rt[3 + i] * Rs[3 + j]) + Rt[6 + i] * Rs[6 + j];
+    t[i] = (Rt[i] * d[0] + Rt[3 + i] * d[1]) + Rt[6 + i] * d[2];
+  }
+  for (int i = 0; i < 9; ++i) R_out[i] = R[i];  // through locals: an output may be one of the inputs
+  for (int i = 0; i < 3; ++i) t_out[i] = t[i];
+  return CSPM_OK;
+}
+
+int cspm_carry_plane_field(int device, const double *src_norm_param, const uint8_t *mask, const cspm_calib *src_calib, int src_view, int w_s, int h_s,
+                           const cspm_calib *dst_calib, int dst_view, int w_t, int h_t, int max_dis, const double *R, const double *t,
+                           const cspm_carry_params *p, double *norm_param_out, uint8_t *state_out, int32_t *source_out) {
+  if (!p) p = &kCarryDefaults;
+  if (const char *msg = carry_params_error(p)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (const char *msg = carry_calib_error(src_calib, src_view)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (const char *msg = carry_calib_error(dst_calib, dst_view)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (const char *msg = carry_motion_error(R, t)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (const char *msg = carry_size_error(w_s, h_s)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (const char *msg = carry_size_error(w_t, h_t)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (max_dis < 0) return fail(nullptr, CSPM_ERR_ARG, "carry: max_dis must be >= 0");
+  if (!src_norm_param) return fail(nullptr, CSPM_ERR_ARG, "carry: no source plane field");
+  const size_t ns = (size_t)w_s * h_s, nt = (size_t)w_t * h_t;
+  std::vector<double> abc(3 * ns), rec(norm_param_out ? 6 * nt : 0);  // in front of the OneShot: its copies read and write them
+  for (size_t i = 0; i < ns; ++i)
+    for (int k = 0; k < 3; ++k) abc[k * ns + i] = src_norm_param[6 * i + 3 + k];
+  OneShot S(device);
+  double *dabc = S.up(abc.data(), 3 * ns);
+  uint8_t *dmask = S.up(mask, ns);
+  uint32_t *dkey = S.buf<uint32_t>(3 * nt);
+  double *dout = S.buf<double>(6 * nt);
+  uint8_t *dstate = S.buf<uint8_t>(nt, state_out != nullptr);
+  int *dsource = S.buf<int>(nt, source_out != nullptr);
+  if (S.rc) return S.finish();
+  const CarryPar k = carry_par(src_calib, src_view, w_s, h_s, dst_calib, dst_view, w_t, h_t, (double)max_dis, R, t, p);
+  const Slabs6 o = six_slabs(dout, nt);
+  if (carry_launch(S.c->stream, k, CarrySrc{dabc, dabc + ns, dabc + 2 * ns, dmask}, reinterpret_cast<unsigned long long *>(dkey),
+                   CarryOut{o.p[0], o.p[1], o.p[2], o.p[3], o.p[4], o.p[5], dstate, dsource, 0}) != hipSuccess)
+    return S.fail(CSPM_ERR_HIP, "carry kernels failed"), S.finish();
+  S.down(rec.data(), dout, rec.size());
+  S.down(state_out, dstate, nt);
+  S.down(source_out, dsource, nt);
+  if (S.finish("carry kernels failed")) return S.rc;
+  if (norm_param_out) interleave_planes(rec.data(), nt, norm_param_out);
+  return CSPM_OK;
+}
+
+int cspm_carry_planes(cspm_ctx *dst, cspm_ctx *src, const cspm_calib *src_calib, const cspm_calib *dst_calib, const double *R, const double *t,
+                      const cspm_carry_params *p, int merge) {
+  if (!dst || !src || dst == src) return dst ? fail(dst, CSPM_ERR_ARG, "cspm_carry_planes needs two different contexts") : CSPM_ERR_ARG;
+  if (!p) p = &kCarryDefaults;
+  if (const char *msg = carry_params_error(p)) return fail(dst, CSPM_ERR_ARG, msg);
+  if (const char *msg = carry_calib_error(src_calib, 0)) return fail(dst, CSPM_ERR_ARG, msg);
+  if (const char *msg = carry_calib_error(dst_calib, 0)) return fail(dst, CSPM_ERR_ARG, msg);
+  if (const char *msg = carry_motion_error(R, t)) return fail(dst, CSPM_ERR_ARG, msg);
+  if (dst->device != src->device) return fail(dst, CSPM_ERR_ARG, "the two contexts are on different devices");
+  if (!src->field_alloc) return fail(dst, CSPM_ERR_STATE, "the source context has no plane field");
+  if (!dst->img0[0]) return fail(dst, CSPM_ERR_STATE, "cspm_set_images first");
+  if (merge) {
+    if (int e = need_cost(dst)) return e;
+  }
+  if (int e = need_field(dst, kNoMergeTarget)) return e;
+  if (dst->max_dis < 1) return fail(dst, CSPM_ERR_STATE, "no max_dis known: build a cost object (or cspm_fpm_begin) first");
+  ON_DEVICE(dst);
+  int rc;
+  const size_t nt = (size_t)dst->W * dst->H;
+  CandBuf cand{};
+  if ((rc = source_check(dst, src)) || (rc = dalloc(dst, dst->mem_field, &dst->carry_mem, 3 * nt))) return rc;
+  if (merge) {
+    if ((rc = ensure_cand(dst, &cand)) || (rc = ensure_consistent(dst))) return rc;
+  } else {
+    dst->field_consistent = false;  // min_cost still belongs to the planes that were replaced
+  }
+  return with_source(dst, src, "cspm_carry_planes", [&]() -> int {
+    dst->repeat.taint_unchecked_run();  // it can no longer be repeated over these planes
+    for (int v = 0; v < 2; ++v) {
+      // view 1's cameras sit one baseline to the right of view 0's: X_s0 = X_s1 + (B_s, 0, 0), X_t1 = X_t0 - (B_t, 0, 0)
+      double tv[3] = {t[0], t[1], t[2]};
+      if (v == 1) {
+        for (int i = 0; i < 3; ++i) tv[i] = t[i] + R[3 * i] * src_calib->baseline;
+        tv[0] = tv[0] - dst_calib->baseline;
+      }
+      const CarryPar k = carry_par(src_calib, v, src->W, src->H, dst_calib, v, dst->W, dst->H, (double)dst->max_dis, R, tv, p);
+      const Field &sf = src->f[v], &df = dst->f[v];
+      const CarryOut out = merge ? CarryOut{cand.planes.p[0], cand.planes.p[1], cand.planes.p[2], cand.planes.p[3], cand.planes.p[4], cand.planes.p[5],
+                                            cand.mask, nullptr, 0}
+                                 : CarryOut{df.nx, df.ny, df.nz, df.a, df.b, df.c, nullptr, nullptr, 1};
+      {
+        Timed tm(dst, CSPM_K_MISC, (long long)src->W * src->H);
+        if (carry_launch(dst->stream, k, CarrySrc{sf.a, sf.b, sf.c, nullptr}, reinterpret_cast<unsigned long long *>(dst->carry_mem), out) != hipSuccess)
+          return fail(dst, CSPM_ERR_HIP, "carry kernels failed");
+      }
+      if (merge) {
+        const CandField cf = cand.field(v);
+        if (int e = do_merge(dst, &cf, &kDefaultParams, v, 1, (long long)nt)) return e;
+      }
+    }
+    return CSPM_OK;
+  });
 }
 
 // N alone on caller maps: the launch cspm_synthesize enqueues.  Arguments first, then the device.

@@ -72,6 +72,15 @@ class CSPatchMatch {
   void PatchMatchSeededBegin(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp);
   void PatchMatchKeep(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp);
   void PatchMatchKeepBegin(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp);
+  // carried start for a moving rig (an addition; include/cspm.h "plane-field carry"): InitRandomPlane, then the final plane field of
+  // `prev` -- the matcher of the previous frame, whose plane cost must still be alive -- carried across the motion X_this = R X_prev + t
+  // between the two left cameras into this frame's disparity space and merged as candidates (cspm_pm_init, cspm_carry_planes with
+  // merge = 1), then iter_num warm iterations (cspm_patchmatch_warm).  params == NULL: the defaults.  The two frames may differ in size.
+  // Begin / End as for PatchMatchFrom; both plane costs must be this library's device costs on one GPU: anything else throws.
+  void PatchMatchCarried(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp, const CSPatchMatch &prev, const cspm_calib &prev_calib,
+                         const cspm_calib &calib, const double *R, const double *t, const cspm_carry_params *params = NULL);
+  void PatchMatchCarriedBegin(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp, const CSPatchMatch &prev, const cspm_calib &prev_calib,
+                              const cspm_calib &calib, const double *R, const double *t, const cspm_carry_params *params = NULL);
 
   // additions (the reference seeds from time(NULL) and has one schedule)
   void set_seed(uint64_t seed) { seed_ = seed; }

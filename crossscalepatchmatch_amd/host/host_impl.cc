@@ -603,6 +603,35 @@ void CSPatchMatch::PatchMatchKeep(const int &iter_num, const IPlaneCost *plane_c
   PatchMatchEnd();
 }
 
+void CSPatchMatch::PatchMatchCarriedBegin(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp, const CSPatchMatch &prev,
+                                          const cspm_calib &prev_calib, const cspm_calib &calib, const double *R, const double *t,
+                                          const cspm_carry_params *params) {
+  const IDevicePlaneCost *dev = dynamic_cast<const IDevicePlaneCost *>(plane_cost);
+  if (!dev) throw std::runtime_error("CSPatchMatch::PatchMatchCarried needs one of this library's device costs (a foreign IPlaneCost runs cold only: PatchMatch)");
+  cspm_ctx *ctx = dev->device_ctx();
+  if (pending_ctx_ && pending_ctx_ != ctx) throw std::runtime_error("CSPatchMatch::PatchMatchCarriedBegin: the previous run has not been ended");
+  if (!prev.last_ctx_ || prev.pending_ctx_) throw std::runtime_error("CSPatchMatch::PatchMatchCarried: the previous matcher has no finished run");
+  if (!DevicePlaneCost::is_live(prev.last_ctx_)) throw std::runtime_error("CSPatchMatch::PatchMatchCarried: the plane cost the previous matcher ran on has been deleted");
+  cspm_pm_params p;
+  cspm_pm_default_params(&p);
+  p.seed = seed_;
+  p.schedule = schedule_;
+  p.rb_rounds = rb_rounds_;
+  p.rb_neighbours = rb_neighbours_;
+  check(cspm_pm_init(ctx, &p), ctx, "cspm_pm_init");
+  check(cspm_carry_planes(ctx, prev.last_ctx_, &prev_calib, &calib, R, t, params, 1), ctx, "cspm_carry_planes");
+  check(cspm_patchmatch_warm(ctx, iter_num, &p), ctx, "cspm_patchmatch_warm");  // asynchronous: enqueued on the context's stream
+  pending_ctx_ = ctx;
+  pending_pp_ = use_pp;
+}
+
+void CSPatchMatch::PatchMatchCarried(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp, const CSPatchMatch &prev,
+                                     const cspm_calib &prev_calib, const cspm_calib &calib, const double *R, const double *t,
+                                     const cspm_carry_params *params) {
+  PatchMatchCarriedBegin(iter_num, plane_cost, use_pp, prev, prev_calib, calib, R, t, params);
+  PatchMatchEnd();
+}
+
 void CSPatchMatch::PatchMatchFrom(const int &iter_num, const IPlaneCost *plane_cost, const bool &use_pp) {
   PatchMatchFromBegin(iter_num, plane_cost, use_pp);
   PatchMatchEnd();

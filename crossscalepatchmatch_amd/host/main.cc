@@ -15,7 +15,9 @@
 // --fuse_max_reproj --fuse_max_rel_depth --fuse_min_cos --fuse_min_views --fuse_no_suppress (with --batch_list and --calib or --rig: the
 // depth maps of all pairs of the list fused into one point cloud in world coordinates; include/cspm.h "depth-map fusion") --fuse_register --fuse_register_window
 // --fuse_poses_out --fuse_reg_iters --fuse_reg_stride --fuse_reg_max_dist --fuse_reg_huber (the poses of that fusion refined, or found
-// without --fuse_poses, by registering the views against each other; include/cspm.h "depth-view registration").
+// without --fuse_poses, by registering the views against each other; include/cspm.h "depth-view registration") --carry_poses --carry_iters
+// --carry_no_fill (with --batch_list and --calib or --rig: the list is one sequence of a moving rig, every pair starts from the previous
+// pair's plane field carried across the motion; include/cspm.h "plane-field carry").
 #include "../../include/cspm.h"
 #include "commfunc.h"
 #include "cs_patchmatch.h"
@@ -163,6 +165,13 @@ DEFINE_int32(fuse_reg_iters, 8, "with --fuse_register: Gauss-Newton iterations p
 DEFINE_int32(fuse_reg_stride, 1, "with --fuse_register: every n-th pixel of a view in x and y is a sample");
 DEFINE_double(fuse_reg_max_dist, 0.5, "with --fuse_register: the largest distance between a point and its associated point, in world units");
 DEFINE_double(fuse_reg_huber, 0.05, "with --fuse_register: residuals beyond it are down-weighted, in world units (0 = plain least squares)");
+DEFINE_string(carry_poses, "", "with --batch_list and --calib (or --rig): the list is ONE sequence of a moving rig, run in list order by one worker on "
+                                "the first device.  A text file with one camera -> world pose of the left rectified camera per pair, in the format of "
+                                "--fuse_poses (it may be the same file).  Pair 0 runs as without the flag; pair i runs the random init, then the plane field "
+                                "of pair i - 1 carried across the motion and merged as candidates (include/cspm.h \"plane-field carry\"), then "
+                                "--carry_iters warm iterations");
+DEFINE_int32(carry_iters, 1, "with --carry_poses: warm PatchMatch iterations of every pair but the first, 0 .. 15");
+DEFINE_bool(carry_no_fill, false, "with --carry_poses: a pixel no carried plane lands on gets no candidate instead of a neighbour's plane");
 DEFINE_bool(fuse_no_suppress, false, "with --fuse_poses: emit a surface from every view that sees it, not only from the first");
 DEFINE_string(batch_list, "", "text file, one stereo pair per line: l_img r_img l_dis r_dis [l_pfm r_pfm [synth_png [synth_pfm]]] (the last two with "
                               "--synth_t, and then `-` skips an optional column); all pairs run with the "
@@ -188,6 +197,8 @@ cspm_calib g_rect_calib;
 // --calib with --batch_list (the fusion): every pair of the list has this calibration
 bool g_batch_calib = false;
 CalibFile g_calib_file;
+// --carry_poses: one pose per pair
+std::vector<CameraPose> g_carry_poses;
 // --fuse_poses: one pose per pair, and the views the workers collect (slot = pair index, or 2 * pair index + view with --fuse_right)
 std::vector<CameraPose> g_poses;
 std::unique_ptr<DepthFusion> g_fusion;
@@ -242,7 +253,8 @@ int ca_method(const string &name) {
   return -1;
 }
 
-void begin(PairRun &p, CCMethod *cost_fn) {
+// prev: --carry_poses, the pair before this one in the sequence (its cost object still alive), or NULL
+void begin(PairRun &p, CCMethod *cost_fn, const PairRun *prev = NULL) {
   if (p.rc != EXIT_SUCCESS) return;
   try {
     p.t0 = static_cast<double>(getTickCount());
@@ -285,7 +297,15 @@ void begin(PairRun &p, CCMethod *cost_fn) {
       if (use_fit) p.matcher->AddCandidateDisparity(v == 0 ? kLeft : kRight, m, fit);
       else p.matcher->AddCandidateDisparity(v == 0 ? kLeft : kRight, m);
     }
-    if (!FLAGS_seed_ca.empty()) {  // keep-init and the iterations are enqueued behind the local stereo on the cost object's stream
+    if (prev) {  // init, the previous pair's field carried across the motion and merged, the warm iterations: all on the cost object's stream
+      double R[9], t[3];
+      const CameraPose &ps = g_carry_poses[prev->index], &pt = g_carry_poses[p.index];
+      if (cspm_carry_relative_pose(ps.R, ps.t, pt.R, pt.t, R, t) != CSPM_OK) throw std::runtime_error(cspm_last_error(NULL));
+      cspm_carry_params cp;
+      cspm_carry_default_params(&cp);
+      cp.fill = FLAGS_carry_no_fill ? 0 : 1;
+      p.matcher->PatchMatchCarriedBegin(FLAGS_carry_iters, p.cost.get(), FLAGS_use_pp, *prev->matcher, prev->calib, p.calib, R, t, &cp);
+    } else if (!FLAGS_seed_ca.empty()) {  // keep-init and the iterations are enqueued behind the local stereo on the cost object's stream
       p.matcher->LocalStereoBegin(ca_method(FLAGS_seed_ca), p.cost.get(), FLAGS_use_pp);
       if (use_fit) p.matcher->FitPlanes(p.cost.get(), fit, FLAGS_fit_merge);
       p.matcher->PatchMatchKeepBegin(FLAGS_iters, p.cost.get(), FLAGS_use_pp);
@@ -319,7 +339,8 @@ void begin(PairRun &p, CCMethod *cost_fn) {
   }
 }
 
-void finish(PairRun &p) {
+// keep_cost: the cost object (and with it the context that holds the plane field) outlives the call: the next pair of a sequence carries from it
+void finish(PairRun &p, bool keep_cost = false) {
   if (p.rc == EXIT_SUCCESS) {
     try {
       p.matcher->PatchMatchEnd();
@@ -407,7 +428,7 @@ void finish(PairRun &p) {
       p.rc = EXIT_FAILURE;
     }
   }
-  p.cost.reset();
+  if (!keep_cost) p.cost.reset();
 }
 
 void write(PairRun &p) {
@@ -599,6 +620,54 @@ int run_batch(const std::vector<BatchJob> &jobs, int skipped, int bad_lines) {
   return failed.load() ? EXIT_FAILURE : EXIT_SUCCESS;
 }
 
+// --carry_poses: the list is one sequence.  One worker on the first device, two device slots used alternately: pair i's context takes
+// its start from pair i - 1's, which is released (parked for pair i + 1) as soon as the carry is enqueued behind it.
+int run_sequence(const std::vector<BatchJob> &jobs) {
+  const std::vector<int> devices = parse_devices();
+  if (devices.empty()) {
+    cout << "Error: --devices must be `all` or a comma-separated list of GPU indices below " << DeviceSlot::device_count()
+         << " (--device likewise); this node has " << DeviceSlot::device_count() << " usable GPU(s)\n";
+    return EXIT_FAILURE;
+  }
+  cout << "Sequence: --carry_poses runs the list in order on GPU " << devices[0] << " with two contexts; --in_flight does not apply\n";
+  DeviceSlot slot_a(devices[0], /*keep_context=*/true), slot_b(devices[0], /*keep_context=*/true);
+  DeviceSlot *const slots[2] = {&slot_a, &slot_b};
+  const std::unique_ptr<CCMethod> cost_fn(GetCCType(FLAGS_cc_name));
+  if (CenGrdCC *cg = dynamic_cast<CenGrdCC *>(cost_fn.get())) cg->set_fused(FLAGS_cc_fused);
+  int failed = 0;
+  const double t0 = static_cast<double>(getTickCount());
+  std::unique_ptr<PairRun> prev;
+  for (size_t k = 0; k < jobs.size(); ++k) {
+    std::unique_ptr<PairRun> cur(new PairRun(jobs[k].files, jobs[k].line_no, k));
+    if (!FLAGS_quiet) cur->log << "Load Image: " << cur->files.l_img << " " << cur->files.r_img << "\n";
+    load(*cur);
+    if (g_batch_calib && cur->rc == EXIT_SUCCESS) cur->calib = ScaledCalib(g_calib_file, cur->left.cols);
+    {
+      DeviceSlot &slot = *slots[k & 1];
+      if (g_rectify) slot.SetRectification(&g_rig, &g_rect);
+      DeviceSlot::Use use(slot);
+      begin(*cur, cost_fn.get(), prev.get());
+    }
+    prev.reset();  // the carry is enqueued: the previous pair's context is parked for the pair after this one
+    finish(*cur, /*keep_cost=*/true);
+    write(*cur);
+    if (cur->rc != EXIT_SUCCESS) {
+      ++failed;
+      cur->log << "Pair FAILED (line " << cur->line_no << "): " << cur->files.l_img << " " << cur->files.r_img << "\n";
+    } else if (!FLAGS_quiet) {
+      cur->log << (k == 0 ? "Sequence pair 0: cold start\n" : "Sequence pair: carried start\n");
+    }
+    cout << cur->log.str() << std::flush;
+    if (cur->rc == EXIT_SUCCESS) prev = std::move(cur);  // a failed pair breaks the chain: the next one starts cold
+  }
+  prev.reset();
+  slot_a.release();
+  slot_b.release();
+  const double seconds = (static_cast<double>(getTickCount()) - t0) / getTickFrequency();
+  cout << "Batch: " << jobs.size() << " pairs in " << seconds << " s, " << failed << " failed, 0 skipped\n";
+  return failed ? EXIT_FAILURE : EXIT_SUCCESS;
+}
+
 int run() {
   if (FLAGS_pp_pfm && !FLAGS_use_pp) {  // checked before anything opens a device
     cout << "Error: --pp_pfm post-processes the PFM maps and needs --use_pp\n";
@@ -731,7 +800,38 @@ int run() {
     return EXIT_FAILURE;
   }
   const bool fusion = !FLAGS_fuse_poses.empty() || !FLAGS_fuse_ply.empty() || FLAGS_fuse_register;
-  if ((geom_out || (!FLAGS_calib.empty() && !fusion)) && !FLAGS_batch_list.empty()) {
+  const bool carry = !FLAGS_carry_poses.empty();
+  if (!carry && (FLAGS_carry_iters != 1 || FLAGS_carry_no_fill)) {  // checked before anything opens a device
+    cout << "Error: --carry_iters and --carry_no_fill need --carry_poses\n";
+    return EXIT_FAILURE;
+  }
+  if (carry) {
+    if (FLAGS_batch_list.empty() || (FLAGS_calib.empty() && FLAGS_rig.empty())) {
+      cout << "Error: --carry_poses needs --batch_list and --calib or --rig\n";
+      return EXIT_FAILURE;
+    }
+    if (FLAGS_carry_iters < 0 || FLAGS_carry_iters > 15) {
+      cout << "Error: --carry_iters must be 0 .. 15\n";
+      return EXIT_FAILURE;
+    }
+    if (fusion || FLAGS_batch_skip_existing || !FLAGS_ca_name.empty() || !FLAGS_warm_ca.empty() || !FLAGS_seed_ca.empty() || FLAGS_seg_step != 0) {
+      cout << "Error: --carry_poses runs plain PatchMatch over every pair of the list: not with the fusion, --batch_skip_existing, --ca_name, --warm_ca, "
+              "--seed_ca or --seg_step\n";
+      return EXIT_FAILURE;
+    }
+    if (FLAGS_pc_name != "PRE" && FLAGS_pc_name != "IMG") {
+      cout << "Error: --carry_poses needs one of this library's plane costs (--pc_name=PRE or IMG), not " << FLAGS_pc_name << "\n";
+      return EXIT_FAILURE;
+    }
+    int bad_line = 0;
+    if (!ReadPoseFile(FLAGS_carry_poses, &g_carry_poses, &bad_line)) {
+      cout << "Error: can not read " << FLAGS_carry_poses << " as a poses file (12 numbers per line, the row-major [R | t])";
+      if (bad_line) cout << ": line " << bad_line;
+      cout << "\n";
+      return EXIT_FAILURE;
+    }
+  }
+  if ((geom_out || (!FLAGS_calib.empty() && !fusion && !carry)) && !FLAGS_batch_list.empty()) {
     cout << "Error: --calib and the point-cloud, depth and mesh outputs belong to one pair: not with --batch_list\n";
     return EXIT_FAILURE;
   }
@@ -901,6 +1001,15 @@ int run() {
     }
     g_batch_calib = !FLAGS_calib.empty();
     g_fusion.reset(new DepthFusion(views));
+  }
+  if (carry) {  // before any pair runs
+    if (bad_lines != 0 || g_carry_poses.size() != jobs.size()) {
+      cout << "Error: " << FLAGS_carry_poses << " holds " << g_carry_poses.size() << " poses, the batch list " << jobs.size() << " pairs"
+           << (bad_lines ? " and lines that are no pairs" : "") << "\n";
+      return EXIT_FAILURE;
+    }
+    g_batch_calib = !FLAGS_calib.empty();
+    return run_sequence(jobs);
   }
   return run_batch(jobs, skipped, bad_lines);
 }

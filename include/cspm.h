@@ -948,6 +948,75 @@ int cspm_fuse_set_pose(cspm_ctx *ctx, int slot, const double *R, const double *t
 int cspm_register_depth_maps(int device, const cspm_reg_params *params, const cspm_fuse_view *views, int n_views, int w, int h, int src,
                              unsigned long long targets, double *R_out, double *t_out, cspm_reg_iter *iters_out);
 
+/* ---- plane-field carry (an addition): a plane field moved into another camera: temporal starts for stereo video ------
+ * A plane in disparity space is a plane in 3-D (G above), so a converged field can be moved across a rigid motion into another camera's
+ * disparity space and pixel grid, with visibility resolved: frame i + 1 of a moving rig starts from frame i's planes.  For the pure
+ * baseline shift it is the reference's view propagation (cs_patchmatch.cc:229-277) as a geometric operation.
+ * The specification C.  Every product, sum, quotient, floor and square root is one IEEE f64 operation in the association written here,
+ * nothing contracted, no reciprocal, no trigonometry.
+ * A carry camera is {f, cxv, cy, B, doffs} of one view of a rectified pair: a cspm_calib and a view v, cxv = cx + (double)v * doffs (G's
+ * cxv), B = baseline.  The host computes once per camera fB = f * B.  Subscript s is the source camera, t the target camera.
+ * The motion (R, t), R row-major, maps source-camera to target-camera coordinates: X_t = R X_s + t.
+ * Inputs: the source planes a, b, c on w_s x h_s (the param part of cspm_get_planes' records), an optional mask of w_s*h_s bytes, both
+ * cameras, (R, t), the target size w_t x h_t, max_dis of the target, cspm_carry_params { fill }, default 1.
+ * Splat, source pixel (x, y), m = y*w_s + x:
+ *  1. No contender when the mask byte is 0 or one of a, b, c is not finite.
+ *  2. D = (a*x + b*y) + c;  tt = D + doffs_s;  continue only when tt > 0.0 (a NaN fails).
+ *     Z = fB_s / tt;  u = x - cxv_s;  wv = y - cy_s;  X = (u*Z) / f_s;  Y = (wv*Z) / f_s                           (G's association)
+ *  3. Q[i] = ((R[i][0]*X + R[i][1]*Y) + R[i][2]*Z) + t[i];  continue only when Q[2] > 0.0.
+ *     pu = (f_t*Q[0]) / Q[2] + cxv_t;  pv = (f_t*Q[1]) / Q[2] + cy_t;  fx = floor(pu + 0.5);  fy = floor(pv + 0.5);
+ *     continue unless fx >= 0.0 && fx <= (double)(w_t-1) && fy >= 0.0 && fy <= (double)(h_t-1) (tested on the doubles, a NaN fails; only
+ *     then are they converted to int: F's step 4).
+ *  4. The 3-D plane is n . P = fB_s with n0 = a*f_s, n1 = b*f_s, n2 = ((a*cxv_s + b*cy_s) + c) + doffs_s.  Rotated:
+ *     n'[i] = (R[i][0]*n0 + R[i][1]*n1) + R[i][2]*n2;  hq = fB_s + ((n'0*t[0] + n'1*t[1]) + n'2*t[2]);
+ *     continue only when hq > 0.0 (a NaN fails): the target camera is on the plane's visible side.
+ *  5. a' = (B_t*n'0) / hq;  b' = (B_t*n'1) / hq;  c' = (((fB_t*n'2) / hq - a'*cxv_t) - b'*cy_t) - doffs_t.
+ *  6. continue unless a', b', c' are finite;  z = (a'*fx + b'*fy) + c';  continue only when z >= 0.0 && z <= max_dis (a NaN fails).
+ *  The pixel is then a contender for target pixel g = fy*w_t + fx with depth Q[2].  Steps 4 and 5 do not depend on (x, y).
+ * Winner of g: the contender with the smallest Q[2] (f64), then the smallest m: independent of scheduling.
+ * Fill (fill = 1): a target pixel (x, y) without a winner looks at (x-1,y), (x+1,y), (x,y-1), (x,y+1) in that order, those inside the image
+ *  that have a winner; for each, z = (a'*x + b'*y) + c' with that winner's (a', b', c') at its OWN (x, y); among those with
+ *  z >= 0.0 && z <= max_dis it takes the smallest z (the background side), the first in the order on a tie.  Fill reads winners only,
+ *  never filled pixels.
+ * Output per target pixel (x, y) with its (a', b') and z (a winner's z is that of step 6):
+ *     len = sqrt((a'*a' + b'*b') + 1.0);  inv = 1.0 / max(len, 1e-8);  normal = (-a'*inv, -b'*inv, 1.0*inv)
+ *     plane = Plane(normal, (x, y, z)), exactly as cspm_fit_planes_host finishes; the record is six doubles, norm then param.
+ *  State S: 1 = a winner, 2 = filled, 0 = none; a pixel of state 0 gets six NaNs ("no candidate" for cspm_merge_planes_host).
+ *  source: the m of the source pixel whose plane the pixel took (its winner's, or for a filled pixel the chosen neighbour's winner's);
+ *  -1 for state 0.
+ * CSPM_ERR_ARG: a calibration the reprojection would refuse (non-finite, f <= 0, baseline <= 0) or a view outside 0 .. 1;
+ * max |R R^T - I| > 1e-6 or a non-finite R or t; max_dis < 0; w or h < 1 or w*h >= 2^31 (source or target); fill outside 0 .. 1. */
+typedef struct cspm_carry_params {
+  int fill; /* 1 (default): a target pixel without a winner takes a neighbouring winner's plane; 0: it stays without a candidate */
+} cspm_carry_params;
+int cspm_carry_default_params(cspm_carry_params *p);
+/* two camera -> world poses (P_world = R P_cam + t, row-major R) into the motion between the cameras, R = Rt^T Rs, t = Rt^T (ts - tt):
+ *     R[i][j] = (Rt[0][i]*Rs[0][j] + Rt[1][i]*Rs[1][j]) + Rt[2][i]*Rs[2][j]
+ *     d = ts - tt (three subtractions);  t[i] = (Rt[0][i]*d[0] + Rt[1][i]*d[1]) + Rt[2][i]*d[2]
+ * Pure host code, no checks beyond NULL (CSPM_ERR_ARG); an output may alias an input. */
+int cspm_carry_relative_pose(const double *Rs, const double *ts, const double *Rt, const double *tt, double *R_out, double *t_out);
+/* C alone on caller memory with a temporary context, synchronous.  src_norm_param: w_s*h_s records of six doubles in the layout of
+ * cspm_get_planes, of which only the param part (entries 3 .. 5) is read; mask w_s*h_s bytes or NULL.  Outputs, each optional:
+ * norm_param_out w_t*h_t*6 doubles in the layout of cspm_get_planes, state_out w_t*h_t bytes, source_out w_t*h_t int32.  Every argument
+ * is checked before a device is opened (the list above, and a NULL field); no output is touched on an error.  A one-shot entry like
+ * cspm_fuse_depth_maps; its name does not end in _host because it relates two cameras, not one kernel family's maps of one view. */
+int cspm_carry_plane_field(int device, const double *src_norm_param, const uint8_t *mask, const cspm_calib *src_calib, int src_view, int w_s,
+                           int h_s, const cspm_calib *dst_calib, int dst_view, int w_t, int h_t, int max_dis, const double *R, const double *t,
+                           const cspm_carry_params *params, double *norm_param_out, uint8_t *state_out, int32_t *source_out);
+/* C from src's stored field into dst, both views; the contexts may differ in size.  (R, t) is the motion between the two VIEW-0 cameras;
+ * view v of dst receives view v of src.  For v = 1 the entry shifts both cameras by their baselines itself (as cspm_fuse_push does):
+ *     t1[i] = t[i] + R[i][0]*B_s for i = 0 .. 2, then t1[0] = t1[0] - B_t;   cxv = cx + doffs on both sides.
+ * max_dis is dst's.
+ *   merge = 1  the candidates go into the context's candidate buffer with S != 0 as the mask and are merged under
+ *              cspm_merge_planes_host's rule, one view after the other; a field that is not consistent is re-scored first.
+ *   merge = 0  pixels that have a candidate are replaced and the field is left not consistent, as cspm_fit_planes does.
+ * Stream ordering and the pending-sweep check are those of cspm_merge_planes.  The keys and winners (12 bytes per pixel of dst) are
+ * allocated by the first call, kept with dst's plane field and counted by CSPM_OPT_DEVICE_BYTES.  Timed as one CSPM_K_MISC bracket per
+ * view with w_s*h_s evaluations; the merge under CSPM_K_INIT.  CSPM_ERR_ARG as above, for dst == src and for two devices;
+ * CSPM_ERR_STATE when src has no plane field, dst no images, no plane field or no max_dis, and with merge when dst has no cost object. */
+int cspm_carry_planes(cspm_ctx *dst, cspm_ctx *src, const cspm_calib *src_calib, const cspm_calib *dst_calib, const double *R, const double *t,
+                      const cspm_carry_params *params, int merge);
+
 /* ---- rectification (an addition): a calibrated RAW pair undistorted and row-aligned on the device ----------------------
  * Every entry above that takes images assumes an undistorted, row-aligned pair, and cspm_reproject a cspm_calib of that pair.  This section
  * produces both from a rig description: two pinhole cameras with Brown-Conrady distortion and the pose of camera 1 in camera 0's frame.
