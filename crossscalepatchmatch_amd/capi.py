@@ -68,6 +68,8 @@ SYMBOLS = [
     "cspm_fuse_run", "cspm_fuse_run_device", "cspm_fuse_end",
     "cspm_reg_default_params", "cspm_fuse_register", "cspm_fuse_get_pose", "cspm_fuse_set_pose", "cspm_register_depth_maps",
     "cspm_carry_default_params", "cspm_carry_relative_pose", "cspm_carry_plane_field", "cspm_carry_planes",
+    "cspm_tsdf_default_params", "cspm_tsdf_begin", "cspm_tsdf_clear", "cspm_tsdf_integrate", "cspm_tsdf_raycast", "cspm_tsdf_raycast_device",
+    "cspm_tsdf_raycast_push", "cspm_tsdf_points", "cspm_tsdf_points_device", "cspm_tsdf_get_volume", "cspm_tsdf_end", "cspm_tsdf_depth_maps",
     "cspm_rect_default_params", "cspm_rectify_compute", "cspm_rectify_host", "cspm_set_rectification", "cspm_get_rect_map",
     "cspm_set_images_raw", "cspm_set_images_raw_device",
 ]
@@ -150,6 +152,17 @@ REG_ITER = np.dtype(dict(names=["pairs", "cost", "rot2", "trans2", "status"], fo
                          itemsize=40))  # RegIter as a numpy record
 
 
+class TsdfParams(C.Structure):
+    """struct cspm_tsdf_params"""
+    _fields_ = [("origin", C.c_double * 3), ("voxel", C.c_double), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("trunc", C.c_double),
+                ("max_weight", C.c_double), ("min_cos", C.c_double), ("step_rel", C.c_double)]
+
+
+class TsdfCamera(C.Structure):
+    """struct cspm_tsdf_camera: a pinhole camera and its camera -> world pose"""
+    _fields_ = [("f", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3)]
+
+
 class CarryParams(C.Structure):
     """struct cspm_carry_params"""
     _fields_ = [("fill", C.c_int)]
@@ -220,6 +233,7 @@ def load_library():
     mshp = C.POINTER(MeshParams)
     rgp, rpp, rcp = C.POINTER(Rig), C.POINTER(RectParams), C.POINTER(Rectification)
     fup, fuv = C.POINTER(FuseParams), C.POINTER(FuseView)
+    tsp, tcp = C.POINTER(TsdfParams), C.POINTER(TsdfCamera)
     rgpp, rgip = C.POINTER(RegParams), C.POINTER(RegIter)
     cyp = C.POINTER(CarryParams)
     sig = {
@@ -324,6 +338,18 @@ def load_library():
         "cspm_fuse_run": (C.c_int, [vp, fup, vp, C.c_size_t, up, up, u8p]),
         "cspm_fuse_run_device": (C.c_int, [vp, fup, vp, C.c_size_t, vp, vp, vp]),
         "cspm_fuse_end": (C.c_int, [vp]),
+        "cspm_tsdf_default_params": (C.c_int, [tsp]),
+        "cspm_tsdf_begin": (C.c_int, [vp, tsp]),
+        "cspm_tsdf_clear": (C.c_int, [vp]),
+        "cspm_tsdf_integrate": (C.c_int, [vp, C.c_int]),
+        "cspm_tsdf_raycast": (C.c_int, [vp, tcp, C.c_int, C.c_int, C.c_double, dp, dp, u8p, C.c_size_t, u8p]),
+        "cspm_tsdf_raycast_device": (C.c_int, [vp, tcp, C.c_int, C.c_int, C.c_double, vp, vp, vp, C.c_size_t, vp]),
+        "cspm_tsdf_raycast_push": (C.c_int, [vp, tcp, C.c_double]),
+        "cspm_tsdf_points": (C.c_int, [vp, vp, C.c_size_t, up]),
+        "cspm_tsdf_points_device": (C.c_int, [vp, vp, C.c_size_t, vp]),
+        "cspm_tsdf_get_volume": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u8p]),
+        "cspm_tsdf_end": (C.c_int, [vp]),
+        "cspm_tsdf_depth_maps": (C.c_int, [C.c_int, tsp, fuv, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, up, C.POINTER(C.c_float), C.POINTER(C.c_float), u8p]),
         "cspm_reg_default_params": (C.c_int, [rgpp]),
         "cspm_fuse_register": (C.c_int, [vp, C.c_int, C.c_ulonglong, rgpp, dp, dp, C.c_int, dp, dp, rgip]),
         "cspm_fuse_get_pose": (C.c_int, [vp, C.c_int, dp, dp]),
@@ -942,6 +968,72 @@ class StereoContext:
         R, t = _pose(R, t)
         self._chk(self.L.cspm_fuse_set_pose(self.p, int(slot), _dp(R), _dp(t)))
 
+    # ---- TSDF fusion ----
+    def tsdf_begin(self, origin, voxel, dims, **params):
+        """a cleared volume of dims = (nx, ny, nz) voxels of edge `voxel` with the world corner `origin`, kept until tsdf_end
+        (cspm_tsdf_begin); params: trunc, max_weight, min_cos, step_rel"""
+        p = tsdf_params(origin, voxel, dims, **params)
+        self._chk(self.L.cspm_tsdf_begin(self.p, C.byref(p)))
+        self._tsdf = (p.nx, p.ny, p.nz)
+
+    def tsdf_clear(self):
+        self._chk(self.L.cspm_tsdf_clear(self.p))
+
+    def tsdf_integrate(self, slot):
+        """one fusion view into the volume (cspm_tsdf_integrate); asynchronous on the context's stream"""
+        self._chk(self.L.cspm_tsdf_integrate(self.p, int(slot)))
+
+    def tsdf_raycast(self, camera, w, h, z_near=0.0, outputs=("depth", "normal", "bgr", "status"), out=None):
+        """the volume seen from `camera` (a dict with f, cx, cy, R, t) as w x h maps (cspm_tsdf_raycast): a dict of the requested outputs
+        depth (h, w) f64, normal (3, h, w) f64, bgr (h, w, 3) uint8, status (h, w) uint8.  out: preallocated arrays to write into."""
+        k = tsdf_camera(camera)
+        res = _ray_outputs(int(h), int(w), outputs, out)
+        self._chk(self.L.cspm_tsdf_raycast(self.p, C.byref(k), int(w), int(h), float(z_near), _opt(_dp, res.get("depth")), _opt(_dp, res.get("normal")),
+                                           _opt(_u8, res.get("bgr")), 3 * int(w), _opt(_u8, res.get("status"))))
+        return res
+
+    def tsdf_raycast_device(self, camera, w, h, z_near=0.0, d_depth=0, d_normal=0, d_bgr=0, stride=0, d_status=0):
+        """the same with device pointers (integers; 0 = not requested); asynchronous (cspm_tsdf_raycast_device)"""
+        k = tsdf_camera(camera)
+        self._chk(self.L.cspm_tsdf_raycast_device(self.p, C.byref(k), int(w), int(h), float(z_near), _dev(d_depth), _dev(d_normal), _dev(d_bgr), int(stride),
+                                                  _dev(d_status)))
+
+    def tsdf_raycast_push(self, camera, z_near=0.0):
+        """a raycast at the fusion views' size into the next fusion slot (cspm_tsdf_raycast_push); asynchronous"""
+        k = tsdf_camera(camera)
+        self._chk(self.L.cspm_tsdf_raycast_push(self.p, C.byref(k), float(z_near)))
+
+    def tsdf_points(self, cloud=True, cloud_cap=None, out=None):
+        """the surface points (cspm_tsdf_points): dict(count, cloud: the Point records in (voxel, axis) order, at most cloud_cap; None = all).
+        out: a dict with a preallocated cloud_buffer to write into (tests poison it)."""
+        nx, ny, nz = self._tsdf
+        cap = 3 * nx * ny * nz if cloud_cap is None else int(cloud_cap)
+        pts = None
+        if cloud:
+            pts = (out or {}).get("cloud_buffer")
+            if pts is None:
+                pts = np.zeros(cap, Point)
+        cnt = C.c_uint(0)
+        self._chk(self.L.cspm_tsdf_points(self.p, _opt(_vp, pts), cap if cloud else 0, C.byref(cnt)))
+        res = dict(count=cnt.value)
+        if cloud:
+            res["cloud"] = pts[:min(cnt.value, cap)]
+        return res
+
+    def tsdf_points_device(self, d_cloud=0, cloud_cap=0, d_count=0):
+        self._chk(self.L.cspm_tsdf_points_device(self.p, _dev(d_cloud), int(cloud_cap), _dev(d_count)))
+
+    def tsdf_volume(self):
+        """-> dict(D, W: (nz, ny, nx) float32, C: (nz, ny, nx, 4) uint8 = b, g, r, has) (cspm_tsdf_get_volume)"""
+        nx, ny, nz = self._tsdf
+        D, W, Cc = np.zeros((nz, ny, nx), np.float32), np.zeros((nz, ny, nx), np.float32), np.zeros((nz, ny, nx, 4), np.uint8)
+        fp = C.POINTER(C.c_float)
+        self._chk(self.L.cspm_tsdf_get_volume(self.p, D.ctypes.data_as(fp), W.ctypes.data_as(fp), _u8(Cc)))
+        return dict(D=D, W=W, C=Cc)
+
+    def tsdf_end(self):
+        self._chk(self.L.cspm_tsdf_end(self.p))
+
     # ---- view synthesis (DESIGN.md section 20) ----
     def synthesize(self, t, source=GEOM_RAW, outputs=("bgr", "disp", "mask"), out=None, **params):
         """the scene from the camera at fraction t of the baseline (0 = view 0, 1 = view 1), rendered from the stored plane field and the
@@ -1269,6 +1361,70 @@ def fuse_depth_maps(views, w, h, cloud=True, cloud_cap=None, state=True, device=
         res["cloud"] = pts[:min(cnt.value, cap)]
     if S is not None:
         res["state"] = S
+    return res
+
+
+def tsdf_params(origin, voxel, dims, **params):
+    """struct cspm_tsdf_params: cspm_tsdf_default_params with the volume and the given fields (trunc, max_weight, min_cos, step_rel)"""
+    p = _params(TsdfParams, "tsdf", "TSDF", params)
+    p.origin = (C.c_double * 3)(*(float(o) for o in origin))
+    p.voxel = float(voxel)
+    p.nx, p.ny, p.nz = (int(d) for d in dims)
+    return p
+
+
+def tsdf_camera(camera):
+    """struct cspm_tsdf_camera from a dict with f, cx, cy, R (3, 3), t (3,)"""
+    R, t = _pose(camera["R"], camera["t"])
+    return TsdfCamera(float(camera["f"]), float(camera["cx"]), float(camera["cy"]), (C.c_double * 9)(*R), (C.c_double * 3)(*t))
+
+
+def _ray_outputs(h, w, outputs, out):
+    shapes = dict(depth=((h, w), np.float64), normal=((3, h, w), np.float64), bgr=((h, w, 3), np.uint8), status=((h, w), np.uint8))
+    res = {}
+    for name in outputs:
+        shape, dtype = shapes[name]
+        a = (out or {}).get(name)
+        res[name] = np.zeros(shape, dtype) if a is None else a
+        assert res[name].shape == shape and res[name].dtype == dtype and res[name].flags.c_contiguous, name
+    return res
+
+
+def tsdf_depth_maps(views, w, h, origin, voxel, dims, cloud=True, cloud_cap=None, volume=True, device=0, out=None, **params):
+    """T alone on host maps (cspm_tsdf_depth_maps): the views (dicts as for fuse_depth_maps) integrated in list order
+    into a cleared volume, then its surface points.  Returns dict(count, cloud, D, W, C) as StereoContext.tsdf_points and tsdf_volume
+    return them.  out: a dict with preallocated cloud_buffer, D, W, C to write into (tests poison them)."""
+    K = len(views)
+    p = tsdf_params(origin, voxel, dims, **params)
+    arr = (FuseView * max(K, 1))()
+    keep = []
+    for k, v in enumerate(views):
+        d, n, img = _fuse_maps(v["depth"], v.get("normal"), v.get("bgr"), w, h)
+        R, t = _pose(v["R"], v["t"])
+        keep.append((d, n, img))
+        arr[k] = FuseView(_dp(d), _opt(_dp, n), _opt(_u8, img), 3 * w, float(v["f"]), float(v["cx"]), float(v["cy"]), (C.c_double * 9)(*R), (C.c_double * 3)(*t))
+    nx, ny, nz = p.nx, p.ny, p.nz
+    nvox = max(nx, 0) * max(ny, 0) * max(nz, 0)
+    cap = 3 * nvox if cloud_cap is None else int(cloud_cap)
+    pts = None
+    if cloud:
+        pts = (out or {}).get("cloud_buffer")
+        if pts is None:
+            pts = np.zeros(cap, Point)
+    vol = {}
+    if volume:
+        for name, shape, dtype in (("D", (nz, ny, nx), np.float32), ("W", (nz, ny, nx), np.float32), ("C", (nz, ny, nx, 4), np.uint8)):
+            a = (out or {}).get(name)
+            vol[name] = np.zeros(tuple(max(s, 0) for s in shape), dtype) if a is None else a
+    cnt = C.c_uint(0)
+    fp = C.POINTER(C.c_float)
+    _check(load_library().cspm_tsdf_depth_maps(device, C.byref(p), arr, K, w, h, _opt(_vp, pts), cap if cloud else 0, C.byref(cnt),
+                                               vol["D"].ctypes.data_as(fp) if volume else None, vol["W"].ctypes.data_as(fp) if volume else None,
+                                               _u8(vol["C"]) if volume else None))
+    del keep
+    res = dict(count=cnt.value, **vol)
+    if cloud:
+        res["cloud"] = pts[:min(cnt.value, cap)]
     return res
 
 

@@ -22,6 +22,7 @@
 #include "cspm_geom.h"
 #include "cspm_mesh.h"
 #include "cspm_fuse.h"
+#include "cspm_tsdf.h"
 #include "cspm_register.h"
 #include "cspm_carry.h"
 #include "cspm_synth.h"
@@ -150,6 +151,7 @@ struct cspm_ctx {
   DevPool mem_field{dev_alloc, dev_free};   // the plane field and what is "kept with the field": until free_field
   DevPool mem_rect{dev_alloc, dev_free};    // the rectification: until free_rect
   DevPool mem_ca{dev_alloc, dev_free};      // local-stereo scratch: until ca_ensure meets a new key or the geometry changes
+  DevPool mem_tsdf{dev_alloc, dev_free};    // the TSDF volume: from cspm_tsdf_begin until cspm_tsdf_end, whatever the fusion views do
   DevPool mem_fuse{dev_alloc, dev_free};    // the fusion views: from cspm_fuse_begin until cspm_fuse_end, whatever the geometry does
   // images
   int W = 0, H = 0;
@@ -237,6 +239,7 @@ struct cspm_ctx {
   // depth-map fusion (cspm_fuse_*): the slots of max_views views of fuse_w x fuse_h, kept in mem_fuse
   bool fuse_on = false;
   int fuse_w = 0, fuse_h = 0, fuse_max = 0, fuse_views = 0;
+  unsigned long long fuse_image_mask = 0;          // bit k: view k came with an image
   bool fuse_normals = false, fuse_images = false;  // the views pushed so far carry normals / at least one of them an image
   double *fuse_depth = nullptr, *fuse_normal = nullptr;  // per view w*h depths; three planes of w*h normals
   uint32_t *fuse_pix = nullptr;                          // per view w*h packed pixels, 0 in a view without an image
@@ -244,6 +247,11 @@ struct cspm_ctx {
   FuseCam *fuse_cams = nullptr;                          // the camera table
   std::vector<FuseCam> fuse_cams_host;                   // ... and the host's copy of it, max_views rows
   double *reg_mem = nullptr;                             // registration scratch (cspm_fuse_register): partials, pose row, records; allocated by the first call
+  // TSDF fusion (cspm_tsdf_*): the volume's three planes and the extraction's counts, kept in mem_tsdf
+  bool tsdf_on = false, tsdf_coloured = false;           // coloured: a view with an image has been integrated since the last clear
+  TsdfVol tsdf{};
+  long long tsdf_nvox = 0;
+  unsigned int *tsdf_counts = nullptr;                   // crossings per workgroup, then the total
   unsigned int *fuse_counts = nullptr;                   // kept pixels per workgroup of every pass, the total, the kept pixels per view
   // rectification (cspm_set_rectification): kept until the context goes or the rectification is dropped
   bool rect_on = false;
@@ -2360,6 +2368,7 @@ int fuse_begin(cspm_ctx *c, int w, int h, int max_views) {
   c->fuse_on = true;
   c->fuse_w = w; c->fuse_h = h; c->fuse_max = max_views; c->fuse_views = 0;
   c->fuse_normals = c->fuse_images = false;
+  c->fuse_image_mask = 0ull;
   return CSPM_OK;
 }
 void fuse_release(cspm_ctx *c) {
@@ -2384,6 +2393,7 @@ int fuse_slot_commit(cspm_ctx *c, bool normals, bool image, double f, double cx,
   HIPCHK(c, hipMemcpyAsync(c->fuse_cams + c->fuse_views, &cam, sizeof cam, hipMemcpyHostToDevice, c->stream));
   c->fuse_normals = normals;
   c->fuse_images = c->fuse_images || image;
+  if (image) c->fuse_image_mask |= 1ull << c->fuse_views;
   c->fuse_views += 1;
   return CSPM_OK;
 }
@@ -2462,6 +2472,174 @@ int fuse_run(cspm_ctx *c, const cspm_fuse_params *p, cspm_point *cloud_out, size
   if (S.finish("fusion download failed")) return S.rc;
   if (count_out) *count_out = total;
   return CSPM_OK;
+}
+
+// ---- TSDF fusion (cspm_tsdf.h) -------------------------------------------------------------------------------
+static_assert(sizeof(cspm_tsdf_camera) == sizeof(FuseCam), "a raycast camera is a row of the camera table");
+const cspm_tsdf_params kTsdfDefaults = {{0.0, 0.0, 0.0}, 0.0, 0, 0, 0, 0.0, 64.0, 0.0, 0.5};
+const char *tsdf_params_error(const cspm_tsdf_params *p) {
+  if (!p) return "tsdf: no parameters";
+  if (!(std::isfinite(p->origin[0]) && std::isfinite(p->origin[1]) && std::isfinite(p->origin[2]) && std::isfinite(p->voxel) && p->voxel > 0.0))
+    return "tsdf: the origin must be finite and voxel finite and > 0";
+  if (p->nx < 1 || p->ny < 1 || p->nz < 1) return "tsdf: nx, ny and nz must be at least 1";
+  if ((long long)p->nx * p->ny >= (1LL << 31) || (long long)p->nx * p->ny * p->nz >= (1LL << 31)) return "tsdf: nx * ny * nz must be below 2^31";
+  if (!(std::isfinite(p->trunc) && p->trunc >= 0.0)) return "tsdf: trunc must be finite and > 0 (0 = 4 * voxel)";
+  if (!(p->max_weight >= 1.0 && p->max_weight <= 16777216.0)) return "tsdf: max_weight must be in [1, 16777216]";
+  if (!(p->min_cos >= 0.0 && p->min_cos <= 1.0)) return "tsdf: min_cos must be in [0, 1]";
+  if (!(p->step_rel > 0.0 && p->step_rel <= 1.0)) return "tsdf: step_rel must be in (0, 1]";
+  return nullptr;
+}
+const char *tsdf_camera_error(const cspm_tsdf_camera *k, double z_near) {
+  if (!k) return "tsdf: no camera";
+  if (const char *msg = fuse_camera_error(k->f, k->cx, k->cy, k->R, k->t)) return msg;
+  if (!(std::isfinite(z_near) && z_near >= 0.0)) return "tsdf: z_near must be finite and >= 0";
+  return nullptr;
+}
+inline FuseCam tsdf_cam(const cspm_tsdf_camera *k) {
+  FuseCam cam;
+  cam.f = k->f; cam.cx = k->cx; cam.cy = k->cy;
+  for (int i = 0; i < 9; ++i) cam.R[i] = k->R[i];
+  for (int i = 0; i < 3; ++i) cam.t[i] = k->t[i];
+  return cam;
+}
+inline unsigned tsdf_blocks(long long nvox) { return (unsigned)((nvox + kTsdfBlock - 1) / kTsdfBlock); }
+
+int tsdf_clear(cspm_ctx *c) {
+  hipLaunchKernelGGL(k_tsdf_clear, dim3(tsdf_blocks(c->tsdf_nvox)), dim3(kTsdfBlock), 0, c->stream, c->tsdf, c->tsdf_nvox);
+  HIPCHK(c, hipGetLastError());
+  c->tsdf_coloured = false;
+  return CSPM_OK;
+}
+void tsdf_release(cspm_ctx *c) {
+  c->mem_tsdf.release();
+  c->tsdf_on = c->tsdf_coloured = false;
+  c->tsdf = TsdfVol{};
+  c->tsdf_nvox = 0;
+}
+int tsdf_begin(cspm_ctx *c, const cspm_tsdf_params *p) {
+  if (const char *msg = tsdf_params_error(p)) return fail(c, CSPM_ERR_ARG, msg);
+  if (c->tsdf_on) return fail(c, CSPM_ERR_STATE, "tsdf: cspm_tsdf_begin twice without cspm_tsdf_end");
+  const size_t nvox = (size_t)p->nx * p->ny * p->nz;
+  TsdfVol &V = c->tsdf;  // its three pointers are the pool's slots
+  int rc;
+  if ((rc = dalloc(c, c->mem_tsdf, &V.D, nvox)) || (rc = dalloc(c, c->mem_tsdf, &V.W, nvox)) || (rc = dalloc(c, c->mem_tsdf, &V.C, nvox)) ||
+      (rc = dalloc(c, c->mem_tsdf, &c->tsdf_counts, (size_t)tsdf_blocks((long long)nvox) + 1))) {
+    c->mem_tsdf.release();
+    return rc;
+  }
+  for (int a = 0; a < 3; ++a) V.origin[a] = p->origin[a];
+  V.voxel = p->voxel;
+  V.trunc = p->trunc == 0.0 ? 4.0 * p->voxel : p->trunc;
+  V.max_weight = p->max_weight;
+  V.min_cos = p->min_cos;
+  V.step = p->step_rel * V.trunc;
+  V.nx = p->nx; V.ny = p->ny; V.nz = p->nz;
+  c->tsdf_nvox = (long long)nvox;
+  c->tsdf_on = true;
+  if ((rc = tsdf_clear(c))) tsdf_release(c);
+  return rc;
+}
+int tsdf_state_check(cspm_ctx *c) { return c->tsdf_on ? CSPM_OK : fail(c, CSPM_ERR_STATE, "tsdf: cspm_tsdf_begin first"); }
+
+// one fusion slot into the volume
+int tsdf_integrate(cspm_ctx *c, int slot) {
+  if (int rc = tsdf_state_check(c)) return rc;
+  if (!c->fuse_on) return fail(c, CSPM_ERR_STATE, "fusion: cspm_fuse_begin first");
+  if (slot < 0 || slot >= c->fuse_views) return fail(c, CSPM_ERR_STATE, "tsdf: no such fusion view");
+  const int w = c->fuse_w, h = c->fuse_h;
+  const long long n = (long long)w * h;
+  const double *depth = c->fuse_depth + (size_t)slot * n, *normal = c->fuse_normal + (size_t)slot * 3 * n;
+  const uint32_t *pix = c->fuse_pix + (size_t)slot * n;
+  const bool normals = c->fuse_normals && c->tsdf.min_cos > 0.0, colour = ((c->fuse_image_mask >> slot) & 1ull) != 0;
+  {
+    Timed t(c, CSPM_K_MISC, c->tsdf_nvox);
+    const dim3 grid(tsdf_blocks(c->tsdf_nvox)), block(kTsdfBlock);
+#define TSDF_INTEGRATE(N, I) \
+  hipLaunchKernelGGL((k_tsdf_integrate<N, I>), grid, block, 0, c->stream, (const FuseCam *)c->fuse_cams, slot, depth, normal, pix, w, h, n, c->tsdf, c->tsdf_nvox)
+    if (normals && colour) TSDF_INTEGRATE(true, true);
+    else if (normals) TSDF_INTEGRATE(true, false);
+    else if (colour) TSDF_INTEGRATE(false, true);
+    else TSDF_INTEGRATE(false, false);
+#undef TSDF_INTEGRATE
+  }
+  HIPCHK(c, hipGetLastError());
+  c->tsdf_coloured = c->tsdf_coloured || colour;
+  return CSPM_OK;
+}
+
+// a raycast into device outputs
+int tsdf_raycast_enqueue(cspm_ctx *c, const FuseCam &cam, int w, int h, double z_near, const TsdfRayOut &out) {
+  {
+    Timed t(c, CSPM_K_MISC, (long long)w * h);
+    hipLaunchKernelGGL(k_tsdf_raycast, dim3((unsigned)((w + kTsdfTileW - 1) / kTsdfTileW), (unsigned)((h + kTsdfTileH - 1) / kTsdfTileH)), dim3(kTsdfBlock), 0,
+                       c->stream, cam, c->tsdf, w, h, z_near, out);
+  }
+  HIPCHK(c, hipGetLastError());
+  return CSPM_OK;
+}
+int tsdf_raycast_check(cspm_ctx *c, const cspm_tsdf_camera *k, int w, int h, double z_near, bool bgr, size_t stride) {
+  if (const char *msg = tsdf_camera_error(k, z_near)) return fail(c, CSPM_ERR_ARG, msg);
+  if (const char *msg = fuse_size_error(w, h)) return fail(c, CSPM_ERR_ARG, msg);
+  if ((h + kTsdfTileH - 1) / kTsdfTileH > 65535) return fail(c, CSPM_ERR_ARG, "tsdf: h must be at most 524280");
+  if (bgr && stride < (size_t)w * 3) return fail(c, CSPM_ERR_ARG, "tsdf: stride is below 3 * w");
+  return tsdf_state_check(c);
+}
+int tsdf_raycast_host(cspm_ctx *c, const cspm_tsdf_camera *k, int w, int h, double z_near, double *depth_out, double *normal_out, uint8_t *bgr_out,
+                      size_t stride, uint8_t *status_out) {
+  const size_t n = (size_t)w * h;
+  Staging S(c);
+  TsdfRayOut out{};
+  out.depth = S.buf<double>(n, depth_out != nullptr);
+  out.normal = S.buf<double>(3 * n, normal_out != nullptr);
+  out.bgr = S.buf<uint8_t>(3 * n, bgr_out != nullptr);
+  out.bgr_stride = (size_t)w * 3;
+  out.status = S.buf<uint8_t>(n, status_out != nullptr);
+  if (S.rc) return S.finish();
+  if (int rc = tsdf_raycast_enqueue(c, tsdf_cam(k), w, h, z_near, out)) return rc;
+  S.down(depth_out, out.depth, n);
+  S.down(normal_out, out.normal, 3 * n);
+  S.down2d(bgr_out, stride, out.bgr, (size_t)w * 3, (size_t)h);
+  S.down(status_out, out.status, n);
+  return S.finish("tsdf: the raycast failed");
+}
+
+// the surface points; every output a device pointer or null
+int tsdf_points_enqueue(cspm_ctx *c, uint4 *cloud, size_t cap, unsigned int *d_count) {
+  const unsigned nb = tsdf_blocks(c->tsdf_nvox);
+  unsigned int *counts = c->tsdf_counts, *total = d_count ? d_count : counts + nb;
+  {
+    Timed t(c, CSPM_K_MISC, c->tsdf_nvox);
+    hipLaunchKernelGGL(k_tsdf_count, dim3(nb), dim3(kTsdfBlock), 0, c->stream, c->tsdf, c->tsdf_nvox, counts);
+    hipLaunchKernelGGL(k_geom_scan, dim3(1), dim3(kGeomScanBlock), 0, c->stream, counts, (int)nb, total);
+    const unsigned int cap32 = (unsigned int)std::min<size_t>(cap, 0xFFFFFFFFull);
+    if (cloud && cap32 != 0)
+      hipLaunchKernelGGL(k_tsdf_points, dim3(nb), dim3(kTsdfBlock), 0, c->stream, c->tsdf, c->tsdf_nvox, (const unsigned int *)counts, cloud, cap32);
+  }
+  HIPCHK(c, hipGetLastError());
+  return CSPM_OK;
+}
+int tsdf_points_host(cspm_ctx *c, cspm_point *cloud_out, size_t cloud_cap, unsigned int *count_out) {
+  const unsigned nb = tsdf_blocks(c->tsdf_nvox);
+  const size_t cap = std::min(cloud_out ? cloud_cap : (size_t)0, 3 * (size_t)c->tsdf_nvox);
+  unsigned int total = 0;  // in front of the Staging: a download writes it
+  Staging S(c);
+  uint4 *dcloud = S.buf<uint4>(2 * cap, cap != 0);
+  if (S.rc) return S.finish();
+  if (int rc = tsdf_points_enqueue(c, dcloud, cap, nullptr)) return rc;
+  S.down(&total, c->tsdf_counts + nb, 1);
+  if (S.finish("tsdf: the extraction failed")) return S.rc;
+  S.down(cloud_out, dcloud, std::min((size_t)total, cap));
+  if (S.finish("tsdf: the download failed")) return S.rc;
+  if (count_out) *count_out = total;
+  return CSPM_OK;
+}
+int tsdf_get_volume(cspm_ctx *c, float *D_out, float *W_out, uint8_t *colour_out) {
+  const size_t nvox = (size_t)c->tsdf_nvox;
+  Staging S(c);
+  S.down(D_out, c->tsdf.D, nvox);
+  S.down(W_out, c->tsdf.W, nvox);
+  S.down(reinterpret_cast<uint32_t *>(colour_out), c->tsdf.C, nvox);
+  return S.finish("tsdf: the download failed");
 }
 
 // ---- depth-view registration (cspm_register.h) ---------------------------------------------------------------
@@ -2645,6 +2823,7 @@ void cspm_destroy(cspm_ctx *c) {
   free_geometry(c);
   free_rect(c);
   fuse_release(c);
+  tsdf_release(c);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
 }
@@ -2795,7 +2974,7 @@ int cspm_get_option(cspm_ctx *c, int key, long long *value) {
     case CSPM_OPT_SWEEP_TIMEOUT_MS: *value = c->sweep_timeout_ms; return CSPM_OK;
     case CSPM_OPT_SWEEP_FALLBACKS: *value = c->sweep_fallbacks; return CSPM_OK;
     case CSPM_OPT_DEVICE_BYTES:
-      *value = (long long)(c->mem_images.bytes() + c->mem_cost.bytes() + c->mem_field.bytes() + c->mem_rect.bytes() + c->mem_ca.bytes() + c->mem_fuse.bytes());
+      *value = (long long)(c->mem_images.bytes() + c->mem_cost.bytes() + c->mem_field.bytes() + c->mem_rect.bytes() + c->mem_ca.bytes() + c->mem_fuse.bytes() + c->mem_tsdf.bytes());
       return CSPM_OK;
     case CSPM_OPT_SWEEP_PAIRS: *value = c->opt_sweep_pairs; return CSPM_OK;
     case CSPM_OPT_TABLE_VOLUMES: *value = c->opt_table_volumes; return CSPM_OK;
@@ -3892,6 +4071,130 @@ int cspm_fuse_depth_maps(int device, const cspm_fuse_params *p, const cspm_fuse_
   if (!rc) rc = fuse_run(S.c, p, cloud_out, cloud_cap, count_out, view_counts_out, state_out);
   S.latch(rc);
   return S.finish("fusion failed");
+}
+
+// T: the TSDF volume of a context, and the one-shot form on caller maps
+int cspm_tsdf_default_params(cspm_tsdf_params *p) {
+  if (!p) return CSPM_ERR_ARG;
+  *p = kTsdfDefaults;
+  return CSPM_OK;
+}
+
+int cspm_tsdf_begin(cspm_ctx *c, const cspm_tsdf_params *p) {
+  if (!c) return CSPM_ERR_ARG;
+  ON_DEVICE(c);
+  return tsdf_begin(c, p);
+}
+
+int cspm_tsdf_clear(cspm_ctx *c) {
+  if (!c) return CSPM_ERR_ARG;
+  if (int rc = tsdf_state_check(c)) return rc;
+  ON_DEVICE(c);
+  return tsdf_clear(c);
+}
+
+int cspm_tsdf_integrate(cspm_ctx *c, int slot) {
+  if (!c) return CSPM_ERR_ARG;
+  ON_DEVICE(c);
+  return tsdf_integrate(c, slot);
+}
+
+int cspm_tsdf_raycast(cspm_ctx *c, const cspm_tsdf_camera *camera, int w, int h, double z_near, double *depth_out, double *normal_out, uint8_t *bgr_out,
+                      size_t stride, uint8_t *status_out) {
+  if (!c) return CSPM_ERR_ARG;
+  if (int rc = tsdf_raycast_check(c, camera, w, h, z_near, bgr_out != nullptr, stride)) return rc;
+  ON_DEVICE(c);
+  return tsdf_raycast_host(c, camera, w, h, z_near, depth_out, normal_out, bgr_out, stride, status_out);
+}
+
+int cspm_tsdf_raycast_device(cspm_ctx *c, const cspm_tsdf_camera *camera, int w, int h, double z_near, void *d_depth_out, void *d_normal_out,
+                             void *d_bgr_out, size_t stride, void *d_status_out) {
+  if (!c) return CSPM_ERR_ARG;
+  if (int rc = tsdf_raycast_check(c, camera, w, h, z_near, d_bgr_out != nullptr, stride)) return rc;
+  if (((uintptr_t)d_depth_out & 7u) || ((uintptr_t)d_normal_out & 7u)) return fail(c, CSPM_ERR_ARG, "tsdf: the depth and normal maps must be 8-byte aligned");
+  ON_DEVICE(c);
+  TsdfRayOut out{};
+  out.depth = (double *)d_depth_out;
+  out.normal = (double *)d_normal_out;
+  out.bgr = (uint8_t *)d_bgr_out;
+  out.bgr_stride = stride;
+  out.status = (uint8_t *)d_status_out;
+  return tsdf_raycast_enqueue(c, tsdf_cam(camera), w, h, z_near, out);
+}
+
+int cspm_tsdf_raycast_push(cspm_ctx *c, const cspm_tsdf_camera *camera, double z_near) {
+  if (!c) return CSPM_ERR_ARG;
+  if (const char *msg = tsdf_camera_error(camera, z_near)) return fail(c, CSPM_ERR_ARG, msg);
+  if (int rc = tsdf_state_check(c)) return rc;
+  if (int rc = fuse_slot_check(c, true, camera->f, camera->cx, camera->cy, camera->R, camera->t)) return rc;
+  if ((c->fuse_h + kTsdfTileH - 1) / kTsdfTileH > 65535) return fail(c, CSPM_ERR_ARG, "tsdf: h must be at most 524280");
+  ON_DEVICE(c);
+  const size_t n = (size_t)c->fuse_w * c->fuse_h, k = (size_t)c->fuse_views;
+  TsdfRayOut out{};
+  out.depth = c->fuse_depth + k * n;
+  out.normal = c->fuse_normal + k * 3 * n;
+  out.pix = c->fuse_pix + k * n;
+  if (int rc = tsdf_raycast_enqueue(c, tsdf_cam(camera), c->fuse_w, c->fuse_h, z_near, out)) return rc;
+  return fuse_slot_commit(c, true, c->tsdf_coloured, camera->f, camera->cx, camera->cy, camera->R, camera->t);
+}
+
+int cspm_tsdf_points(cspm_ctx *c, cspm_point *cloud_out, size_t cloud_cap, unsigned int *count_out) {
+  if (!c) return CSPM_ERR_ARG;
+  if (int rc = tsdf_state_check(c)) return rc;
+  ON_DEVICE(c);
+  return tsdf_points_host(c, cloud_out, cloud_cap, count_out);
+}
+
+int cspm_tsdf_points_device(cspm_ctx *c, void *d_cloud_out, size_t cloud_cap, void *d_count_out) {
+  if (!c) return CSPM_ERR_ARG;
+  if (int rc = tsdf_state_check(c)) return rc;
+  if (d_cloud_out && ((uintptr_t)d_cloud_out & 15u)) return fail(c, CSPM_ERR_ARG, "tsdf: the cloud buffer must be 16-byte aligned");
+  if ((uintptr_t)d_count_out & 3u) return fail(c, CSPM_ERR_ARG, "tsdf: the count must be 4-byte aligned");
+  ON_DEVICE(c);
+  return tsdf_points_enqueue(c, (uint4 *)d_cloud_out, d_cloud_out ? cloud_cap : 0, (unsigned int *)d_count_out);
+}
+
+int cspm_tsdf_get_volume(cspm_ctx *c, float *D_out, float *W_out, uint8_t *colour_out) {
+  if (!c) return CSPM_ERR_ARG;
+  if (int rc = tsdf_state_check(c)) return rc;
+  ON_DEVICE(c);
+  return tsdf_get_volume(c, D_out, W_out, colour_out);
+}
+
+int cspm_tsdf_end(cspm_ctx *c) {
+  if (!c) return CSPM_ERR_ARG;
+  if (int rc = tsdf_state_check(c)) return rc;
+  ON_DEVICE(c);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  tsdf_release(c);
+  return CSPM_OK;
+}
+
+int cspm_tsdf_depth_maps(int device, const cspm_tsdf_params *p, const cspm_fuse_view *views, int n_views, int w, int h, cspm_point *cloud_out, size_t cloud_cap,
+                         unsigned int *count_out, float *D_out, float *W_out, uint8_t *colour_out) {
+  if (const char *msg = tsdf_params_error(p)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  if (n_views < 1 || n_views > kFuseMaxViews) return fail(nullptr, CSPM_ERR_ARG, "fusion: the number of views must be in 1 .. 64");
+  if (!views) return fail(nullptr, CSPM_ERR_ARG, "fusion: no views");
+  if (const char *msg = fuse_size_error(w, h)) return fail(nullptr, CSPM_ERR_ARG, msg);
+  for (int k = 0; k < n_views; ++k) {
+    const cspm_fuse_view &v = views[k];
+    if (const char *msg = fuse_camera_error(v.f, v.cx, v.cy, v.R, v.t)) return fail(nullptr, CSPM_ERR_ARG, msg);
+    if (const char *msg = fuse_maps_error(v.depth, v.bgr, v.bgr_stride, w)) return fail(nullptr, CSPM_ERR_ARG, msg);
+    if ((v.normal != nullptr) != (views[0].normal != nullptr)) return fail(nullptr, CSPM_ERR_ARG, "fusion: normals in some views but not all");
+  }
+  OneShot S(device);
+  if (S.rc) return S.finish();
+  int rc = fuse_begin(S.c, w, h, n_views);
+  if (!rc) rc = tsdf_begin(S.c, p);
+  for (int k = 0; k < n_views && !rc; ++k) {
+    const cspm_fuse_view &v = views[k];
+    rc = fuse_push_maps(S.c, v.depth, v.normal, v.bgr, v.bgr_stride, v.f, v.cx, v.cy, v.R, v.t);
+    if (!rc) rc = tsdf_integrate(S.c, k);
+  }
+  if (!rc) rc = tsdf_points_host(S.c, cloud_out, cloud_cap, count_out);
+  if (!rc) rc = tsdf_get_volume(S.c, D_out, W_out, colour_out);
+  S.latch(rc);
+  return S.finish("tsdf fusion failed");
 }
 
 // R: a fusion view registered against other fusion views, and the one-shot form on caller maps

@@ -79,6 +79,24 @@ class DepthFusion {
     return p;
   }
 
+  // the slots as the C ABI takes them (pointers into this object: valid until a view is set again), and their common size.  Throws for an
+  // unset slot and for views of different sizes.
+  std::vector<cspm_fuse_view> Views(int *w, int *h) const {
+    if (views_.empty()) throw std::runtime_error("DepthFusion::Views: no views");
+    std::vector<cspm_fuse_view> arr(views_.size());
+    for (size_t k = 0; k < views_.size(); ++k) {
+      const View &v = views_[k];
+      if (!v.set) throw std::runtime_error("DepthFusion::Views: a view is missing");
+      if (v.wid != views_[0].wid || v.hei != views_[0].hei) throw std::runtime_error("DepthFusion::Views: the views are not of one size");
+      arr[k] = AbiView(v);
+    }
+    *w = views_[0].wid;
+    *h = views_[0].hei;
+    return arr;
+  }
+  // pair i's left view takes (R, t) and its right view follows by the baseline (what Register does with a refined pose)
+  void SetPose(size_t i, int per_pair, const double *R, const double *t) { SetLeftPose(i, per_pair, R, t); }
+
   // F over the slots in their order.  Returns the number of kept pixels; cloud: the records in (slot, raster) order; view_counts: the
   // kept pixels per slot.  Throws for an unset slot, views of different sizes and for what the C ABI refuses.
   size_t Fuse(int device, const cspm_fuse_params &params, std::vector<cspm_point> *cloud, std::vector<unsigned int> *view_counts) const {

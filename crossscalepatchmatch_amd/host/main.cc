@@ -17,7 +17,9 @@
 // --fuse_poses_out --fuse_reg_iters --fuse_reg_stride --fuse_reg_max_dist --fuse_reg_huber (the poses of that fusion refined, or found
 // without --fuse_poses, by registering the views against each other; include/cspm.h "depth-view registration") --carry_poses --carry_iters
 // --carry_no_fill (with --batch_list and --calib or --rig: the list is one sequence of a moving rig, every pair starts from the previous
-// pair's plane field carried across the motion; include/cspm.h "plane-field carry").
+// pair's plane field carried across the motion; include/cspm.h "plane-field carry") --tsdf_ply --tsdf_origin --tsdf_dims --tsdf_voxel
+// --tsdf_trunc --tsdf_max_weight --tsdf_min_cos --tsdf_register (with the fusion flags: the same views integrated in list order into one
+// TSDF volume, its surface points written as PLY, and --fuse_register done frame to model; include/cspm.h "TSDF fusion").
 #include "../../include/cspm.h"
 #include "commfunc.h"
 #include "cs_patchmatch.h"
@@ -28,6 +30,7 @@
 #include "plane_cost/pre_ss_pc.h"
 #include "calib_io.h"
 #include "depth_fusion.h"
+#include "tsdf_volume.h"
 #include "pfm_io.h"
 #include "ply_io.h"
 #include "rig_io.h"
@@ -172,6 +175,17 @@ DEFINE_string(carry_poses, "", "with --batch_list and --calib (or --rig): the li
                                 "--carry_iters warm iterations");
 DEFINE_int32(carry_iters, 1, "with --carry_poses: warm PatchMatch iterations of every pair but the first, 0 .. 15");
 DEFINE_bool(carry_no_fill, false, "with --carry_poses: a pixel no carried plane lands on gets no candidate instead of a neighbour's plane");
+DEFINE_string(tsdf_ply, "", "with the fusion flags: the views the fusion collects are also integrated, in list order, into one TSDF volume "
+                           "(include/cspm.h \"TSDF fusion\") and its surface points are written in the format of --fuse_ply.  Needs --tsdf_origin, "
+                           "--tsdf_dims and --tsdf_voxel");
+DEFINE_string(tsdf_origin, "", "with --tsdf_ply: x,y,z, the world corner of voxel (0, 0, 0)");
+DEFINE_string(tsdf_dims, "", "with --tsdf_ply: nx,ny,nz, the number of voxels per axis");
+DEFINE_double(tsdf_voxel, 0.0, "with --tsdf_ply: the edge length of a voxel, in world units");
+DEFINE_double(tsdf_trunc, 0.0, "with --tsdf_ply: the truncation distance (0 = 4 voxels)");
+DEFINE_double(tsdf_max_weight, 64.0, "with --tsdf_ply: a voxel's weight saturates here, 1 .. 16777216");
+DEFINE_double(tsdf_min_cos, 0.0, "with --tsdf_ply: the least cosine between a pixel's normal and its view ray (0 = no test)");
+DEFINE_bool(tsdf_register, false, "with --fuse_register and --tsdf_ply: view i is registered against a raycast of the volume built from views 0 .. i - 1, at "
+                                  "view i - 1's pose (frame to model), instead of against the raw views before it");
 DEFINE_bool(fuse_no_suppress, false, "with --fuse_poses: emit a surface from every view that sees it, not only from the first");
 DEFINE_string(batch_list, "", "text file, one stereo pair per line: l_img r_img l_dis r_dis [l_pfm r_pfm [synth_png [synth_pfm]]] (the last two with "
                               "--synth_t, and then `-` skips an optional column); all pairs run with the "
@@ -199,6 +213,7 @@ bool g_batch_calib = false;
 CalibFile g_calib_file;
 // --carry_poses: one pose per pair
 std::vector<CameraPose> g_carry_poses;
+std::unique_ptr<TsdfVolume> g_tsdf;  // --tsdf_ply: the volume the fusion's views are integrated into
 // --fuse_poses: one pose per pair, and the views the workers collect (slot = pair index, or 2 * pair index + view with --fuse_right)
 std::vector<CameraPose> g_poses;
 std::unique_ptr<DepthFusion> g_fusion;
@@ -577,7 +592,8 @@ int run_batch(const std::vector<BatchJob> &jobs, int skipped, int bad_lines) {
         const size_t pairs = g_fusion->size() / per_pair;
         std::vector<std::vector<cspm_reg_iter> > recs;
         const double r0 = static_cast<double>(getTickCount());
-        g_fusion->Register(devices[0], rp, FLAGS_fuse_register_window, per_pair, FLAGS_fuse_poses.empty(), &recs);
+        if (FLAGS_tsdf_register) g_tsdf->Register(devices[0], g_fusion.get(), rp, per_pair, FLAGS_fuse_poses.empty(), &recs);
+        else g_fusion->Register(devices[0], rp, FLAGS_fuse_register_window, per_pair, FLAGS_fuse_poses.empty(), &recs);
         if (!FLAGS_quiet) {
           for (size_t i = 1; i < pairs; ++i) {
             int taken = 0;
@@ -609,6 +625,18 @@ int run_batch(const std::vector<BatchJob> &jobs, int skipped, int bad_lines) {
       if (!WritePLY(FLAGS_fuse_ply, cloud.data(), cloud.size())) {
         cout << "Error: can not write " << FLAGS_fuse_ply << "\n";
         return EXIT_FAILURE;
+      }
+      if (g_tsdf) {  // the same views in the same list order, whatever worker or GPU produced them
+        const double s0 = static_cast<double>(getTickCount());
+        std::vector<cspm_point> surface;
+        const size_t points = g_tsdf->Fuse(devices[0], *g_fusion, &surface);
+        if (!FLAGS_quiet)
+          cout << "TSDF: " << g_fusion->size() << " views, " << points << " surface points, " << (static_cast<double>(getTickCount()) - s0) / getTickFrequency() * 1e3
+               << " ms\n";
+        if (!WritePLY(FLAGS_tsdf_ply, surface.data(), surface.size())) {
+          cout << "Error: can not write " << FLAGS_tsdf_ply << "\n";
+          return EXIT_FAILURE;
+        }
       }
     } catch (const std::exception &e) {
       cout << "Error: " << e.what() << "\n";
@@ -800,6 +828,38 @@ int run() {
     return EXIT_FAILURE;
   }
   const bool fusion = !FLAGS_fuse_poses.empty() || !FLAGS_fuse_ply.empty() || FLAGS_fuse_register;
+  {  // the TSDF flags, checked before anything opens a device
+    const bool tsdf_any = !FLAGS_tsdf_ply.empty() || !FLAGS_tsdf_origin.empty() || !FLAGS_tsdf_dims.empty() || FLAGS_tsdf_voxel != 0.0 || FLAGS_tsdf_trunc != 0.0 ||
+                          FLAGS_tsdf_max_weight != 64.0 || FLAGS_tsdf_min_cos != 0.0 || FLAGS_tsdf_register;
+    if (tsdf_any && (FLAGS_tsdf_ply.empty() || FLAGS_tsdf_origin.empty() || FLAGS_tsdf_dims.empty() || !fusion)) {
+      cout << "Error: the TSDF flags need --tsdf_ply, --tsdf_origin, --tsdf_dims, --tsdf_voxel and the fusion (--fuse_poses or --fuse_register, --fuse_ply)\n";
+      return EXIT_FAILURE;
+    }
+    if (FLAGS_tsdf_register && !FLAGS_fuse_register) {
+      cout << "Error: --tsdf_register changes what --fuse_register registers against: it needs --fuse_register\n";
+      return EXIT_FAILURE;
+    }
+    if (tsdf_any) {
+      cspm_tsdf_params tp;
+      cspm_tsdf_default_params(&tp);
+      int dims[3];
+      if (!ParseTsdfTriple(FLAGS_tsdf_origin.c_str(), tp.origin) || !ParseTsdfDims(FLAGS_tsdf_dims.c_str(), dims)) {
+        cout << "Error: --tsdf_origin must be x,y,z and --tsdf_dims nx,ny,nz\n";
+        return EXIT_FAILURE;
+      }
+      tp.nx = dims[0]; tp.ny = dims[1]; tp.nz = dims[2];
+      tp.voxel = FLAGS_tsdf_voxel; tp.trunc = FLAGS_tsdf_trunc; tp.max_weight = FLAGS_tsdf_max_weight; tp.min_cos = FLAGS_tsdf_min_cos;
+      const bool finite = std::isfinite(tp.origin[0]) && std::isfinite(tp.origin[1]) && std::isfinite(tp.origin[2]) && std::isfinite(tp.voxel) && std::isfinite(tp.trunc);
+      if (!finite || !(tp.voxel > 0.0) || tp.nx < 1 || tp.ny < 1 || tp.nz < 1 || (long long)tp.nx * tp.ny >= (1LL << 31) ||
+          (long long)tp.nx * tp.ny * tp.nz >= (1LL << 31) || !(tp.trunc >= 0.0) || !(tp.max_weight >= 1.0 && tp.max_weight <= 16777216.0) ||
+          !(tp.min_cos >= 0.0 && tp.min_cos <= 1.0)) {
+        cout << "Error: --tsdf_origin must be finite, --tsdf_voxel > 0, --tsdf_dims at least 1,1,1 with fewer than 2^31 voxels, --tsdf_trunc >= 0 (0 = 4 voxels), "
+                "--tsdf_max_weight 1 .. 16777216 and --tsdf_min_cos 0 .. 1\n";
+        return EXIT_FAILURE;
+      }
+      g_tsdf.reset(new TsdfVolume(tp));
+    }
+  }
   const bool carry = !FLAGS_carry_poses.empty();
   if (!carry && (FLAGS_carry_iters != 1 || FLAGS_carry_no_fill)) {  // checked before anything opens a device
     cout << "Error: --carry_iters and --carry_no_fill need --carry_poses\n";

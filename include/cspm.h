@@ -1017,6 +1017,124 @@ int cspm_carry_plane_field(int device, const double *src_norm_param, const uint8
 int cspm_carry_planes(cspm_ctx *dst, cspm_ctx *src, const cspm_calib *src_calib, const cspm_calib *dst_calib, const double *R, const double *t,
                       const cspm_carry_params *params, int merge);
 
+/* ---- TSDF fusion (an addition): the fusion views averaged into one implicit surface --------------------------------
+ * F ends in a point cloud and R registers a view against raw views.  A truncated signed distance volume (Curless & Levoy; KinectFusion)
+ * averages every view into one surface that can be raycast from any pose into the (depth, normal, colour) triple a fusion slot holds --
+ * an output and a target for cspm_fuse_register (frame to model) -- and whose zero level set is written out as oriented points.
+ * Triangles (marching cubes) are out of scope: the output is the surface points with normals in a defined order.
+ * The specification T.  Every product, sum, quotient, floor and square root is one IEEE f64 operation in the association written here,
+ * nothing contracted, no reciprocal, no trigonometry.  back, world, cam, proj and rot are F's; lerp(a, b, t) = a + t*(b - a).
+ * Volume: cspm_tsdf_params { origin[3], voxel, nx, ny, nz, trunc, max_weight, min_cos, step_rel }: voxel > 0, nx, ny, nz >= 1,
+ * nx*ny*nz < 2^31, trunc > 0 (0, the default, = 4.0*voxel), 1 <= max_weight <= 2^24 (default 64; W stays an exact integer in f32),
+ * min_cos in [0, 1] (default 0 = no test), step_rel in (0, 1] (default 0.5); chosen, not tuned.  The host computes once
+ * step = step_rel * trunc.  Voxel (i, j, k) has flat index v = (k*ny + j)*nx + i and centre C[a] = origin[a] + ((double)idx_a + 0.5)*voxel.
+ * State per voxel, 12 bytes: D (f32), W (f32), colour b, g, r and a byte has.  A cleared volume has D = 1, W = 0, colour bytes 0.
+ * Integrate view k (a fusion slot), every voxel on its own:
+ *  1. Q = cam(k, C); if proj(k, Q) fails, leave (behind).  fx = floor(pu + 0.5), fy = floor(pv + 0.5); leave (outside) unless
+ *     fx >= 0.0 && fx <= (double)(w-1) && fy >= 0.0 && fy <= (double)(h-1) (on the doubles, F's step 4); m = fy*w + fx.
+ *     Z = depth_k[m]; leave (hole) unless it is finite and > 0.0.
+ *  2. sdf = Z - Q[2]; leave (occluded) unless sdf >= -trunc.
+ *  3. With normal maps and min_cos > 0.0: (n0, n1, n2) = n_k[m]; (X, Y, Z) = back(k, fx, fy, Z);
+ *     num = (n0*X + n1*Y) + n2*Z;  ln = sqrt((n0*n0 + n1*n1) + n2*n2);  ls = sqrt((X*X + Y*Y) + Z*Z);  c = (-num) / (ln*ls):
+ *     the cosine between the pixel's normal and the direction from the surface point to the camera.  Leave (grazing) unless
+ *     c >= min_cos (a NaN fails).
+ *  4. d = sdf / trunc; if (d > 1.0) d = 1.0.  Wo = (double)W;  Wn = Wo + 1.0;  D = (float)(((double)D*Wo + d) / Wn);
+ *     W = (float)(Wn > max_weight ? max_weight : Wn)   (D is read before it is written, Wo is the weight before the update).
+ *  5. When view k has an image and sdf <= trunc: Wc = has ? Wo : 0.0; each of b, g, r = floor(((double)old*Wc + (double)new) / (Wc + 1.0) + 0.5)
+ *     with new the byte of pixel m; has = 1.
+ * Views are integrated in the order of the calls, one launch each; a voxel is owned by one lane: nothing depends on scheduling.
+ * Raycast from a camera (f, cx, cy, R, t) into w x h maps, z_near finite and >= 0.  Pixel (x, y):
+ *     dir = rot((((double)x - cx)/f, ((double)y - cy)/f, 1.0)), so the ray parameter lam IS the depth along the optical axis;
+ *     P(lam)[a] = t[a] + lam*dir[a].
+ *  Clip against the box of voxel CENTRES: when one of nx, ny, nz is below 2 the box is empty and the ray misses (status 0).  Otherwise
+ *     l0 = z_near, l1 = +infinity; for a = x, y, z: lo = origin[a] + 0.5*voxel, hi = origin[a] + ((double)n_a - 0.5)*voxel; when
+ *     dir[a] == 0.0 the ray misses unless lo <= t[a] <= hi; else ta = (lo - t[a])/dir[a], tb = (hi - t[a])/dir[a], swapped when ta > tb,
+ *     if (ta > l0) l0 = ta, if (tb < l1) l1 = tb.  The ray misses (status 0) unless l0 <= l1.
+ *  March lam_m = l0 + (double)m*step, m = 0, 1, .. while lam_m <= l1 (at most 2^20 samples).  A sample at P(lam_m):
+ *     g[a] = (P[a] - origin[a])/voxel - 0.5;  c[a] = floor(g[a]);  fr[a] = g[a] - c[a];  it is KNOWN iff 0 <= c[a] <= n_a - 2 on every
+ *     axis (on the doubles) and all eight corners (c + (dx, dy, dz)) have W > 0.  With d[dz][dy][dx] the corners' (double)D its value is
+ *     val = lerp(lerp(lerp(d000, d001, fr0), lerp(d010, d011, fr0), fr1), lerp(lerp(d100, d101, fr0), lerp(d110, d111, fr0), fr1), fr2).
+ *  An unknown sample forgets prev.  A known sample > 0 becomes prev.  A known sample cur <= 0 ends the ray: directly behind a known
+ *  prev > 0 it is a hit, lam* = lam_prev + (step*prev)/(prev - cur); otherwise a miss with status 3 (a back face).  A ray that leaves
+ *  the march without either is a miss with status 2.
+ *  Hit: depth = lam*, status 1.  In the cell of P(lam*) (its c, fr, d as above) the analytic gradient of the interpolant is
+ *     g0 = lerp(lerp(d001-d000, d011-d010, fr1), lerp(d101-d100, d111-d110, fr1), fr2)
+ *     g1 = lerp(lerp(d010-d000, d011-d001, fr0), lerp(d110-d100, d111-d101, fr0), fr2)
+ *     g2 = lerp(lerp(d100-d000, d101-d001, fr0), lerp(d110-d010, d111-d011, fr0), fr1)
+ *     len = sqrt((g0*g0 + g1*g1) + g2*g2);  nw = g/len;  normal[j] = (R[0][j]*nw[0] + R[1][j]*nw[1]) + R[2][j]*nw[2]   (R^T nw).
+ *  D grows towards the free space in front of a surface, so the normal points towards the camera that saw it, like G's normals (section
+ *  19: they face the camera).  Colour: 0 when a corner has has = 0, else per channel floor(val(the corners' bytes) + 0.5).  When that cell
+ *  is not known (the hit point may lie in another cell than both samples) the normal is NaN and the colour 0; depth and status stay.
+ *  Miss: depth NaN, normal NaN, colour 0, status 0 (missed the box), 2 (ran out of the box) or 3 (met a back face).
+ * Surface points: voxels v in flat order; for a voxel with W > 0 its +x, +y, +z neighbours in that order.  A neighbour inside the volume
+ *  counts when it has W > 0 and exactly one of the two D is > 0.  Each counted neighbour gives one cspm_point in WORLD coordinates:
+ *     t = Da/(Da - Db) on the (double)D of the voxel (a) and the neighbour (b);  x, y, z = (float)lerp(Ca[e], Cb[e], t);
+ *     G_v[e] = (double)D(v + e) - (double)D(v - e), NaN when one of the two is outside the volume or has W = 0;
+ *     G[e] = lerp(G_a[e], G_b[e], t);  len = sqrt((G0*G0 + G1*G1) + G2*G2);  nx, ny, nz = (float)(G[e]/len): one NaN component makes
+ *     len, and with it all three, NaN; b, g, r = floor(lerp(colour_a, colour_b, t) + 0.5) and a = 255 when both have has = 1, else all
+ *     four bytes 0; pixel = v.
+ *  *count = their number whatever the capacity; when count > cap the first cap records are written, the rest of the buffer is untouched.
+ * CSPM_ERR_ARG: parameters outside the ranges above ("tsdf: ..."), a NULL or bad camera (the fusion's messages), a bad z_near, w or
+ * h < 1, w*h >= 2^31, a stride below 3*w.  CSPM_ERR_STATE: no cspm_tsdf_begin ("tsdf: cspm_tsdf_begin first"), a second begin, and for
+ * cspm_tsdf_integrate no cspm_fuse_begin or a slot that holds no view. */
+typedef struct cspm_tsdf_params {
+  double origin[3];  /* the world corner of voxel (0, 0, 0) */
+  double voxel;      /* edge length */
+  int nx, ny, nz;
+  double trunc;      /* truncation distance; 0 = 4 * voxel */
+  double max_weight; /* a voxel's weight saturates here */
+  double min_cos;    /* with normals: the least cosine between a pixel's normal and its view ray; 0 = no test */
+  double step_rel;   /* the raycast's step as a fraction of trunc */
+} cspm_tsdf_params;
+typedef struct cspm_tsdf_camera {
+  double f, cx, cy;
+  double R[9], t[3]; /* camera -> world */
+} cspm_tsdf_camera;
+/* origin 0, voxel 0 and dims 0 (to be set), trunc 0, max_weight 64, min_cos 0, step_rel 0.5 */
+int cspm_tsdf_default_params(cspm_tsdf_params *p);
+/* The volume lives in a pool of its own from cspm_tsdf_begin to cspm_tsdf_end (or cspm_destroy), counted by CSPM_OPT_DEVICE_BYTES, whatever
+ * happens to the fusion views in between; it starts cleared.  12 bytes per voxel and the extraction's counts.  CSPM_ERR_ARG for bad
+ * parameters, CSPM_ERR_STATE ("tsdf: cspm_tsdf_begin twice without cspm_tsdf_end") for a second begin, CSPM_ERR_HIP without memory. */
+int cspm_tsdf_begin(cspm_ctx *ctx, const cspm_tsdf_params *params);
+/* D = 1, W = 0, colour 0.  Asynchronous on the ctx stream.  CSPM_ERR_STATE without a begin. */
+int cspm_tsdf_clear(cspm_ctx *ctx);
+/* integrates one fusion slot (its depth, normals, image and row of the camera table as they are on the device when the launch runs).
+ * Asynchronous on the ctx stream.  Timed as one CSPM_K_MISC bracket with nx*ny*nz evaluations.  CSPM_ERR_STATE without a TSDF begin
+ * ("tsdf: cspm_tsdf_begin first"), without a fusion begin ("fusion: cspm_fuse_begin first") or for a slot that holds no view
+ * ("tsdf: no such fusion view"). */
+int cspm_tsdf_integrate(cspm_ctx *ctx, int slot);
+/* raycast into host maps, each optional: depth w*h f64, normal three planes of w*h f64, bgr 8UC3 rows of `stride` bytes, status w*h
+ * bytes.  Synchronous.  Timed as one CSPM_K_MISC bracket with w*h evaluations.  CSPM_ERR_ARG for a NULL or bad camera, a bad z_near
+ * ("tsdf: z_near must be finite and >= 0"), a bad size (the fusion's messages; h above 524280: "tsdf: h must be at most 524280"), a stride
+ * below 3*w ("tsdf: stride is below 3 * w"); CSPM_ERR_STATE without a begin. */
+int cspm_tsdf_raycast(cspm_ctx *ctx, const cspm_tsdf_camera *camera, int w, int h, double z_near, double *depth_out, double *normal_out,
+                      uint8_t *bgr_out, size_t stride, uint8_t *status_out);
+/* the same with device pointers (depth and normal 8-byte aligned); enqueues on the ctx stream and returns */
+int cspm_tsdf_raycast_device(cspm_ctx *ctx, const cspm_tsdf_camera *camera, int w, int h, double z_near, void *d_depth_out, void *d_normal_out,
+                             void *d_bgr_out, size_t stride, void *d_status_out);
+/* raycast at the fusion pool's w x h INTO THE NEXT FUSION SLOT without leaving the device: the slot's depth (NaN where the ray
+ * missed), normals, colour and camera.  The slot is a view like any other: a source and a target for cspm_fuse_register and cspm_fuse_run;
+ * it counts as a view with an image when a view with an image has been integrated since the last clear.  Asynchronous.  The errors of the
+ * raycast, and those of a push: CSPM_ERR_STATE without a fusion begin or a free slot, CSPM_ERR_ARG when earlier views have no normals. */
+int cspm_tsdf_raycast_push(cspm_ctx *ctx, const cspm_tsdf_camera *camera, double z_near);
+/* the surface points: cloud, capacity and count as in cspm_fuse_run.  Synchronous; host outputs, each optional.  Timed as one CSPM_K_MISC
+ * bracket with nx*ny*nz evaluations.  CSPM_ERR_STATE without a begin. */
+int cspm_tsdf_points(cspm_ctx *ctx, cspm_point *cloud_out, size_t cloud_cap, unsigned int *count_out);
+/* the same with device pointers (the cloud 16-byte aligned, the count a 4-byte aligned unsigned int); enqueues and returns.  CSPM_ERR_ARG
+ * ("tsdf: the cloud buffer must be 16-byte aligned", "tsdf: the count must be 4-byte aligned"). */
+int cspm_tsdf_points_device(cspm_ctx *ctx, void *d_cloud_out, size_t cloud_cap, void *d_count_out);
+/* downloads the volume in flat order, each output optional: D and W nx*ny*nz floats, colour 4 bytes per voxel (b, g, r, has).
+ * Synchronous.  CSPM_ERR_STATE without a begin. */
+int cspm_tsdf_get_volume(cspm_ctx *ctx, float *D_out, float *W_out, uint8_t *colour_out);
+/* waits for the stream and frees the volume.  CSPM_ERR_STATE without a begin. */
+int cspm_tsdf_end(cspm_ctx *ctx);
+/* T alone on caller memory with a temporary context: fusion begin and TSDF begin, then per view one cspm_fuse_push_maps and one
+ * cspm_tsdf_integrate in the order of `views`, the surface points and the volume (outputs as in cspm_tsdf_points and
+ * cspm_tsdf_get_volume, each optional).  Synchronous.  Every argument is checked before a device is opened: the parameters, and what
+ * cspm_fuse_depth_maps checks in views, n_views, w, h (with its messages). */
+int cspm_tsdf_depth_maps(int device, const cspm_tsdf_params *params, const cspm_fuse_view *views, int n_views, int w, int h,
+                         cspm_point *cloud_out, size_t cloud_cap, unsigned int *count_out, float *D_out, float *W_out, uint8_t *colour_out);
+
 /* ---- rectification (an addition): a calibrated RAW pair undistorted and row-aligned on the device ----------------------
  * Every entry above that takes images assumes an undistorted, row-aligned pair, and cspm_reproject a cspm_calib of that pair.  This section
  * produces both from a rig description: two pinhole cameras with Brown-Conrady distortion and the pose of camera 1 in camera 0's frame.
