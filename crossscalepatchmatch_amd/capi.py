@@ -70,6 +70,7 @@ SYMBOLS = [
     "cspm_carry_default_params", "cspm_carry_relative_pose", "cspm_carry_plane_field", "cspm_carry_planes",
     "cspm_tsdf_default_params", "cspm_tsdf_begin", "cspm_tsdf_clear", "cspm_tsdf_integrate", "cspm_tsdf_raycast", "cspm_tsdf_raycast_device",
     "cspm_tsdf_raycast_push", "cspm_tsdf_points", "cspm_tsdf_points_device", "cspm_tsdf_get_volume", "cspm_tsdf_end", "cspm_tsdf_depth_maps",
+    "cspm_tsdf_mesh", "cspm_tsdf_mesh_device", "cspm_tsdf_set_volume", "cspm_tsdf_mesh_depth_maps",
     "cspm_rect_default_params", "cspm_rectify_compute", "cspm_rectify_host", "cspm_set_rectification", "cspm_get_rect_map",
     "cspm_set_images_raw", "cspm_set_images_raw_device",
 ]
@@ -349,6 +350,10 @@ def load_library():
         "cspm_tsdf_points_device": (C.c_int, [vp, vp, C.c_size_t, vp]),
         "cspm_tsdf_get_volume": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u8p]),
         "cspm_tsdf_end": (C.c_int, [vp]),
+        "cspm_tsdf_mesh": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, up, up]),
+        "cspm_tsdf_mesh_device": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, vp, vp]),
+        "cspm_tsdf_set_volume": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), u8p]),
+        "cspm_tsdf_mesh_depth_maps": (C.c_int, [C.c_int, tsp, fuv, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, vp, C.c_size_t, up, up]),
         "cspm_tsdf_depth_maps": (C.c_int, [C.c_int, tsp, fuv, C.c_int, C.c_int, C.c_int, vp, C.c_size_t, up, C.POINTER(C.c_float), C.POINTER(C.c_float), u8p]),
         "cspm_reg_default_params": (C.c_int, [rgpp]),
         "cspm_fuse_register": (C.c_int, [vp, C.c_int, C.c_ulonglong, rgpp, dp, dp, C.c_int, dp, dp, rgip]),
@@ -1031,6 +1036,37 @@ class StereoContext:
         self._chk(self.L.cspm_tsdf_get_volume(self.p, D.ctypes.data_as(fp), W.ctypes.data_as(fp), _u8(Cc)))
         return dict(D=D, W=W, C=Cc)
 
+    def tsdf_set_volume(self, D=None, W=None, colour=None):
+        """uploads the given planes of the volume as their bytes stand (cspm_tsdf_set_volume): D, W nx*ny*nz float32, colour (.., 4) uint8 =
+        b, g, r, has; None leaves a plane as it is"""
+        nx, ny, nz = self._tsdf
+        nvox = nx * ny * nz
+        planes = []
+        for a, dtype, size in ((D, np.float32, nvox), (W, np.float32, nvox), (colour, np.uint8, 4 * nvox)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype)
+                assert a.size == size, "a plane of the volume has nx*ny*nz elements"
+            planes.append(a)
+        fp = C.POINTER(C.c_float)
+        self._chk(self.L.cspm_tsdf_set_volume(self.p, planes[0].ctypes.data_as(fp) if planes[0] is not None else None,
+                                              planes[1].ctypes.data_as(fp) if planes[1] is not None else None, _opt(_u8, planes[2])))
+
+    def tsdf_mesh(self, vertices=True, faces=True, vertex_cap=None, face_cap=None, out=None):
+        """the triangle mesh of the volume (cspm_tsdf_mesh): dict(n_vertices, n_faces, vertices: the Point records of
+        tsdf_points, at most vertex_cap; faces: the Face records, at most face_cap; None = all).  The mesh is complete only when both
+        counts fit.  out: a dict with preallocated vertex_buffer / face_buffer to write into (tests poison them)."""
+        nx, ny, nz = self._tsdf
+        vcap, fcap = _tsdf_mesh_caps(nx, ny, nz, vertex_cap, face_cap)
+        pts, tri = _tsdf_mesh_buffers(vertices, faces, vcap, fcap, out)
+        nv, nf = C.c_uint(0), C.c_uint(0)
+        self._chk(self.L.cspm_tsdf_mesh(self.p, _opt(_vp, pts), vcap if vertices else 0, _opt(_vp, tri), fcap if faces else 0, C.byref(nv), C.byref(nf)))
+        return _tsdf_mesh_result(nv.value, nf.value, pts, tri, vcap, fcap)
+
+    def tsdf_mesh_device(self, d_vertices=0, vertex_cap=0, d_faces=0, face_cap=0, d_n_vertices=0, d_n_faces=0):
+        """the same with device pointers (integers; 0 = not requested); asynchronous on the context's stream (cspm_tsdf_mesh_device)"""
+        self._chk(self.L.cspm_tsdf_mesh_device(self.p, _dev(d_vertices), int(vertex_cap), _dev(d_faces), int(face_cap), _dev(d_n_vertices),
+                                               _dev(d_n_faces)))
+
     def tsdf_end(self):
         self._chk(self.L.cspm_tsdf_end(self.p))
 
@@ -1426,6 +1462,55 @@ def tsdf_depth_maps(views, w, h, origin, voxel, dims, cloud=True, cloud_cap=None
     if cloud:
         res["cloud"] = pts[:min(cnt.value, cap)]
     return res
+
+
+def _tsdf_mesh_caps(nx, ny, nz, vertex_cap, face_cap):
+    nvox = max(nx, 0) * max(ny, 0) * max(nz, 0)
+    cells = max(nx - 1, 0) * max(ny - 1, 0) * max(nz - 1, 0)
+    return 3 * nvox if vertex_cap is None else int(vertex_cap), 5 * cells if face_cap is None else int(face_cap)
+
+
+def _tsdf_mesh_buffers(vertices, faces, vcap, fcap, out):
+    pts = tri = None
+    if vertices:
+        pts = (out or {}).get("vertex_buffer")
+        if pts is None:
+            pts = np.zeros(vcap, Point)
+    if faces:
+        tri = (out or {}).get("face_buffer")
+        if tri is None:
+            tri = np.zeros(fcap, Face)
+    return pts, tri
+
+
+def _tsdf_mesh_result(nv, nf, pts, tri, vcap, fcap):
+    res = dict(n_vertices=nv, n_faces=nf)
+    if pts is not None:
+        res["vertices"] = pts[:min(nv, vcap)]
+    if tri is not None:
+        res["faces"] = tri[:min(nf, fcap)]
+    return res
+
+
+def tsdf_mesh_depth_maps(views, w, h, origin, voxel, dims, vertices=True, faces=True, vertex_cap=None, face_cap=None, device=0, out=None, **params):
+    """MC alone on host maps (cspm_tsdf_mesh_depth_maps): the views (dicts as for fuse_depth_maps) integrated in list
+    order into a cleared volume, then its mesh.  Returns what StereoContext.tsdf_mesh returns."""
+    K = len(views)
+    p = tsdf_params(origin, voxel, dims, **params)
+    arr = (FuseView * max(K, 1))()
+    keep = []
+    for k, v in enumerate(views):
+        d, n, img = _fuse_maps(v["depth"], v.get("normal"), v.get("bgr"), w, h)
+        R, t = _pose(v["R"], v["t"])
+        keep.append((d, n, img))
+        arr[k] = FuseView(_dp(d), _opt(_dp, n), _opt(_u8, img), 3 * w, float(v["f"]), float(v["cx"]), float(v["cy"]), (C.c_double * 9)(*R), (C.c_double * 3)(*t))
+    vcap, fcap = _tsdf_mesh_caps(p.nx, p.ny, p.nz, vertex_cap, face_cap)
+    pts, tri = _tsdf_mesh_buffers(vertices, faces, vcap, fcap, out)
+    nv, nf = C.c_uint(0), C.c_uint(0)
+    _check(load_library().cspm_tsdf_mesh_depth_maps(device, C.byref(p), arr, K, w, h, _opt(_vp, pts), vcap if vertices else 0, _opt(_vp, tri),
+                                                    fcap if faces else 0, C.byref(nv), C.byref(nf)))
+    del keep
+    return _tsdf_mesh_result(nv.value, nf.value, pts, tri, vcap, fcap)
 
 
 def reg_params(**params):

@@ -23,6 +23,7 @@
 #include "cspm_mesh.h"
 #include "cspm_fuse.h"
 #include "cspm_tsdf.h"
+#include "cspm_tsdf_mesh.h"
 #include "cspm_register.h"
 #include "cspm_carry.h"
 #include "cspm_synth.h"
@@ -252,6 +253,8 @@ struct cspm_ctx {
   TsdfVol tsdf{};
   long long tsdf_nvox = 0;
   unsigned int *tsdf_counts = nullptr;                   // crossings per workgroup, then the total
+  unsigned int *tsdf_first = nullptr;                    // cspm_tsdf_mesh (section 29), from its first call: a voxel's first vertex number
+  unsigned int *tsdf_fcounts = nullptr;                  //   and the triangles per workgroup, then the total
   unsigned int *fuse_counts = nullptr;                   // kept pixels per workgroup of every pass, the total, the kept pixels per view
   // rectification (cspm_set_rectification): kept until the context goes or the rectification is dropped
   bool rect_on = false;
@@ -2641,6 +2644,66 @@ int tsdf_get_volume(cspm_ctx *c, float *D_out, float *W_out, uint8_t *colour_out
   S.down(reinterpret_cast<uint32_t *>(colour_out), c->tsdf.C, nvox);
   return S.finish("tsdf: the download failed");
 }
+int tsdf_set_volume(cspm_ctx *c, const float *D, const float *W, const uint8_t *colour) {
+  const size_t nvox = (size_t)c->tsdf_nvox;
+  Staging S(c);
+  if (D) S.put(c->tsdf.D, D, nvox);
+  if (W) S.put(c->tsdf.W, W, nvox);
+  if (colour) S.put(c->tsdf.C, reinterpret_cast<const uint32_t *>(colour), nvox);
+  if (S.finish("tsdf: the upload failed")) return S.rc;
+  if (colour) c->tsdf_coloured = true;
+  return CSPM_OK;
+}
+
+// MC (cspm_tsdf_mesh.h): the surface points as vertices and the faces over them; every output a device pointer or null
+inline size_t tsdf_max_faces(const TsdfVol &V) {
+  return V.nx < 2 || V.ny < 2 || V.nz < 2 ? 0 : (size_t)kMcMaxTris * (size_t)(V.nx - 1) * (size_t)(V.ny - 1) * (size_t)(V.nz - 1);
+}
+int tsdf_mesh_enqueue(cspm_ctx *c, uint4 *verts, size_t vcap, uint32_t *faces, size_t fcap, unsigned int *d_nv, unsigned int *d_nf) {
+  const unsigned nb = tsdf_blocks(c->tsdf_nvox);
+  int rc;
+  if ((rc = dalloc(c, c->mem_tsdf, &c->tsdf_first, (size_t)c->tsdf_nvox)) || (rc = dalloc(c, c->mem_tsdf, &c->tsdf_fcounts, (size_t)nb + 1))) return rc;
+  unsigned int *counts = c->tsdf_counts, *fcounts = c->tsdf_fcounts;
+  {
+    Timed t(c, CSPM_K_MISC, c->tsdf_nvox);
+    const dim3 grid(nb), block(kTsdfBlock);
+    hipLaunchKernelGGL(k_tsdf_count, grid, block, 0, c->stream, c->tsdf, c->tsdf_nvox, counts);
+    hipLaunchKernelGGL(k_tsdf_mesh_count, grid, block, 0, c->stream, c->tsdf, c->tsdf_nvox, fcounts);
+    hipLaunchKernelGGL(k_geom_scan, dim3(1), dim3(kGeomScanBlock), 0, c->stream, counts, (int)nb, d_nv ? d_nv : counts + nb);
+    hipLaunchKernelGGL(k_geom_scan, dim3(1), dim3(kGeomScanBlock), 0, c->stream, fcounts, (int)nb, d_nf ? d_nf : fcounts + nb);
+    const unsigned int vcap32 = (unsigned int)std::min<size_t>(vcap, 0xFFFFFFFFull), fcap32 = (unsigned int)std::min<size_t>(fcap, 0xFFFFFFFFull);
+    if (verts && vcap32 != 0)
+      hipLaunchKernelGGL(k_tsdf_points, grid, block, 0, c->stream, c->tsdf, c->tsdf_nvox, (const unsigned int *)counts, verts, vcap32);
+    if (faces && fcap32 != 0) {
+      hipLaunchKernelGGL(k_tsdf_first, grid, block, 0, c->stream, c->tsdf, c->tsdf_nvox, (const unsigned int *)counts, c->tsdf_first);
+      hipLaunchKernelGGL(k_tsdf_mesh_faces, grid, block, 0, c->stream, c->tsdf, c->tsdf_nvox, (const unsigned int *)fcounts, (const unsigned int *)c->tsdf_first,
+                         faces, fcap32);
+    }
+  }
+  HIPCHK(c, hipGetLastError());
+  return CSPM_OK;
+}
+int tsdf_mesh_host(cspm_ctx *c, cspm_point *vertices_out, size_t vertex_cap, cspm_face *faces_out, size_t face_cap, unsigned int *n_vertices_out,
+                   unsigned int *n_faces_out) {
+  const unsigned nb = tsdf_blocks(c->tsdf_nvox);
+  const size_t vcap = std::min(vertices_out ? vertex_cap : (size_t)0, 3 * (size_t)c->tsdf_nvox);
+  const size_t fcap = std::min(faces_out ? face_cap : (size_t)0, tsdf_max_faces(c->tsdf));
+  unsigned int nv = 0, nf = 0;  // in front of the Staging: downloads write them
+  Staging S(c);
+  uint4 *dverts = S.buf<uint4>(2 * vcap, vcap != 0);
+  uint32_t *dfaces = S.buf<uint32_t>(3 * fcap, fcap != 0);
+  if (S.rc) return S.finish();
+  if (int rc = tsdf_mesh_enqueue(c, dverts, vcap, dfaces, fcap, nullptr, nullptr)) return rc;
+  S.down(&nv, c->tsdf_counts + nb, 1);
+  S.down(&nf, c->tsdf_fcounts + nb, 1);
+  if (S.finish("tsdf: the mesh extraction failed")) return S.rc;
+  S.down(vertices_out, dverts, std::min((size_t)nv, vcap));  // the counts first, then the records that were written
+  S.down(faces_out, dfaces, std::min((size_t)nf, fcap));
+  if (S.finish("tsdf: the mesh download failed")) return S.rc;
+  if (n_vertices_out) *n_vertices_out = nv;
+  if (n_faces_out) *n_faces_out = nf;
+  return CSPM_OK;
+}
 
 // ---- depth-view registration (cspm_register.h) ---------------------------------------------------------------
 static_assert(CSPM_REG_MAX_ITERS == kRegMaxIters, "cspm.h and cspm_register.h agree on the number of iterations");
@@ -4161,6 +4224,33 @@ int cspm_tsdf_get_volume(cspm_ctx *c, float *D_out, float *W_out, uint8_t *colou
   return tsdf_get_volume(c, D_out, W_out, colour_out);
 }
 
+int cspm_tsdf_set_volume(cspm_ctx *c, const float *D, const float *W, const uint8_t *colour) {
+  if (!c) return CSPM_ERR_ARG;
+  if (int rc = tsdf_state_check(c)) return rc;
+  ON_DEVICE(c);
+  return tsdf_set_volume(c, D, W, colour);
+}
+
+int cspm_tsdf_mesh(cspm_ctx *c, cspm_point *vertices_out, size_t vertex_cap, cspm_face *faces_out, size_t face_cap, unsigned int *n_vertices_out,
+                   unsigned int *n_faces_out) {
+  if (!c) return CSPM_ERR_ARG;
+  if (int rc = tsdf_state_check(c)) return rc;
+  ON_DEVICE(c);
+  return tsdf_mesh_host(c, vertices_out, vertex_cap, faces_out, face_cap, n_vertices_out, n_faces_out);
+}
+
+int cspm_tsdf_mesh_device(cspm_ctx *c, void *d_vertices_out, size_t vertex_cap, void *d_faces_out, size_t face_cap, void *d_n_vertices_out,
+                          void *d_n_faces_out) {
+  if (!c) return CSPM_ERR_ARG;
+  if (int rc = tsdf_state_check(c)) return rc;
+  if (d_vertices_out && ((uintptr_t)d_vertices_out & 15u)) return fail(c, CSPM_ERR_ARG, "tsdf: the vertex buffer must be 16-byte aligned");
+  if (d_faces_out && ((uintptr_t)d_faces_out & 3u)) return fail(c, CSPM_ERR_ARG, "tsdf: the face buffer must be 4-byte aligned");
+  if (((uintptr_t)d_n_vertices_out & 3u) || ((uintptr_t)d_n_faces_out & 3u)) return fail(c, CSPM_ERR_ARG, "tsdf: the counts must be 4-byte aligned");
+  ON_DEVICE(c);
+  return tsdf_mesh_enqueue(c, (uint4 *)d_vertices_out, d_vertices_out ? vertex_cap : 0, (uint32_t *)d_faces_out, d_faces_out ? face_cap : 0,
+                           (unsigned int *)d_n_vertices_out, (unsigned int *)d_n_faces_out);
+}
+
 int cspm_tsdf_end(cspm_ctx *c) {
   if (!c) return CSPM_ERR_ARG;
   if (int rc = tsdf_state_check(c)) return rc;
@@ -4170,8 +4260,8 @@ int cspm_tsdf_end(cspm_ctx *c) {
   return CSPM_OK;
 }
 
-int cspm_tsdf_depth_maps(int device, const cspm_tsdf_params *p, const cspm_fuse_view *views, int n_views, int w, int h, cspm_point *cloud_out, size_t cloud_cap,
-                         unsigned int *count_out, float *D_out, float *W_out, uint8_t *colour_out) {
+// what both one-shot entries check before a device is opened, and the views into a cleared volume of the temporary context
+static int tsdf_one_shot_check(const cspm_tsdf_params *p, const cspm_fuse_view *views, int n_views, int w, int h) {
   if (const char *msg = tsdf_params_error(p)) return fail(nullptr, CSPM_ERR_ARG, msg);
   if (n_views < 1 || n_views > kFuseMaxViews) return fail(nullptr, CSPM_ERR_ARG, "fusion: the number of views must be in 1 .. 64");
   if (!views) return fail(nullptr, CSPM_ERR_ARG, "fusion: no views");
@@ -4182,15 +4272,36 @@ int cspm_tsdf_depth_maps(int device, const cspm_tsdf_params *p, const cspm_fuse_
     if (const char *msg = fuse_maps_error(v.depth, v.bgr, v.bgr_stride, w)) return fail(nullptr, CSPM_ERR_ARG, msg);
     if ((v.normal != nullptr) != (views[0].normal != nullptr)) return fail(nullptr, CSPM_ERR_ARG, "fusion: normals in some views but not all");
   }
-  OneShot S(device);
-  if (S.rc) return S.finish();
-  int rc = fuse_begin(S.c, w, h, n_views);
-  if (!rc) rc = tsdf_begin(S.c, p);
+  return CSPM_OK;
+}
+static int tsdf_one_shot_integrate(cspm_ctx *c, const cspm_tsdf_params *p, const cspm_fuse_view *views, int n_views, int w, int h) {
+  int rc = fuse_begin(c, w, h, n_views);
+  if (!rc) rc = tsdf_begin(c, p);
   for (int k = 0; k < n_views && !rc; ++k) {
     const cspm_fuse_view &v = views[k];
-    rc = fuse_push_maps(S.c, v.depth, v.normal, v.bgr, v.bgr_stride, v.f, v.cx, v.cy, v.R, v.t);
-    if (!rc) rc = tsdf_integrate(S.c, k);
+    rc = fuse_push_maps(c, v.depth, v.normal, v.bgr, v.bgr_stride, v.f, v.cx, v.cy, v.R, v.t);
+    if (!rc) rc = tsdf_integrate(c, k);
   }
+  return rc;
+}
+
+int cspm_tsdf_mesh_depth_maps(int device, const cspm_tsdf_params *p, const cspm_fuse_view *views, int n_views, int w, int h, cspm_point *vertices_out,
+                              size_t vertex_cap, cspm_face *faces_out, size_t face_cap, unsigned int *n_vertices_out, unsigned int *n_faces_out) {
+  if (int rc = tsdf_one_shot_check(p, views, n_views, w, h)) return rc;
+  OneShot S(device);
+  if (S.rc) return S.finish();
+  int rc = tsdf_one_shot_integrate(S.c, p, views, n_views, w, h);
+  if (!rc) rc = tsdf_mesh_host(S.c, vertices_out, vertex_cap, faces_out, face_cap, n_vertices_out, n_faces_out);
+  S.latch(rc);
+  return S.finish("tsdf meshing failed");
+}
+
+int cspm_tsdf_depth_maps(int device, const cspm_tsdf_params *p, const cspm_fuse_view *views, int n_views, int w, int h, cspm_point *cloud_out, size_t cloud_cap,
+                         unsigned int *count_out, float *D_out, float *W_out, uint8_t *colour_out) {
+  if (int rc = tsdf_one_shot_check(p, views, n_views, w, h)) return rc;
+  OneShot S(device);
+  if (S.rc) return S.finish();
+  int rc = tsdf_one_shot_integrate(S.c, p, views, n_views, w, h);
   if (!rc) rc = tsdf_points_host(S.c, cloud_out, cloud_cap, count_out);
   if (!rc) rc = tsdf_get_volume(S.c, D_out, W_out, colour_out);
   S.latch(rc);

@@ -18,8 +18,9 @@
 // without --fuse_poses, by registering the views against each other; include/cspm.h "depth-view registration") --carry_poses --carry_iters
 // --carry_no_fill (with --batch_list and --calib or --rig: the list is one sequence of a moving rig, every pair starts from the previous
 // pair's plane field carried across the motion; include/cspm.h "plane-field carry") --tsdf_ply --tsdf_origin --tsdf_dims --tsdf_voxel
-// --tsdf_trunc --tsdf_max_weight --tsdf_min_cos --tsdf_register (with the fusion flags: the same views integrated in list order into one
-// TSDF volume, its surface points written as PLY, and --fuse_register done frame to model; include/cspm.h "TSDF fusion").
+// --tsdf_trunc --tsdf_max_weight --tsdf_min_cos --tsdf_register --tsdf_mesh_ply (with the fusion flags: the same views integrated in list
+// order into one TSDF volume, its surface points written as PLY or as the vertices of a triangle mesh, and --fuse_register done frame to
+// model; include/cspm.h "TSDF fusion" and "TSDF meshes").
 #include "../../include/cspm.h"
 #include "commfunc.h"
 #include "cs_patchmatch.h"
@@ -178,6 +179,8 @@ DEFINE_bool(carry_no_fill, false, "with --carry_poses: a pixel no carried plane 
 DEFINE_string(tsdf_ply, "", "with the fusion flags: the views the fusion collects are also integrated, in list order, into one TSDF volume "
                            "(include/cspm.h \"TSDF fusion\") and its surface points are written in the format of --fuse_ply.  Needs --tsdf_origin, "
                            "--tsdf_dims and --tsdf_voxel");
+DEFINE_string(tsdf_mesh_ply, "", "with the fusion flags: the triangle mesh of the TSDF volume (include/cspm.h \"TSDF meshes\") in the format of --l_mesh_ply: "
+                                "the vertices of --tsdf_ply, then the faces.  Needs what --tsdf_ply needs; --tsdf_ply itself may then be absent");
 DEFINE_string(tsdf_origin, "", "with --tsdf_ply: x,y,z, the world corner of voxel (0, 0, 0)");
 DEFINE_string(tsdf_dims, "", "with --tsdf_ply: nx,ny,nz, the number of voxels per axis");
 DEFINE_double(tsdf_voxel, 0.0, "with --tsdf_ply: the edge length of a voxel, in world units");
@@ -626,7 +629,7 @@ int run_batch(const std::vector<BatchJob> &jobs, int skipped, int bad_lines) {
         cout << "Error: can not write " << FLAGS_fuse_ply << "\n";
         return EXIT_FAILURE;
       }
-      if (g_tsdf) {  // the same views in the same list order, whatever worker or GPU produced them
+      if (g_tsdf && !FLAGS_tsdf_ply.empty()) {  // the same views in the same list order, whatever worker or GPU produced them
         const double s0 = static_cast<double>(getTickCount());
         std::vector<cspm_point> surface;
         const size_t points = g_tsdf->Fuse(devices[0], *g_fusion, &surface);
@@ -635,6 +638,19 @@ int run_batch(const std::vector<BatchJob> &jobs, int skipped, int bad_lines) {
                << " ms\n";
         if (!WritePLY(FLAGS_tsdf_ply, surface.data(), surface.size())) {
           cout << "Error: can not write " << FLAGS_tsdf_ply << "\n";
+          return EXIT_FAILURE;
+        }
+      }
+      if (g_tsdf && !FLAGS_tsdf_mesh_ply.empty()) {
+        const double s0 = static_cast<double>(getTickCount());
+        std::vector<cspm_point> vertices;
+        std::vector<cspm_face> faces;
+        g_tsdf->Mesh(devices[0], *g_fusion, &vertices, &faces);
+        if (!FLAGS_quiet)
+          cout << "TSDF mesh: " << g_fusion->size() << " views, " << vertices.size() << " vertices, " << faces.size() << " faces, "
+               << (static_cast<double>(getTickCount()) - s0) / getTickFrequency() * 1e3 << " ms\n";
+        if (!WritePLYMesh(FLAGS_tsdf_mesh_ply, vertices.data(), vertices.size(), faces.data(), faces.size())) {
+          cout << "Error: can not write " << FLAGS_tsdf_mesh_ply << "\n";
           return EXIT_FAILURE;
         }
       }
@@ -829,10 +845,11 @@ int run() {
   }
   const bool fusion = !FLAGS_fuse_poses.empty() || !FLAGS_fuse_ply.empty() || FLAGS_fuse_register;
   {  // the TSDF flags, checked before anything opens a device
-    const bool tsdf_any = !FLAGS_tsdf_ply.empty() || !FLAGS_tsdf_origin.empty() || !FLAGS_tsdf_dims.empty() || FLAGS_tsdf_voxel != 0.0 || FLAGS_tsdf_trunc != 0.0 ||
+    const bool tsdf_any = !FLAGS_tsdf_ply.empty() || !FLAGS_tsdf_mesh_ply.empty() || !FLAGS_tsdf_origin.empty() || !FLAGS_tsdf_dims.empty() || FLAGS_tsdf_voxel != 0.0 || FLAGS_tsdf_trunc != 0.0 ||
                           FLAGS_tsdf_max_weight != 64.0 || FLAGS_tsdf_min_cos != 0.0 || FLAGS_tsdf_register;
-    if (tsdf_any && (FLAGS_tsdf_ply.empty() || FLAGS_tsdf_origin.empty() || FLAGS_tsdf_dims.empty() || !fusion)) {
-      cout << "Error: the TSDF flags need --tsdf_ply, --tsdf_origin, --tsdf_dims, --tsdf_voxel and the fusion (--fuse_poses or --fuse_register, --fuse_ply)\n";
+    if (tsdf_any && ((FLAGS_tsdf_ply.empty() && FLAGS_tsdf_mesh_ply.empty()) || FLAGS_tsdf_origin.empty() || FLAGS_tsdf_dims.empty() || !fusion)) {
+      cout << "Error: the TSDF flags need --tsdf_ply, --tsdf_origin, --tsdf_dims, --tsdf_voxel and the fusion (--fuse_poses or --fuse_register, --fuse_ply); "
+              "--tsdf_mesh_ply may stand for --tsdf_ply\n";
       return EXIT_FAILURE;
     }
     if (FLAGS_tsdf_register && !FLAGS_fuse_register) {

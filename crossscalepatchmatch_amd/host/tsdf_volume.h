@@ -1,6 +1,6 @@
 // tsdf_volume.h -- class TsdfVolume: the views a DepthFusion collected, integrated in list order into one TSDF volume whose surface
-// points come back as a cloud (include/cspm.h "TSDF fusion"), and the frame-to-model registration of those views
-// against raycasts of the growing volume.  An addition; the reference has nothing like it.
+// points come back as a cloud (include/cspm.h "TSDF fusion") or as the vertices of a triangle mesh ("TSDF meshes",
+// section 29), and the frame-to-model registration of those views against raycasts of the growing volume.  An addition; the reference has nothing like it.
 #pragma once
 #include <cstdlib>
 #include <stdexcept>
@@ -57,6 +57,23 @@ class TsdfVolume {
     }
     if (rc != CSPM_OK) throw std::runtime_error(std::string("cspm_tsdf_depth_maps: ") + cspm_last_error(NULL));
     return count;
+  }
+
+  // MC over the same views: the surface points as vertices and the faces over them.  Returns the number of faces.  Throws like Fuse.
+  size_t Mesh(int device, const DepthFusion &fusion, std::vector<cspm_point> *vertices, std::vector<cspm_face> *faces) const {
+    int w = 0, h = 0;
+    const std::vector<cspm_fuse_view> arr = fusion.Views(&w, &h);
+    unsigned int nv = 0, nf = 0;
+    // the counts first, then buffers of exactly those sizes
+    int rc = cspm_tsdf_mesh_depth_maps(device, &p_, arr.data(), (int)arr.size(), w, h, NULL, 0, NULL, 0, &nv, &nf);
+    if (rc == CSPM_OK && (vertices || faces)) {
+      if (vertices) vertices->resize(nv);
+      if (faces) faces->resize(nf);
+      rc = cspm_tsdf_mesh_depth_maps(device, &p_, arr.data(), (int)arr.size(), w, h, vertices ? vertices->data() : NULL, vertices ? vertices->size() : 0,
+                                     faces ? faces->data() : NULL, faces ? faces->size() : 0, &nv, &nf);
+    }
+    if (rc != CSPM_OK) throw std::runtime_error(std::string("cspm_tsdf_mesh_depth_maps: ") + cspm_last_error(NULL));
+    return nf;
   }
 
   // The poses of the pairs refined in list order FRAME TO MODEL: pair 0 keeps its pose and is integrated; pair i's left view starts from

@@ -1021,7 +1021,7 @@ int cspm_carry_planes(cspm_ctx *dst, cspm_ctx *src, const cspm_calib *src_calib,
  * F ends in a point cloud and R registers a view against raw views.  A truncated signed distance volume (Curless & Levoy; KinectFusion)
  * averages every view into one surface that can be raycast from any pose into the (depth, normal, colour) triple a fusion slot holds --
  * an output and a target for cspm_fuse_register (frame to model) -- and whose zero level set is written out as oriented points.
- * Triangles (marching cubes) are out of scope: the output is the surface points with normals in a defined order.
+ * The surface points with normals come in a defined order; the triangles over them (marching cubes) are the section "TSDF meshes" below.
  * The specification T.  Every product, sum, quotient, floor and square root is one IEEE f64 operation in the association written here,
  * nothing contracted, no reciprocal, no trigonometry.  back, world, cam, proj and rot are F's; lerp(a, b, t) = a + t*(b - a).
  * Volume: cspm_tsdf_params { origin[3], voxel, nx, ny, nz, trunc, max_weight, min_cos, step_rel }: voxel > 0, nx, ny, nz >= 1,
@@ -1134,6 +1134,62 @@ int cspm_tsdf_end(cspm_ctx *ctx);
  * cspm_fuse_depth_maps checks in views, n_views, w, h (with its messages). */
 int cspm_tsdf_depth_maps(int device, const cspm_tsdf_params *params, const cspm_fuse_view *views, int n_views, int w, int h,
                          cspm_point *cloud_out, size_t cloud_cap, unsigned int *count_out, float *D_out, float *W_out, uint8_t *colour_out);
+
+/* ---- TSDF meshes (an addition): the zero level set of the volume as triangles -----------------------------------------
+ * T's surface points lie one on every sign change between 6-neighbours, which is where marching cubes puts its vertices.  The mesh reuses
+ * them record for record, as cspm_mesh reuses the reprojection's points; what this section adds is connectivity.
+ * The specification MC.  It holds no arithmetic of its own: predicates on T's D and W, and integers.
+ * Cells and cases.  A cell (i, j, k) exists for 0 <= i <= nx-2, 0 <= j <= ny-2, 0 <= k <= nz-2; its eight corners are the voxels
+ *  (i+dx, j+dy, k+dz), corner number c = dx | dy<<1 | dz<<2.  A volume with a dimension below 2 has no cells and so no faces.  A cell is
+ *  KNOWN iff all eight corners have W > 0; an unknown cell emits nothing.  The case of a known cell has bit c set iff D(corner c) > 0.0f:
+ *  the predicate of T's surface points, so a NaN or -0.0 corner is "not positive", as it is there.
+ * Edges.  The cube edge along axis a whose lower corner has the offsets (u, w) on the two other axes, in increasing axis order, has the
+ *  number e = 4*a + u + 2*w.  It belongs to the voxel at its lower corner and to axis a.  A sign-change edge of a known cell is by
+ *  construction a counted neighbour of T's surface points (both W > 0, exactly one D > 0).
+ * The table, derived and not typed (tools/gen_mc_table.py writes csrc/cspm_mc_table.h; tests/tsdfmesh_ref.py derives it again).
+ *  Each of the six cube faces has its four corners in cyclic order, counter-clockwise seen from outside the cube in the right-handed frame
+ *  x, y, z: for the face "axis a, side 1" with b = (a+1)%3, c = (a+2)%3 the (b, c) offsets run (0,0), (1,0), (1,1), (0,1); side 0 takes the
+ *  reverse order.  Going round a face, every maximal run of positive corners is entered over one face edge (negative -> positive) and left
+ *  over one (positive -> negative): next[entering edge] = leaving edge.  On a face with two diagonal positive corners each positive corner is
+ *  thereby cut off on its own.  The rule looks only at the face's four signs, so the two cells that share a face always agree.  Every
+ *  sign-change edge of the cube is entering on exactly one of its two faces and leaving on the other, so `next` is a permutation of the
+ *  sign-change edges and falls into loops.  Take the loops in increasing order of their lowest edge number L0; follow next from there,
+ *  L0, L1, .., L(m-1); emit the fan (L0, L(i+1), L(i)) for i = 1 .. m-2.  With this winding (v1 - v0) x (v2 - v0) points towards positive
+ *  D: the free space, the direction of the surface points' own normals.  Case 1 gives (0, 8, 4), case 254 gives (0, 4, 8), case 0x69 gives
+ *  (0,8,4), (1,11,5), (2,9,7), (3,10,6); 820 triangles over the 256 cases, at most 5 per cell.
+ * Vertices: exactly the records of cspm_tsdf_points, in its order; vertex number = rank of the surface point.  The vertex on the edge
+ *  (voxel u, axis a) has the number first[u] + the number of u's counted neighbours on the axes before a, first[u] being the number of
+ *  surface points of all voxels before u in flat order.  Points on edges with no known cell around them stay in the list unreferenced.
+ *  When D is exactly 0 at a corner several vertices coincide and some faces have zero area; they are emitted all the same, because the
+ *  topology must stay closed.
+ * Faces: one 12-byte cspm_face each; cells in flat order of their corner-0 voxel, within a cell the table's order, v[] the three vertex
+ *  numbers in the table's order.
+ * Counts and capacities are cspm_mesh's rule: both counts are reported whatever the capacities, the first `cap` records of each buffer are
+ *  written and the rest is untouched.  Faces always carry full vertex numbers, so the mesh is complete only when both counts fit.  (Counts
+ *  are 32-bit: a volume with more than 2^32 / 5 cells can overflow the face count.)
+ * Memory: the first mesh call allocates first[] (4 bytes per voxel) and one count per 256 voxels, plus one, in the volume's pool; they are
+ *  counted by CSPM_OPT_DEVICE_BYTES and freed with the volume.  A context that never meshes allocates and launches nothing new. */
+/* the mesh of the volume into host buffers, each output optional (NULL buffers ask for the counts only).  Synchronous.  Timed as one
+ * CSPM_K_MISC bracket with nx*ny*nz evaluations.  CSPM_ERR_STATE without a begin ("tsdf: cspm_tsdf_begin first"); CSPM_ERR_HIP without
+ * memory or when a launch or a download fails ("tsdf: the mesh extraction failed", "tsdf: the mesh download failed"). */
+int cspm_tsdf_mesh(cspm_ctx *ctx, cspm_point *vertices_out, size_t vertex_cap, cspm_face *faces_out, size_t face_cap,
+                   unsigned int *n_vertices_out, unsigned int *n_faces_out);
+/* the same with device pointers, each optional; enqueues on the ctx stream and returns.  CSPM_ERR_STATE without a begin; CSPM_ERR_ARG
+ * ("tsdf: the vertex buffer must be 16-byte aligned", "tsdf: the face buffer must be 4-byte aligned", "tsdf: the counts must be 4-byte
+ * aligned"); CSPM_ERR_HIP without memory. */
+int cspm_tsdf_mesh_device(cspm_ctx *ctx, void *d_vertices_out, size_t vertex_cap, void *d_faces_out, size_t face_cap, void *d_n_vertices_out,
+                          void *d_n_faces_out);
+/* the counterpart of cspm_tsdf_get_volume: uploads the planes that are given, as their bytes stand (D and W nx*ny*nz floats, colour 4 bytes
+ * per voxel b, g, r, has); a NULL plane stays as it is.  Nothing is checked: a W that is no integer in [0, max_weight] is the caller's.  With
+ * a colour plane the volume counts as coloured for cspm_tsdf_raycast_push.  Synchronous.  It keeps a model between sessions.
+ * CSPM_ERR_STATE without a begin ("tsdf: cspm_tsdf_begin first"); CSPM_ERR_HIP when the upload fails ("tsdf: the upload failed"). */
+int cspm_tsdf_set_volume(cspm_ctx *ctx, const float *D, const float *W, const uint8_t *colour);
+/* MC alone on caller memory with a temporary context: what cspm_tsdf_depth_maps does up to the last integration, then the mesh (outputs
+ * as in cspm_tsdf_mesh, each optional).  Synchronous.  Every argument is checked before a device is opened, with cspm_tsdf_depth_maps'
+ * messages (CSPM_ERR_ARG); CSPM_ERR_HIP without a device or when the run fails ("tsdf meshing failed"). */
+int cspm_tsdf_mesh_depth_maps(int device, const cspm_tsdf_params *params, const cspm_fuse_view *views, int n_views, int w, int h,
+                              cspm_point *vertices_out, size_t vertex_cap, cspm_face *faces_out, size_t face_cap, unsigned int *n_vertices_out,
+                              unsigned int *n_faces_out);
 
 /* ---- rectification (an addition): a calibrated RAW pair undistorted and row-aligned on the device ----------------------
  * Every entry above that takes images assumes an undistorted, row-aligned pair, and cspm_reproject a cspm_calib of that pair.  This section

@@ -7,9 +7,13 @@
     median and min - max of --repeats.  Repeated calls on the same volume: WARM-CACHE figures.  bytes = 24 per voxel (12 read, 12
     written; an upper bound: voxels that leave early write nothing) plus the view's 36 bytes per pixel; the share of the 8 TB/s HBM peak
     follows from them.
-(b) Raycast of the 256^3 volume at 1242 x 375 and 741 x 500, and (c) the extraction of its surface points, timed the same way.
+(b) Raycast of the 256^3 volume at 1242 x 375 and 741 x 500, and (c) the extraction of its surface points, timed the same way; next to
+    it the triangle mesh of the same volume, counts only and with records: the points extraction is the figure the
+    mesh is to be compared with (it reads the same two planes about four times over), with the share of vertices no face refers to.
 (d) Motorcycle at 741 x 500 after three iterations, both views of the pair integrated (PP source, consistent pixels), raycast at the
-    left pose: bad-2.0 of d = f B / z - doffs on the status-1 pixels against the ground truth, next to the post-processed map itself."""
+    left pose: bad-2.0 of d = f B / z - doffs on the status-1 pixels against the ground truth, next to the post-processed map itself; and
+    the mesh of that volume: faces, and whether it has a boundary away from unknown cells (an edge used in one direction only whose two
+    vertices' edges are surrounded by known cells)."""
 import argparse
 import json
 import os
@@ -70,8 +74,28 @@ def rendered(ctx, args):
             res = _timed(ctx, lambda: cnt.update(ctx.tsdf_points()), args)
             res.update(case="extract", volume=f"{n}^3", points=cnt["count"], cache="warm")
             print(json.dumps(res), flush=True)
+            mesh = {}
+            res = _timed(ctx, lambda: mesh.update(ctx.tsdf_mesh(vertices=False, faces=False)), args)
+            res.update(case="mesh_count_only", volume=f"{n}^3", vertices=mesh["n_vertices"], faces=mesh["n_faces"], cache="warm")
+            print(json.dumps(res), flush=True)
+            res = _timed(ctx, lambda: mesh.update(ctx.tsdf_mesh()), args)
+            used = len(np.unique(mesh["faces"]["v"]))
+            res.update(case="mesh", volume=f"{n}^3", vertices=mesh["n_vertices"], faces=mesh["n_faces"],
+                       unreferenced_vertex_share=round(1.0 - used / max(mesh["n_vertices"], 1), 5), cache="warm",
+                       note="the bracket holds the kernels alone; the downloads of the records are outside it")
+            print(json.dumps(res), flush=True)
         ctx.tsdf_end()
     ctx.fuse_end()
+
+
+def open_edges(faces, n_vertices):
+    """-> (directed edges without their reverse, the vertices on them): the boundary of the mesh"""
+    v = faces["v"].astype(np.int64)
+    a = np.concatenate([v[:, 0], v[:, 1], v[:, 2]])
+    b = np.concatenate([v[:, 1], v[:, 2], v[:, 0]])
+    fwd, back = a * n_vertices + b, b * n_vertices + a
+    alone = ~np.isin(fwd, back)
+    return int(alone.sum()), np.unique(np.concatenate([a[alone], b[alone]]))
 
 
 def _bad(disp, gt):
@@ -109,7 +133,22 @@ def motorcycle(ctx, capi, rd):
     for v in (0, 1):
         ctx.tsdf_integrate(v)
     ray = ctx.tsdf_raycast(dict(f=f, cx=cx, cy=cy, R=eye, t=zero), w, h, 0.0, outputs=("depth", "status"))
+    mesh = ctx.tsdf_mesh()
+    W = ctx.tsdf_volume()["W"].reshape(-1)
     ctx.tsdf_end()
+    # a boundary edge is "at an unknown cell" when a voxel within one step of either vertex's voxel has W = 0 or lies at the volume's border
+    n_open, on_open = open_edges(mesh["faces"], mesh["n_vertices"])
+    vox = mesh["vertices"]["pixel"][on_open].astype(np.int64)
+    i, j, k = vox % n, (vox // n) % n, vox // (n * n)
+    near_unknown = np.zeros(len(vox), bool)
+    for dk in (-1, 0, 1, 2):
+        for dj in (-1, 0, 1, 2):
+            for di in (-1, 0, 1, 2):
+                ii, jj, kk = i + di, j + dj, k + dk
+                inside = (ii >= 0) & (ii < n) & (jj >= 0) & (jj < n) & (kk >= 0) & (kk < n)
+                near_unknown |= ~inside | (W[np.clip((kk * n + jj) * n + ii, 0, n ** 3 - 1)] <= 0.0)
+    print(json.dumps({"case": "motorcycle_mesh", "volume": f"{n}^3", "vertices": mesh["n_vertices"], "faces": mesh["n_faces"], "open_edges": n_open,
+                      "open_edge_vertices_away_from_unknown_voxels": int((~near_unknown).sum())}), flush=True)
     ctx.fuse_end()
     d = np.where(ray["status"] == 1, f * B / ray["depth"] - doffs, np.nan)
     bad, known = _bad(d, gt)
